@@ -8,6 +8,7 @@ score + one float64 structure score per window).  A "step" is ONE pass of the ho
 path over the whole batch, inputs already resident in HBM.
 
     python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs DIR     # + the last step's outputs as DIR/*.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -97,6 +98,61 @@ def dry_run(args, world):
     return result
 
 
+DUMP_BYTES = 48 << 20          # --dump-outputs: what one run writes at most (all ranks together), headers and indices aside
+DUMP_SEED = 20240601           # the record sample of --dump-outputs
+
+
+def dump_sample_records(records, k):
+    """the fixed, seeded, sorted sample of k of `records` record indices that --dump-outputs keeps (all when k >= records)"""
+    if k >= records:
+        return np.arange(records, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(records, size=max(1, k), replace=False)).astype(np.int64)
+
+
+def collect_outputs(torch, dev, args, world, stride, out_seq, out_st, hits):
+    """--dump-outputs: what the timed path handed its caller in the LAST timed step, as float32 / float64 host arrays.
+
+    all-scores modes: the window scores (float32 sequence, float64 structure) of the records of dump_sample_records(), the
+    budget deciding how many, as [records kept, length - width + 1] rows: the windows that lie inside a record.  The
+    stream's other positions (a window over the record's end and its separator) hold no window; they are left out.
+    hits modes: the hits sorted by (position, motif) -- the device entry points append them in no particular order --
+    with the position (and motif index) as float64; when they exceed the budget, only those that start in the records of
+    dump_sample_records() (a share of the records the size of the budget's share of the hits) are kept."""
+    budget = DUMP_BYTES // world
+    out = {}
+    if hits is None:
+        n_win = args.length - args.width + 1
+        per_record = n_win * (4 + (8 if out_st is not None else 0))
+        rec = dump_sample_records(args.records, budget // per_record)
+        idx = (torch.from_numpy(rec).to(dev)[:, None] * stride + torch.arange(n_win, device=dev)[None, :]).reshape(-1)
+        out["record_index"] = rec.astype(np.float64)
+        out["scores_seq"] = out_seq[idx].cpu().numpy().reshape(len(rec), n_win)
+        if out_st is not None:
+            out["scores_struct"] = out_st[idx].cpu().numpy().reshape(len(rec), n_win)
+        return out
+    total, pos, motif, sq, st = hits
+    order = np.lexsort((motif, pos)) if motif is not None else np.argsort(pos, kind="stable")
+    cols = {"hit_pos": pos, "hit_motif": motif, "hit_seq": sq, "hit_struct": st}
+    cols = {k: v[order] for k, v in cols.items() if v is not None}
+    per_hit = sum(8 if k != "hit_seq" else 4 for k in cols)
+    if len(pos) * per_hit > budget:
+        rec = dump_sample_records(args.records, args.records * budget // (len(pos) * per_hit))
+        keep = np.isin(cols["hit_pos"] // stride, rec)
+        hard = budget * 5 // 4 // per_hit                     # hits crowded into the sampled records: the first ones only
+        cols = {k: v[keep][:hard] for k, v in cols.items()}
+        out["record_index"] = rec.astype(np.float64)
+    out["hit_count"] = np.array([total], dtype=np.float64)
+    for k, v in cols.items():
+        out[k] = v.astype(np.float32 if k == "hit_seq" else np.float64)
+    return out
+
+
+def write_outputs(outdir, arrays, rank, world):
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, ("rank%d_%s.npy" % (rank, name)) if world > 1 else name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=None,
@@ -153,7 +209,15 @@ def main():
                          "of the scan chunks that do not (DESIGN.md section 3; the same kernel runs 2.2 ms or 1.96 ms depending on this); plain: "
                          "the same allocator without the measurement; torch: torch's caching allocator, wherever that puts them")
     ap.add_argument("--hit-rate", type=float, default=1e-4, help="target combined hit rate of the auto structure threshold (SURVEY 8d C5)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (float32 / float64, at most "
+                         "48 MB over all ranks: a fixed, seeded sample of records when the outputs are larger; all-scores runs "
+                         "write the windows inside the records; with N ranks the "
+                         "names start with rank<k>_).  The inputs depend on the arguments alone, so two builds can be compared "
+                         "output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.minscore is not None:
         args.minscore_seq = args.minscore_struct = args.minscore
     if args.from_host and args.mode == "scores":
@@ -285,15 +349,15 @@ def main():
         hit_st = torch.empty(cap, dtype=torch.float64, device=dev)
         hit_count = torch.zeros(1, dtype=torch.int64, device=dev)
 
-    host_hits = [0]
+    host_hits = [0, None]
     if args.from_host:
         codes_h = codes.cpu().numpy()
         profile_h = None if seq_only else profile.cpu().numpy()
 
     def step():
         if args.from_host:
-            pos, _, _ = ctx.hits_pipeline_host(motif, codes_h, profile_h, thr_seq, thr_struct, args.chunk_positions)
-            host_hits[0] = len(pos)
+            pos, sq, st = ctx.hits_pipeline_host(motif, codes_h, profile_h, thr_seq, thr_struct, args.chunk_positions)
+            host_hits[0], host_hits[1] = len(pos), (pos, sq, st)
             return
         if is_lib:
             ctx.library_hits_dev(library, None if struct_lib else codes.data_ptr(), profile.data_ptr(), ptype, n_pos,
@@ -349,6 +413,17 @@ def main():
     n_hits = None
     if args.mode != "scores":
         n_hits = host_hits[0] if args.from_host else int(hit_count.item())
+    if args.dump_outputs:
+        hits = None
+        if args.from_host:
+            pos, sq, st = host_hits[1]
+            hits = (n_hits, pos, None, sq, st)
+        elif args.mode != "scores":
+            k = min(n_hits, cap)
+            hits = (n_hits, hit_pos[:k].cpu().numpy(), hit_motif[:k].cpu().numpy() if is_lib else None,
+                    None if struct_lib else hit_seq[:k].cpu().numpy(), None if seq_only else hit_st[:k].cpu().numpy())
+        write_outputs(args.dump_outputs, collect_outputs(torch, dev, args, world, args.length + 1, out_seq,
+                                                         None if seq_only else out_st, hits), rank, world)
 
     # ---- the same kernel on arrays from the DEFAULT allocator (what callers that do not use pfmscan_place_alloc get), after
     # the timed region and under the same clocks: the line carries both, so the kernel's share and the placement's share of

@@ -18,6 +18,9 @@ What is captured, and from what:
       (tests/motif_scan_test.py:37-40, tests/preprocess_seq_test.py) -- data only.
   (5) ``data/``: the reference's example/ and tests/ DATA files (PFM tables, the
       FASTA records, one averaged-structure profile).  No source text.
+  (6) ``ref_pwm_random.npz``: the C loop of (1) on seeded random inputs
+      (every width class, lengths m - 1 .. 3000, foreign letters, -inf cells),
+      stored with those inputs.
 
 How the Python functions are imported: Biopython is not installed in this image
 and is not in the reference tree, so ``import rnascan.rnascan`` fails on its
@@ -453,6 +456,41 @@ def main():
         json.dump(G, f, indent=1)
     print("wrote", os.path.join(out_dir, "golden.json"),
           "pwm cases:", len(pwm_cases), "py cases:", len(py_cases), "avg cases:", len(avg_cases))
+    write_ref_pwm_random(refpwm, out_dir)
+
+
+def ref_pwm_random_inputs():
+    """(name, sequence, matrix) of test_oracle_vs_reference_build: mixed-case letters, T/t, N and a foreign X, widths
+    1 .. 40, lengths m - 1 .. 3000, a -inf cell in every matrix wider than 3"""
+    rng = np.random.default_rng(123)
+    letters = np.array(list("ACGUacgutTNX"))
+    cases = []
+    for m in (1, 3, 8, 12, 18, 40):
+        for L in (m - 1, m, m + 1, 100, 3000):
+            if L < 0:
+                continue
+            seq = "".join(rng.choice(letters, size=L))
+            M = rng.normal(0, 5, size=(m, 4))
+            if m > 3:
+                M[1, 2] = -np.inf
+            cases.append(("m%d_L%d" % (m, L), seq, M))
+    return cases
+
+
+def write_ref_pwm_random(refpwm, out_dir):
+    """(6) ``ref_pwm_random.npz``: the reference C loop's float32 scores on the inputs of ref_pwm_random_inputs(), stored
+    with the inputs (``<name>.seq`` ASCII bytes, ``<name>.matrix``, ``<name>.scores``) so that the comparison runs
+    where oracle/_ref cannot be built"""
+    arrays = {}
+    for name, seq, M in ref_pwm_random_inputs():
+        scores = refpwm.calculate(seq, M)
+        assert scores.dtype == np.float32
+        arrays[name + ".seq"] = np.frombuffer(seq.encode("ascii"), dtype=np.uint8)
+        arrays[name + ".matrix"] = M
+        arrays[name + ".scores"] = scores
+    path = os.path.join(out_dir, "ref_pwm_random.npz")
+    np.savez_compressed(path, **arrays)
+    print("wrote", path, "cases:", len(arrays) // 3)
 
 
 if __name__ == "__main__":

@@ -1,12 +1,11 @@
 """The CPU oracle against every golden vector captured from the reference
-(tests/golden/make_golden.py) and, where oracle/_ref exists, against the
-reference's own compiled _pwm.c on fresh random inputs."""
+(tests/golden/make_golden.py), among them the reference's own compiled _pwm.c
+on seeded random inputs (checked live as well where oracle/_ref exists)."""
 import os
 
 import numpy as np
-import pytest
 
-from conftest import assert_f32_bits_equal, DATA_DIR
+from conftest import assert_f32_bits_equal, DATA_DIR, GOLDEN_DIR
 
 
 def test_pwm_goldens(oracle, golden):
@@ -30,20 +29,19 @@ def test_pwm_survey_known_values(oracle, golden):
 
 
 def test_oracle_vs_reference_build(oracle):
+    """the reference's compiled _pwm.c on seeded random inputs, stored by make_golden.py (ref_pwm_random.npz); where
+    oracle/_ref is built, the live reference loop must still give the stored scores"""
     ref = oracle.ref_pwm()
-    if ref is None:
-        pytest.skip("oracle/_ref not built (reference tree absent)")
-    rng = np.random.default_rng(123)
-    letters = np.array(list("ACGUacgutTNX"))
-    for m in (1, 3, 8, 12, 18, 40):
-        for L in (m - 1, m, m + 1, 100, 3000):
-            if L < 0:
-                continue
-            seq = "".join(rng.choice(letters, size=L))
-            M = rng.normal(0, 5, size=(m, 4))
-            if m > 3:
-                M[1, 2] = -np.inf
-            assert_f32_bits_equal(oracle.pwm_calculate(seq, M), ref.calculate(seq, M))
+    with np.load(os.path.join(GOLDEN_DIR, "ref_pwm_random.npz")) as z:
+        names = sorted({k.rsplit(".", 1)[0] for k in z.files})
+        assert len(names) == 30
+        for name in names:
+            seq = z[name + ".seq"].tobytes().decode("ascii")
+            M, want = z[name + ".matrix"], z[name + ".scores"]
+            assert want.dtype == np.float32 and len(seq) == int(name.split("_L")[1])
+            assert_f32_bits_equal(oracle.pwm_calculate(seq, M), want)
+            if ref is not None:
+                assert_f32_bits_equal(ref.calculate(seq, M), want)
 
 
 def test_py_calculate_goldens(oracle, golden):

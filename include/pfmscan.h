@@ -52,7 +52,7 @@
 extern "C" {
 #endif
 
-#define PFMSCAN_ABI_VERSION 8
+#define PFMSCAN_ABI_VERSION 9
 #define PFMSCAN_NCODE   8      /* columns of a letter table */
 #define PFMSCAN_SEP     7      /* separator / foreign-letter code */
 #define PFMSCAN_NSTRUCT 7      /* columns of a structure profile / structure PSSM */
@@ -421,6 +421,42 @@ int pfmscan_upload_source_file(pfmscan_ctx *ctx, const void *base, size_t length
  * read in the mapping's place); PFMSCAN_E_BADARG otherwise, and uploads keep reading the mapping. */
 int pfmscan_upload_source_file_checked(pfmscan_ctx *ctx, const void *base, size_t length, const char *path,
                                        int64_t file_offset, int64_t st_dev, int64_t st_ino, int64_t st_size);
+
+/* ---- dot-bracket structures -> structure-context letters ------------------------------------------------------
+ * Replaces scripts/parse_secondary_structure.cpp (parse(), :65-221, and the line loop of its main(), :235-261): the
+ * separate binary that turns folding output such as `((..((...))..))` into the EHTBLRM letters every structure-letter
+ * mode reads.  Input: a packed stream in the layout above whose letters are dot-bracket codes
+ *     '.' = 0, '(' = 1, ')' = 2, any other byte = 3          (PFMSCAN_SEP after every record)
+ * (pfmscan_fasta_encode with that LUT).  Output: the same layout, each position the code of its context letter through
+ * `map` (7 entries, the caller's codes of E H T B L R M, each 0..6; {0,1,2,3,4,5,6} for the order EHTBLRM),
+ * PFMSCAN_SEP at separators, case bit clear -- what the letter scans (pfmscan_hits_letters_f64_*, pfmscan_hits_pair_*,
+ * letter libraries) read.  The rules (a run of dots [a, b) between brackets k = a - 1 and m = b, p[] = partner):
+ *     '(' -> L, ')' -> R;  a run at either end of its record -> E;  '(' .. ')' -> H;  ')' .. '(' -> M inside a pair,
+ *     E outside;  '(' .. '(' or ')' .. ')' -> B when p[m] + 1 == p[k], else T -- except that such a run becomes M when it
+ *     ends at p[j] - 1 or starts at p[m'] + 1 for a ')' at j followed by a '(' or by a multiloop run whose next bracket
+ *     is m'.
+ * Deviation: the reference reads past the end of an unbalanced string and drops characters it does not know; here a
+ * stream with an unbalanced record, a byte outside "().", or no separator at its end is REJECTED: PFMSCAN_E_BADARG,
+ * *first_bad = the first stream position at which it is invalid (a depth below zero, a separator at depth above zero,
+ * a code 3, or a last position that is not a separator), nothing is written.  A record of 2^31 positions or more:
+ * PFMSCAN_E_BADSHAPE, *first_bad = its separator.  On success *first_bad = -1.
+ * counts: the histogram of the written codes 0..6 (int64 [7]): compute_background's letter counts of the annotated
+ * records (rnascan.py:440-465) without another pass.
+ *
+ * _dev: d_in and d_out are device buffers of n_pos bytes that must not overlap; d_counts a device int64 [7] or NULL.
+ *   Asynchronous on `stream` (NULL: the ctx's stream) EXCEPT for the validity verdict: `stream` is synchronised once
+ *   after the validation pass.  Device scratch (depth, partners, tile sums) belongs to the ctx. */
+int pfmscan_dotbracket_annotate_dev(pfmscan_ctx *ctx, const uint8_t *d_in, uint8_t *d_out, int64_t n_pos,
+                                    const uint8_t *map, int64_t *d_counts, int64_t *first_bad, void *stream);
+/* Upload host dot-bracket codes and leave the ANNOTATED stream staged: which = 0 in the codes slot (as pfmscan_stage
+ * with codes only; nothing is staged after an error), which = 1 as the second code stream (as pfmscan_stage_codes2: a
+ * stream of the same n_pos must be staged).  Every *_staged letter entry point and pfmscan_library_hits_staged of a
+ * letter library then scan it with no further H2D.  counts: host int64 [7] or NULL. */
+int pfmscan_dotbracket_stage(pfmscan_ctx *ctx, const uint8_t *codes, int64_t n_pos, int which, const uint8_t *map,
+                             int64_t *counts, int64_t *first_bad);
+/* Host buffers in and out (out: n_pos bytes); leaves the staged stream alone.  counts: host int64 [7] or NULL. */
+int pfmscan_dotbracket_annotate_host(pfmscan_ctx *ctx, const uint8_t *in, uint8_t *out, int64_t n_pos,
+                                     const uint8_t *map, int64_t *counts, int64_t *first_bad);
 
 /* ---- host ingest and output (no device needed; no context: errors via pfmscan_last_error(NULL)) ---------------
  * The two pieces of host work that dwarf the kernel at scale, in native code.

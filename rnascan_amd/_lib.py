@@ -22,7 +22,7 @@ NCODE = 8
 NSTRUCT = 7
 MAX_M = 64            # widest PFM of the tuned kernels and of PFM libraries
 MAX_WIDTH = 4096      # widest PFM accepted (wider than MAX_M: the plain rolled-loop kernel)
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 # every symbol include/pfmscan.h declares (checked by tests/test_abi.py)
 SYMBOLS = [
@@ -40,6 +40,7 @@ SYMBOLS = [
     "pfmscan_hits_pair_dev", "pfmscan_stage_codes2", "pfmscan_hits_pair_staged", "pfmscan_hits_pair_host", "pfmscan_round_decimals",
     "pfmscan_set_upload_mode", "pfmscan_upload_source_file", "pfmscan_upload_source_file_checked", "pfmscan_fasta_lone_cr", "pfmscan_count_bytes", "pfmscan_fasta_index", "pfmscan_fasta_ids", "pfmscan_gather_spans", "pfmscan_fasta_encode", "pfmscan_tsv_format", "pfmscan_profile_parse", "pfmscan_tsv_number",
     "pfmscan_place_alloc", "pfmscan_place_free", "pfmscan_place_note", "pfmscan_place_trim",
+    "pfmscan_dotbracket_annotate_dev", "pfmscan_dotbracket_stage", "pfmscan_dotbracket_annotate_host",
 ]
 TSV_CONST, TSV_I64, TSV_F32, TSV_F64, TSV_INDEXED, TSV_FIXED, TSV_WINDOW, TSV_SPAN = range(8)
 
@@ -137,6 +138,9 @@ def load():
     L.pfmscan_upload_source_file.argtypes = [vp, vp, ctypes.c_size_t, ctypes.c_char_p, i64]
     L.pfmscan_upload_source_file_checked.argtypes = [vp, vp, ctypes.c_size_t, ctypes.c_char_p, i64, i64, i64, i64]
     L.pfmscan_fasta_lone_cr.argtypes = [vp, i64, ctypes.POINTER(i32), i32]
+    L.pfmscan_dotbracket_annotate_dev.argtypes = [vp, vp, vp, i64, vp, vp, ctypes.POINTER(i64), vp]
+    L.pfmscan_dotbracket_stage.argtypes = [vp, vp, i64, i32, vp, vp, ctypes.POINTER(i64)]
+    L.pfmscan_dotbracket_annotate_host.argtypes = [vp, vp, vp, i64, vp, vp, ctypes.POINTER(i64)]
     L.pfmscan_count_bytes.argtypes = [vp, i64, vp, i32]
     L.pfmscan_place_alloc.argtypes = [vp, i32, vp, vp, i32]
     L.pfmscan_place_free.argtypes = [vp, vp]
@@ -657,6 +661,59 @@ class Context(object):
             self._check(rc, k.value)
             k = int(k.value)
             return pos[:k].copy(), (sq[:k].copy() if motif.has_letters else None), (st[:k].copy() if motif.has_struct else None)
+
+    # -- dot-bracket structures -> structure-context letters ---------------------------------------------------
+    def _dotbracket_check(self, rc, bad):
+        """a rejected stream raises ValueError whose ``position`` attribute is the first bad stream position"""
+        if rc in (E_BADARG, E_BADSHAPE) and bad.value >= 0:
+            err = ValueError(self._L.pfmscan_last_error(self._h).decode("utf-8", "replace"))
+            err.position = int(bad.value)
+            raise err
+        self._check(rc)
+
+    @staticmethod
+    def _dotbracket_map(letter_map):
+        m = np.ascontiguousarray(np.arange(7) if letter_map is None else letter_map, dtype=np.uint8)
+        if m.shape != (7,):
+            raise ValueError("the letter map has 7 entries (the codes of E, H, T, B, L, R, M)")
+        return m
+
+    def dotbracket_annotate_host(self, codes, letter_map=None, want_counts=True):
+        """dot-bracket codes (dotbracket.LUT) -> structure-letter codes of the same layout, and int64 [7] letter counts
+        (or None).  ValueError naming the first invalid stream position (``.position``) on a rejected stream."""
+        codes = np.ascontiguousarray(codes, dtype=np.uint8)
+        out = np.empty_like(codes)
+        counts = np.zeros(7, dtype=np.int64) if want_counts else None
+        bad = ctypes.c_int64(-1)
+        rc = self._L.pfmscan_dotbracket_annotate_host(self._h, _ptr(codes), _ptr(out), codes.size,
+                                                      _ptr(self._dotbracket_map(letter_map)), _ptr(counts), ctypes.byref(bad))
+        self._dotbracket_check(rc, bad)
+        return out, counts
+
+    def dotbracket_stage(self, codes, which=0, letter_map=None):
+        """upload dot-bracket codes and leave the annotated stream staged (which = 0: the codes slot, 1: the second code
+        stream); returns the int64 [7] letter counts"""
+        codes = np.ascontiguousarray(codes, dtype=np.uint8)
+        counts = np.zeros(7, dtype=np.int64)
+        bad = ctypes.c_int64(-1)
+        if which == 0:
+            self.scratch_gen += 1
+            self._staged_n = -1
+        rc = self._L.pfmscan_dotbracket_stage(self._h, _ptr(codes), codes.size, int(which),
+                                              _ptr(self._dotbracket_map(letter_map)), _ptr(counts), ctypes.byref(bad))
+        self._dotbracket_check(rc, bad)
+        if which == 0:
+            self._staged_n = codes.size
+        return counts
+
+    def dotbracket_annotate_dev(self, d_in, d_out, n_pos, letter_map=None, d_counts=None, stream=None):
+        """device buffers (raw addresses or objects with data_ptr()); asynchronous on `stream` except for the verdict"""
+        bad = ctypes.c_int64(-1)
+        addr = lambda a: None if a is None else (a.data_ptr() if hasattr(a, "data_ptr") else a)   # noqa: E731
+        rc = self._L.pfmscan_dotbracket_annotate_dev(self._h, _ptr(addr(d_in)), _ptr(addr(d_out)), int(n_pos),
+                                                     _ptr(self._dotbracket_map(letter_map)), _ptr(addr(d_counts)),
+                                                     ctypes.byref(bad), _ptr(stream))
+        self._dotbracket_check(rc, bad)
 
     # -- generic-alphabet letter hits in fp64; two code streams ---------------------------------
     def hits_letters_f64_staged(self, motif, thr, capacity=None):

@@ -9,13 +9,14 @@ of the profiles.  ``-c/--cores`` and ``-x/--debug`` are accepted and
 ignored: there is no process pool, a batch is one kernel launch.
 """
 import argparse
+import atexit
 import os
 import sys
 import time
 
 import numpy as np
 
-from . import fasta, pack, pssm as pssm_mod, scanner, shard, store, table
+from . import dotbracket, fasta, pack, pssm as pssm_mod, scanner, shard, store, table
 
 from . import __version__
 
@@ -73,6 +74,11 @@ def getoptions(argv=None):
                            "error of at most 2^-24 x (sum over the PFM's rows of the largest finite |log-odds|); auto takes "
                            "float32 when that bound is below 5e-7 for the structure PFM at hand, else float64, and says so on "
                            "stderr [%(default)s]"))
+    gpu.add_argument("--struct-format", choices=["auto", "letters", "dotbracket"], default="auto",
+                     help=("structure FASTA / -t structure: 'letters' reads EHTBLRM strings (the reference's input), "
+                           "'dotbracket' reads '((..))' strings and annotates them on the GPU with the letters the "
+                           "reference's parse_secondary_structure would write, 'auto' takes dotbracket when the records "
+                           "hold a '(' and no structure letter [%(default)s]"))
     args = parser.parse_args(argv)
     if not (args.pfm_seq or args.pfm_struct):
         parser.error("Must specify PFMs with -p and/or -q")
@@ -156,6 +162,64 @@ def _same_records(seq_fasta, struct_fasta):
     ids = list(recs.ids)
     ok = len(recs) == len(srecs) and len(recs) > 0 and ids == list(srecs.ids) and len(set(ids)) == len(ids)
     return (recs, srecs) if ok else None
+
+
+def _rank_device(args):
+    """the device this process scans on: what _init_distributed will pick under a launcher, else --device"""
+    rank, world = shard.env_rank_world()
+    if world > 1 and os.environ.get("RNASCAN_ONE_DEVICE") != "1":
+        return int(os.environ.get("LOCAL_RANK", str(args.device)))
+    return args.device
+
+
+def _remove_quietly(path):
+    try:
+        os.remove(path)
+    except OSError:
+        pass
+
+
+def struct_input(args, seq_type, testseq_stack, get_engine):
+    """--struct-format: a dot-bracket structure FASTA (or -t structure string) is annotated on the GPU before anything
+    reads it, and every structure-letter mode then runs on the letters exactly as on a file of them (the reference's
+    parse_secondary_structure run first).  The FASTA's annotated copy is a temporary file removed at exit; it replaces
+    the structure file in args.fastafiles.  A rejected record ends the run (exit 1) before any output."""
+    if seq_type not in ("SS", "RNASS"):
+        return
+    fmt = getattr(args, "struct_format", "letters")
+    if args.testseq:
+        at = -1 if seq_type == "SS" else -2
+        if len(testseq_stack) < -at:
+            return
+        s = testseq_stack[at]
+        if fmt == "dotbracket" or (fmt == "auto" and dotbracket.is_dotbracket_string(s)):
+            try:
+                testseq_stack[at] = dotbracket.annotate_string(get_engine().ctx, s)
+            except dotbracket.DotBracketError as e:
+                fasta.eprint(str(e))
+                sys.exit(1)
+        elif "(" in s or ")" in s:
+            fasta.eprint("The test structure holds '(' or ')': for dot-bracket input use --struct-format dotbracket")
+        return
+    i = 0 if seq_type == "SS" else 1
+    if i >= len(args.fastafiles) or not os.path.isfile(args.fastafiles[i]) or store.is_store(args.fastafiles[i]):
+        return                                           # averaged-structure profiles: not a structure-letter input
+    path = args.fastafiles[i]
+    counts = dotbracket.body_counts(path)
+    kind = fmt if fmt != "auto" else ("dotbracket" if counts[dotbracket.OPEN] > 0 and counts[dotbracket._LETTER] == 0 else "letters")
+    if kind == "letters":
+        if counts[dotbracket.OPEN] or counts[dotbracket.CLOSE]:
+            fasta.eprint("%s holds '(' or ')' in its records: for dot-bracket structures use --struct-format dotbracket" % path)
+        return
+    fasta.eprint("Annotating dot-bracket structures of %s on the GPU" % path)
+    try:
+        tmp = dotbracket.annotated_copy(get_engine().ctx, path)
+    except dotbracket.DotBracketError as e:
+        fasta.eprint(str(e))
+        sys.exit(1)
+    atexit.register(_remove_quietly, tmp)
+    args.fastafiles = list(args.fastafiles)
+    args.fastafiles[i] = tmp
 
 
 def load_motif(pfm_file, pseudocount, letters, background):
@@ -304,6 +368,15 @@ def main(argv=None, engine=None, out=None):
             engine = scanner.HipEngine(args.device)     # raises without libpfmscan / a gfx950 device
             own_engine = True
         return engine
+
+    def annotation_engine():
+        nonlocal engine, own_engine
+        if engine is None:                              # on the device this rank will scan on (see _init_distributed)
+            engine = scanner.HipEngine(_rank_device(args))
+            own_engine = True
+        return engine
+
+    struct_input(args, seq_type, testseq_stack, annotation_engine)
 
     if seq_type in ("RNA", "RNASS"):
         bg = None

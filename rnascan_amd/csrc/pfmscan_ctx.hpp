@@ -49,6 +49,7 @@ struct pfmscan_ctx {
     DevBuf sort_keys_in, sort_keys_out, sort_vals_in, sort_vals_out, sort_temp, sort_seq, sort_struct;   // pfmscan_sort.hip
     DevBuf hit_motif, sort_motif;               // library scans: motif index per hit
     DevBuf lib_pos, lib_motif, lib_seq, lib_struct, lib_count;   // library scans: sharded hits of the _dev form
+    DevBuf db_in, db_out, db_tree, db_part, db_marks, db_tiles, db_flags;   // dot-bracket annotation (pfmscan_dotbracket.hip)
     DevBuf pipe_codes[2], pipe_profile[2];      // chunked host pipeline: double-buffered chunk of the stream
     hipEvent_t pipe_copied[2] = {nullptr, nullptr}, pipe_scanned[2] = {nullptr, nullptr};
     // host ranges known to be read-only mappings of files (pfmscan_upload_source_file): the staged uploader preads them
@@ -92,6 +93,9 @@ int finish_sorted_hits(pfmscan_ctx *ctx, bool has_seq, bool has_struct, int64_t 
 int upload(pfmscan_ctx *ctx, void *d_dst, const void *h_src, size_t bytes, hipStream_t st);
 void upload_release(pfmscan_ctx *ctx);
 void place_release_all(pfmscan_ctx *ctx);   // pfmscan_place.hip
+// pfmscan_dotbracket.hip: dot-bracket codes d_in -> structure-letter codes d_out on `st` (see pfmscan_dotbracket_annotate_dev)
+int dotbracket_annotate(pfmscan_ctx *ctx, const uint8_t *d_in, uint8_t *d_out, int64_t n, const uint8_t *map,
+                        int64_t *d_counts, int64_t *host_counts, int64_t *first_bad, hipStream_t st);
 inline bool misaligned(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; }
 
 }  // namespace pfmscan

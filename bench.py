@@ -9,6 +9,7 @@ path over the whole batch, inputs already resident in HBM.
 
     python bench.py --gpus 1 --steps 20 --warmup 3
     python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs DIR     # + the last step's outputs as DIR/*.npy
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full                 # + baselines, floors, parity, secondary legs
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -16,14 +17,20 @@ Multi-GPU: records are independent, so every rank scans its own
 shard (weak scaling), no data-path collective; only the timing barrier and a MAX
 over ranks use RCCL.  With 8 ranks the default shard is 125k records: BASELINE
 configs[3] ("C4": 1M records x 3 kb over 8 GPUs); the line then carries every rank's
-kernel time and a per-rank parity sample against the CPU oracle.
+kernel time and (--full) a per-rank parity sample against the CPU oracle.
 
 Prints ONE JSON line (rank 0).  ``roofline`` is computed from the ALGORITHMIC
 bytes (29 B read per position + 12 B written per window)
 and the average kernel duration measured with HIP events on the launch stream.
-``cpu_baseline`` times the CPU oracle (oracle/pfm_oracle.c, OpenMP) on a bounded
-sample of the same records on this box's host cores, and the same sample is
-used as a parity check of the GPU scores.
+
+A plain run does only what that line needs: set up, settle and warm up, time the
+steps, write --dump-outputs, print.  ``--full`` adds what takes runs of its own
+after the timed region: the same kernel on default-allocator arrays, this GPU's
+live memory floor (tools/hbm_mixed), the per-rank parity sample of multi-GPU runs,
+``cpu_baseline`` (the CPU oracle, oracle/pfm_oracle.c with OpenMP, on a bounded
+sample of the same records on this box's host cores, the same sample used as a
+parity check of the GPU scores), the reference-structured baseline and the
+secondary legs (bench_legs.py).
 """
 import argparse
 import json
@@ -168,13 +175,17 @@ def main():
                     help="records per GPU [100000; 125000 with 8 GPUs = C4: 1M records over the node]")
     ap.add_argument("--length", type=int, default=3000)
     ap.add_argument("--width", type=int, default=12)
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU work for the cpu_baseline sample")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also measure and check what the headline does not need: the same kernel on "
+                         "default-allocator arrays, the live memory floor, the per-rank parity sample, the CPU baselines with "
+                         "their parity check and the secondary legs.  The --no-* options below leave parts of it out")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU work for the cpu_baseline sample (--full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines and the parity checks against the oracle")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the secondary legs of the default line (C5, its structure-only form and C2 hits on the resident "
+                    help="--full without the secondary legs (C5, its structure-only form and C2 hits on the resident "
                          "stream, after the headline's timed region)")
     ap.add_argument("--no-ref-structured", action="store_true",
-                    help="skip the reference-structured Python baseline (B-ref of BASELINE.md section 3)")
+                    help="--full without the reference-structured Python baseline (B-ref of BASELINE.md section 3)")
     ap.add_argument("--workload", choices=["c3", "c2", "c5", "c5s"], default="c3",
                     help="c3: seq+struct w=12 (the headline metric); c2: sequence-only PFM (BASELINE configs[1], use --width 8); "
                          "c5: a library of --motifs seq+struct PFM pairs over the same resident records, every motif in ONE "
@@ -432,7 +443,8 @@ def main():
     # (not under a profiler: the kernel trace's average for this kernel is compared with `kernel_ms`, which times the placed arrays)
     under_profiler = "rocprof" in os.environ.get("LD_PRELOAD", "") or any(k.startswith(("ROCPROF", "ROCP_")) for k in os.environ) or \
         bool(os.environ.get("PFMSCAN_BENCH_NO_FLOOR"))
-    if placed is not None and args.mode == "scores" and not is_lib and not os.environ.get("PFMSCAN_BENCH_NO_DEFAULT_ALLOC") and not under_profiler:
+    if (args.full and placed is not None and args.mode == "scores" and not is_lib and not os.environ.get("PFMSCAN_BENCH_NO_DEFAULT_ALLOC")
+            and not under_profiler):
         try:
             d_codes, d_prof = codes.clone(), (None if seq_only else profile.clone())
             d_seq, d_st = torch.zeros(n_pos, dtype=torch.float32, device=dev), (None if seq_only else torch.zeros(n_pos, dtype=torch.float64, device=dev))
@@ -459,7 +471,7 @@ def main():
 
     # ---- this rank's memory floor (tools/hbm_mixed on THIS rank's GPU): a slow rank and a badly placed one look different
     rank_floor = None
-    if not is_lib and args.mode == "scores" and (seq_only or args.profile_dtype == "float32") and not args.from_host:
+    if args.full and not is_lib and args.mode == "scores" and (seq_only or args.profile_dtype == "float32") and not args.from_host:
         # one rank after the other: the tool is a child process on the rank's GPU, and a node should never see more than ONE extra
         # process beside the N ranks (process limits of shared boxes), nor two floors disturbing each other's memory traffic
         for turn in range(world):
@@ -471,7 +483,7 @@ def main():
 
     # ---- per-rank parity sample (multi-GPU runs): a few records of THIS rank's shard against the CPU oracle
     rank_parity = None
-    if dist is not None and args.mode == "scores" and not seq_only and not args.no_cpu_baseline:
+    if args.full and dist is not None and args.mode == "scores" and not seq_only and not args.no_cpu_baseline:
         from oracle import oracle
         if rank == 0:
             oracle.build()                   # one rank compiles (when stale at all), the others load the finished library
@@ -591,7 +603,7 @@ def main():
                 result["roofline"]["mixed_read_write_floor"] = {
                     "ms": floor["floor_ms"], "tb_per_s": floor["floor_tb_per_s"], "frac_of_floor": floor["floor_ms"] / kernel_ms,
                     "source": floor["source"], "note": "stored measurement of tools/hbm_mixed (its fastest form) on ANOTHER box, not taken in this run "
-                                                       "(tools/hbm_mixed is not built here): boxes of the pool differ by up to 10 % on it"}
+                                                       "(--full takes it live where tools/hbm_mixed is built): boxes differ by up to 10 % on it"}
         if traffic is not None:
             result["roofline"]["traffic_pmc_round"] = pmc_entry("c2" if seq_only else "c3").get("round")
         if default_alloc is not None:
@@ -639,7 +651,7 @@ def main():
                                                   n_hits, rate_seq)
             result["roofline"].update({"kernel_ms_median": float(np.median(step_ms)), "kernel_ms_min": float(step_ms.min()),
                                        "kernel_ms_max": float(step_ms.max())})
-        if dist is None and not args.no_cpu_baseline and args.mode == "scores" and not seq_only:
+        if args.full and dist is None and not args.no_cpu_baseline and args.mode == "scores" and not seq_only:
             usable = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else os.cpu_count()
             from oracle import oracle
             oracle.build()
@@ -727,7 +739,7 @@ def main():
                               % (cores, n_seq, t_seq, n_st, t_st),
                 }
                 result["speedup_vs_reference_structured"] = result["value"] / (wpr / per_rec)
-        if (dist is None and not args.no_secondary and args.workload == "c3" and args.mode == "scores" and not args.from_host
+        if (args.full and dist is None and not args.no_secondary and args.workload == "c3" and args.mode == "scores" and not args.from_host
                 and args.profile_dtype == "float32"):
             # last: the legs reuse (and overwrite) the headline's output arrays, whose parity sample has been checked above
             result["secondary"] = secondary_legs(torch, _lib, ctx, args, dev, codes, profile, ptype, n_pos, out_seq, out_st,

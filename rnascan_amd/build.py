@@ -112,7 +112,7 @@ def runtime_indexed_registers(path=LIB):
 
 
 def build_floor_tool(force=False):
-    """tools/hbm_mixed: the microbenchmark that moves the headline kernel's byte mix without scoring (bench.py runs its
+    """tools/hbm_mixed: the microbenchmark that moves the headline kernel's byte mix without scoring (bench.py --full runs its
     `quick` form beside the headline so that `roofline.mixed_read_write_floor` is a measurement of the SAME box)."""
     tools = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools")
     src, exe = os.path.join(tools, "hbm_mixed.hip"), os.path.join(tools, "hbm_mixed")

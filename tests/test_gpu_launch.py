@@ -26,7 +26,7 @@ def _clean_env(**extra):
 @pytest.mark.timeout(600)
 def test_bench_gpus_2_rehearsal_reports_two_ranks():
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--records", "4000", "--steps", "3",
-                        "--warmup", "1", "--settle", "2"], env=_clean_env(PFMSCAN_BENCH_REHEARSE="1"),
+                        "--warmup", "1", "--settle", "2", "--full"], env=_clean_env(PFMSCAN_BENCH_REHEARSE="1"),
                        capture_output=True, text=True, timeout=560)
     assert r.returncode == 0, r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -70,7 +70,7 @@ def test_bench_placements_give_the_same_line_but_for_the_time(placement):
     """bench.py --placement tuned | plain | torch: the resident arrays come from pfmscan_place_alloc (measured / driver order) or
     from torch's allocator; the line says which, the parity sample is bit-exact either way and the value is that of its time"""
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--records", "20000", "--steps", "3", "--warmup", "1", "--settle", "2",
-                        "--no-secondary", "--no-ref-structured", "--cpu-seconds", "1", "--placement", placement],
+                        "--full", "--no-secondary", "--no-ref-structured", "--cpu-seconds", "1", "--placement", placement],
                        env=_clean_env(PFMSCAN_BENCH_NO_FLOOR="1"), capture_output=True, text=True, timeout=560)
     assert r.returncode == 0, r.stderr[-4000:]
     res = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
@@ -81,3 +81,23 @@ def test_bench_placements_give_the_same_line_but_for_the_time(placement):
     assert res["parity_on_sample"]["seq_f32_bit_exact"] is True and res["parity_on_sample"]["struct_within_1e-6"] is True
     assert res["roofline"]["kernel"] == "k_profile_fixed"
     assert res["value"] == pytest.approx(20000 * (3000 - 12 + 1) * 3 / (res["ms_per_step"] * 3e-3), rel=1e-6)
+
+
+@pytest.mark.timeout(600)
+def test_bench_plain_run_carries_the_headline_alone():
+    """bench.py without --full: the timed steps and the line they make, none of the measurements or checks that take runs of
+    their own after the timed region (default-allocator arrays, live floor, CPU baselines and their parity, secondary legs)"""
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--records", "4000", "--steps", "3",
+                        "--warmup", "1", "--settle", "2"], env=_clean_env(), capture_output=True, text=True, timeout=560)
+    assert r.returncode == 0, r.stderr[-4000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    res = json.loads(lines[0])
+    assert res["n_gpus"] == 1 and res["steps"] == 3 and res["warmup"] == 1 and res["unit"] == "windows/s"
+    assert res["higher_is_better"] is True and res["dtype"] == "f64"
+    assert res["value"] == pytest.approx(4000 * (3000 - 12 + 1) * 3 / (res["ms_per_step"] * 3e-3), rel=1e-6)
+    assert res["roofline"]["kernel"] == "k_profile_fixed" and res["roofline"]["kernel_ms"] > 0
+    for key in ("cpu_baseline", "parity_on_sample", "cpu_baseline_reference_structured", "secondary", "per_rank"):
+        assert key not in res, key
+    for key in ("default_allocator", "kernel_ms_default_allocator", "mixed_read_write_floor"):
+        assert key not in res["roofline"], key

@@ -9,6 +9,6 @@ print('$2', 'ms', round(d['ms_per_step'],4), 'kernel_ms', round(r['kernel_ms'],4
 for w in ${WIDTHS:-8 8 4 6 10 12 16 20 40}; do
   for v in fixed generic; do
     if [ $v = generic ]; then export PFMSCAN_LETTERS_GENERIC=1; else unset PFMSCAN_LETTERS_GENERIC; fi
-    PFMSCAN_BENCH_NO_FLOOR=${NOFLOOR:-1} python3 bench.py --workload c2 --width $w --no-cpu-baseline --steps 50 2>>$O/err.log | tail -1 > $O/bench_c2_w${w}_$v.json; line $O/bench_c2_w${w}_$v.json "c2 w$w $v"
+    PFMSCAN_BENCH_NO_FLOOR=${NOFLOOR:-1} python3 bench.py --full --workload c2 --width $w --no-cpu-baseline --steps 50 2>>$O/err.log | tail -1 > $O/bench_c2_w${w}_$v.json; line $O/bench_c2_w${w}_$v.json "c2 w$w $v"
   done
 done

@@ -10,15 +10,15 @@ print('$2', 'ms', round(d['ms_per_step'],4), 'kernel_ms', round(r['kernel_ms'],4
 for r in 1 2; do
   for v in fixed generic; do
     if [ $v = generic ]; then export PFMSCAN_LETTERS_GENERIC=1; else unset PFMSCAN_LETTERS_GENERIC; fi
-    python3 bench.py --workload c2 --width 8 --no-cpu-baseline --steps 50 2>>$O/err.log | tail -1 > $O/bench_c2_$v.json; line $O/bench_c2_$v.json "c2 w8 $v"
+    python3 bench.py --full --workload c2 --width 8 --no-cpu-baseline --steps 50 2>>$O/err.log | tail -1 > $O/bench_c2_$v.json; line $O/bench_c2_$v.json "c2 w8 $v"
   done
 done
 unset PFMSCAN_LETTERS_GENERIC
-python3 bench.py --workload c2 --width 8 --no-cpu-baseline --steps 50 --placement torch 2>>$O/err.log | tail -1 > $O/bench_c2_torch.json; line $O/bench_c2_torch.json "c2 w8 fixed torch-alloc"
+python3 bench.py --full --workload c2 --width 8 --no-cpu-baseline --steps 50 --placement torch 2>>$O/err.log | tail -1 > $O/bench_c2_torch.json; line $O/bench_c2_torch.json "c2 w8 fixed torch-alloc"
 for w in 4 6 12 16; do
   for v in fixed generic; do
     if [ $v = generic ]; then export PFMSCAN_LETTERS_GENERIC=1; else unset PFMSCAN_LETTERS_GENERIC; fi
-    PFMSCAN_BENCH_NO_FLOOR=1 python3 bench.py --workload c2 --width $w --no-cpu-baseline --steps 50 2>>$O/err.log | tail -1 > $O/bench_c2_w${w}_$v.json; line $O/bench_c2_w${w}_$v.json "c2 w$w $v"
+    PFMSCAN_BENCH_NO_FLOOR=1 python3 bench.py --full --workload c2 --width $w --no-cpu-baseline --steps 50 2>>$O/err.log | tail -1 > $O/bench_c2_w${w}_$v.json; line $O/bench_c2_w${w}_$v.json "c2 w$w $v"
   done
 done
 unset PFMSCAN_LETTERS_GENERIC

@@ -7,7 +7,7 @@ OUT=gpurun_out/$R
 mkdir -p $OUT
 run() { name=$1; shift; echo "== $name: bench.py $*"; python3 bench.py "$@" 2>>$OUT/err.log | tail -1 > $OUT/$name.json; python3 -c "
 import json,sys; d=json.load(open('$OUT/$name.json')); print('   ms_per_step %.4f value %.4g %s' % (d['ms_per_step'], d['value'], d['unit']))"; }
-run bench_c3_default
+run bench_c3_default --full
 run bench_c3_variant_inf --variant inf --no-ref-structured --no-cpu-baseline
 run bench_c3_profile_f64 --profile-dtype float64 --no-ref-structured
 run bench_c3_hits --mode hits --no-cpu-baseline

@@ -7,7 +7,7 @@ mkdir -p $OUT
 ROOT=$(pwd)
 run() { name=$1; shift; echo "== $name: bench.py $*"; python3 bench.py "$@" 2>>$OUT/err.log | tail -1 > $OUT/$name.json; python3 -c "
 import json,sys; d=json.load(open('$OUT/$name.json')); print('   ms_per_step %.4f value %.4g %s' % (d['ms_per_step'], d['value'], d['unit']))"; }
-run bench_c3_default
+run bench_c3_default --full
 run bench_c5_library --workload c5 --steps 10 --warmup 2 --no-cpu-baseline
 run bench_c5_library_inf --workload c5 --variant inf --steps 5 --warmup 1 --no-cpu-baseline
 run bench_c3_hits --mode hits --no-cpu-baseline

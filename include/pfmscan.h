@@ -52,7 +52,7 @@
 extern "C" {
 #endif
 
-#define PFMSCAN_ABI_VERSION 9
+#define PFMSCAN_ABI_VERSION 10
 #define PFMSCAN_NCODE   8      /* columns of a letter table */
 #define PFMSCAN_SEP     7      /* separator / foreign-letter code */
 #define PFMSCAN_NSTRUCT 7      /* columns of a structure profile / structure PSSM */
@@ -457,6 +457,72 @@ int pfmscan_dotbracket_stage(pfmscan_ctx *ctx, const uint8_t *codes, int64_t n_p
 /* Host buffers in and out (out: n_pos bytes); leaves the staged stream alone.  counts: host int64 [7] or NULL. */
 int pfmscan_dotbracket_annotate_host(pfmscan_ctx *ctx, const uint8_t *in, uint8_t *out, int64_t n_pos,
                                      const uint8_t *map, int64_t *counts, int64_t *first_bad);
+
+/* ---- fragment structures -> averaged-structure profile rows ------------------------------------------------
+ * Replaces the averaging of rnascan/average_structure.py, get_structure_probability_matrix_for_sequence (:44-99), as
+ * scripts/run_folding (fold(), :60-70) runs it per record of length L > 50 (the skip, :63-65, is the caller's):
+ *   fragment starts  i in range(-w/2, L - w/2, w - o) in Python 2 integer arithmetic (:47): -ceil(w/2) .. L - floor(w/2)
+ *   fragment i       seq[max(i, 0) : i + w], folded (RNAfold -p, centroid structure: line 4, first ' ' field, :134-141)
+ *                    and annotated to EHTBLRM (parse_secondary_structure, :76-83)
+ *   alignment        '-' * i + letters + '-' * (L - (i + w)) (:89-92): the letters cover rows [max(i, 0), + their length)
+ *   counts           B E H L M R T per row, gaps skipped (struct_pfm_from_aligned, :28-42)
+ *   value            c / n in fp64, n = the fragments covering the row (norm_pfm, pfmutil.py:136-151), written with str()
+ *                    (write_pfm, pfmutil.py:61-87) and read back by the scan with pandas (rnascan.py:296-297)
+ * Here a row's value in column k is table[n (n + 1) / 2 + c] for the row's coverage n and count c, 0 <= c <= n <= n_max:
+ * the caller's table -- pfmscan_profile_parse of repr(c / n) gives what a scan of the reference's text reads, c / n itself
+ * what that text must show.  Rows come out in the packed-store layout (store.py): [n_rows][7] in B E H L M R T order, each
+ * record's rec_len rows followed by one zero row; out_dtype PFMSCAN_PROFILE_F64, or F32 (the round-to-nearest cast).
+ *
+ * Tables (int64; rows are 0-based rows of `out`):
+ *   fragment f   frag_off[f] = stream position of its first letter, frag_len[f] >= 1 letters, frag_row[f] = the output
+ *                row of its first letter.  Sorted by record, then by frag_row.
+ *   record r     rec_row[r] = its first row (rec_row[0] = 0, each record right after the previous one's zero row),
+ *                rec_len[r] = its length, fragments [rec_frag[r], rec_frag[r + 1]) (rec_frag has n_rec + 1 entries,
+ *                rec_frag[0] = 0, rec_frag[n_rec] = n_frag).  Every fragment lies inside its record.
+ * Rejections (nothing counts as written; *first_bad and *bad_kind say where and what):
+ *   PFMSCAN_AVG_UNCOVERED   a row of a record that no fragment covers: PFMSCAN_E_BADARG, *first_bad = the row (the
+ *                           reference divides by zero there, norm_pfm)
+ *   PFMSCAN_AVG_COVER       a row covered more than n_max times: PFMSCAN_E_BADSHAPE, *first_bad = the row
+ *   PFMSCAN_AVG_BAD_TABLE   tables that break the rules above: PFMSCAN_E_BADARG, *first_bad = the record
+ *   PFMSCAN_AVG_DOTBRACKET  (_host / _stage) an invalid dot-bracket fragment: as pfmscan_dotbracket_annotate_dev,
+ *                           *first_bad = the stream position
+ * The earliest row wins when several rows are rejected.  n_max <= PFMSCAN_MAX_COVER.
+ *
+ * _dev: d_letters = annotated codes whose code IS the column (annotate with map {1, 2, 6, 0, 3, 5, 4}: E H T B L R M ->
+ *   B E H L M R T columns); max_len >= every frag_len; all tables and the table of (n_max + 1)(n_max + 2) / 2 doubles are
+ *   device buffers; d_out holds n_rows rows.  Asynchronous on `stream` (NULL: the ctx's) except for the verdict: `stream`
+ *   is synchronised once.  Device scratch: 8 bytes per 256 rows.
+ * _host: `codes` = the fragments' dot-bracket codes in the stream layout (dotbracket LUT, PFMSCAN_SEP after each), the
+ *   tables and `table` on the host; uploads, annotates and averages, and copies the rows to `out` (host).  Device scratch
+ *   ~ 2 n_pos + 24 n_frag + 24 n_rec bytes + the rows: the caller bounds it by batching records.
+ * _stage: as _host, but the rows stay staged in the profile slot (as pfmscan_stage with a profile only; *n_rows = their
+ *   number): pfmscan_scan_staged / pfmscan_hits_staged / pfmscan_library_hits_staged of structure motifs scan them with no
+ *   H2D.  Nothing is staged after an error. */
+#define PFMSCAN_MAX_COVER 1024
+#define PFMSCAN_AVG_OK         0
+#define PFMSCAN_AVG_DOTBRACKET 1
+#define PFMSCAN_AVG_UNCOVERED  2
+#define PFMSCAN_AVG_COVER      3
+#define PFMSCAN_AVG_BAD_TABLE  4
+int pfmscan_average_dev(pfmscan_ctx *ctx, const uint8_t *d_letters, int64_t n_letters, const int64_t *d_frag_off,
+                        const int64_t *d_frag_len, const int64_t *d_frag_row, int64_t n_frag, int64_t max_len,
+                        const int64_t *d_rec_row, const int64_t *d_rec_len, const int64_t *d_rec_frag, int64_t n_rec,
+                        int64_t n_rows, const double *d_table, int n_max, void *d_out, int out_dtype, int64_t *first_bad,
+                        int *bad_kind, void *stream);
+int pfmscan_average_host(pfmscan_ctx *ctx, const uint8_t *codes, int64_t n_pos, const int64_t *frag_off,
+                         const int64_t *frag_len, const int64_t *frag_row, int64_t n_frag, const int64_t *rec_row,
+                         const int64_t *rec_len, const int64_t *rec_frag, int64_t n_rec, const double *table, int n_max,
+                         void *out, int out_dtype, int64_t *first_bad, int *bad_kind);
+int pfmscan_average_stage(pfmscan_ctx *ctx, const uint8_t *codes, int64_t n_pos, const int64_t *frag_off,
+                          const int64_t *frag_len, const int64_t *frag_row, int64_t n_frag, const int64_t *rec_row,
+                          const int64_t *rec_len, const int64_t *rec_frag, int64_t n_rec, const double *table, int n_max,
+                          int out_dtype, int64_t *n_rows, int64_t *first_bad, int *bad_kind);
+/* Fragment ids (host only, no ctx): the id spans of pfmscan_fasta_ids (id_off, id_len into buf) of fragments named as
+ * run_folding names them, <id>_frag_<i> (average_structure.py:58) -> key_len[k] (the key is buf[id_off[k], + key_len[k]):
+ * everything before the LAST "_frag_", at least one byte) and start[k] (the signed decimal after it: an optional '-' and
+ * 1..18 digits, nothing else).  PFMSCAN_E_BADARG with *first_bad = the first id that does not parse. */
+int pfmscan_fragment_ids(const uint8_t *buf, const int64_t *id_off, const int64_t *id_len, int64_t n, int64_t *key_len,
+                         int64_t *start, int64_t *first_bad);
 
 /* ---- host ingest and output (no device needed; no context: errors via pfmscan_last_error(NULL)) ---------------
  * The two pieces of host work that dwarf the kernel at scale, in native code.

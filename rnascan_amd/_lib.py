@@ -22,7 +22,7 @@ NCODE = 8
 NSTRUCT = 7
 MAX_M = 64            # widest PFM of the tuned kernels and of PFM libraries
 MAX_WIDTH = 4096      # widest PFM accepted (wider than MAX_M: the plain rolled-loop kernel)
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 # every symbol include/pfmscan.h declares (checked by tests/test_abi.py)
 SYMBOLS = [
@@ -41,7 +41,10 @@ SYMBOLS = [
     "pfmscan_set_upload_mode", "pfmscan_upload_source_file", "pfmscan_upload_source_file_checked", "pfmscan_fasta_lone_cr", "pfmscan_count_bytes", "pfmscan_fasta_index", "pfmscan_fasta_ids", "pfmscan_gather_spans", "pfmscan_fasta_encode", "pfmscan_tsv_format", "pfmscan_profile_parse", "pfmscan_tsv_number",
     "pfmscan_place_alloc", "pfmscan_place_free", "pfmscan_place_note", "pfmscan_place_trim",
     "pfmscan_dotbracket_annotate_dev", "pfmscan_dotbracket_stage", "pfmscan_dotbracket_annotate_host",
+    "pfmscan_average_dev", "pfmscan_average_host", "pfmscan_average_stage", "pfmscan_fragment_ids",
 ]
+MAX_COVER = 1024      # largest coverage of a row the averaging accepts
+AVG_OK, AVG_DOTBRACKET, AVG_UNCOVERED, AVG_COVER, AVG_BAD_TABLE = range(5)   # what a rejected averaging names
 TSV_CONST, TSV_I64, TSV_F32, TSV_F64, TSV_INDEXED, TSV_FIXED, TSV_WINDOW, TSV_SPAN = range(8)
 
 
@@ -141,6 +144,13 @@ def load():
     L.pfmscan_dotbracket_annotate_dev.argtypes = [vp, vp, vp, i64, vp, vp, ctypes.POINTER(i64), vp]
     L.pfmscan_dotbracket_stage.argtypes = [vp, vp, i64, i32, vp, vp, ctypes.POINTER(i64)]
     L.pfmscan_dotbracket_annotate_host.argtypes = [vp, vp, vp, i64, vp, vp, ctypes.POINTER(i64)]
+    L.pfmscan_average_dev.argtypes = [vp, vp, i64, vp, vp, vp, i64, i64, vp, vp, vp, i64, i64, vp, i32, vp, i32,
+                                      ctypes.POINTER(i64), ctypes.POINTER(i32), vp]
+    L.pfmscan_average_host.argtypes = [vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, i64, vp, i32, vp, i32,
+                                       ctypes.POINTER(i64), ctypes.POINTER(i32)]
+    L.pfmscan_average_stage.argtypes = [vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, i64, vp, i32, i32,
+                                        ctypes.POINTER(i64), ctypes.POINTER(i64), ctypes.POINTER(i32)]
+    L.pfmscan_fragment_ids.argtypes = [vp, vp, vp, i64, vp, vp, ctypes.POINTER(i64)]
     L.pfmscan_count_bytes.argtypes = [vp, i64, vp, i32]
     L.pfmscan_place_alloc.argtypes = [vp, i32, vp, vp, i32]
     L.pfmscan_place_free.argtypes = [vp, vp]
@@ -264,6 +274,23 @@ def fasta_ids(buf, hdr_off, hdr_len):
     if rc != OK:
         _raise(L, None, rc)
     return np.stack([off, ln], axis=1), bool(ascii_.value)
+
+
+def fragment_ids(buf, id_spans):
+    """id spans (int64 [n][2], pfmscan_fasta_ids) of ids named <key>_frag_<start> -> (key lengths int64 [n], starts int64 [n]);
+    ValueError with ``.index`` = the first id that does not parse"""
+    L = load()
+    spans = np.ascontiguousarray(id_spans, dtype=np.int64).reshape(-1, 2)
+    n = int(spans.shape[0])
+    off, ln = np.ascontiguousarray(spans[:, 0]), np.ascontiguousarray(spans[:, 1])
+    key_len, start = np.empty(n, dtype=np.int64), np.empty(n, dtype=np.int64)
+    bad = ctypes.c_int64(-1)
+    rc = L.pfmscan_fragment_ids(_ptr(np.asarray(buf)), _ptr(off), _ptr(ln), n, _ptr(key_len), _ptr(start), ctypes.byref(bad))
+    if rc != OK:
+        err = ValueError(L.pfmscan_last_error(None).decode("utf-8", "replace"))
+        err.index = int(bad.value)
+        raise err
+    return key_len, start
 
 
 def gather_spans(buf, spans, separator=10):
@@ -714,6 +741,69 @@ class Context(object):
                                                      _ptr(self._dotbracket_map(letter_map)), _ptr(addr(d_counts)),
                                                      ctypes.byref(bad), _ptr(stream))
         self._dotbracket_check(rc, bad)
+
+    # -- fragment structures -> averaged-structure profile rows ------------------------------------------------
+    def _average_check(self, rc, bad, kind):
+        """a rejected averaging raises ValueError with ``kind`` (AVG_*) and ``position`` (row, stream position or record)"""
+        if rc in (E_BADARG, E_BADSHAPE) and kind.value != AVG_OK:
+            err = ValueError(self._L.pfmscan_last_error(self._h).decode("utf-8", "replace"))
+            err.kind, err.position = int(kind.value), int(bad.value)
+            raise err
+        self._check(rc)
+
+    @staticmethod
+    def _average_args(codes, frag_off, frag_len, frag_row, rec_row, rec_len, rec_frag, table, n_max):
+        arrs = [np.ascontiguousarray(codes, dtype=np.uint8)] + \
+               [np.ascontiguousarray(a, dtype=np.int64) for a in (frag_off, frag_len, frag_row, rec_row, rec_len, rec_frag)]
+        table = np.ascontiguousarray(table, dtype=np.float64)
+        if table.size < (n_max + 1) * (n_max + 2) // 2:
+            raise ValueError("the table needs (n_max + 1)(n_max + 2) / 2 entries")
+        if arrs[6].size != arrs[4].size + 1:
+            raise ValueError("rec_frag needs n_rec + 1 entries")
+        return arrs, table
+
+    def average_host(self, codes, frag_off, frag_len, frag_row, rec_row, rec_len, rec_frag, table, n_max, dtype=np.float64):
+        """dot-bracket codes of the fragments (dotbracket.LUT, stream layout) + the fragment and record tables ->
+        profile rows [n_rows][7] (B E H L M R T, a zero row after each record) in ``dtype``; see include/pfmscan.h"""
+        (c, fo, fl, fr, rr, rl, rf), table = self._average_args(codes, frag_off, frag_len, frag_row, rec_row, rec_len, rec_frag,
+                                                                table, n_max)
+        dtype = np.dtype(dtype)
+        n_rows = int(rl.sum()) + rl.size
+        out = np.empty((n_rows, NSTRUCT), dtype=dtype)
+        bad, kind = ctypes.c_int64(-1), ctypes.c_int32(0)
+        rc = self._L.pfmscan_average_host(self._h, _ptr(c), c.size, _ptr(fo), _ptr(fl), _ptr(fr), fo.size, _ptr(rr), _ptr(rl),
+                                          _ptr(rf), rl.size, _ptr(table), int(n_max), _ptr(out),
+                                          PROFILE_F32 if dtype == np.float32 else PROFILE_F64, ctypes.byref(bad), ctypes.byref(kind))
+        self._average_check(rc, bad, kind)
+        return out
+
+    def average_stage(self, codes, frag_off, frag_len, frag_row, rec_row, rec_len, rec_frag, table, n_max, dtype=np.float64):
+        """average_host's rows left staged in the profile slot (structure motifs then scan them with *_staged); returns n_rows"""
+        (c, fo, fl, fr, rr, rl, rf), table = self._average_args(codes, frag_off, frag_len, frag_row, rec_row, rec_len, rec_frag,
+                                                                table, n_max)
+        n_rows, bad, kind = ctypes.c_int64(0), ctypes.c_int64(-1), ctypes.c_int32(0)
+        self.scratch_gen += 1
+        self._staged_n = -1
+        rc = self._L.pfmscan_average_stage(self._h, _ptr(c), c.size, _ptr(fo), _ptr(fl), _ptr(fr), fo.size, _ptr(rr), _ptr(rl),
+                                           _ptr(rf), rl.size, _ptr(table), int(n_max),
+                                           PROFILE_F32 if np.dtype(dtype) == np.float32 else PROFILE_F64,
+                                           ctypes.byref(n_rows), ctypes.byref(bad), ctypes.byref(kind))
+        self._average_check(rc, bad, kind)
+        self._staged_n = int(n_rows.value)
+        return self._staged_n
+
+    def average_dev(self, d_letters, n_letters, d_frag_off, d_frag_len, d_frag_row, n_frag, max_len, d_rec_row, d_rec_len,
+                    d_rec_frag, n_rec, n_rows, d_table, n_max, d_out, dtype=np.float64, stream=None):
+        """device buffers (raw addresses or objects with data_ptr()); asynchronous on `stream` except for the verdict"""
+        addr = lambda a: None if a is None else (a.data_ptr() if hasattr(a, "data_ptr") else a)   # noqa: E731
+        bad, kind = ctypes.c_int64(-1), ctypes.c_int32(0)
+        rc = self._L.pfmscan_average_dev(self._h, _ptr(addr(d_letters)), int(n_letters), _ptr(addr(d_frag_off)),
+                                         _ptr(addr(d_frag_len)), _ptr(addr(d_frag_row)), int(n_frag), int(max_len),
+                                         _ptr(addr(d_rec_row)), _ptr(addr(d_rec_len)), _ptr(addr(d_rec_frag)), int(n_rec),
+                                         int(n_rows), _ptr(addr(d_table)), int(n_max), _ptr(addr(d_out)),
+                                         PROFILE_F32 if np.dtype(dtype) == np.float32 else PROFILE_F64,
+                                         ctypes.byref(bad), ctypes.byref(kind), _ptr(stream))
+        self._average_check(rc, bad, kind)
 
     # -- generic-alphabet letter hits in fp64; two code streams ---------------------------------
     def hits_letters_f64_staged(self, motif, thr, capacity=None):

@@ -74,17 +74,26 @@ def getoptions(argv=None):
                            "error of at most 2^-24 x (sum over the PFM's rows of the largest finite |log-odds|); auto takes "
                            "float32 when that bound is below 5e-7 for the structure PFM at hand, else float64, and says so on "
                            "stderr [%(default)s]"))
-    gpu.add_argument("--struct-format", choices=["auto", "letters", "dotbracket"], default="auto",
+    gpu.add_argument("--struct-format", choices=["auto", "letters", "dotbracket", "fragments", "fragments-rnafold"],
+                     default="auto",
                      help=("structure FASTA / -t structure: 'letters' reads EHTBLRM strings (the reference's input), "
                            "'dotbracket' reads '((..))' strings and annotates them on the GPU with the letters the "
                            "reference's parse_secondary_structure would write, 'auto' takes dotbracket when the records "
-                           "hold a '(' and no structure letter [%(default)s]"))
+                           "hold a '(' and no structure letter.  'fragments' reads the folded windows of run_folding as "
+                           "dot-bracket FASTA records named <id>_frag_<start> ('fragments-rnafold': RNAfold -p output) and "
+                           "averages them on the GPU into the averaged-structure profiles the scan then reads; auto never "
+                           "picks these two [%(default)s]"))
     args = parser.parse_args(argv)
     if not (args.pfm_seq or args.pfm_struct):
         parser.error("Must specify PFMs with -p and/or -q")
     if args.uniform_background and (args.bg_seq or args.bg_struct):
         parser.error("You cannot set uniform and custom background options at the same time\n")
+    if args.struct_format in FRAGMENT_FORMATS and args.testseq:
+        parser.error("--struct-format %s reads a file of fragments: it cannot be used with -t" % args.struct_format)
     return args
+
+
+FRAGMENT_FORMATS = {"fragments": "fasta", "fragments-rnafold": "rnafold"}
 
 
 def _guess_seq_type(args):
@@ -202,6 +211,9 @@ def struct_input(args, seq_type, testseq_stack, get_engine):
             fasta.eprint("The test structure holds '(' or ')': for dot-bracket input use --struct-format dotbracket")
         return
     i = 0 if seq_type == "SS" else 1
+    if fmt in FRAGMENT_FORMATS and i < len(args.fastafiles):
+        fragment_input(args, i, FRAGMENT_FORMATS[fmt], get_engine)
+        return
     if i >= len(args.fastafiles) or not os.path.isfile(args.fastafiles[i]) or store.is_store(args.fastafiles[i]):
         return                                           # averaged-structure profiles: not a structure-letter input
     path = args.fastafiles[i]
@@ -218,6 +230,25 @@ def struct_input(args, seq_type, testseq_stack, get_engine):
         fasta.eprint(str(e))
         sys.exit(1)
     atexit.register(_remove_quietly, tmp)
+    args.fastafiles = list(args.fastafiles)
+    args.fastafiles[i] = tmp
+
+
+def fragment_input(args, i, input_fmt, get_engine):
+    """--struct-format fragments / fragments-rnafold: the fragment structures are averaged on the GPU into a temporary
+    packed profile store (average.py) that replaces them in args.fastafiles; everything after is the store path.  The
+    store lies under TMPDIR and is removed at exit.  A rejected fragment or record ends the run (exit 1) before any
+    output."""
+    import shutil
+    from . import average
+    path = args.fastafiles[i]
+    fasta.eprint("Averaging fragment structures of %s on the GPU" % path)
+    try:
+        tmp = average.built_store(get_engine().ctx, path, input_fmt)
+    except (average.AverageError, OSError) as e:
+        fasta.eprint(str(e))
+        sys.exit(1)
+    atexit.register(shutil.rmtree, tmp, True)
     args.fastafiles = list(args.fastafiles)
     args.fastafiles[i] = tmp
 

@@ -57,11 +57,16 @@ def build_store(directory, store_dir, dtype=np.float64):
                 ids.append(sid)
                 lengths.append(int(prof.shape[0]))
     os.replace(tmp, os.path.join(store_dir, name))
-    index = {"format": FORMAT_VERSION, "dtype": dtype.name, "letters": letters0, "ids": ids, "lengths": lengths,
+    write_index(store_dir, ids, lengths, letters0, dtype, name)
+    return len(ids)
+
+
+def write_index(store_dir, ids, lengths, letters, dtype, name):
+    """index.json of a store whose rows file ``name`` is written: ids, lengths (ints), column letters, dtype"""
+    index = {"format": FORMAT_VERSION, "dtype": np.dtype(dtype).name, "letters": letters, "ids": ids, "lengths": lengths,
              "n_pos": int(sum(lengths) + len(lengths)), "file": name, "separator_rows": "one zero row after each record"}
     with open(os.path.join(store_dir, INDEX), "w") as f:
         json.dump(index, f)
-    return len(ids)
 
 
 class ProfileStore(object):

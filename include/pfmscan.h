@@ -52,7 +52,7 @@
 extern "C" {
 #endif
 
-#define PFMSCAN_ABI_VERSION 10
+#define PFMSCAN_ABI_VERSION 11
 #define PFMSCAN_NCODE   8      /* columns of a letter table */
 #define PFMSCAN_SEP     7      /* separator / foreign-letter code */
 #define PFMSCAN_NSTRUCT 7      /* columns of a structure profile / structure PSSM */
@@ -523,6 +523,42 @@ int pfmscan_average_stage(pfmscan_ctx *ctx, const uint8_t *codes, int64_t n_pos,
  * 1..18 digits, nothing else).  PFMSCAN_E_BADARG with *first_bad = the first id that does not parse. */
 int pfmscan_fragment_ids(const uint8_t *buf, const int64_t *id_off, const int64_t *id_len, int64_t n, int64_t *key_len,
                          int64_t *start, int64_t *first_bad);
+
+/* ---- averaged-structure profiles -> per-record column sums (the structure background of a profile input) ----------
+ * compute_background (rnascan.py:440-465) counts the letters of the input records; `load_background` (:468-484) hands it
+ * whatever the structure input is, and for an averaged-structure directory that is no FASTA file: the reference has no
+ * background for its fourth mode.  For profiles the count of letter c is the sum of column c over every row of every
+ * record (the expected number of that letter; for one-hot rows exactly compute_background's count).  These entry points
+ * give the sums PER RECORD, double [n_rec][7] in the profile's column order; the caller adds the records up (math.fsum per
+ * column: exactly rounded, so independent of batches, chunks and ranks) and applies (count + 1) / (7 + sum of counts).
+ * A record's sums depend on that record's rows alone, in a fixed order of fp64 additions anchored at its first row
+ * (float32 rows are widened first): rows in pieces of 2048; in a piece lane t of 256 adds rows t, t + 256, ... in order;
+ * the 64 lanes of each of the four waves are folded as a[i] += a[i + s] for s = 32 .. 1; the waves as
+ * ((w0 + w1) + w2) + w3; the pieces one after the other.  No atomics: the same input gives the same bits on every run.
+ *   rec_off / rec_len  int64 [n_rec]: first row and length of every record, as pack.Stream / store.ProfileStore keep
+ *                them: ascending, every record followed by at least one (separator) row that belongs to no record and
+ *                is not read as data.  A table that breaks this: PFMSCAN_E_BADARG, *first_bad = -1.
+ * Rejection: a cell of a record that is NaN, +-inf or negative makes a background meaningless (the scan itself keeps
+ * accepting such cells, rnascan.py:306 nan_to_num): PFMSCAN_E_BADARG, *first_bad = the flat element index row * 7 +
+ * column of the EARLIEST such cell of the stream; the sums are not to be used.  *first_bad = -1 on success.
+ *
+ * _dev: d_profile (16-byte aligned), the tables and d_sums are device buffers.  Asynchronous on `stream` (NULL: the
+ *   ctx's) except for the verdict: `stream` is synchronised once.  Device scratch (56 bytes per piece) belongs to the ctx.
+ * _host: a host stream of ANY length (a numpy array or a mapped packed store; through the ctx's upload mode, see
+ *   pfmscan_set_upload_mode / pfmscan_upload_source_file) with bounded device scratch: it is cut at record boundaries into
+ *   pieces of at most 2^24 rows (PFMSCAN_COLSUMS_CHUNK in the environment overrides; a longer record is a piece of its
+ *   own), the upload of piece k + 1 runs beside the sums of piece k in two alternating buffers.  Leaves the staged
+ *   stream alone.  sums: host double [n_rec][7].
+ * _staged: the profile that pfmscan_stage / pfmscan_average_stage left on the device; rec_off, rec_len and sums on the
+ *   host. */
+int pfmscan_profile_colsums_dev(pfmscan_ctx *ctx, const void *d_profile, int profile_dtype, int64_t n_pos,
+                                const int64_t *d_rec_off, const int64_t *d_rec_len, int64_t n_rec, double *d_sums,
+                                int64_t *first_bad, void *stream);
+int pfmscan_profile_colsums_host(pfmscan_ctx *ctx, const void *profile, int profile_dtype, int64_t n_pos,
+                                 const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec, double *sums,
+                                 int64_t *first_bad);
+int pfmscan_profile_colsums_staged(pfmscan_ctx *ctx, const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec,
+                                   double *sums, int64_t *first_bad);
 
 /* ---- host ingest and output (no device needed; no context: errors via pfmscan_last_error(NULL)) ---------------
  * The two pieces of host work that dwarf the kernel at scale, in native code.

@@ -22,7 +22,7 @@ NCODE = 8
 NSTRUCT = 7
 MAX_M = 64            # widest PFM of the tuned kernels and of PFM libraries
 MAX_WIDTH = 4096      # widest PFM accepted (wider than MAX_M: the plain rolled-loop kernel)
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 # every symbol include/pfmscan.h declares (checked by tests/test_abi.py)
 SYMBOLS = [
@@ -42,6 +42,7 @@ SYMBOLS = [
     "pfmscan_place_alloc", "pfmscan_place_free", "pfmscan_place_note", "pfmscan_place_trim",
     "pfmscan_dotbracket_annotate_dev", "pfmscan_dotbracket_stage", "pfmscan_dotbracket_annotate_host",
     "pfmscan_average_dev", "pfmscan_average_host", "pfmscan_average_stage", "pfmscan_fragment_ids",
+    "pfmscan_profile_colsums_dev", "pfmscan_profile_colsums_host", "pfmscan_profile_colsums_staged",
 ]
 MAX_COVER = 1024      # largest coverage of a row the averaging accepts
 AVG_OK, AVG_DOTBRACKET, AVG_UNCOVERED, AVG_COVER, AVG_BAD_TABLE = range(5)   # what a rejected averaging names
@@ -151,6 +152,9 @@ def load():
     L.pfmscan_average_stage.argtypes = [vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, i64, vp, i32, i32,
                                         ctypes.POINTER(i64), ctypes.POINTER(i64), ctypes.POINTER(i32)]
     L.pfmscan_fragment_ids.argtypes = [vp, vp, vp, i64, vp, vp, ctypes.POINTER(i64)]
+    L.pfmscan_profile_colsums_dev.argtypes = [vp, vp, i32, i64, vp, vp, i64, vp, ctypes.POINTER(i64), vp]
+    L.pfmscan_profile_colsums_host.argtypes = [vp, vp, i32, i64, vp, vp, i64, vp, ctypes.POINTER(i64)]
+    L.pfmscan_profile_colsums_staged.argtypes = [vp, vp, vp, i64, vp, ctypes.POINTER(i64)]
     L.pfmscan_count_bytes.argtypes = [vp, i64, vp, i32]
     L.pfmscan_place_alloc.argtypes = [vp, i32, vp, vp, i32]
     L.pfmscan_place_free.argtypes = [vp, vp]
@@ -804,6 +808,57 @@ class Context(object):
                                          PROFILE_F32 if np.dtype(dtype) == np.float32 else PROFILE_F64,
                                          ctypes.byref(bad), ctypes.byref(kind), _ptr(stream))
         self._average_check(rc, bad, kind)
+
+    # -- averaged-structure profiles -> per-record column sums -------------------------------------------------
+    def _colsums_check(self, rc, bad):
+        """a rejected cell raises ValueError whose ``element`` attribute is its flat index row * 7 + column"""
+        if rc == E_BADARG and bad.value >= 0:
+            err = ValueError(self._L.pfmscan_last_error(self._h).decode("utf-8", "replace"))
+            err.element = int(bad.value)
+            raise err
+        self._check(rc)
+
+    @staticmethod
+    def _colsums_tables(offsets, lengths):
+        off = np.ascontiguousarray(offsets, dtype=np.int64)
+        ln = np.ascontiguousarray(lengths, dtype=np.int64)
+        if off.ndim != 1 or off.shape != ln.shape:
+            raise ValueError("offsets and lengths must be one-dimensional and of the same size")
+        return off, ln
+
+    def profile_colsums_host(self, profile, offsets, lengths):
+        """per-record column sums, float64 [n_rec][7], of a packed host profile (numpy array or memory map) of any
+        length; see include/pfmscan.h.  ValueError (``.element``) when a record holds a NaN, infinite or negative cell"""
+        off, ln = self._colsums_tables(offsets, lengths)
+        if profile.dtype not in (np.float32, np.float64) or profile.ndim != 2 or profile.shape[1] != NSTRUCT:
+            raise ValueError("profile must be float32 or float64 [n_pos][7]")
+        profile = np.ascontiguousarray(profile)
+        sums = np.zeros((off.size, NSTRUCT), dtype=np.float64)
+        bad = ctypes.c_int64(-1)
+        self._upload_mode_for(profile)
+        rc = self._L.pfmscan_profile_colsums_host(self._h, _ptr(profile), PROFILE_F32 if profile.dtype == np.float32 else PROFILE_F64,
+                                                  profile.shape[0], _ptr(off), _ptr(ln), off.size, _ptr(sums), ctypes.byref(bad))
+        self._colsums_check(rc, bad)
+        return sums
+
+    def profile_colsums_staged(self, offsets, lengths):
+        """the same for the profile that stage() / average_stage() left on the device"""
+        off, ln = self._colsums_tables(offsets, lengths)
+        sums = np.zeros((off.size, NSTRUCT), dtype=np.float64)
+        bad = ctypes.c_int64(-1)
+        rc = self._L.pfmscan_profile_colsums_staged(self._h, _ptr(off), _ptr(ln), off.size, _ptr(sums), ctypes.byref(bad))
+        self._colsums_check(rc, bad)
+        return sums
+
+    def profile_colsums_dev(self, d_profile, dtype, n_pos, d_offsets, d_lengths, n_rec, d_sums, stream=None):
+        """device buffers (raw addresses or objects with data_ptr()); asynchronous on `stream` except for the verdict"""
+        addr = lambda a: None if a is None else (a.data_ptr() if hasattr(a, "data_ptr") else a)   # noqa: E731
+        bad = ctypes.c_int64(-1)
+        rc = self._L.pfmscan_profile_colsums_dev(self._h, _ptr(addr(d_profile)),
+                                                 PROFILE_F32 if np.dtype(dtype) == np.float32 else PROFILE_F64, int(n_pos),
+                                                 _ptr(addr(d_offsets)), _ptr(addr(d_lengths)), int(n_rec), _ptr(addr(d_sums)),
+                                                 ctypes.byref(bad), _ptr(stream))
+        self._colsums_check(rc, bad)
 
     # -- generic-alphabet letter hits in fp64; two code streams ---------------------------------
     def hits_letters_f64_staged(self, motif, thr, capacity=None):

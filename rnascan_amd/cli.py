@@ -16,7 +16,7 @@ import time
 
 import numpy as np
 
-from . import dotbracket, fasta, pack, pssm as pssm_mod, scanner, shard, store, table
+from . import background, dotbracket, fasta, pack, pssm as pssm_mod, scanner, shard, store, table
 
 from . import __version__
 
@@ -44,9 +44,12 @@ def getoptions(argv=None):
     bg_grp = parser.add_argument_group("Background frequency options")
     bg_grp.add_argument("-u", "--uniformbg", action="store_true", default=False, dest="uniform_background",
                         help=("Use uniform background for calculating log-odds [%(default)s]. Default is to "
-                              "compute background from input sequences. This option is mutually exclusive with -B."))
+                              "compute background from input sequences. This option is mutually exclusive with -B. "
+                              "(Averaged-structure profiles are covered: their default structure background is the "
+                              "expected letter content of the profiles, summed on the GPU.)"))
     bg_grp.add_argument("-g", "--bgonly", action="store_true", default=False, dest="bgonly",
                         help=("Compute background probabilities from input sequences (STDOUT) and exit. "
+                              "Covers averaged-structure profiles too (-q pfm dir/): the printed dict loads with -B. "
                               "[%(default)s]"))
     bg_grp.add_argument("-b", "--bg_seq", default=None, dest="bg_seq",
                         help="Load file of pre-computed background probabilities for nucleotide sequences")
@@ -427,8 +430,24 @@ def main(argv=None, engine=None, out=None):
             struct_source = fasta.Record("testseq", "", testseq_stack.pop())
         else:
             struct_source = args.fastafiles[0] if seq_type == "SS" else args.fastafiles[1]
-            bg = fasta.load_background(args.bg_struct, args.uniform_background, struct_source, fasta.STRUCT,
-                                       not args.bgonly)
+            if os.path.isdir(struct_source) and not args.bg_struct and not args.uniform_background:
+                # averaged-structure profiles (directory or packed store): the reference has no background for them
+                # (load_background hands the directory to the FASTA reader).  Here: the expected letter content of the
+                # profiles, summed per record on the GPU (background.py).  Several ranks need the process group now: each
+                # sums its own share, the per-record sums are exchanged once, every rank builds the same PSSM.
+                bg_rank, bg_world, bg_dist = _init_distributed(args)
+                try:
+                    bg = background.profile_background(annotation_engine(), struct_source, bg_rank, bg_world, bg_dist,
+                                                       not args.bgonly)
+                except (background.BackgroundError, background.InputError) as e:
+                    if bg_rank == 0:
+                        fasta.eprint(str(e))
+                    sys.exit(1)
+                if args.bgonly and bg_rank != 0:
+                    sys.exit()
+            else:
+                bg = fasta.load_background(args.bg_struct, args.uniform_background, struct_source, fasta.STRUCT,
+                                           not args.bgonly)
         if args.bgonly:
             print(dict(bg), file=out)
             sys.exit()

@@ -51,6 +51,7 @@ struct pfmscan_ctx {
     DevBuf lib_pos, lib_motif, lib_seq, lib_struct, lib_count;   // library scans: sharded hits of the _dev form
     DevBuf db_in, db_out, db_tree, db_part, db_marks, db_tiles, db_flags;   // dot-bracket annotation (pfmscan_dotbracket.hip)
     DevBuf avg_tab, avg_blk, avg_out;           // fragment averaging (pfmscan_average.hip): tables + T, verdicts, host rows
+    DevBuf bg_tab, bg_part, bg_blk, bg_sums;    // profile column sums (pfmscan_background.hip): record tables, piece sums, verdicts, record sums
     DevBuf pipe_codes[2], pipe_profile[2];      // chunked host pipeline: double-buffered chunk of the stream
     hipEvent_t pipe_copied[2] = {nullptr, nullptr}, pipe_scanned[2] = {nullptr, nullptr};
     // host ranges known to be read-only mappings of files (pfmscan_upload_source_file): the staged uploader preads them

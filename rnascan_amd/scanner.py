@@ -120,6 +120,20 @@ class HipEngine(object):
         self._stage(stream)
         return self.ctx.hits_staged(motif, thr_seq, thr_struct)
 
+    def profile_colsums(self, stream):
+        """per-record column sums of ``stream.profile`` -> float64 [n_records][7] (pfmscan_profile_colsums_*): the counts
+        behind the structure background of an averaged-structure input (background.py).  Bit-reproducible: a record's
+        sums depend on its own rows alone.  A stream that is staged is summed where it lies; any other goes through the
+        chunked upload-beside-sum pipeline and leaves the staged stream alone.  ValueError with ``element`` (flat index
+        row * 7 + column) when a record holds a NaN, infinite or negative cell."""
+        if stream.profile is None:
+            raise ValueError("the stream has no profile")
+        if len(stream.offsets) == 0:
+            return np.zeros((0, 7), dtype=np.float64)
+        if self._staged is not None and self._staged[0] is stream and self._staged[1] == self.ctx.scratch_gen:
+            return self.ctx.profile_colsums_staged(stream.offsets, stream.lengths)
+        return self.ctx.profile_colsums_host(stream.profile, stream.offsets, stream.lengths)
+
 
 def _library_hits(self, stream, letter_tables, struct_pssms, thr_seq, thr_struct=None, one_shot=True):
     """hits of EVERY motif of a library in one pass over the stream: letter_tables [n][m][8] or None,

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from conftest import assert_f32_bits_equal, assert_struct_close
+from precision_rules import assert_struct_tight
 from test_gpu_parity import rand_stream, rand_struct_pssm, rand_table
 
 pytestmark = pytest.mark.gpu
@@ -58,6 +59,7 @@ def test_random_single_motif_configurations(ctx, oracle, seed):
         assert_f32_bits_equal(got_seq, want_seq)
     if P is not None:
         assert_struct_close(got_st, want_st)
+        assert_struct_tight(got_st, s.profile, P)
     thr_seq = _threshold(rng, cfg["thr_kind"], want_seq) if T is not None else -np.inf
     thr_st = _threshold(rng, cfg["thr_kind"], want_st) if P is not None else -np.inf
     pos, sq, st = ctx.hits_host(motif, s.codes if T is not None else None, s.profile if P is not None else None,
@@ -68,6 +70,7 @@ def test_random_single_motif_configurations(ctx, oracle, seed):
         assert_f32_bits_equal(sq, want_seq[want_pos])
     if P is not None:
         assert_struct_close(st, want_st[want_pos])
+        assert_struct_tight(st, s.profile, P, positions=pos)
     motif.close()
 
 
@@ -99,4 +102,5 @@ def test_random_library_configurations(ctx, oracle, seed):
             assert_f32_bits_equal(sq[sel], want_seq[k][want_pos])
         if LP is not None:
             assert_struct_close(st[sel], want_st[k][want_pos])
+            assert_struct_tight(st[sel], s.profile, LP[k], positions=pos[sel])
     lib.close()

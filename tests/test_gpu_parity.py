@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from conftest import assert_f32_bits_equal, assert_struct_close
+from precision_rules import assert_struct_tight
 
 pytestmark = pytest.mark.gpu
 
@@ -125,6 +126,7 @@ def test_stream_seqstruct_vs_oracle(ctx, oracle, m, inf_frac):
     got_seq, got_st = ctx.scan_host(motif, s.codes, s.profile)
     assert_f32_bits_equal(got_seq, oracle.stream_seq(s.codes, T))
     assert_struct_close(got_st, oracle.stream_struct(s.profile, P))
+    assert_struct_tight(got_st, s.profile, P)
     motif.close()
 
 
@@ -145,6 +147,7 @@ def test_stream_tail_sizes(ctx, oracle, dtype, n_pos_extra):
         got_seq, got_st = ctx.scan_host(motif, s.codes, s.profile)
         assert_f32_bits_equal(got_seq, oracle.stream_seq(s.codes, T))
         assert_struct_close(got_st, oracle.stream_struct(s.profile, P))
+        assert_struct_tight(got_st, s.profile, P)
     motif.close()
 
 
@@ -584,6 +587,8 @@ def test_fixed_width_profile_kernel_equals_the_generic_one(ctx, oracle, monkeypa
     motif.close()
     assert np.array_equal(fixed_st.view(np.uint64), gen_st.view(np.uint64))
     assert_struct_close(fixed_st, oracle.stream_struct(s.profile, P))
+    assert_struct_tight(fixed_st, s.profile, P)
+    assert_struct_tight(fixed_hits[2], s.profile, P, positions=fixed_hits[0])
     if has_seq:
         assert np.array_equal(fixed_seq.view(np.uint32), gen_seq.view(np.uint32))
         assert_f32_bits_equal(fixed_seq, oracle.stream_seq(s.codes, T))

@@ -7,6 +7,7 @@ import pytest
 from hypothesis import HealthCheck, given, settings, strategies as st
 
 from conftest import assert_f32_bits_equal, assert_struct_close
+from precision_rules import assert_struct_tight
 from rnascan_amd import pack
 
 pytestmark = pytest.mark.gpu
@@ -56,12 +57,14 @@ def test_random_streams_match_the_oracle(ctx, oracle, case):
     got_seq, got_st = ctx.scan_host(motif, s.codes, s.profile)
     assert_f32_bits_equal(got_seq, want_seq)
     assert_struct_close(got_st, want_st)
+    assert_struct_tight(got_st, s.profile, P)
     # combined hits (fused or candidate-then-verify, whichever the library picks) == filtering the oracle scores
     pos, hs, ht = ctx.hits_host(motif, s.codes, s.profile, thr_seq=thr, thr_struct=thr)
     want = oracle.stream_hits(want_seq, want_st, thr, thr)
     assert np.array_equal(pos, want)
     assert_f32_bits_equal(hs, want_seq[want])
     assert_struct_close(ht, want_st[want])
+    assert_struct_tight(ht, s.profile, P, positions=pos)
     # letters only, fp64 out (matrix.py:25-43): exact
     lo = ctx.motif(letter_table=T)
     f64 = ctx.scan_letters_f64_host(lo, s.codes)
@@ -124,5 +127,6 @@ def test_random_libraries_match_the_oracle(ctx, oracle, case):
         assert_f32_bits_equal(sq[sel], w_seq[want])
         if P is not None:
             assert_struct_close(st[sel], w_st[want])
+            assert_struct_tight(st[sel], s.profile, P[k], positions=pos[sel])
         k0 += len(want)
     assert k0 == len(pos)

@@ -89,19 +89,12 @@ int pfmscan_ctx_create(int device, pfmscan_ctx **out)
         delete ctx;
         return fail_hip(nullptr, e, "hipStreamCreate");
     }
-    if (const char *v = std::getenv("PFMSCAN_V")) {
-        int x = std::atoi(v);
-        if (x == 5 || x == 7) ctx->tune.v = x;
-    }
-    if (const char *v = std::getenv("PFMSCAN_DMA")) ctx->tune.dma = std::atoi(v) != 0;
-    if (const char *v = std::getenv("PFMSCAN_ABLATE")) ctx->tune.ablate = std::atoi(v);
     if (const char *v = std::getenv("PFMSCAN_PRIO")) ctx->tune.prio = std::atoi(v) != 0;
     if (const char *v = std::getenv("PFMSCAN_DMA_TAIL")) ctx->tune.dma_whole = std::atoi(v) == 0;
     if (const char *v = std::getenv("PFMSCAN_TWO_PHASE")) ctx->tune.two_phase = std::atoi(v) != 0;
     if (const char *v = std::getenv("PFMSCAN_TILES_PER_BLOCK")) ctx->tune.tiles_per_block = std::max(0, std::min(1024, std::atoi(v)));
     if (const char *v = std::getenv("PFMSCAN_PREFILTER")) ctx->tune.prefilter = std::atoi(v) != 0;
     if (const char *v = std::getenv("PFMSCAN_CREDITS")) ctx->tune.credits = std::atoi(v) != 0;
-    if (const char *v = std::getenv("PFMSCAN_QUAD")) ctx->tune.quad = std::atoi(v) != 0;
     *out = ctx;
     return PFMSCAN_OK;
 }
@@ -207,8 +200,6 @@ int pfmscan_motif_create(pfmscan_ctx *ctx, const double *letter_table, const dou
             if (four && m <= 32) {
                 pair_sums(letter_table, m, mo->h_pairsum);
                 mo->has_pairsum = true;
-                mo->h_quadsum = new (std::nothrow) double[(size_t)((m + 3) / 4) * 256];
-                if (mo->h_quadsum) quad_sums(letter_table, m, mo->h_quadsum);
             }
             if (four) e = hipMalloc((void **)&mo->d_pairs, sizeof(float) * pairs.size());
             if (four && e == hipSuccess) e = hipMemcpy(mo->d_pairs, pairs.data(), sizeof(float) * pairs.size(), hipMemcpyHostToDevice);
@@ -238,8 +229,6 @@ void pfmscan_motif_destroy(pfmscan_motif *mo)
     if (mo->d_letters) (void)hipFree(mo->d_letters);
     if (mo->d_pairs) (void)hipFree(mo->d_pairs);
     if (mo->d_struct) (void)hipFree(mo->d_struct);
-    quad_cache_release(mo->quad_cache);
-    delete[] mo->h_quadsum;
     delete[] mo->h_letters;
     delete mo;
 }
@@ -269,9 +258,6 @@ int pfmscan::check_and_fill(pfmscan_ctx *ctx, const pfmscan_motif *mo, const uin
     a.pair_table = ctx->tune.prefilter ? mo->d_pairs : nullptr;
     a.pair_eps = mo->pair_eps;
     a.h_pairsum = mo->has_pairsum ? mo->h_pairsum : nullptr;
-    a.h_quadsum = mo->h_quadsum;
-    a.d_quad = nullptr;
-    a.quad_cache = &mo->quad_cache;
     a.cred_cache = &mo->cred_cache;
     a.h_letters = mo->h_letters;
     a.cred8_cache = &mo->cred8_cache;
@@ -279,7 +265,6 @@ int pfmscan::check_and_fill(pfmscan_ctx *ctx, const pfmscan_motif *mo, const uin
     a.m = mo->m;
     a.struct_finite = mo->struct_finite;
     a.struct_band = mo->struct_band;
-    a.ablate = ctx->tune.ablate;
     a.prio = ctx->tune.prio;
     a.dma_whole = ctx->tune.dma_whole;
     return PFMSCAN_OK;

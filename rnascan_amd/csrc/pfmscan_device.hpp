@@ -161,6 +161,6 @@ __device__ __forceinline__ void emit_hits_block(const uint32_t passmask, PosF po
     __syncthreads();                                   // hb_* may be reused by the next call
 }
 
-constexpr int WQ_CAP = 256;                           // hits a wave can park (k_letters_pre / _cred / _quad)
+constexpr int WQ_CAP = 256;                           // hits a wave can park (k_letters_pre / _cred)
 
 }  // namespace pfmscan

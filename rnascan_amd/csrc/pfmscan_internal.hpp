@@ -23,26 +23,6 @@ struct Cred8Cache {
     uint16_t cr[32 * 8];
 };
 
-// k_letters_quad's credit tables (launch_letters_quad): a small ring of (threshold, device table) slots kept with the motif.
-// A new threshold goes through the slot's PINNED host copy with hipMemcpyAsync on the caller's stream -- no device-wide
-// synchronisation and no blocking copy inside the asynchronous `_dev` entry points; `ready` orders other streams behind
-// the copy, `used` (recorded after the last launch that read the slot) is what a reuse of the slot waits for.
-struct QuadSlot {
-    double thr = __builtin_nan("");
-    uint32_t *d_tab = nullptr;   // device: 256 entries of up to 16 bytes
-    uint32_t *h_tab = nullptr;   // pinned host copy the asynchronous upload reads
-    hipEvent_t ready = nullptr, used = nullptr;
-    hipStream_t last_stream = nullptr;
-    bool many_streams = false;   // launches from more than one stream have read this slot since it was filled
-};
-struct QuadCache {
-    static constexpr int SLOTS = 4;
-    QuadSlot slot[SLOTS];
-    int next = 0;
-    bool unusable = false;       // the motif's four-letter sums hold +inf / NaN: the fp32 prefilter handles it
-};
-void quad_cache_release(QuadCache &qc);      // pfmscan_kernels.hip: frees the slots' memory and events
-
 struct ScanArgs {
     const uint8_t *codes;        // [n_pos] device, may be null when the motif has no letter table
     const void *profile;         // [n_pos][7] float or double, device, may be null
@@ -56,9 +36,6 @@ struct ScanArgs {
     double pair_eps;             // |fp32 pair-table score - exact score| <= pair_eps for every window
     const double *h_pairsum;     // HOST: [(m+1)/2][16] exact two-letter sums (4-letter alphabets): the launcher builds the
                                  // integer credit table of k_letters_cred from them for the call's threshold
-    const double *h_quadsum;     // HOST: [(m+3)/4][256] exact four-letter sums (m <= 32): operand of k_letters_quad's credit table
-    const uint32_t *d_quad;      // DEVICE: the table of the call's threshold (a slot of quad_cache; set by the launcher)
-    QuadCache *quad_cache;       // HOST: owned by the motif
     CredCache *cred_cache;       // HOST: owned by the motif
     const uint8_t *codes2;       // two-FASTA combined scan fused into k_letters_cred: the second code stream (device) or null
     const double *letter_table2; // ... and its letter table [m][8] (device); hits then need seq > thr_seq AND letters2 > thr_struct
@@ -87,7 +64,6 @@ struct ScanArgs {
                                      // b & (hit_shards-1), i.e. to slots [shard*capacity, (shard+1)*capacity)
     int prio;                    // k_profile: staging instructions at raised wave priority (Tuning::prio)
     int dma_whole;               // k_profile: the last LDS-DMA piece of a region in full (Tuning::dma_whole; default: only the lanes with needed bytes)
-    int ablate;                  // timing diagnostics (PFMSCAN_ABLATE): 1 no scoring, 2 no staging, 4 no output
     int64_t pos_offset;          // added to every reported hit position (chunked host pipeline: position of the chunk in the stream)
 };
 
@@ -97,21 +73,14 @@ constexpr int HIT_COUNTER_STRIDE = 16;   // one 128-byte line per shard counter
 constexpr int HIT_SHARDS = 32;           // shards of the ctx-owned hit / candidate buffers
 
 struct Tuning {
-    int v = 5;              // windows per thread in k_profile: 5 or 7 (odd: conflict-free LDS rows)
-    int dma = 1;            // k_profile: stage the tile with LDS-DMA (global_load_lds, 2.34 ms on C3) instead of
-                            // through registers (2.51 ms)
     int prio = 1;           // k_profile: s_setprio 3 while a new workgroup issues its tile's loads (PFMSCAN_PRIO=0: off)
     int dma_whole = 0;      // PFMSCAN_DMA_TAIL=0: 1
-    int ablate = 0;         // see ScanArgs::ablate; results are WRONG when non-zero
     int prefilter = 1;      // hits over 4-letter alphabets: fp32 two-letter prefilter, exact fp64 re-score of survivors
     int tiles_per_block = 0; // k_letters_pre: 0 = pick from the stream length; > 0 forces it (PFMSCAN_TILES_PER_BLOCK, tests)
     int n_cu = 256;         // compute units of the ctx's device (set at ctx creation): sizes the grids of the tile-walking kernels
     int two_phase = 1;      // combined hits through the host/staged API: letters first, structure only at candidates
     int credits = 1;        // hits over 4-letter alphabets, m <= 32: integer position-keyed prefilter (k_letters_cred) instead of
                             // the fp32 one (k_letters_pre); PFMSCAN_CREDITS=0 for A/B runs and tests
-    int quad = 0;           // PFMSCAN_QUAD=1: FOUR-letter credit tables (k_letters_quad) instead -- a third of the VALU instructions,
-                            // but its 256-entry look-ups are lane-random over all LDS banks: measured 8-25 % SLOWER at every width
-                            // (profiles/r3/ab_single_motif_hits_kernels.txt); kept for that A/B and covered by the parity tests
 };
 
 hipError_t launch_scan(const ScanArgs &a, const Tuning &t, hipStream_t stream, const char **what);
@@ -150,7 +119,6 @@ inline hipError_t allow_dynamic_lds(const void *kern, std::atomic<uint64_t> &don
 // window cannot be a hit.  Returns the one-sided slack in score units (inf: no prefilter possible).  Host code.
 double build_credits(const double *pairsum, int npair, double thr, uint16_t *out, int bits = 16, int nent = 16);
 void pair_sums(const double *letter_table, int m, double *out);      // [m][8] -> [ceil(m/2)][16]
-void quad_sums(const double *letter_table, int m, double *out);      // [m][8] -> [ceil(m/4)][256] four-letter sums
 
 // Second phase of the candidate-then-verify combined scan: structure score of the windows
 // listed in cand_pos[0 .. min(*cand_count, cand_cap)) (hits of a letters-only pass, whose

@@ -80,9 +80,9 @@ __global__ __launch_bounds__(BLOCK) void k_letters(const ScanArgs a)
     const int64_t n_pos = a.n_pos;
     const int64_t tile0 = (int64_t)blockIdx.x * LET_TILE;
     CodeStage<LET_TILE> cs;
-    if (!(a.ablate & 2)) cs.fetch(a.codes, tile0, n_pos);
+    cs.fetch(a.codes, tile0, n_pos);
     for (int i = threadIdx.x; i < m * 8; i += BLOCK) tbl[i] = a.letter_table[i];
-    if (!(a.ablate & 2)) cs.park(cbuf);
+    cs.park(cbuf);
     __syncthreads();
 
     OUT_T *__restrict__ out = reinterpret_cast<OUT_T *>(sizeof(OUT_T) == 4 ? (void *)a.out_seq : (void *)a.out_letters_f64);
@@ -158,16 +158,12 @@ __global__ __launch_bounds__(BLOCK) void k_letters(const ScanArgs a)
                 if ((pbase + it * (BLOCK * W) + v < n_pos) && (cmp > a.thr_seq)) mask |= 1u << (W * it + v);
             }
         }
-        if (a.ablate & 8) {                 // timing diagnostic: no hit emission at all
-            if (mask == 0xdeadbeefu) a.hit_pos[0] = pbase;
-            return;
-        }
         emit_hits_block<ROUNDS * W>(
             mask, [&](int i) { return pbase + (int64_t)(i / W) * (BLOCK * W) + (i % W); },
             [&](int i) { return (float)res[i / W][i % W]; }, [&](int i) { return res[i / W][i % W]; }, a);
         return;
     }
-    if (W == 8 && sizeof(OUT_T) == 4 && !(a.ablate & 4)) {
+    if (W == 8 && sizeof(OUT_T) == 4) {
         // 8 windows per thread: transpose through a wave-private LDS strip so that every store
         // instruction still writes 1 KiB contiguous (LDS operations of one wave execute in order)
         __shared__ __align__(16) float strip[BLOCK / 64][64 * 8];
@@ -206,9 +202,7 @@ __global__ __launch_bounds__(BLOCK) void k_letters(const ScanArgs a)
         for (int h = 0; h < W / 4; ++h) {
             const int64_t p0 = tile0 + (int64_t)it * (BLOCK * W) + (int64_t)threadIdx.x * W + 4 * h;
             const double *r4 = &res[it][4 * h];
-            if (a.ablate & 4) {
-                if (r4[0] + r4[1] + r4[2] + r4[3] == 1.2345e300) out[0] = (OUT_T)r4[0];
-            } else if (sizeof(OUT_T) == 4) {
+            if (sizeof(OUT_T) == 4) {
                 float *o = reinterpret_cast<float *>(out) + p0;
                 if (p0 + 4 <= n_pos) {
                     f32x4 r = {(float)r4[0], (float)r4[1], (float)r4[2], (float)r4[3]};
@@ -689,223 +683,6 @@ __global__ __launch_bounds__(BLOCK) void k_letters_cred(const ScanArgs a, const 
 }
 
 // ---------------------------------------------------------------------------
-// k_letters_quad -- k_letters_cred with FOUR-letter credit tables (PFMs up to width 32, 4-letter alphabet, finite threshold).
-//
-// k_letters_cred is VALU-issue bound (14 instructions per window at w = 8: one table look-up per POSITION, but every
-// look-up brings ceil(m/2)/2 dwords to add, and every position's index costs three bit operations).  Here a table
-// entry covers four motif positions: entry[idx] for the 4-mer idx = c0 | c1 << 2 | c2 << 4 | c3 << 6 holds the credit of
-// EVERY quad row t (motif positions 4t .. 4t+3), two rows per dword, ceil(m/4) rows in all (host: quad_sums +
-// build_credits, same one-sided rounding, threshold folded into row 0, "may be a hit" = bit 15 of the sum):
-//   * half the rows: w = 8 has TWO, one dword per entry -- sum(w) = lo(e[w]) + hi(e[w + 4]) is ONE v_add (SDWA), nothing
-//     to accumulate; wider PFMs add one dword per 8 motif positions (PK[w] = sum_s dword_s(e[w + 8 s + 4]),
-//     sum(w) = hi(PK[w]) + lo(PK[w - 4]));
-//   * the index of the 4-mer at byte position q is ONE v_dot4_u32_u8 of the (pre-scaled) code bytes with the weights
-//     1, 4, 16, 64 -- plus one v_alignbyte when q is not dword aligned -- and arrives already multiplied by the entry size;
-//   * fewer rows also mean finer credits: V = 32767 / (rows - 1) levels, the prefilter keeps next to nothing but hits.
-// The table is 256 entries of 4 / 8 / 16 bytes (1-4 KB of LDS, look-ups lane-random over all banks).  Survivors and hits:
-// as in k_letters_cred (wave-private LDS queues, exact fp64 re-score 64 at a time, one returning atomic per flush).
-// ---------------------------------------------------------------------------
-template <int NQ> struct QuadEntry { typedef u32x4 type; };          // 5..8 quad rows: 16-byte entries
-template <> struct QuadEntry<4> { typedef u32x2 type; };
-template <> struct QuadEntry<3> { typedef u32x2 type; };
-template <> struct QuadEntry<2> { typedef uint32_t type; };
-template <> struct QuadEntry<1> { typedef uint32_t type; };
-
-template <int NQ>
-__global__ __launch_bounds__(BLOCK) void k_letters_quad(const ScanArgs a)
-{
-    constexpr int W = 16;                              // windows per lane = one round per tile
-    constexpr int LET_TILE = BLOCK * W;
-    constexpr int ND = (NQ + 1) / 2;                   // dwords of an entry that carry credits
-    constexpr int ESH = NQ <= 2 ? 2 : (NQ <= 4 ? 3 : 4);   // log2 of the entry size in bytes
-    constexpr int NPOS = W + 4 * (NQ - 1);             // positions a lane looks up: q = 0 .. W + 4 NQ - 5
-    constexpr int NWD = (NPOS + 3 + 3) / 4;            // code dwords holding bytes 0 .. NPOS + 2 (the 4-mer at q ends at q + 3)
-    constexpr int TROWS = NQ <= 4 ? 16 : 32;           // rows of the exact letter table (rows m .. are zeros)
-    constexpr int NWAVE = BLOCK / 64;
-    typedef typename QuadEntry<NQ>::type entry_t;
-    __shared__ __align__(16) double tbl[TROWS * 8];
-    __shared__ __align__(16) uint32_t qtab[256 << (ESH - 2)];
-    __shared__ __align__(16) uint8_t cbuf[2][LET_TILE + CODE_HALO];
-    __shared__ int64_t q_pos[NWAVE][WQ_CAP];
-    __shared__ float q_sc[NWAVE][WQ_CAP];
-    __shared__ int q_n[NWAVE], snap[2][NWAVE];
-    __shared__ unsigned long long s_base;
-    __shared__ int64_t sv_pos[NWAVE][128];             // survivors of the prefilter waiting for their exact score
-    const int m = a.m;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t n_pos = a.n_pos;
-    const int ntile = a.tiles_per_block;
-    const int64_t first = (int64_t)blockIdx.x * ntile * LET_TILE;
-    if (first >= n_pos) return;                        // whole workgroup
-
-    CodeStage<LET_TILE> cs;
-    cs.fetch(a.codes, first, n_pos);
-    // rows m .. are zeros: x + 0.0 == x for every x a sum that started at +0.0 can hold (never -0.0)
-    for (int i = threadIdx.x; i < TROWS * 8; i += BLOCK) tbl[i] = i < m * 8 ? a.letter_table[i] : 0.0;
-    for (int i = threadIdx.x; i < (256 << (ESH - 2)); i += BLOCK) qtab[i] = a.d_quad[i];
-    if (threadIdx.x < NWAVE) q_n[threadIdx.x] = 0;
-    cs.park(cbuf[0]);
-    if (ntile > 1 && first + LET_TILE < n_pos) cs.fetch(a.codes, first + LET_TILE, n_pos);
-    __syncthreads();
-
-    const char *qbytes = (const char *)qtab;
-    const int shard = blockIdx.x & (a.hit_shards - 1);
-    const unsigned long long shard_off = (unsigned long long)shard * (unsigned long long)a.capacity;
-    unsigned long long *counter = a.hit_count + shard * HIT_COUNTER_STRIDE;
-    int64_t *my_pos = q_pos[wave];
-    float *my_sc = q_sc[wave];
-
-    auto store_hit = [&](unsigned long long slot, int64_t pos, float sc) {
-        if ((int64_t)slot < a.capacity) {             // capacity is per shard
-            a.hit_pos[shard_off + slot] = pos + a.pos_offset;
-            if (a.hit_seq) a.hit_seq[shard_off + slot] = sc;
-            if (a.hit_struct) a.hit_struct[shard_off + slot] = (double)sc;
-        }
-    };
-    auto drain = [&](unsigned long long base, int n) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        for (int i = lane; i < n; i += 64) store_hit(base + i, my_pos[i], my_sc[i]);
-        if (lane == 0) q_n[wave] = 0;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-    };
-    auto wave_flush = [&]() {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        const int n = __builtin_amdgcn_readfirstlane(q_n[wave]);
-        if (n == 0) return;
-        unsigned long long base = 0;
-        if (lane == 0) base = atomicAdd(counter, (unsigned long long)n);
-        const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)base), hi = __builtin_amdgcn_readfirstlane((uint32_t)(base >> 32));
-        drain(((unsigned long long)hi << 32) | lo, n);
-    };
-
-    int qn_ub = 0;                                     // wave-uniform upper bound of q_n[wave]
-    int sv_n = 0;                                      // wave-uniform length of the survivor queue (< 64 between windows)
-    int64_t *my_sv = sv_pos[wave];
-    // exact score of survivors [at, at + cnt) of this wave's queue, one per lane (_pwm.c:34-68)
-    auto exact_batch = [&](int at, int cnt) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        if (qn_ub + cnt > WQ_CAP) {                    // room for a hit per lane in the hit queue
-            wave_flush();
-            qn_ub = 0;
-        }
-        qn_ub += cnt;
-        if (lane < cnt) {
-            const int64_t p = my_sv[at + lane];
-            const int64_t al = p & ~(int64_t)3;
-            uint32_t raw[NQ + 1];
-#pragma unroll
-            for (int k = 0; k < NQ + 1; ++k) raw[k] = load_codes4(a.codes, al + 4 * k, n_pos);
-            double sc = 0.0;
-#pragma unroll
-            for (int k = 0; k < NQ; ++k) {
-                const uint32_t cw = __builtin_amdgcn_alignbyte(raw[k + 1], raw[k], (uint32_t)(p & 3));
-#pragma unroll
-                for (int b = 0; b < 4; ++b) sc += tbl[(4 * k + b) * 8 + ((cw >> (8 * b)) & 7u)];      // rows m .. 4 NQ - 1 are zeros
-            }
-            const float f = (float)sc;
-            if ((double)f > a.thr_seq) {
-                const int slot = atomicAdd(&q_n[wave], 1);     // LDS
-                my_pos[slot] = p;
-                my_sc[slot] = f;
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-    };
-    for (int tb = 0; tb < ntile; ++tb) {
-        const int64_t tile0 = first + (int64_t)tb * LET_TILE;
-        if (tile0 >= n_pos) break;                     // uniform; the previous tile flushed (it was the last)
-        const uint8_t *cb = cbuf[tb & 1];
-        const int off0 = threadIdx.x * W;
-        // xs[d] byte k = (code at byte 4d + k, its low two bits) << ESH: a foreign letter or separator looks like one of
-        // the four letters here and is rejected by the exact score (NaN), as in k_letters_cred
-        uint32_t xs[NWD + 1];
-#pragma unroll
-        for (int d = 0; d < NWD + 1; ++d)
-            xs[d] = (*reinterpret_cast<const uint32_t *>(cb + off0 + 4 * d) & 0x03030303u) << ESH;       // inside the halo
-        // one look-up per position; PK[w] in the text above is pk[w + 4] here (w = -4 .. W-1)
-        uint32_t pk[W + 4];
-#pragma unroll
-        for (int i = 0; i < W + 4; ++i) pk[i] = 0u;
-        static_for<0, NPOS>([&](auto qc) __attribute__((always_inline)) {          // q, s2: constant expressions (see k_letters_cred)
-            constexpr int q = decltype(qc)::value;
-            const uint32_t by = (q & 3) ? __builtin_amdgcn_alignbyte(xs[(q >> 2) + 1], xs[q >> 2], (uint32_t)(q & 3)) : xs[q >> 2];
-            const uint32_t off = __builtin_amdgcn_udot4(by, 0x40100401u, 0u, false);      // 4-mer index x entry size
-            uint32_t dw[4] = {0u, 0u, 0u, 0u};
-            if constexpr (ND == 1) {
-                dw[0] = *reinterpret_cast<const entry_t *>(qbytes + off);
-            } else {
-                const entry_t e = *reinterpret_cast<const entry_t *>(qbytes + off);
-                static_for<0, ND>([&](auto sc) __attribute__((always_inline)) { dw[decltype(sc)::value] = e[decltype(sc)::value]; });
-            }
-            static_for<0, ND>([&](auto sc) __attribute__((always_inline)) {
-                constexpr int s2 = decltype(sc)::value;
-                constexpr int wi = q - 8 * s2 - 4;     // rows 2 s2 (lo: window wi + 4) and 2 s2 + 1 (hi: window wi)
-                if constexpr (wi >= -4 && wi <= W - 1) pk[wi + 4] += dw[s2];
-            });
-        });
-        uint32_t sum[W];
-        uint32_t any = 0;
-#pragma unroll
-        for (int v = 0; v < W; ++v) {
-            sum[v] = (pk[v + 4] >> 16) + (pk[v] & 0xFFFFu);
-            any |= sum[v];
-        }
-        // Survivors -> the wave's queue (positions only; windows past the end hold SEP codes and score NaN later)
-        if (__builtin_amdgcn_ballot_w64((any & 0x8000u) != 0)) {
-#pragma unroll
-            for (int v = 0; v < W; ++v) {
-                const bool sv = (sum[v] & 0x8000u) != 0;
-                const unsigned long long sb = __builtin_amdgcn_ballot_w64(sv);
-                if (sb) {                               // wave-uniform
-                    if (sv) my_sv[sv_n + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(sb >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)sb, 0u))] = tile0 + off0 + v;
-                    sv_n += __popcll(sb);
-                    if (sv_n >= 64) {                   // the top 64 get their exact score, the rest stays
-                        exact_batch(sv_n - 64, 64);
-                        sv_n -= 64;
-                    }
-                }
-            }
-        }
-
-        // tile boundary: publish the next tile's codes and this wave's queue length, ONE barrier
-        const bool more = tb + 1 < ntile && tile0 + LET_TILE < n_pos;
-        if (!more && sv_n > 0) {                       // last tile of the workgroup: the waiting survivors, then the final flush
-            exact_batch(0, sv_n);
-            sv_n = 0;
-        }
-        if (more) cs.park(cbuf[(tb + 1) & 1]);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        if (lane == 0) snap[tb & 1][wave] = q_n[wave];
-        __syncthreads();
-        if (tb + 2 < ntile && tile0 + 2 * (int64_t)LET_TILE < n_pos) cs.fetch(a.codes, tile0 + 2 * (int64_t)LET_TILE, n_pos);
-        int nq[NWAVE], total = 0, most = 0, before = 0;
-#pragma unroll
-        for (int k = 0; k < NWAVE; ++k) {
-            nq[k] = snap[tb & 1][k];
-            if (k < wave) before += nq[k];
-            total += nq[k];
-            most = most > nq[k] ? most : nq[k];
-        }
-        qn_ub = nq[wave];
-        if (most >= WQ_CAP / 2 || (!more && total > 0)) {          // uniform: every thread read the same snapshot
-            if (threadIdx.x == 0) s_base = atomicAdd(counter, (unsigned long long)total);
-            __syncthreads();
-            drain(s_base + (unsigned long long)before, nq[wave]);
-            qn_ub = 0;
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------
 // k_profile
 // ---------------------------------------------------------------------------
 // Score V consecutive windows per thread from a staged tile.  The sum over j is
@@ -986,9 +763,9 @@ __device__ __forceinline__ void compute_tile(const PROF_T *prof_lds, const unsig
 }
 
 // one tile per workgroup; overlap comes from several resident workgroups per CU
-// launch bound = the residency the LDS tile allows (4 workgroups/CU at V=5, 3 at V=7)
-template <int V, bool HAS_SEQ, typename PROF_T, bool FINITE, bool HITS, int DMA>
-__global__ __launch_bounds__(BLOCK, (V <= 3 ? 5 : (V <= 5 ? 4 : 3))) void k_profile(const ScanArgs a)
+// launch bound = the residency the LDS tile allows (4 workgroups/CU at V=5)
+template <int V, bool HAS_SEQ, typename PROF_T, bool FINITE, bool HITS>
+__global__ __launch_bounds__(BLOCK, 4) void k_profile(const ScanArgs a)
 {
     using L = ProfileLayout<V, PROF_T>;
     extern __shared__ __align__(16) unsigned char smem[];
@@ -1001,36 +778,22 @@ __global__ __launch_bounds__(BLOCK, (V <= 3 ? 5 : (V <= 5 ? 4 : 3))) void k_prof
     // in flight at once (C3: 2.209 -> 2.198 and 2.215 -> 2.195 ms in two interleaved A/B pairs, profiles/r4/NOTES.md;
     // the same for the stores of a finished wave changed nothing).  PFMSCAN_PRIO=0 turns it off.
     if (a.prio) __builtin_amdgcn_s_setprio(3);
-    if (!(a.ablate & 2)) stage_tile<V, HAS_SEQ, PROF_T, DMA>(a, tile0, smem, m);
+    stage_tile<V, HAS_SEQ, PROF_T>(a, tile0, smem, m);
     if (HAS_SEQ)
         for (int i = threadIdx.x; i < m * 8; i += BLOCK) reinterpret_cast<double *>(tseq_lds)[i] = a.letter_table[i];
     if (a.prio) __builtin_amdgcn_s_setprio(0);
-    if (DMA == 2) dma_wait_all();
+    dma_wait_all();
     __syncthreads();
     const int la = threadIdx.x * V;
     double acc_st[V], acc_sq[V];
-    if (a.ablate & 1) {            // timing diagnostic only (PFMSCAN_ABLATE): skip the scoring loop
-#pragma unroll
-        for (int v = 0; v < V; ++v) {
-            acc_st[v] = (double)reinterpret_cast<const PROF_T *>(smem)[(la + v) * 7];
-            acc_sq[v] = (double)smem[prof_bytes + la + v];
-        }
+    compute_tile<V, HAS_SEQ, PROF_T, FINITE>(reinterpret_cast<const PROF_T *>(smem), smem + prof_bytes, tseq_lds,
+                                             a.struct_pssm, m, la, acc_st, acc_sq);
+    if (HITS) {
+        settle_near<V, PROF_T>(a, reinterpret_cast<const PROF_T *>(smem), la, acc_st);
+        emit_tile_hits<V, HAS_SEQ>(a, tile0, la, acc_st, acc_sq);
     } else {
-        compute_tile<V, HAS_SEQ, PROF_T, FINITE>(reinterpret_cast<const PROF_T *>(smem), smem + prof_bytes, tseq_lds,
-                                                 a.struct_pssm, m, la, acc_st, acc_sq);
-    }
-    if (a.ablate & 4) {            // timing diagnostic only: skip the output path (keep the sums alive)
-        double keep = 0.0;
-#pragma unroll
-        for (int v = 0; v < V; ++v) keep += acc_st[v] + acc_sq[v];
-        if (keep == 1.2345e300) a.out_struct[0] = keep;
-        return;
-    }
-    if (HITS) settle_near<V, PROF_T>(a, reinterpret_cast<const PROF_T *>(smem), la, acc_st);
-    if (HITS || (a.ablate & 8))
-        emit_tile<V, HAS_SEQ, HITS>(a, tile0, la, acc_st, acc_sq, smem);
-    else
         emit_tile_wave<V, HAS_SEQ, PROF_T>(a, tile0, la, acc_st, acc_sq, smem, m);
+    }
 }
 
 // ---------------------------------------------------------------------------
@@ -1203,7 +966,7 @@ hipError_t launch_struct_at(const ScanArgs &a, const int64_t *cand_pos, const fl
 // launchers
 // ---------------------------------------------------------------------------
 // integer position-keyed prefilter (k_letters_cred) for a single 4-letter motif of width <= 32 with a finite threshold;
-// Tiles one workgroup of a tile-walking hits kernel (k_letters_pre / _cred / _quad) takes.  A workgroup pays its table load,
+// Tiles one workgroup of a tile-walking hits kernel (k_letters_pre / _cred) takes.  A workgroup pays its table load,
 // its final flush and its launch once, so more tiles per workgroup are cheaper -- until the grid is only a round or two of
 // the 5-6 workgroups a CU holds (26 KB of LDS each): 32 tiles on C2 = 2290 workgroups = 1.5 rounds of 1536, and the second
 // round ran on a half-empty chip (4.2 resident waves per SIMD on average in the counters).  ~24 workgroups per CU = four
@@ -1287,97 +1050,6 @@ bool launch_letters_cred(const ScanArgs &a, const Tuning &t, hipStream_t stream,
     return true;
 }
 
-// four-letter credit tables (k_letters_quad): the table of the call's threshold is built on the host and kept with the motif in
-// a ring of QuadCache::SLOTS (threshold, device table) slots.  A threshold the ring does not hold takes the oldest slot: its
-// table goes through the slot's pinned host copy with hipMemcpyAsync on the CALLER's stream -- the `_dev` entry points stay
-// asynchronous (no hipDeviceSynchronize, no blocking copy: ADVICE round 4 on the cred8 twin of this code).  Ordering:
-// `ready` (recorded behind the copy) is what launches from other streams wait for; `used` (recorded behind every launch that
-// reads the slot) is what the host waits for before it overwrites the slot -- with a device-wide wait only in the case that
-// launches from several streams have read it, whose completion one event cannot vouch for.
-static std::mutex quad_mu;
-
-void quad_cache_release(QuadCache &qc)
-{
-    for (QuadSlot &s : qc.slot) {
-        if (s.used) (void)hipEventSynchronize(s.used);
-        if (s.d_tab) (void)hipFree(s.d_tab);
-        if (s.h_tab) (void)hipHostFree(s.h_tab);
-        if (s.ready) (void)hipEventDestroy(s.ready);
-        if (s.used) (void)hipEventDestroy(s.used);
-        s = QuadSlot();
-    }
-}
-
-static bool launch_letters_quad(const ScanArgs &a, const Tuning &t, hipStream_t stream, hipError_t *err)
-{
-    if (!(a.hits && !a.f64_hits && a.pair_table && a.h_quadsum && a.quad_cache && a.m <= 32 && t.credits && t.quad && std::isfinite(a.thr_seq)))
-        return false;
-    constexpr int QUAD_TILE = BLOCK * 16;
-    constexpr size_t TAB_BYTES = 256 * 16;
-    const int nq = (a.m + 3) / 4;
-    const int edw = nq <= 2 ? 1 : (nq <= 4 ? 2 : 4);       // dwords per table entry
-    QuadCache &qc = *a.quad_cache;
-    std::lock_guard<std::mutex> lock(quad_mu);
-    if (qc.unusable) return false;
-    QuadSlot *slot = nullptr;
-    for (QuadSlot &s : qc.slot)
-        if (s.d_tab && s.h_tab && s.ready && s.used && s.thr == a.thr_seq) slot = &s;
-    if (!slot) {
-        std::vector<uint16_t> cr((size_t)nq * 256);
-        const double slack = build_credits(a.h_quadsum, nq, a.thr_seq, cr.data(), 16, 256);
-        if (!std::isfinite(slack)) {                       // +inf / NaN four-letter sums: the fp32 prefilter handles those
-            qc.unusable = true;                            // (a property of the motif, not of the threshold)
-            return false;
-        }
-        slot = &qc.slot[qc.next];
-        qc.next = (qc.next + 1) % QuadCache::SLOTS;
-        if (!slot->d_tab || !slot->h_tab || !slot->ready || !slot->used) {     // first use (or an allocation failed half way)
-            slot->thr = __builtin_nan("");
-            if (!slot->d_tab && (*err = hipMalloc((void **)&slot->d_tab, TAB_BYTES)) != hipSuccess) return true;
-            if (!slot->h_tab && (*err = hipHostMalloc((void **)&slot->h_tab, TAB_BYTES, hipHostMallocDefault)) != hipSuccess) return true;
-            if (!slot->ready && (*err = hipEventCreateWithFlags(&slot->ready, hipEventDisableTiming)) != hipSuccess) return true;
-            if (!slot->used && (*err = hipEventCreateWithFlags(&slot->used, hipEventDisableTiming)) != hipSuccess) return true;
-        } else {
-            // the launches that read the old table (and the copy that filled it) must be over before the pinned copy changes
-            *err = slot->many_streams ? hipDeviceSynchronize() : hipEventSynchronize(slot->used);
-            if (*err != hipSuccess) return true;
-        }
-        slot->thr = __builtin_nan("");
-        std::memset(slot->h_tab, 0, TAB_BYTES);
-        for (int i = 0; i < 256; ++i)
-            for (int r = 0; r < nq; ++r) slot->h_tab[(size_t)i * edw + (r >> 1)] |= (uint32_t)cr[(size_t)r * 256 + i] << (16 * (r & 1));
-        if ((*err = hipMemcpyAsync(slot->d_tab, slot->h_tab, (size_t)256 * edw * 4, hipMemcpyHostToDevice, stream)) != hipSuccess) return true;
-        if ((*err = hipEventRecord(slot->ready, stream)) != hipSuccess) return true;
-        if ((*err = hipEventRecord(slot->used, stream)) != hipSuccess) return true;     // (a reuse before any launch waits for the copy)
-        slot->thr = a.thr_seq;
-        slot->last_stream = stream;
-        slot->many_streams = false;
-    } else if (slot->last_stream != stream) {
-        if ((*err = hipStreamWaitEvent(stream, slot->ready, 0)) != hipSuccess) return true;   // the copy ran on another stream
-        slot->many_streams = true;
-        slot->last_stream = stream;
-    }
-    ScanArgs b = a;
-    b.d_quad = slot->d_tab;
-    const int64_t ntiles = (a.n_pos + QUAD_TILE - 1) / QUAD_TILE;
-    b.tiles_per_block = walk_tiles(ntiles, t);
-    if (t.tiles_per_block > 0) b.tiles_per_block = t.tiles_per_block;
-    const unsigned g = (unsigned)((ntiles + b.tiles_per_block - 1) / b.tiles_per_block);
-    switch (nq) {
-    case 1: hipLaunchKernelGGL((k_letters_quad<1>), dim3(g), dim3(BLOCK), 0, stream, b); break;
-    case 2: hipLaunchKernelGGL((k_letters_quad<2>), dim3(g), dim3(BLOCK), 0, stream, b); break;
-    case 3: hipLaunchKernelGGL((k_letters_quad<3>), dim3(g), dim3(BLOCK), 0, stream, b); break;
-    case 4: hipLaunchKernelGGL((k_letters_quad<4>), dim3(g), dim3(BLOCK), 0, stream, b); break;
-    case 5: hipLaunchKernelGGL((k_letters_quad<5>), dim3(g), dim3(BLOCK), 0, stream, b); break;
-    case 6: hipLaunchKernelGGL((k_letters_quad<6>), dim3(g), dim3(BLOCK), 0, stream, b); break;
-    case 7: hipLaunchKernelGGL((k_letters_quad<7>), dim3(g), dim3(BLOCK), 0, stream, b); break;
-    default: hipLaunchKernelGGL((k_letters_quad<8>), dim3(g), dim3(BLOCK), 0, stream, b); break;
-    }
-    *err = hipGetLastError();
-    if (*err == hipSuccess) *err = hipEventRecord(slot->used, stream);
-    return true;
-}
-
 template <int NDW>
 static hipError_t launch_letters_ndw(const ScanArgs &a, const Tuning &t, hipStream_t stream)
 {
@@ -1411,7 +1083,6 @@ static hipError_t launch_letters_ndw(const ScanArgs &a, const Tuning &t, hipStre
 static hipError_t launch_letters(const ScanArgs &a, const Tuning &t, hipStream_t stream)
 {
     hipError_t e = hipSuccess;
-    if (launch_letters_quad(a, t, stream, &e)) return e;     // PFMSCAN_QUAD=1 only: measured slower (profiles/r3/NOTES.md, "tried and dropped")
     if (launch_letters_cred(a, t, stream, &e)) return e;
     if (launch_letters_cred8(a, t, stream, &e)) return e;    // fp64 hits of a generic alphabet at a finite threshold
     if (launch_letters_fixed(a, stream, &e)) return e;       // all float32 scores, widths 2 .. 32: the width is a compile-time constant
@@ -1420,13 +1091,13 @@ static hipError_t launch_letters(const ScanArgs &a, const Tuning &t, hipStream_t
     return launch_letters_ndw<17>(a, t, stream);
 }
 
-template <int V, bool HAS_SEQ, typename PROF_T, bool FINITE, bool HITS, int DMA>
+template <bool HAS_SEQ, typename PROF_T, bool FINITE, bool HITS>
 static hipError_t launch_profile_inst(const ScanArgs &a, hipStream_t stream)
 {
-    using L = ProfileLayout<V, PROF_T>;
+    using L = ProfileLayout<PROFILE_V, PROF_T>;
     const unsigned grid = (unsigned)((a.n_pos + L::TILE - 1) / L::TILE);
     const int lds = L::total(a.m, HAS_SEQ, 1);
-    auto kern = k_profile<V, HAS_SEQ, PROF_T, FINITE, HITS, DMA>;
+    auto kern = k_profile<PROFILE_V, HAS_SEQ, PROF_T, FINITE, HITS>;
     static std::atomic<uint64_t> configured{0};     // per instantiation, one bit per device
     hipError_t e = allow_full_lds(reinterpret_cast<const void *>(kern), configured);
     if (e != hipSuccess) return e;
@@ -1434,28 +1105,23 @@ static hipError_t launch_profile_inst(const ScanArgs &a, hipStream_t stream)
     return hipGetLastError();
 }
 
-template <int V, bool HAS_SEQ, typename PROF_T, int DMA>
+template <bool HAS_SEQ, typename PROF_T>
 static hipError_t launch_profile_v(const ScanArgs &a, hipStream_t stream)
 {
     if (a.hits) {
-        if (a.struct_finite) return launch_profile_inst<V, HAS_SEQ, PROF_T, true, true, DMA>(a, stream);
-        return launch_profile_inst<V, HAS_SEQ, PROF_T, false, true, DMA>(a, stream);
+        if (a.struct_finite) return launch_profile_inst<HAS_SEQ, PROF_T, true, true>(a, stream);
+        return launch_profile_inst<HAS_SEQ, PROF_T, false, true>(a, stream);
     }
-    if (a.struct_finite) return launch_profile_inst<V, HAS_SEQ, PROF_T, true, false, DMA>(a, stream);
-    return launch_profile_inst<V, HAS_SEQ, PROF_T, false, false, DMA>(a, stream);
+    if (a.struct_finite) return launch_profile_inst<HAS_SEQ, PROF_T, true, false>(a, stream);
+    return launch_profile_inst<HAS_SEQ, PROF_T, false, false>(a, stream);
 }
 
 template <bool HAS_SEQ, typename PROF_T>
-static hipError_t launch_profile_t(const ScanArgs &a, const Tuning &t, hipStream_t stream)
+static hipError_t launch_profile_t(const ScanArgs &a, hipStream_t stream)
 {
-    if (t.dma) {
-        hipError_t e = hipSuccess;
-        if (t.v == 5 && launch_profile_fixed(a, stream, &e)) return e;        // a width with an unrolled instantiation (all scores and the fused hits pass)
-        if (t.v == 7) return launch_profile_v<7, HAS_SEQ, PROF_T, 2>(a, stream);
-        return launch_profile_v<5, HAS_SEQ, PROF_T, 2>(a, stream);
-    }
-    if (t.v == 7) return launch_profile_v<7, HAS_SEQ, PROF_T, 0>(a, stream);
-    return launch_profile_v<5, HAS_SEQ, PROF_T, 0>(a, stream);
+    hipError_t e = hipSuccess;
+    if (launch_profile_fixed(a, stream, &e)) return e;        // a width with an unrolled instantiation (all scores and the fused hits pass)
+    return launch_profile_v<HAS_SEQ, PROF_T>(a, stream);
 }
 
 // ---------------------------------------------------------------------------
@@ -1542,14 +1208,10 @@ hipError_t launch_scan(const ScanArgs &a, const Tuning &t, hipStream_t stream, c
     if (!a.struct_pssm) return launch_letters(a, t, stream);
     if (a.out_letters_f64 || a.profile == nullptr) return hipErrorInvalidValue;
     const bool has_seq = a.letter_table != nullptr;
-    if (a.profile_dtype == PFMSCAN_PROFILE_F64) {
-        // fp64-stored profile (strict-parity storage): 56 B per position in LDS,
-        // so the tile is kept at V = 5 (72 KB, two workgroups per CU).
-        Tuning t5 = t;
-        t5.v = 5;
-        return has_seq ? launch_profile_t<true, double>(a, t5, stream) : launch_profile_t<false, double>(a, t5, stream);
-    }
-    return has_seq ? launch_profile_t<true, float>(a, t, stream) : launch_profile_t<false, float>(a, t, stream);
+    // fp64-stored profile (strict-parity storage): 56 B per position in LDS, 72 KB per tile, two workgroups per CU
+    if (a.profile_dtype == PFMSCAN_PROFILE_F64)
+        return has_seq ? launch_profile_t<true, double>(a, stream) : launch_profile_t<false, double>(a, stream);
+    return has_seq ? launch_profile_t<true, float>(a, stream) : launch_profile_t<false, float>(a, stream);
 }
 
 }  // namespace pfmscan

@@ -93,7 +93,7 @@ __global__ __launch_bounds__(BLOCK) void k_letters_fixed(const ScanArgs a)
 // true when a fixed-width instantiation took the scan (all float32 scores of a letters-only motif), result in *err
 bool launch_letters_fixed(const ScanArgs &a, hipStream_t stream, hipError_t *err)
 {
-    if (a.hits || a.struct_pssm || !a.letter_table || !a.codes || !a.out_seq || a.out_letters_f64 || a.ablate) return false;
+    if (a.hits || a.struct_pssm || !a.letter_table || !a.codes || !a.out_seq || a.out_letters_f64) return false;
     if (std::getenv("PFMSCAN_LETTERS_GENERIC")) return false;                  // tests and A/B runs: the width-generic kernel
     constexpr int LET_TILE = BLOCK * 16;
     const unsigned grid = (unsigned)((a.n_pos + LET_TILE - 1) / LET_TILE);

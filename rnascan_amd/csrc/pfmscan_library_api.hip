@@ -45,7 +45,7 @@ struct LibPass {
 
 double pfmscan::build_credits(const double *pairsum, int npair, double thr, uint16_t *out, int bits, int nent)
 {
-    // (written for rows of 16 two-letter sums; `nent` = 256 makes the same rows of FOUR-letter sums: k_letters_quad)
+    // (written for rows of 16 two-letter sums; `nent` = 8 makes the same rows of single letters: k_letters_cred8, k_library8)
     std::fill(out, out + (size_t)npair * nent, (uint16_t)0);
     if (thr == INFINITY) return 0.0;                      // nothing exceeds +inf: all credits 0, the flag bit never set
     const int half = 1 << (bits - 1);                     // the flag bit of a credit sum: 32768 (16-bit) or 512 (10-bit credits)
@@ -103,20 +103,6 @@ void pfmscan::pair_sums(const double *T, int m, double *out)
         for (int c0 = 0; c0 < 4; ++c0)
             for (int c1 = 0; c1 < 4; ++c1)
                 out[t * 16 + (c0 | c1 << 2)] = T[(2 * t) * 8 + c0] + (2 * t + 1 < m ? T[(2 * t + 1) * 8 + c1] : 0.0);
-}
-
-// exact four-letter sums of one letter table [m][8] -> [ceil(m/4)][256], index c0 | c1 << 2 | c2 << 4 | c3 << 6 (positions
-// beyond the width add nothing)
-void pfmscan::quad_sums(const double *T, int m, double *out)
-{
-    const int nq = (m + 3) / 4;
-    for (int t = 0; t < nq; ++t)
-        for (int idx = 0; idx < 256; ++idx) {
-            double v = 0.0;
-            for (int i = 0; i < 4; ++i)
-                if (4 * t + i < m) v += T[(4 * t + i) * 8 + ((idx >> (2 * i)) & 3)];
-            out[t * 256 + idx] = v;
-        }
 }
 
 struct pfmscan_library {
@@ -404,17 +390,6 @@ int pfmscan_debug_library8_credits(const double *letter_table, int m, double thr
     for (int j = 0; j < m; ++j)
         for (int c = 0; c < 8; ++c) r8[(size_t)j * 8 + c] = std::isnan(letter_table[j * 8 + c]) ? -INFINITY : letter_table[j * 8 + c];
     const double s = build_credits(r8.data(), rows, thr, credits, 16, 8);
-    if (slack) *slack = s;
-    return PFMSCAN_OK;
-}
-
-int pfmscan_debug_quad_table(const double *letter_table, int m, double thr_seq, uint16_t *credits, double *slack)
-{
-    if (!letter_table || !credits || m < 1 || m > 32 || std::isnan(thr_seq)) return PFMSCAN_E_BADARG;
-    const int nq = (m + 3) / 4;
-    std::vector<double> qs((size_t)nq * 256);
-    quad_sums(letter_table, m, qs.data());
-    const double s = build_credits(qs.data(), nq, thr_seq, credits, 16, 256);
     if (slack) *slack = s;
     return PFMSCAN_OK;
 }

@@ -9,6 +9,10 @@ namespace pfmscan {
 
 __host__ __device__ constexpr int round_up(int x, int q) { return (x + q - 1) / q * q; }
 
+// Windows per thread of k_profile and k_profile_fixed: 1280-position tiles, four workgroups per CU.  ODD, so that the per-lane
+// LDS row stride (7 * V dwords) is odd and the row reads are free of bank conflicts.
+constexpr int PROFILE_V = 5;
+
 template <int V, typename PROF_T>
 struct ProfileLayout {
     static constexpr int TILE = V * BLOCK;
@@ -82,10 +86,10 @@ __device__ __forceinline__ uint32_t lds_addr(const void *p)
 }
 
 // Stage one tile (profile rows [tile0, tile0+TILE+m-1) and their codes) into an
-// LDS buffer.  Interior tiles: LDS-DMA (DMA) or 16-byte register staging;
+// LDS buffer.  Interior tiles: LDS-DMA (inline asm);
 // tiles that touch the end of the stream: dword loads with zero / SEP fill.
 // Returns nothing; completion is observed by the caller's vmcnt(0) + barrier.
-template <int V, bool HAS_SEQ, typename PROF_T, int DMA>   // DMA: 0 = through registers, 2 = LDS-DMA (inline asm)
+template <int V, bool HAS_SEQ, typename PROF_T>
 __device__ __forceinline__ void stage_tile(const ScanArgs &a, int64_t tile0, unsigned char *buf, int m)
 {
     using L = ProfileLayout<V, PROF_T>;
@@ -98,40 +102,24 @@ __device__ __forceinline__ void stage_tile(const ScanArgs &a, int64_t tile0, uns
     const unsigned char *gsrc = reinterpret_cast<const unsigned char *>(a.profile) + g0;
     const bool interior = (g0 + prof_bytes <= total_bytes) && (!HAS_SEQ || tile0 + code_bytes <= n_pos);
     if (interior) {
-        if (DMA == 2) {
-            // each wave-instruction moves 64 x 16 B into a lane-linear 1-KiB LDS piece
-            const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-            const int npiece = prof_bytes >> 10;
-            const uint32_t base = lds_addr(buf);
-            // only the lanes whose 16 bytes hold rows / letters the tile reads take part in the LAST piece of each region: the
-            // pieces are whole KiB of LDS, the tile needs (TILE + m) rows = 36 176 of 36 864 B and TILE + m of 2 048 code bytes at
-            // w = 12 -- 1.4 KB per tile that the neighbouring tile (on another XCD) requests again (PFMSCAN_DMA_TAIL=0: whole pieces)
-            const int pneed = a.dma_whole ? prof_bytes : (L::TILE + m) * 7 * (int)sizeof(PROF_T);
-            const int cneed = a.dma_whole ? code_bytes : L::TILE + m;
-            for (int pc = wave; pc < npiece; pc += BLOCK / 64)      // pc is wave-uniform: only a region's last piece pays the lane test
-                if (pc + 1 < npiece || (pc << 10) + (lane << 4) < pneed)
-                    dma_issue16(gsrc + ((size_t)pc << 10) + (lane << 4), base + ((uint32_t)pc << 10));
-            if (HAS_SEQ) {
-                const unsigned char *csrc = a.codes + tile0;
-                const int ncp = code_bytes >> 10;
-                for (int pc = wave; pc < ncp; pc += BLOCK / 64)
-                    if (pc + 1 < ncp || (pc << 10) + (lane << 4) < cneed)
-                        dma_issue16(csrc + ((size_t)pc << 10) + (lane << 4), base + (uint32_t)prof_bytes + ((uint32_t)pc << 10));
-            }
-        } else {
-            // register staging, 4 x 16 B per thread in flight per round (measured faster
-            // than issuing all ~9 loads first: 2.68 vs 2.99 ms on C3)
-            const int nch = prof_bytes >> 4;
-            // nontemporal: the stream is read once, keep it out of L2/MALL's way (-8 % on the
-            // no-compute floor, -2 % end to end on C3)
-#pragma unroll 4
-            for (int c = tid; c < nch; c += BLOCK)
-                reinterpret_cast<u32x4 *>(buf)[c] = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(gsrc) + c);
-            if (HAS_SEQ) {
-                const int ncc = code_bytes >> 4;
-                for (int c = tid; c < ncc; c += BLOCK)
-                    reinterpret_cast<uint4 *>(buf + prof_bytes)[c] = reinterpret_cast<const uint4 *>(a.codes + tile0)[c];
-            }
+        // each wave-instruction moves 64 x 16 B into a lane-linear 1-KiB LDS piece
+        const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+        const int npiece = prof_bytes >> 10;
+        const uint32_t base = lds_addr(buf);
+        // only the lanes whose 16 bytes hold rows / letters the tile reads take part in the LAST piece of each region: the
+        // pieces are whole KiB of LDS, the tile needs (TILE + m) rows = 36 176 of 36 864 B and TILE + m of 2 048 code bytes at
+        // w = 12 -- 1.4 KB per tile that the neighbouring tile (on another XCD) requests again (PFMSCAN_DMA_TAIL=0: whole pieces)
+        const int pneed = a.dma_whole ? prof_bytes : (L::TILE + m) * 7 * (int)sizeof(PROF_T);
+        const int cneed = a.dma_whole ? code_bytes : L::TILE + m;
+        for (int pc = wave; pc < npiece; pc += BLOCK / 64)      // pc is wave-uniform: only a region's last piece pays the lane test
+            if (pc + 1 < npiece || (pc << 10) + (lane << 4) < pneed)
+                dma_issue16(gsrc + ((size_t)pc << 10) + (lane << 4), base + ((uint32_t)pc << 10));
+        if (HAS_SEQ) {
+            const unsigned char *csrc = a.codes + tile0;
+            const int ncp = code_bytes >> 10;
+            for (int pc = wave; pc < ncp; pc += BLOCK / 64)
+                if (pc + 1 < ncp || (pc << 10) + (lane << 4) < cneed)
+                    dma_issue16(csrc + ((size_t)pc << 10) + (lane << 4), base + (uint32_t)prof_bytes + ((uint32_t)pc << 10));
         }
     } else {
         const int ndw = prof_bytes >> 2;
@@ -230,64 +218,27 @@ __device__ __forceinline__ void emit_tile_wave(const ScanArgs &a, int64_t tile0,
     }
 }
 
-// outputs of one tile: hits, or LDS transpose + 16-byte coalesced stores.
-// `stage` may alias the tile buffer (callers barrier before and after).
-template <int V, bool HAS_SEQ, bool HITS>
-__device__ __forceinline__ void emit_tile(const ScanArgs &a, int64_t tile0, int la, double (&acc_st)[V], double (&acc_sq)[V],
-                                          unsigned char *stage)
+// hits of one tile: the thread's windows that pass the threshold(s) go through the workgroup's hit scan
+template <int V, bool HAS_SEQ>
+__device__ __forceinline__ void emit_tile_hits(const ScanArgs &a, int64_t tile0, int la, double (&acc_st)[V], double (&acc_sq)[V])
 {
-    constexpr int TILE = V * BLOCK;
-    const int tid = threadIdx.x;
     const int64_t n_pos = a.n_pos;
-    if (tile0 + TILE + a.m > n_pos) {               // workgroup-uniform: only the last tile(s) of the stream
+    if (tile0 + V * BLOCK + a.m > n_pos) {          // workgroup-uniform: only the last tile(s) of the stream
         const double qnan = __longlong_as_double(0x7ff8000000000000ll);
 #pragma unroll
         for (int v = 0; v < V; ++v)
             if (tile0 + la + v + a.m > n_pos) acc_st[v] = qnan;   // window runs past the stream end
     }
-    if (HITS) {
-        uint32_t mask = 0;
-#pragma unroll
-        for (int v = 0; v < V; ++v) {
-            bool pass = (tile0 + la + v < n_pos) && (acc_st[v] > a.thr_struct);
-            if (HAS_SEQ) pass = pass && ((double)(float)acc_sq[v] > a.thr_seq);
-            if (pass) mask |= 1u << v;
-        }
-        emit_hits_block<V>(
-            mask, [&](int i) { return tile0 + la + i; }, [&](int i) { return (float)acc_sq[i]; },
-            [&](int i) { return acc_st[i]; }, a);
-        return;
-    }
-    __syncthreads();                               // every wave is done with the tile
-    float *so = reinterpret_cast<float *>(stage);
-    double *sto = reinterpret_cast<double *>(stage + TILE * 4);
+    uint32_t mask = 0;
 #pragma unroll
     for (int v = 0; v < V; ++v) {
-        if (HAS_SEQ) so[la + v] = (float)acc_sq[v];
-        sto[la + v] = acc_st[v];
+        bool pass = (tile0 + la + v < n_pos) && (acc_st[v] > a.thr_struct);
+        if (HAS_SEQ) pass = pass && ((double)(float)acc_sq[v] > a.thr_seq);
+        if (pass) mask |= 1u << v;
     }
-    __syncthreads();
-    if (HAS_SEQ && a.out_seq) {
-        for (int c = tid; c < TILE / 4; c += BLOCK) {
-            const int64_t p = tile0 + 4 * (int64_t)c;
-            if (p + 4 <= n_pos) {
-                __builtin_nontemporal_store(reinterpret_cast<const f32x4 *>(so)[c], reinterpret_cast<f32x4 *>(a.out_seq + p));
-            } else {
-                for (int e = 0; e < 4; ++e)
-                    if (p + e < n_pos) a.out_seq[p + e] = so[4 * c + e];
-            }
-        }
-    }
-    if (a.out_struct) {
-        for (int c = tid; c < TILE / 2; c += BLOCK) {
-            const int64_t p = tile0 + 2 * (int64_t)c;
-            if (p + 2 <= n_pos) {
-                __builtin_nontemporal_store(reinterpret_cast<const f64x2 *>(sto)[c], reinterpret_cast<f64x2 *>(a.out_struct + p));
-            } else if (p < n_pos) {
-                a.out_struct[p] = sto[2 * c];
-            }
-        }
-    }
+    emit_hits_block<V>(
+        mask, [&](int i) { return tile0 + la + i; }, [&](int i) { return (float)acc_sq[i]; },
+        [&](int i) { return acc_st[i]; }, a);
 }
 
 // allow the kernel all of the CU's 160 KB of LDS (static part included); per device, see allow_dynamic_lds

@@ -8,8 +8,7 @@
 //   * the stager walks the tile's pieces on the scalar unit and leaves the codes as offsets into the letter table, so a letter
 //     look-up needs no address arithmetic (27 + 32); the interior tile's output path addresses LDS and memory by one lane
 //     register + immediates (profiles/fixed_isa/isa_count.md: 708 -> 630 VALU instructions per wave and tile at w = 12).
-// Widths without an instantiation (below 9 rows by measurement, above 18) and register staging run the generic kernel
-// (launch_profile_fixed says no).
+// Widths without an instantiation (below 9 rows by measurement, above 18) run the generic kernel (launch_profile_fixed says no).
 #include <cstdlib>
 #include "pfmscan_profile.hpp"
 
@@ -270,7 +269,7 @@ __global__ __launch_bounds__(BLOCK, 4) void k_profile_fixed(const ScanArgs a)
                                                               la, acc_st, acc_sq);
     if (HITS) {
         settle_near<V, PROF_T>(a, reinterpret_cast<const PROF_T *>(smem), la, acc_st);
-        emit_tile<V, HAS_SEQ, true>(a, tile0, la, acc_st, acc_sq, smem);      // the fused combined filter: seq > thr && struct > thr
+        emit_tile_hits<V, HAS_SEQ>(a, tile0, la, acc_st, acc_sq);      // the fused combined filter: seq > thr && struct > thr
     }
     else if (ends_inside(tile0 + V * BLOCK + MW, a.n_pos))                    // workgroup-uniform: false only for the last tile(s) of the stream
         emit_tile_wave_inside<V, MW, HAS_SEQ, PROF_T>(a, tile0, acc_st, acc_sq, smem);
@@ -281,7 +280,7 @@ __global__ __launch_bounds__(BLOCK, 4) void k_profile_fixed(const ScanArgs a)
 template <int MW, bool HAS_SEQ, typename PROF_T, bool FINITE, bool HITS>
 static hipError_t launch_fixed_inst(const ScanArgs &a, hipStream_t stream, bool *taken)
 {
-    constexpr int V = 5;       // 7 windows per thread (1792-position tiles, 162 VGPRs, 3 workgroups per CU): 2.14-2.16 ms on C3 beside 2.07-2.15
+    constexpr int V = PROFILE_V;
     using L = ProfileLayout<V, PROF_T>;
     const unsigned grid = (unsigned)((a.n_pos + L::TILE - 1) / L::TILE);
     const int lds = L::total(MW, HAS_SEQ, 1);
@@ -327,7 +326,7 @@ static hipError_t launch_fixed_width(const ScanArgs &a, hipStream_t stream, bool
 bool launch_profile_fixed(const ScanArgs &a, hipStream_t stream, hipError_t *err)
 {
     const bool off = std::getenv("PFMSCAN_PROFILE_GENERIC") != nullptr;      // tests and A/B runs: the width-generic kernel
-    if (off || a.ablate || !a.struct_pssm || !a.profile || a.out_letters_f64) return false;
+    if (off || !a.struct_pssm || !a.profile || a.out_letters_f64) return false;
     // C3 with placed arrays, generic / fixed in ms (tools/ab_fixed.sh, three interleaved pairs each, profiles/r4/NOTES.md):
     // w = 6: 2.00 / 1.99, 8: 1.960 / 1.974, 9: 1.990 / 1.976, 10: 2.038 / 1.966, 11: 2.107 / 1.993, 12: 2.188 / 2.052,
     // 16: 2.538 / 2.328, 18: 2.707 / 2.475 -- below nine rows the generic loop's two full rounds of five cost nothing extra

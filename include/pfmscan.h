@@ -20,6 +20,13 @@
  *     host-only entry points (FASTA / profile text / TSV, no ctx) may be called
  *     from any number of threads, their message (pfmscan_last_error(NULL)) is
  *     thread-local.
+ *   - a `_dev` entry point works on the `stream` it is given: its memsets,
+ *     table uploads, count read-backs and helper kernels are issued there.
+ *     A ctx's device scratch and a library's threshold table are per-call
+ *     state, not per-stream state: calls on one ctx or one library must be
+ *     issued in ONE stream order, or be ordered by the caller (an event
+ *     between the streams).  Two streams that run calls of the same ctx side
+ *     by side share its scratch.
  *   - positions are 0-based at this level; rnascan's 1-based inclusive
  *     Start/End (rnascan.py:264-271, :311) are made in the table layer.
  *
@@ -305,7 +312,13 @@ void pfmscan_library_destroy(pfmscan_library *lib);
  * +inf / NaN log-odds sums runs without prefilter); any pointer may be NULL */
 int pfmscan_library_info(const pfmscan_library *lib, int *n_motifs, int *m, int *n_passes,
                          int *motifs_per_pass, double *max_eps);
-/* Device-resident form, asynchronous on `stream`.  Hits in no particular order:
+/* Device-resident form, asynchronous on `stream` WHILE THE THRESHOLDS REPEAT: a
+ * call whose thresholds differ from the previous call's on this library (the
+ * first call included) synchronises `stream` once before it rewrites the
+ * library's threshold and credit tables -- the previous scan may still be
+ * reading them -- and uploads the new ones on `stream`; the scan itself is
+ * asynchronous again.  The same holds for pfmscan_library_hits_letters_dev.
+ * Hits in no particular order:
  *   d_hit_pos int64 [capacity], d_hit_motif int32 [capacity] (motif index 0..n-1),
  *   d_hit_seq float [capacity] or NULL, d_hit_struct double [capacity] or NULL,
  *   d_hit_count: one uint64 (need not be zeroed); afterwards the TOTAL number of hits.  A value
@@ -482,7 +495,8 @@ int pfmscan_dotbracket_annotate_host(pfmscan_ctx *ctx, const uint8_t *in, uint8_
  *   PFMSCAN_AVG_BAD_TABLE   tables that break the rules above: PFMSCAN_E_BADARG, *first_bad = the record
  *   PFMSCAN_AVG_DOTBRACKET  (_host / _stage) an invalid dot-bracket fragment: as pfmscan_dotbracket_annotate_dev,
  *                           *first_bad = the stream position
- * The earliest row wins when several rows are rejected.  n_max <= PFMSCAN_MAX_COVER.
+ * The earliest row wins when several rows are rejected; a broken table (its earliest record) wins over every row, since
+ * rows computed from it mean nothing.  n_max <= PFMSCAN_MAX_COVER.
  *
  * _dev: d_letters = annotated codes whose code IS the column (annotate with map {1, 2, 6, 0, 3, 5, 4}: E H T B L R M ->
  *   B E H L M R T columns); max_len >= every frag_len; all tables and the table of (n_max + 1)(n_max + 2) / 2 doubles are

@@ -172,14 +172,22 @@ __global__ __launch_bounds__(AVG_BLOCK) void k_avg_rows(AvgTables a, const doubl
     if (threadIdx.x == 0) blk[blockIdx.x] = m;
 }
 
-__global__ __launch_bounds__(AVG_VERDICT_BLOCK) void k_avg_verdict(const int64_t *__restrict__ blk, int64_t n,
+// blk[0, n_check) are k_avg_check's keys (records), blk[n_check, n) k_avg_rows' (rows).  A record index and a row index do not
+// compare: rows computed from a broken table mean nothing, so the earliest broken record wins over every row (record 0 with
+// its row 0 left uncovered by a fragment of length 0 used to come out as AVG_UNCOVERED at row 0).
+__global__ __launch_bounds__(AVG_VERDICT_BLOCK) void k_avg_verdict(const int64_t *__restrict__ blk, int64_t n_check, int64_t n,
                                                                    int64_t *__restrict__ verdict)
 {
     __shared__ int64_t sh[AVG_VERDICT_BLOCK];
-    int64_t m = AVG_NONE;
-    for (int64_t i = threadIdx.x; i < n; i += AVG_VERDICT_BLOCK) m = min(m, blk[i]);
-    m = block_min(m, sh);
-    if (threadIdx.x == 0) verdict[0] = m;
+    int64_t mt = AVG_NONE, mr = AVG_NONE;
+    for (int64_t i = threadIdx.x; i < n; i += AVG_VERDICT_BLOCK) {
+        if (i < n_check) mt = min(mt, blk[i]);
+        else mr = min(mr, blk[i]);
+    }
+    mt = block_min(mt, sh);
+    __syncthreads();
+    mr = block_min(mr, sh);
+    if (threadIdx.x == 0) verdict[0] = mt != AVG_NONE ? mt : mr;
 }
 
 // E H T B L R M (the annotation's letter order) -> their columns in B E H L M R T (write_pfm's sorted order)
@@ -228,7 +236,7 @@ int average_rows(pfmscan_ctx *ctx, const AvgTables &a, const double *d_T, int n_
             hipLaunchKernelGGL(k_avg_rows<float>, dim3((unsigned)nb_rows), dim3(AVG_BLOCK), 0, st, a, d_T, n_T, n_max,
                                static_cast<float *>(d_out), blk + nb_check);
     }
-    hipLaunchKernelGGL(k_avg_verdict, dim3(1), dim3(AVG_VERDICT_BLOCK), 0, st, blk, nb_check + nb_rows, verdict);
+    hipLaunchKernelGGL(k_avg_verdict, dim3(1), dim3(AVG_VERDICT_BLOCK), 0, st, blk, nb_check, nb_check + nb_rows, verdict);
     HIP_TRY(ctx, hipGetLastError());
     int64_t v = AVG_NONE;
     HIP_TRY(ctx, hipMemcpyAsync(&v, verdict, sizeof(v), hipMemcpyDeviceToHost, st));

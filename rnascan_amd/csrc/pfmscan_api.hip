@@ -1,5 +1,6 @@
 // pfmscan_api.hip -- the C ABI declared in include/pfmscan.h: contexts, PSSM
 // operands, device-pointer launches, host-buffer staging, error reporting.
+// The thresholded entry points keep their hits in sharded buffers through the helpers of pfmscan_hits.hpp.
 // There is no CPU fallback in this library: without a gfx950 device every
 // entry point fails with PFMSCAN_E_HIP.
 #include <algorithm>
@@ -12,7 +13,7 @@
 #include <string>
 #include <vector>
 
-#include "pfmscan_ctx.hpp"
+#include "pfmscan_hits.hpp"
 
 using namespace pfmscan;
 
@@ -112,9 +113,9 @@ void pfmscan_ctx_destroy(pfmscan_ctx *ctx)
         (void)hipStreamDestroy(ctx->copy_stream);
     }
     for (DevBuf *b : {&ctx->codes, &ctx->profile, &ctx->out_seq, &ctx->out_struct, &ctx->hit_pos,
-                      &ctx->hit_seq, &ctx->hit_struct, &ctx->count, &ctx->table, &ctx->cand_pos, &ctx->cand_seq,
+                      &ctx->hit_seq, &ctx->hit_struct, &ctx->count, &ctx->cand_pos, &ctx->cand_seq,
                       &ctx->cand_count, &ctx->sort_keys_in, &ctx->sort_keys_out, &ctx->sort_vals_in, &ctx->sort_vals_out,
-                      &ctx->sort_temp, &ctx->sort_seq, &ctx->sort_struct, &ctx->hit_motif, &ctx->sort_motif, &ctx->lib_pos,
+                      &ctx->sort_temp, &ctx->sort_seq, &ctx->sort_struct, &ctx->sort_motif, &ctx->lib_pos,
                       &ctx->lib_motif, &ctx->lib_seq, &ctx->lib_struct, &ctx->lib_count, &ctx->pipe_codes[0], &ctx->pipe_codes[1],
                       &ctx->pipe_profile[0], &ctx->pipe_profile[1], &ctx->codes2, &ctx->db_in, &ctx->db_out,
                       &ctx->db_tree, &ctx->db_part, &ctx->db_marks, &ctx->db_tiles, &ctx->db_flags,
@@ -279,71 +280,6 @@ int pfmscan::do_launch(pfmscan_ctx *ctx, const ScanArgs &a, void *stream)
     return PFMSCAN_OK;
 }
 
-// The ctx-owned sharded hit buffers (HIT_SHARDS regions of shard_cap slots, counters in ctx->count) -> the caller's host
-// arrays, sorted by position: capacity check, device sort (pfmscan_sort.hip), three contiguous copies.  Synchronises
-// ctx->stream.  Hit positions lie in [0, n_pos).
-int pfmscan::finish_sorted_hits(pfmscan_ctx *ctx, bool has_seq, bool has_struct, int64_t n_pos, int64_t capacity, int64_t shard_cap,
-                                int64_t *hit_pos, float *hit_seq, double *hit_struct, int64_t *n_hits)
-{
-    int rc;
-    const size_t counter_bytes = (size_t)HIT_SHARDS * HIT_COUNTER_STRIDE * 8;
-    std::vector<unsigned long long> counters((size_t)HIT_SHARDS * HIT_COUNTER_STRIDE);
-    HIP_TRY(ctx, hipMemcpyAsync(counters.data(), ctx->count.p, counter_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    uint64_t total = 0, worst = 0;
-    for (int s = 0; s < HIT_SHARDS; ++s) {
-        total += counters[(size_t)s * HIT_COUNTER_STRIDE];
-        worst = std::max<uint64_t>(worst, counters[(size_t)s * HIT_COUNTER_STRIDE]);
-    }
-    *n_hits = (int64_t)total;
-    if ((int64_t)total > capacity || (int64_t)worst > shard_cap) {
-        // ask for enough that every shard fits next time
-        *n_hits = (int64_t)std::max<uint64_t>(total, worst * HIT_SHARDS);
-        return fail(ctx, PFMSCAN_E_CAPACITY, "hit buffer too small: " + std::to_string(total) + " hits, capacity " + std::to_string(capacity));
-    }
-    if (total == 0) return PFMSCAN_OK;
-    // shards -> one run in position order, on the device (pfmscan_sort.hip); three contiguous copies come back
-    int key_bits = 1;
-    while (key_bits < 63 && ((int64_t)1 << key_bits) < n_pos) ++key_bits;
-    size_t temp_bytes = 0;
-    HIP_TRY(ctx, sort_temp_bytes((int64_t)total, key_bits, &temp_bytes));
-    if ((rc = ensure(ctx, ctx->sort_keys_in, total * 8))) return rc;
-    if ((rc = ensure(ctx, ctx->sort_keys_out, total * 8))) return rc;
-    if ((rc = ensure(ctx, ctx->sort_vals_in, total * 8))) return rc;
-    if ((rc = ensure(ctx, ctx->sort_vals_out, total * 8))) return rc;
-    if ((rc = ensure(ctx, ctx->sort_temp, std::max<size_t>(temp_bytes, 256)))) return rc;
-    if ((rc = ensure(ctx, ctx->sort_seq, total * 4))) return rc;
-    if ((rc = ensure(ctx, ctx->sort_struct, total * 8))) return rc;
-    GatherArgs g;
-    g.hit_pos = (const int64_t *)ctx->hit_pos.p;
-    g.hit_seq = has_seq ? (const float *)ctx->hit_seq.p : nullptr;
-    g.hit_struct = has_struct ? (const double *)ctx->hit_struct.p : nullptr;
-    g.counts = (const unsigned long long *)ctx->count.p;
-    g.shards = HIT_SHARDS;
-    g.shard_cap = shard_cap;
-    g.total = (int64_t)total;
-    g.key_bits = key_bits;
-    g.keys_in = (int64_t *)ctx->sort_keys_in.p;
-    g.keys_out = (int64_t *)ctx->sort_keys_out.p;
-    g.vals_in = (int64_t *)ctx->sort_vals_in.p;
-    g.vals_out = (int64_t *)ctx->sort_vals_out.p;
-    g.temp = ctx->sort_temp.p;
-    g.temp_bytes = ctx->sort_temp.cap;
-    g.seq_out = (float *)ctx->sort_seq.p;
-    g.struct_out = (double *)ctx->sort_struct.p;
-    {
-        hipError_t e = launch_gather_sorted(g, ctx->stream);
-        if (e != hipSuccess) return fail_hip(ctx, e, "gather + sort of the hits");
-    }
-    HIP_TRY(ctx, hipMemcpyAsync(hit_pos, g.keys_out, total * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (hit_seq && has_seq) HIP_TRY(ctx, hipMemcpyAsync(hit_seq, g.seq_out, total * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (hit_struct && has_struct) HIP_TRY(ctx, hipMemcpyAsync(hit_struct, g.struct_out, total * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (hit_seq && !has_seq) std::fill(hit_seq, hit_seq + total, NAN);
-    if (hit_struct && !has_struct) std::fill(hit_struct, hit_struct + total, (double)NAN);
-    return PFMSCAN_OK;
-}
-
 extern "C" {
 
 int pfmscan_scan_dev(pfmscan_ctx *ctx, const pfmscan_motif *mo, const uint8_t *d_codes, const void *d_profile,
@@ -382,6 +318,12 @@ int pfmscan_scan_letters_f64_dev(pfmscan_ctx *ctx, const pfmscan_motif *mo, cons
     return do_launch(ctx, a, stream);
 }
 
+// the caller's device arrays of a _dev form as a sink: one shard of `capacity` slots, the counter zeroed by the caller
+static HitSink dev_sink(int64_t *d_hit_pos, float *d_hit_seq, double *d_hit_struct, uint64_t *d_hit_count, int64_t capacity)
+{
+    return {d_hit_pos, nullptr, d_hit_seq, d_hit_struct, reinterpret_cast<unsigned long long *>(d_hit_count), 1, capacity};
+}
+
 int pfmscan_hits_dev(pfmscan_ctx *ctx, const pfmscan_motif *mo, const uint8_t *d_codes, const void *d_profile,
                      int profile_dtype, int64_t n_pos, double thr_seq, double thr_struct, int64_t capacity,
                      int64_t *d_hit_pos, float *d_hit_seq, double *d_hit_struct, uint64_t *d_hit_count, void *stream)
@@ -392,41 +334,11 @@ int pfmscan_hits_dev(pfmscan_ctx *ctx, const pfmscan_motif *mo, const uint8_t *d
     if (capacity < 0 || !d_hit_count || (capacity > 0 && !d_hit_pos))
         return fail(ctx, PFMSCAN_E_BADARG, "pfmscan_hits_dev: bad hit buffers");
     if (std::isnan(thr_seq) || std::isnan(thr_struct)) return fail(ctx, PFMSCAN_E_BADARG, "NaN threshold");
-    a.hits = 1;
-    a.thr_seq = thr_seq;
-    a.thr_struct = thr_struct;
-    a.capacity = capacity;
-    a.hit_pos = d_hit_pos;
-    a.hit_seq = mo->d_letters ? d_hit_seq : nullptr;
-    a.hit_struct = mo->d_struct ? d_hit_struct : nullptr;
-    a.hit_count = reinterpret_cast<unsigned long long *>(d_hit_count);
-    a.hit_shards = 1;
+    fill_hits(a, dev_sink(d_hit_pos, d_hit_seq, d_hit_struct, d_hit_count, capacity), mo->d_letters != nullptr, mo->d_struct != nullptr, thr_seq, thr_struct);
     return do_launch(ctx, a, stream);
 }
 
 // ---- combined hits, candidate-then-verify ---------------------------------------------
-struct HitSink {                 // where hits go: `shards` regions of `shard_cap` slots, one counter per region
-    int64_t *pos;
-    float *seq;
-    double *st;
-    unsigned long long *count;   // shards counters, HIT_COUNTER_STRIDE words apart (zeroed by the caller)
-    int shards;
-    int64_t shard_cap;
-};
-
-static void fill_sink(ScanArgs &a, const pfmscan_motif *mo, const HitSink &k, double thr_seq, double thr_struct)
-{
-    a.hits = 1;
-    a.thr_seq = thr_seq;
-    a.thr_struct = thr_struct;
-    a.capacity = k.shard_cap;
-    a.hit_pos = k.pos;
-    a.hit_seq = mo->d_letters ? k.seq : nullptr;
-    a.hit_struct = mo->d_struct ? k.st : nullptr;
-    a.hit_count = k.count;
-    a.hit_shards = k.shards;
-}
-
 // One fused pass, or -- when the motif has both parts and the letter threshold is selective --
 // letters pass + structure verification at its hits.  Synchronises `st` when it takes two passes.
 static int hits_core(pfmscan_ctx *ctx, const pfmscan_motif *mo, const ScanArgs &base, double thr_seq, double thr_struct,
@@ -435,7 +347,7 @@ static int hits_core(pfmscan_ctx *ctx, const pfmscan_motif *mo, const ScanArgs &
     const int64_t n_pos = base.n_pos;
     const bool two = allow_two_phase && ctx->tune.two_phase && mo->d_letters && mo->d_struct && !std::isinf(thr_seq) && n_pos > 0;
     ScanArgs fused = base;
-    fill_sink(fused, mo, sink, thr_seq, thr_struct);
+    fill_hits(fused, sink, mo->d_letters != nullptr, mo->d_struct != nullptr, thr_seq, thr_struct);
     if (!two) return do_launch(ctx, fused, st);
     // phase 1: letters only (1 B per position) -> candidates.  Measured on C3 (w = 12): letters pass 0.23 ms,
     // verify ~0.1 ms per 1 M candidates (0.3 % of the windows), fused pass 2.1 ms -> two passes pay while
@@ -443,48 +355,29 @@ static int hits_core(pfmscan_ctx *ctx, const pfmscan_motif *mo, const ScanArgs &
     // A pilot over a prefix of the stream estimates that rate first.
     int rc;
     const int64_t cand_cap = std::max<int64_t>(n_pos / 32, 1024);
-    const int64_t cand_shard_cap = std::min<int64_t>(cand_cap, cand_cap / HIT_SHARDS * 2 + 4096);
-    const size_t cand_slots = (size_t)cand_shard_cap * HIT_SHARDS;
-    const size_t counter_bytes = (size_t)HIT_SHARDS * HIT_COUNTER_STRIDE * 8;
-    if ((rc = ensure(ctx, ctx->cand_pos, cand_slots * 8))) return rc;
-    if ((rc = ensure(ctx, ctx->cand_seq, cand_slots * 4))) return rc;
-    if ((rc = ensure(ctx, ctx->cand_count, counter_bytes))) return rc;
+    const SinkBufs cand = cand_bufs(ctx);
+    HitSink cs;
+    if ((rc = acquire_sink(ctx, cand, HIT_SHARDS, cand_shard_cap(cand_cap), st, cs))) return rc;
     ScanArgs a1 = base;
     a1.struct_pssm = nullptr;
     a1.profile = nullptr;
-    HitSink cs = {(int64_t *)ctx->cand_pos.p, (float *)ctx->cand_seq.p, nullptr, (unsigned long long *)ctx->cand_count.p,
-                  HIT_SHARDS, cand_shard_cap};
-    pfmscan_motif letters_only = *mo;
-    letters_only.d_struct = nullptr;
-    fill_sink(a1, &letters_only, cs, thr_seq, -INFINITY);
-    std::vector<unsigned long long> counters((size_t)HIT_SHARDS * HIT_COUNTER_STRIDE);
-    auto read_counts = [&](uint64_t &total, uint64_t &worst) -> int {
-        HIP_TRY(ctx, hipMemcpyAsync(counters.data(), ctx->cand_count.p, counter_bytes, hipMemcpyDeviceToHost, st));
-        HIP_TRY(ctx, hipStreamSynchronize(st));
-        total = worst = 0;
-        for (int s = 0; s < HIT_SHARDS; ++s) {
-            total += counters[(size_t)s * HIT_COUNTER_STRIDE];
-            worst = std::max<uint64_t>(worst, counters[(size_t)s * HIT_COUNTER_STRIDE]);
-        }
-        return PFMSCAN_OK;
-    };
+    fill_hits(a1, cs, true, false, thr_seq, -INFINITY);
     uint64_t n_cand = 0, worst = 0;
     const int64_t pilot_n = std::max<int64_t>((int64_t)1 << 22, n_pos / 64);
     if (pilot_n < n_pos && !ctx->two_phase_hot) {
         ScanArgs ap = a1;
         ap.n_pos = pilot_n;
-        HIP_TRY(ctx, hipMemsetAsync(ctx->cand_count.p, 0, counter_bytes, st));
         if ((rc = do_launch(ctx, ap, st))) return rc;
-        if ((rc = read_counts(n_cand, worst))) return rc;
+        if ((rc = read_hit_counts(ctx, cs.count, cs.shards, st, n_cand, worst))) return rc;
         if ((int64_t)n_cand * 32 > pilot_n) {                                      // not selective: one fused pass
             ctx->two_phase_hot = false;
             return do_launch(ctx, fused, st);
         }
+        if ((rc = acquire_sink(ctx, cand, HIT_SHARDS, cs.shard_cap, st, cs))) return rc;   // the counters back to zero
     }
-    HIP_TRY(ctx, hipMemsetAsync(ctx->cand_count.p, 0, counter_bytes, st));
     if ((rc = do_launch(ctx, a1, st))) return rc;
-    if ((rc = read_counts(n_cand, worst))) return rc;
-    if ((int64_t)worst > cand_shard_cap) {                                          // pilot under-estimated
+    if ((rc = read_hit_counts(ctx, cs.count, cs.shards, st, n_cand, worst))) return rc;
+    if ((int64_t)worst > cs.shard_cap) {                                            // pilot under-estimated
         ctx->two_phase_hot = false;
         return do_launch(ctx, fused, st);
     }
@@ -493,8 +386,7 @@ static int hits_core(pfmscan_ctx *ctx, const pfmscan_motif *mo, const ScanArgs &
     ctx->two_phase_hot = (int64_t)n_cand * 4 < cand_cap;
     if (n_cand == 0) return PFMSCAN_OK;
     // phase 2: structure score at the candidates only
-    hipError_t e = launch_struct_at(fused, (const int64_t *)ctx->cand_pos.p, (const float *)ctx->cand_seq.p,
-                                    (const unsigned long long *)ctx->cand_count.p, HIT_SHARDS, cand_shard_cap, st);
+    hipError_t e = launch_struct_at(fused, cs.pos, cs.seq, cs.count, cs.shards, cs.shard_cap, st);
     if (e != hipSuccess) return fail_hip(ctx, e, "launch k_struct_at");
     return PFMSCAN_OK;
 }
@@ -510,7 +402,7 @@ int pfmscan_hits_adaptive_dev(pfmscan_ctx *ctx, const pfmscan_motif *mo, const u
     if (capacity < 0 || !d_hit_count || (capacity > 0 && !d_hit_pos)) return fail(ctx, PFMSCAN_E_BADARG, "bad hit buffers");
     if (std::isnan(thr_seq) || std::isnan(thr_struct)) return fail(ctx, PFMSCAN_E_BADARG, "NaN threshold");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HitSink sink = {d_hit_pos, d_hit_seq, d_hit_struct, reinterpret_cast<unsigned long long *>(d_hit_count), 1, capacity};
+    const HitSink sink = dev_sink(d_hit_pos, d_hit_seq, d_hit_struct, d_hit_count, capacity);
     return hits_core(ctx, mo, a, thr_seq, thr_struct, sink, stream ? (hipStream_t)stream : ctx->stream, true);
 }
 
@@ -619,24 +511,12 @@ int pfmscan_hits_staged(pfmscan_ctx *ctx, const pfmscan_motif *mo, double thr_se
     if (n_pos == 0) return PFMSCAN_OK;
     if (capacity > 0 && !hit_pos) return fail(ctx, PFMSCAN_E_BADARG, "hit_pos is NULL");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    // ctx-owned, sharded hit buffers: shard s = workgroup & 31 gets every 32nd tile, so the shards fill
-    // evenly; each has room for 2x its share
-    // (small streams have few workgroups, i.e. few shards in use: there every shard can take everything)
-    const int64_t shard_cap = std::max<int64_t>(std::min<int64_t>(capacity, capacity / HIT_SHARDS * 2 + 4096), 1);
-    const size_t slots = (size_t)shard_cap * HIT_SHARDS;
-    const size_t counter_bytes = (size_t)HIT_SHARDS * HIT_COUNTER_STRIDE * 8;
-    if ((rc = ensure(ctx, ctx->hit_pos, slots * 8))) return rc;
-    if ((rc = ensure(ctx, ctx->hit_seq, slots * 4))) return rc;
-    if ((rc = ensure(ctx, ctx->hit_struct, slots * 8))) return rc;
-    if ((rc = ensure(ctx, ctx->count, counter_bytes))) return rc;
-    HIP_TRY(ctx, hipMemsetAsync(ctx->count.p, 0, counter_bytes, ctx->stream));
+    HitSink sink;
+    if ((rc = acquire_sink(ctx, hit_bufs(ctx), HIT_SHARDS, hit_shard_cap(capacity), ctx->stream, sink))) return rc;
     ScanArgs a;
     if ((rc = check_and_fill(ctx, mo, (const uint8_t *)ctx->codes.p, ctx->profile.p, ctx->staged_dtype, n_pos, a))) return rc;
-    HitSink sink = {(int64_t *)ctx->hit_pos.p, (float *)ctx->hit_seq.p, (double *)ctx->hit_struct.p,
-                    (unsigned long long *)ctx->count.p, HIT_SHARDS, shard_cap};
     if ((rc = hits_core(ctx, mo, a, thr_seq, thr_struct, sink, ctx->stream, true))) return rc;
-    return finish_sorted_hits(ctx, mo->d_letters != nullptr, mo->d_struct != nullptr, n_pos, capacity, shard_cap, hit_pos, hit_seq,
-                              hit_struct, n_hits);
+    return finish_sorted_hits(ctx, sink, mo->d_letters != nullptr, mo->d_struct != nullptr, 0, n_pos, capacity, hit_pos, nullptr, hit_seq, hit_struct, n_hits);
 }
 
 int pfmscan_hits_host(pfmscan_ctx *ctx, const pfmscan_motif *mo, const uint8_t *codes, const void *profile,
@@ -655,7 +535,8 @@ int pfmscan_hits_host(pfmscan_ctx *ctx, const pfmscan_motif *mo, const uint8_t *
 }
 
 // ---- generic-alphabet letter hits in fp64 (structure letter strings: SURVEY 8f N4) ---------------------------
-static int fill_f64_hits(pfmscan_ctx *ctx, const pfmscan_motif *mo, const uint8_t *d_codes, int64_t n_pos, double thr, ScanArgs &a)
+static int fill_f64_hits(pfmscan_ctx *ctx, const pfmscan_motif *mo, const uint8_t *d_codes, int64_t n_pos, double thr, const HitSink &sink,
+                         ScanArgs &a)
 {
     int rc = check_and_fill(ctx, mo, d_codes, nullptr, PFMSCAN_PROFILE_NONE, n_pos, a);
     if (rc) return rc;
@@ -663,10 +544,8 @@ static int fill_f64_hits(pfmscan_ctx *ctx, const pfmscan_motif *mo, const uint8_
     if (std::isnan(thr)) return fail(ctx, PFMSCAN_E_BADARG, "NaN threshold");
     a.struct_pssm = nullptr;
     a.profile = nullptr;
-    a.hits = 1;
     a.f64_hits = 1;
-    a.thr_seq = thr;
-    a.thr_struct = -INFINITY;
+    fill_hits(a, sink, false, true, thr, -INFINITY);      // the fp64 score travels in the structure column
     return PFMSCAN_OK;
 }
 
@@ -674,15 +553,9 @@ int pfmscan_hits_letters_f64_dev(pfmscan_ctx *ctx, const pfmscan_motif *mo, cons
                                  int64_t capacity, int64_t *d_hit_pos, double *d_hit_score, uint64_t *d_hit_count, void *stream)
 {
     ScanArgs a;
-    int rc = fill_f64_hits(ctx, mo, d_codes, n_pos, thr, a);
+    int rc = fill_f64_hits(ctx, mo, d_codes, n_pos, thr, dev_sink(d_hit_pos, nullptr, d_hit_score, d_hit_count, capacity), a);
     if (rc) return rc;
     if (capacity < 0 || !d_hit_count || (capacity > 0 && !d_hit_pos)) return fail(ctx, PFMSCAN_E_BADARG, "pfmscan_hits_letters_f64_dev: bad hit buffers");
-    a.capacity = capacity;
-    a.hit_pos = d_hit_pos;
-    a.hit_seq = nullptr;
-    a.hit_struct = d_hit_score;
-    a.hit_count = reinterpret_cast<unsigned long long *>(d_hit_count);
-    a.hit_shards = 1;
     return do_launch(ctx, a, stream);
 }
 
@@ -699,23 +572,14 @@ int pfmscan_hits_letters_f64_staged(pfmscan_ctx *ctx, const pfmscan_motif *mo, d
     if (n_pos == 0) return PFMSCAN_OK;
     if (capacity > 0 && !hit_pos) return fail(ctx, PFMSCAN_E_BADARG, "hit_pos is NULL");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const int64_t shard_cap = std::max<int64_t>(std::min<int64_t>(capacity, capacity / HIT_SHARDS * 2 + 4096), 1);
-    const size_t slots = (size_t)shard_cap * HIT_SHARDS;
-    const size_t counter_bytes = (size_t)HIT_SHARDS * HIT_COUNTER_STRIDE * 8;
-    if ((rc = ensure(ctx, ctx->hit_pos, slots * 8))) return rc;
-    if ((rc = ensure(ctx, ctx->hit_struct, slots * 8))) return rc;
-    if ((rc = ensure(ctx, ctx->count, counter_bytes))) return rc;
-    HIP_TRY(ctx, hipMemsetAsync(ctx->count.p, 0, counter_bytes, ctx->stream));
+    SinkBufs bufs = hit_bufs(ctx);
+    bufs.seq = nullptr;                                   // no float32 column
+    HitSink sink;
+    if ((rc = acquire_sink(ctx, bufs, HIT_SHARDS, hit_shard_cap(capacity), ctx->stream, sink))) return rc;
     ScanArgs a;
-    if ((rc = fill_f64_hits(ctx, mo, (const uint8_t *)ctx->codes.p, n_pos, thr, a))) return rc;
-    a.capacity = shard_cap;
-    a.hit_pos = (int64_t *)ctx->hit_pos.p;
-    a.hit_seq = nullptr;
-    a.hit_struct = (double *)ctx->hit_struct.p;
-    a.hit_count = (unsigned long long *)ctx->count.p;
-    a.hit_shards = HIT_SHARDS;
+    if ((rc = fill_f64_hits(ctx, mo, (const uint8_t *)ctx->codes.p, n_pos, thr, sink, a))) return rc;
     if ((rc = do_launch(ctx, a, ctx->stream))) return rc;
-    return finish_sorted_hits(ctx, false, true, n_pos, capacity, shard_cap, hit_pos, nullptr, hit_score, n_hits);
+    return finish_sorted_hits(ctx, sink, false, true, 0, n_pos, capacity, hit_pos, nullptr, nullptr, hit_score, n_hits);
 }
 
 int pfmscan_hits_letters_f64_host(pfmscan_ctx *ctx, const pfmscan_motif *mo, const uint8_t *codes, int64_t n_pos, double thr,
@@ -748,9 +612,7 @@ static int pair_core(pfmscan_ctx *ctx, const pfmscan_motif *mo_seq, const pfmsca
     // kernel verifies the second stream for its own survivors (k_letters_cred<.., PAIR>); PFMSCAN_PAIR_TWO_PHASE=1: A/B
     if (!std::getenv("PFMSCAN_PAIR_TWO_PHASE")) {
         ScanArgs f = a1;
-        pfmscan_motif both1 = *mo_seq;
-        both1.d_struct = mo_st->d_letters;
-        fill_sink(f, &both1, sink, thr_seq, thr_struct);
+        fill_hits(f, sink, true, true, thr_seq, thr_struct);
         f.codes2 = d_codes2;
         f.letter_table2 = mo_st->d_letters;
         hipError_t e1 = hipSuccess;
@@ -760,40 +622,22 @@ static int pair_core(pfmscan_ctx *ctx, const pfmscan_motif *mo_seq, const pfmsca
             return PFMSCAN_OK;
         }
     }
-    const size_t counter_bytes = (size_t)HIT_SHARDS * HIT_COUNTER_STRIDE * 8;
-    if ((rc = ensure(ctx, ctx->cand_count, counter_bytes))) return rc;
-    std::vector<unsigned long long> counters((size_t)HIT_SHARDS * HIT_COUNTER_STRIDE);
-    pfmscan_motif letters_only = *mo_seq;
-    letters_only.d_struct = nullptr;
-    int64_t cand_shard_cap = std::max<int64_t>(n_pos / 32 / HIT_SHARDS * 2 + 4096, 1);
+    HitSink cs;
+    int64_t shard_cap = pair_cand_shard_cap(n_pos);
     uint64_t n_cand = 0, worst = 0;
     for (int attempt = 0; attempt < 2; ++attempt) {
-        const size_t cand_slots = (size_t)cand_shard_cap * HIT_SHARDS;
-        if ((rc = ensure(ctx, ctx->cand_pos, cand_slots * 8))) return rc;
-        if ((rc = ensure(ctx, ctx->cand_seq, cand_slots * 4))) return rc;
-        HitSink cs = {(int64_t *)ctx->cand_pos.p, (float *)ctx->cand_seq.p, nullptr, (unsigned long long *)ctx->cand_count.p,
-                      HIT_SHARDS, cand_shard_cap};
+        if ((rc = acquire_sink(ctx, cand_bufs(ctx), HIT_SHARDS, shard_cap, st, cs))) return rc;
         ScanArgs p1 = a1;
-        fill_sink(p1, &letters_only, cs, thr_seq, -INFINITY);
-        HIP_TRY(ctx, hipMemsetAsync(ctx->cand_count.p, 0, counter_bytes, st));
+        fill_hits(p1, cs, true, false, thr_seq, -INFINITY);
         if ((rc = do_launch(ctx, p1, st))) return rc;
-        HIP_TRY(ctx, hipMemcpyAsync(counters.data(), ctx->cand_count.p, counter_bytes, hipMemcpyDeviceToHost, st));
-        HIP_TRY(ctx, hipStreamSynchronize(st));
-        n_cand = worst = 0;
-        for (int s = 0; s < HIT_SHARDS; ++s) {
-            n_cand += counters[(size_t)s * HIT_COUNTER_STRIDE];
-            worst = std::max<uint64_t>(worst, counters[(size_t)s * HIT_COUNTER_STRIDE]);
-        }
-        if ((int64_t)worst <= cand_shard_cap) break;
+        if ((rc = read_hit_counts(ctx, cs.count, cs.shards, st, n_cand, worst))) return rc;
+        if ((int64_t)worst <= shard_cap) break;
         if (attempt == 1) return fail(ctx, PFMSCAN_E_HIP, "candidate counts changed between two identical passes");
-        cand_shard_cap = (int64_t)worst;                    // the same pass again, every shard sized for what it reported
+        shard_cap = (int64_t)worst;                         // the same pass again, every shard sized for what it reported
     }
     if (n_cand == 0) return PFMSCAN_OK;
-    pfmscan_motif both = *mo_seq;                          // fill_sink: which hit arrays exist
-    both.d_struct = mo_st->d_letters;
-    fill_sink(a2, &both, sink, thr_seq, thr_struct);
-    hipError_t e = launch_letters_at(a2, (const int64_t *)ctx->cand_pos.p, (const float *)ctx->cand_seq.p,
-                                     (const unsigned long long *)ctx->cand_count.p, HIT_SHARDS, cand_shard_cap, st);
+    fill_hits(a2, sink, true, true, thr_seq, thr_struct);
+    hipError_t e = launch_letters_at(a2, cs.pos, cs.seq, cs.count, cs.shards, cs.shard_cap, st);
     if (e != hipSuccess) return fail_hip(ctx, e, "launch k_letters_at");
     return PFMSCAN_OK;
 }
@@ -820,7 +664,7 @@ int pfmscan_hits_pair_dev(pfmscan_ctx *ctx, const pfmscan_motif *mo_seq, const p
     if (n_pos == 0) return PFMSCAN_OK;
     if (!d_codes || !d_codes2) return fail(ctx, PFMSCAN_E_BADARG, "codes is NULL");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HitSink sink = {d_hit_pos, d_hit_seq, d_hit_struct, reinterpret_cast<unsigned long long *>(d_hit_count), 1, capacity};
+    const HitSink sink = dev_sink(d_hit_pos, d_hit_seq, d_hit_struct, d_hit_count, capacity);
     return pair_core(ctx, mo_seq, mo_st, d_codes, d_codes2, n_pos, thr_seq, thr_struct, sink, stream ? (hipStream_t)stream : ctx->stream);
 }
 
@@ -857,20 +701,12 @@ int pfmscan_hits_pair_staged(pfmscan_ctx *ctx, const pfmscan_motif *mo_seq, cons
     if (n_pos == 0) return PFMSCAN_OK;
     if (capacity > 0 && !hit_pos) return fail(ctx, PFMSCAN_E_BADARG, "hit_pos is NULL");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const int64_t shard_cap = std::max<int64_t>(std::min<int64_t>(capacity, capacity / HIT_SHARDS * 2 + 4096), 1);
-    const size_t slots = (size_t)shard_cap * HIT_SHARDS;
-    const size_t counter_bytes = (size_t)HIT_SHARDS * HIT_COUNTER_STRIDE * 8;
-    if ((rc = ensure(ctx, ctx->hit_pos, slots * 8))) return rc;
-    if ((rc = ensure(ctx, ctx->hit_seq, slots * 4))) return rc;
-    if ((rc = ensure(ctx, ctx->hit_struct, slots * 8))) return rc;
-    if ((rc = ensure(ctx, ctx->count, counter_bytes))) return rc;
-    HIP_TRY(ctx, hipMemsetAsync(ctx->count.p, 0, counter_bytes, ctx->stream));
-    HitSink sink = {(int64_t *)ctx->hit_pos.p, (float *)ctx->hit_seq.p, (double *)ctx->hit_struct.p,
-                    (unsigned long long *)ctx->count.p, HIT_SHARDS, shard_cap};
+    HitSink sink;
+    if ((rc = acquire_sink(ctx, hit_bufs(ctx), HIT_SHARDS, hit_shard_cap(capacity), ctx->stream, sink))) return rc;
     if ((rc = pair_core(ctx, mo_seq, mo_st, (const uint8_t *)ctx->codes.p, (const uint8_t *)ctx->codes2.p, n_pos, thr_seq, thr_struct,
                         sink, ctx->stream)))
         return rc;
-    return finish_sorted_hits(ctx, true, true, n_pos, capacity, shard_cap, hit_pos, hit_seq, hit_struct, n_hits);
+    return finish_sorted_hits(ctx, sink, true, true, 0, n_pos, capacity, hit_pos, nullptr, hit_seq, hit_struct, n_hits);
 }
 
 int pfmscan_hits_pair_host(pfmscan_ctx *ctx, const pfmscan_motif *mo_seq, const pfmscan_motif *mo_st, const uint8_t *codes,

@@ -42,10 +42,10 @@ struct pfmscan_ctx {
     int64_t hbm = 0;
     char name[128] = {0};
     DevBuf codes2;                              // second code stream of the two-FASTA combined scan (pfmscan_stage_codes2)
-    DevBuf codes, profile, out_seq, out_struct, hit_pos, hit_seq, hit_struct, count, table;
+    DevBuf codes, profile, out_seq, out_struct, hit_pos, hit_seq, hit_struct, count;
     DevBuf cand_pos, cand_seq, cand_count;      // candidates of the two-phase combined scan
     DevBuf sort_keys_in, sort_keys_out, sort_vals_in, sort_vals_out, sort_temp, sort_seq, sort_struct;   // pfmscan_sort.hip
-    DevBuf hit_motif, sort_motif;               // library scans: motif index per hit
+    DevBuf sort_motif;                          // library scans: motif index per hit
     DevBuf lib_pos, lib_motif, lib_seq, lib_struct, lib_count;   // library scans: sharded hits of the _dev form
     DevBuf db_in, db_out, db_tree, db_part, db_marks, db_tiles, db_flags;   // dot-bracket annotation (pfmscan_dotbracket.hip)
     DevBuf avg_tab, avg_blk, avg_out;           // fragment averaging (pfmscan_average.hip): tables + T, verdicts, host rows
@@ -83,12 +83,11 @@ int fail(pfmscan_ctx *ctx, int code, const std::string &msg);
 int fail_hip(pfmscan_ctx *ctx, hipError_t e, const char *what);
 int ensure(pfmscan_ctx *ctx, DevBuf &b, size_t bytes);
 void release(DevBuf &b);
-// pfmscan_api.hip: argument checks + ScanArgs of a scan of DEVICE buffers; launch on a stream; sharded hits -> sorted host arrays
+// pfmscan_api.hip: argument checks + ScanArgs of a scan of DEVICE buffers; launch on a stream (sharded hits -> sorted host
+// arrays: pfmscan_hits.hpp)
 int check_and_fill(pfmscan_ctx *ctx, const pfmscan_motif *mo, const uint8_t *d_codes, const void *d_profile, int profile_dtype,
                    int64_t n_pos, ScanArgs &a);
 int do_launch(pfmscan_ctx *ctx, const ScanArgs &a, void *stream);
-int finish_sorted_hits(pfmscan_ctx *ctx, bool has_seq, bool has_struct, int64_t n_pos, int64_t capacity, int64_t shard_cap,
-                       int64_t *hit_pos, float *hit_seq, double *hit_struct, int64_t *n_hits);
 // pfmscan_upload.hip: asynchronous host -> device copy on `st`; the source may be reused when it returns
 int upload(pfmscan_ctx *ctx, void *d_dst, const void *h_src, size_t bytes, hipStream_t st);
 void upload_release(pfmscan_ctx *ctx);

@@ -1,5 +1,6 @@
 // pfmscan_library_api.hip -- C ABI of the multi-PFM library scan (include/pfmscan.h, "library" section): table
-// construction for k_library (pfmscan_library.hip), passes, hit packing / sorting.
+// construction for k_library (pfmscan_library.hip), passes, hit packing for the _dev form.  The sharded hit buffers, the
+// capacity verdict and the sorted copy home are pfmscan_hits.hpp's, the chunk loop of the pipeline form too.
 //
 // The prefilter of k_library may only DROP windows that cannot be hits.  For motif k with threshold thr and pair rows
 // e_t[idx] (t < npair; exact fp64 sums of two letter log-odds), with hi_t = max finite e_t:
@@ -24,7 +25,7 @@
 #include <string>
 #include <vector>
 
-#include "pfmscan_ctx.hpp"
+#include "pfmscan_hits.hpp"
 
 using namespace pfmscan;
 
@@ -517,21 +518,9 @@ static int lib_set_thresholds(pfmscan_ctx *ctx, pfmscan_library *lib, const doub
 
 constexpr int64_t LIB_SEG = (int64_t)1 << LIB_SEG_SHIFT;        // windows per work segment (segment s -> workgroup s mod grid, shard s mod 256)
 
-static int64_t lib_work_unit(const pfmscan_library *lib);
-
-struct LibSink {
-    int64_t *pos;
-    int32_t *motif;
-    float *seq;
-    double *st;
-    unsigned long long *count;
-    int shards;
-    int64_t shard_cap;
-};
-
 // every pass of the library over [0, n_pos); asynchronous on `st`
 static int lib_run(pfmscan_ctx *ctx, pfmscan_library *lib, const uint8_t *d_codes, const void *d_profile, int profile_dtype,
-                   int64_t n_pos, const LibSink &sink, hipStream_t st, int64_t pos_offset = 0)
+                   int64_t n_pos, const HitSink &sink, hipStream_t st, int64_t pos_offset = 0)
 {
     if (lib->letters8) {
         // generic-alphabet letter library: its passes one after the other (each re-reads only the 1-byte codes)
@@ -703,27 +692,10 @@ static int lib_check(pfmscan_ctx *ctx, const pfmscan_library *lib, const uint8_t
     return PFMSCAN_OK;
 }
 
-static int lib_scratch(pfmscan_ctx *ctx, int64_t capacity, int64_t n_pos, LibSink &sink, int64_t work_unit = LIB_SEG)
+// the ctx's library hit buffers sized for `capacity` hits of a scan of n_pos positions, counters zeroed on `st`
+static int lib_acquire(pfmscan_ctx *ctx, const pfmscan_library *lib, int64_t capacity, int64_t n_pos, hipStream_t st, HitSink &sink)
 {
-    // shard s = workgroup & 255 gets every 256th 16k-window segment: the shards in use fill evenly, each has room for
-    // twice its share (short streams use few shards, small capacities let every shard take everything)
-    const int64_t active = std::max<int64_t>(1, std::min<int64_t>(LIB_SHARDS, (n_pos + work_unit - 1) / work_unit));
-    const int64_t shard_cap = std::max<int64_t>(std::min<int64_t>(capacity, capacity / active * 2 + 1024), 1);
-    const size_t slots = (size_t)shard_cap * LIB_SHARDS;
-    int rc;
-    if ((rc = ensure(ctx, ctx->lib_pos, slots * 8))) return rc;
-    if ((rc = ensure(ctx, ctx->lib_motif, slots * 4))) return rc;
-    if ((rc = ensure(ctx, ctx->lib_seq, slots * 4))) return rc;
-    if ((rc = ensure(ctx, ctx->lib_struct, slots * 8))) return rc;
-    if ((rc = ensure(ctx, ctx->lib_count, (size_t)(LIB_SHARDS + 2) * HIT_COUNTER_STRIDE * 8 + (LIB_SHARDS + 1) * 8))) return rc;
-    sink.pos = (int64_t *)ctx->lib_pos.p;
-    sink.motif = (int32_t *)ctx->lib_motif.p;
-    sink.seq = (float *)ctx->lib_seq.p;
-    sink.st = (double *)ctx->lib_struct.p;
-    sink.count = (unsigned long long *)ctx->lib_count.p;
-    sink.shards = LIB_SHARDS;
-    sink.shard_cap = shard_cap;
-    return PFMSCAN_OK;
+    return acquire_sink(ctx, lib_bufs(ctx), LIB_SHARDS, lib_shard_cap(capacity, n_pos, lib_work_unit(lib)), st, sink);
 }
 
 // ---- sharded hits -> the caller's contiguous device arrays (order unspecified) ----
@@ -790,77 +762,6 @@ __global__ __launch_bounds__(PACK_BLOCK) void k_lib_pack(const int64_t *__restri
 
 }  // namespace pfmscan
 
-// the sharded hits of a library scan -> the caller's host arrays, sorted by (position, motif): capacity check, device
-// sort (pfmscan_sort.hip), contiguous copies.  Synchronises ctx->stream.  Positions lie in [0, n_pos).
-static int lib_finish_sorted(pfmscan_ctx *ctx, pfmscan_library *lib, int64_t n_pos, int64_t capacity, const LibSink &sink,
-                             int64_t *hit_pos, int32_t *hit_motif, float *hit_seq, double *hit_struct, int64_t *n_hits)
-{
-    int rc;
-    hipStream_t st = ctx->stream;
-    const size_t counter_bytes = (size_t)LIB_SHARDS * HIT_COUNTER_STRIDE * 8;
-    std::vector<unsigned long long> counters((size_t)LIB_SHARDS * HIT_COUNTER_STRIDE);
-    HIP_TRY(ctx, hipMemcpyAsync(counters.data(), sink.count, counter_bytes, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    uint64_t total = 0, worst = 0;
-    for (int s = 0; s < LIB_SHARDS; ++s) {
-        total += counters[(size_t)s * HIT_COUNTER_STRIDE];
-        worst = std::max<uint64_t>(worst, counters[(size_t)s * HIT_COUNTER_STRIDE]);
-    }
-    *n_hits = (int64_t)total;
-    if ((int64_t)total > capacity || (int64_t)worst > sink.shard_cap) {
-        *n_hits = (int64_t)std::max<uint64_t>(total, worst * LIB_SHARDS);       // enough that every shard fits next time
-        return lib_fail(ctx, PFMSCAN_E_CAPACITY, "hit buffer too small: " + std::to_string(total) + " hits, capacity " + std::to_string(capacity));
-    }
-    if (total == 0) return PFMSCAN_OK;
-    // shards -> one run ordered by (position, motif) on the device (pfmscan_sort.hip)
-    int key_bits = 1, motif_bits = 1;
-    while (key_bits < 62 && ((int64_t)1 << key_bits) < n_pos) ++key_bits;
-    while (motif_bits < 16 && (1 << motif_bits) < lib->n) ++motif_bits;
-    if (key_bits + motif_bits > 63) return lib_fail(ctx, PFMSCAN_E_BADARG, "stream too long for the (position, motif) sort key");
-    size_t temp_bytes = 0;
-    HIP_TRY(ctx, sort_temp_bytes((int64_t)total, key_bits + motif_bits, &temp_bytes));
-    if ((rc = ensure(ctx, ctx->sort_keys_in, total * 8))) return rc;
-    if ((rc = ensure(ctx, ctx->sort_keys_out, total * 8))) return rc;
-    if ((rc = ensure(ctx, ctx->sort_vals_in, total * 8))) return rc;
-    if ((rc = ensure(ctx, ctx->sort_vals_out, total * 8))) return rc;
-    if ((rc = ensure(ctx, ctx->sort_temp, std::max<size_t>(temp_bytes, 256)))) return rc;
-    if ((rc = ensure(ctx, ctx->sort_seq, total * 4))) return rc;
-    if ((rc = ensure(ctx, ctx->sort_struct, total * 8))) return rc;
-    if ((rc = ensure(ctx, ctx->sort_motif, total * 4))) return rc;
-    GatherArgs g;
-    g.hit_pos = sink.pos;
-    g.hit_seq = lib->has_letters ? sink.seq : nullptr;
-    g.hit_struct = lib->has_struct ? sink.st : nullptr;
-    g.counts = sink.count;
-    g.shards = LIB_SHARDS;
-    g.shard_cap = sink.shard_cap;
-    g.total = (int64_t)total;
-    g.key_bits = key_bits;
-    g.keys_in = (int64_t *)ctx->sort_keys_in.p;
-    g.keys_out = (int64_t *)ctx->sort_keys_out.p;
-    g.vals_in = (int64_t *)ctx->sort_vals_in.p;
-    g.vals_out = (int64_t *)ctx->sort_vals_out.p;
-    g.temp = ctx->sort_temp.p;
-    g.temp_bytes = ctx->sort_temp.cap;
-    g.seq_out = (float *)ctx->sort_seq.p;
-    g.struct_out = (double *)ctx->sort_struct.p;
-    g.hit_motif = sink.motif;
-    g.motif_out = (int32_t *)ctx->sort_motif.p;
-    g.motif_bits = motif_bits;
-    {
-        hipError_t e = launch_gather_sorted(g, st);
-        if (e != hipSuccess) return fail_hip(ctx, e, "gather + sort of the library hits");
-    }
-    HIP_TRY(ctx, hipMemcpyAsync(hit_pos, g.keys_out, total * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipMemcpyAsync(hit_motif, g.motif_out, total * 4, hipMemcpyDeviceToHost, st));
-    if (hit_seq && lib->has_letters) HIP_TRY(ctx, hipMemcpyAsync(hit_seq, g.seq_out, total * 4, hipMemcpyDeviceToHost, st));
-    if (hit_struct && lib->has_struct) HIP_TRY(ctx, hipMemcpyAsync(hit_struct, g.struct_out, total * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    if (hit_struct && !lib->has_struct) std::fill(hit_struct, hit_struct + total, (double)NAN);
-    if (hit_seq && !lib->has_letters) std::fill(hit_seq, hit_seq + total, NAN);
-    return PFMSCAN_OK;
-}
-
 extern "C" {
 
 int pfmscan_library_hits_dev(pfmscan_ctx *ctx, pfmscan_library *lib, const uint8_t *d_codes, const void *d_profile,
@@ -876,12 +777,10 @@ int pfmscan_library_hits_dev(pfmscan_ctx *ctx, pfmscan_library *lib, const uint8
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
     if ((rc = lib_set_thresholds(ctx, lib, thr_seq, thr_struct, st))) return rc;
-    LibSink sink;
-    if ((rc = lib_scratch(ctx, capacity, n_pos, sink, lib_work_unit(lib)))) return rc;
-    const size_t counter_bytes = (size_t)LIB_SHARDS * HIT_COUNTER_STRIDE * 8;
-    HIP_TRY(ctx, hipMemsetAsync(sink.count, 0, counter_bytes, st));
+    HitSink sink;
+    if ((rc = lib_acquire(ctx, lib, capacity, n_pos, st, sink))) return rc;
     if ((rc = lib_run(ctx, lib, d_codes, d_profile, profile_dtype, n_pos, sink, st))) return rc;
-    int64_t *starts = reinterpret_cast<int64_t *>(reinterpret_cast<unsigned char *>(sink.count) + (size_t)(LIB_SHARDS + 2) * HIT_COUNTER_STRIDE * 8);
+    int64_t *starts = lib_starts(sink);
     hipLaunchKernelGGL(k_lib_prefix, dim3(1), dim3(PACK_BLOCK), 0, st, sink.count, LIB_SHARDS, sink.shard_cap, capacity, starts,
                        reinterpret_cast<unsigned long long *>(d_hit_count));
     HIP_TRY(ctx, hipGetLastError());
@@ -918,12 +817,10 @@ int pfmscan_library_hits_staged(pfmscan_ctx *ctx, pfmscan_library *lib, const do
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     if ((rc = lib_set_thresholds(ctx, lib, thr_seq, thr_struct, st))) return rc;
-    LibSink sink;
-    if ((rc = lib_scratch(ctx, capacity, n_pos, sink, lib_work_unit(lib)))) return rc;
-    const size_t counter_bytes = (size_t)LIB_SHARDS * HIT_COUNTER_STRIDE * 8;
-    HIP_TRY(ctx, hipMemsetAsync(sink.count, 0, counter_bytes, st));
+    HitSink sink;
+    if ((rc = lib_acquire(ctx, lib, capacity, n_pos, st, sink))) return rc;
     if ((rc = lib_run(ctx, lib, (const uint8_t *)ctx->codes.p, second, ctx->staged_dtype, n_pos, sink, st))) return rc;
-    return lib_finish_sorted(ctx, lib, n_pos, capacity, sink, hit_pos, hit_motif, hit_seq, hit_struct, n_hits);
+    return finish_sorted_hits(ctx, sink, lib->has_letters, lib->has_struct, lib->n, n_pos, capacity, hit_pos, hit_motif, hit_seq, hit_struct, n_hits);
 }
 
 int pfmscan_library_hits_letters_dev(pfmscan_ctx *ctx, pfmscan_library *lib, const uint8_t *d_codes, const uint8_t *d_codes2,
@@ -953,10 +850,9 @@ int pfmscan_library_hits_letters_host(pfmscan_ctx *ctx, pfmscan_library *lib, co
     return pfmscan_library_hits_staged(ctx, lib, thr_seq, thr_struct, capacity, hit_pos, hit_motif, hit_seq, hit_struct, n_hits);
 }
 
-// The library twin of pfmscan_hits_pipeline_host (pfmscan_pipeline.hip): a HOST-resident stream of any length, chunk by
-// chunk through two alternating device buffers, the upload of chunk k + 1 (copy stream) beside the scan of chunk k.  A chunk
-// holds its positions plus the m - 1 after them, so every window starting inside it sees its letters / rows; windows starting
-// in the overhang run past the buffer's end and are never reported (they belong to the next chunk).
+// The library twin of pfmscan_hits_pipeline_host: a HOST-resident stream of any length through pipeline_chunks
+// (pfmscan_pipeline.hip), every pass of the library over each chunk.  Windows starting in a chunk's overhang run past the
+// buffer's end and are never reported (they belong to the next chunk).
 int pfmscan_library_hits_pipeline_host(pfmscan_ctx *ctx, pfmscan_library *lib, const uint8_t *codes, const void *profile,
                                        int profile_dtype, int64_t n_pos, int64_t chunk_positions, const double *thr_seq,
                                        const double *thr_struct, int64_t capacity, int64_t *hit_pos, int32_t *hit_motif,
@@ -975,50 +871,16 @@ int pfmscan_library_hits_pipeline_host(pfmscan_ctx *ctx, pfmscan_library *lib, c
     chunk_positions = std::max<int64_t>((chunk_positions + LIB_SEG - 1) / LIB_SEG * LIB_SEG, LIB_SEG);    // whole work segments, 16-byte aligned starts
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     ctx->staged_n = -1;                                                      // nothing stays staged
-    const int m = lib->m;
     const size_t row_bytes = lib->has_struct ? (size_t)7 * (profile_dtype == PFMSCAN_PROFILE_F32 ? 4 : 8) : 0;
-    const int64_t buf_positions = std::min<int64_t>(n_pos, chunk_positions + m - 1);
-    if (!ctx->copy_stream) HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
-    for (int i = 0; i < 2; ++i) {
-        if (lib->has_letters && (rc = ensure(ctx, ctx->pipe_codes[i], (size_t)buf_positions))) return rc;
-        if (lib->has_struct && (rc = ensure(ctx, ctx->pipe_profile[i], (size_t)buf_positions * row_bytes))) return rc;
-        if (!ctx->pipe_copied[i]) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->pipe_copied[i], hipEventDisableTiming));
-        if (!ctx->pipe_scanned[i]) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->pipe_scanned[i], hipEventDisableTiming));
-    }
     hipStream_t st = ctx->stream;
     if ((rc = lib_set_thresholds(ctx, lib, thr_seq, thr_struct, st))) return rc;
-    LibSink sink;
-    if ((rc = lib_scratch(ctx, capacity, n_pos, sink, lib_work_unit(lib)))) return rc;
-    const size_t counter_bytes = (size_t)LIB_SHARDS * HIT_COUNTER_STRIDE * 8;
-    HIP_TRY(ctx, hipMemsetAsync(sink.count, 0, counter_bytes, st));          // cleared once: the chunks' hits accumulate
-
-    const int64_t n_chunks = (n_pos + chunk_positions - 1) / chunk_positions;
-    auto upload_chunk = [&](int64_t k) -> int {
-        const int b = (int)(k & 1);
-        const int64_t a0 = k * chunk_positions;
-        const int64_t len = std::min<int64_t>(n_pos - a0, chunk_positions + m - 1);
-        if (k >= 2) HIP_TRY(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->pipe_scanned[b], 0));    // the buffer's previous chunk is scanned
-        if (lib->has_letters)
-            if (int urc = pfmscan::upload(ctx, ctx->pipe_codes[b].p, codes + a0, (size_t)len, ctx->copy_stream)) return urc;
-        if (lib->has_struct)
-            if (int urc = pfmscan::upload(ctx, ctx->pipe_profile[b].p, reinterpret_cast<const unsigned char *>(profile) + (size_t)a0 * row_bytes,
-                                          (size_t)len * row_bytes, ctx->copy_stream))
-                return urc;
-        HIP_TRY(ctx, hipEventRecord(ctx->pipe_copied[b], ctx->copy_stream));
-        return PFMSCAN_OK;
-    };
-    if ((rc = upload_chunk(0))) return rc;
-    for (int64_t k = 0; k < n_chunks; ++k) {
-        const int b = (int)(k & 1);
-        const int64_t a0 = k * chunk_positions;
-        const int64_t len = std::min<int64_t>(n_pos - a0, chunk_positions + m - 1);
-        HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->pipe_copied[b], 0));
-        if ((rc = lib_run(ctx, lib, (const uint8_t *)ctx->pipe_codes[b].p, ctx->pipe_profile[b].p, profile_dtype, len, sink, st, a0))) return rc;
-        HIP_TRY(ctx, hipEventRecord(ctx->pipe_scanned[b], st));
-        if (k + 1 < n_chunks && (rc = upload_chunk(k + 1))) return rc;
-    }
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->copy_stream));
-    return lib_finish_sorted(ctx, lib, n_pos, capacity, sink, hit_pos, hit_motif, hit_seq, hit_struct, n_hits);
+    HitSink sink;                                                            // cleared once: the chunks' hits accumulate
+    if ((rc = lib_acquire(ctx, lib, capacity, n_pos, st, sink))) return rc;
+    rc = pipeline_chunks(ctx, lib->has_letters ? codes : nullptr, profile, row_bytes, n_pos, chunk_positions, lib->m, [&](int b, int64_t a0, int64_t len) -> int {
+        return lib_run(ctx, lib, (const uint8_t *)ctx->pipe_codes[b].p, ctx->pipe_profile[b].p, profile_dtype, len, sink, st, a0);
+    });
+    if (rc) return rc;
+    return finish_sorted_hits(ctx, sink, lib->has_letters, lib->has_struct, lib->n, n_pos, capacity, hit_pos, hit_motif, hit_seq, hit_struct, n_hits);
 }
 
 int pfmscan_library_hits_host(pfmscan_ctx *ctx, pfmscan_library *lib, const uint8_t *codes, const void *profile,

@@ -14,14 +14,56 @@
 // chunk) -- the end-of-stream rule of the kernels does the bookkeeping.  Every chunk is ONE fused hits launch
 // (k_profile / k_letters in hits mode; no count read-back in between), hits go to the ctx's sharded buffers with
 // their stream position (ScanArgs::pos_offset) and are sorted once at the end.  Device scratch: two chunks,
-// whatever the stream length.
+// whatever the stream length.  pipeline_chunks is that loop; the library form (pfmscan_library_hits_pipeline_host,
+// pfmscan_library_api.hip) runs its passes through it too.
 #include <algorithm>
 #include <cmath>
 #include <string>
 
-#include "pfmscan_ctx.hpp"
+#include "pfmscan_hits.hpp"
 
 using namespace pfmscan;
+
+int pfmscan::pipeline_chunks(pfmscan_ctx *ctx, const uint8_t *codes, const void *profile, size_t row_bytes, int64_t n_pos,
+                             int64_t chunk_positions, int m, const std::function<int(int b, int64_t a0, int64_t len)> &scan)
+{
+    int rc;
+    const int64_t buf_positions = std::min<int64_t>(n_pos, chunk_positions + m - 1);
+    if (!ctx->copy_stream) HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
+    for (int i = 0; i < 2; ++i) {
+        if (codes && (rc = ensure(ctx, ctx->pipe_codes[i], (size_t)buf_positions))) return rc;
+        if (row_bytes && (rc = ensure(ctx, ctx->pipe_profile[i], (size_t)buf_positions * row_bytes))) return rc;
+        if (!ctx->pipe_copied[i]) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->pipe_copied[i], hipEventDisableTiming));
+        if (!ctx->pipe_scanned[i]) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->pipe_scanned[i], hipEventDisableTiming));
+    }
+    const int64_t n_chunks = (n_pos + chunk_positions - 1) / chunk_positions;
+    auto upload_chunk = [&](int64_t k) -> int {
+        const int b = (int)(k & 1);
+        const int64_t a0 = k * chunk_positions;
+        const int64_t len = std::min<int64_t>(n_pos - a0, chunk_positions + m - 1);
+        if (k >= 2) HIP_TRY(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->pipe_scanned[b], 0));    // the buffer's previous chunk is scanned
+        if (codes)
+            if (int urc = upload(ctx, ctx->pipe_codes[b].p, codes + a0, (size_t)len, ctx->copy_stream)) return urc;
+        if (row_bytes)
+            if (int urc = upload(ctx, ctx->pipe_profile[b].p, reinterpret_cast<const unsigned char *>(profile) + (size_t)a0 * row_bytes,
+                                 (size_t)len * row_bytes, ctx->copy_stream))
+                return urc;
+        HIP_TRY(ctx, hipEventRecord(ctx->pipe_copied[b], ctx->copy_stream));
+        return PFMSCAN_OK;
+    };
+    if ((rc = upload_chunk(0))) return rc;
+    for (int64_t k = 0; k < n_chunks; ++k) {
+        const int b = (int)(k & 1);
+        const int64_t a0 = k * chunk_positions;
+        const int64_t len = std::min<int64_t>(n_pos - a0, chunk_positions + m - 1);
+        HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->pipe_copied[b], 0));
+        if ((rc = scan(b, a0, len))) return rc;                             // asynchronous: the next upload runs beside it
+        HIP_TRY(ctx, hipEventRecord(ctx->pipe_scanned[b], ctx->stream));
+        if (k + 1 < n_chunks && (rc = upload_chunk(k + 1))) return rc;
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->copy_stream));
+    return PFMSCAN_OK;
+}
 
 extern "C" {
 
@@ -43,66 +85,20 @@ int pfmscan_hits_pipeline_host(pfmscan_ctx *ctx, const pfmscan_motif *mo, const 
     chunk_positions = std::max<int64_t>((chunk_positions + 1023) & ~(int64_t)1023, 4096);   // 16-byte aligned chunk starts
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     ctx->staged_n = -1;                                                      // nothing stays staged
-    const int m = mo->m;
-    const size_t row_bytes = mo->d_struct ? (size_t)7 * (profile_dtype == PFMSCAN_PROFILE_F32 ? 4 : 8) : 0;
-    const int64_t buf_positions = std::min<int64_t>(n_pos, chunk_positions + m - 1);
+    const bool has_seq = mo->d_letters != nullptr, has_struct = mo->d_struct != nullptr;
+    const size_t row_bytes = has_struct ? (size_t)7 * (profile_dtype == PFMSCAN_PROFILE_F32 ? 4 : 8) : 0;
     int rc;
-    if (!ctx->copy_stream) HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
-    for (int i = 0; i < 2; ++i) {
-        if (mo->d_letters && (rc = ensure(ctx, ctx->pipe_codes[i], (size_t)buf_positions))) return rc;
-        if (mo->d_struct && (rc = ensure(ctx, ctx->pipe_profile[i], (size_t)buf_positions * row_bytes))) return rc;
-        if (!ctx->pipe_copied[i]) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->pipe_copied[i], hipEventDisableTiming));
-        if (!ctx->pipe_scanned[i]) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->pipe_scanned[i], hipEventDisableTiming));
-    }
-    // the ctx's sharded hit buffers, as pfmscan_hits_staged sizes them; counters are cleared once, hits accumulate
-    const int64_t shard_cap = std::max<int64_t>(std::min<int64_t>(capacity, capacity / HIT_SHARDS * 2 + 4096), 1);
-    const size_t slots = (size_t)shard_cap * HIT_SHARDS;
-    const size_t counter_bytes = (size_t)HIT_SHARDS * HIT_COUNTER_STRIDE * 8;
-    if ((rc = ensure(ctx, ctx->hit_pos, slots * 8))) return rc;
-    if ((rc = ensure(ctx, ctx->hit_seq, slots * 4))) return rc;
-    if ((rc = ensure(ctx, ctx->hit_struct, slots * 8))) return rc;
-    if ((rc = ensure(ctx, ctx->count, counter_bytes))) return rc;
-    HIP_TRY(ctx, hipMemsetAsync(ctx->count.p, 0, counter_bytes, ctx->stream));
-
-    const int64_t n_chunks = (n_pos + chunk_positions - 1) / chunk_positions;
-    auto upload = [&](int64_t k) -> int {
-        const int b = (int)(k & 1);
-        const int64_t a0 = k * chunk_positions;
-        const int64_t len = std::min<int64_t>(n_pos - a0, chunk_positions + m - 1);
-        if (k >= 2) HIP_TRY(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->pipe_scanned[b], 0));    // the buffer's previous chunk is scanned
-        if (mo->d_letters)
-            if (int urc = pfmscan::upload(ctx, ctx->pipe_codes[b].p, codes + a0, (size_t)len, ctx->copy_stream)) return urc;
-        if (mo->d_struct)
-            if (int urc = pfmscan::upload(ctx, ctx->pipe_profile[b].p, reinterpret_cast<const unsigned char *>(profile) + (size_t)a0 * row_bytes,
-                                          (size_t)len * row_bytes, ctx->copy_stream))
-                return urc;
-        HIP_TRY(ctx, hipEventRecord(ctx->pipe_copied[b], ctx->copy_stream));
-        return PFMSCAN_OK;
-    };
-    if ((rc = upload(0))) return rc;
-    for (int64_t k = 0; k < n_chunks; ++k) {
-        const int b = (int)(k & 1);
-        const int64_t a0 = k * chunk_positions;
-        const int64_t len = std::min<int64_t>(n_pos - a0, chunk_positions + m - 1);
-        HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->pipe_copied[b], 0));
+    HitSink sink;                                                            // cleared once: the chunks' hits accumulate
+    if ((rc = acquire_sink(ctx, hit_bufs(ctx), HIT_SHARDS, hit_shard_cap(capacity), ctx->stream, sink))) return rc;
+    rc = pipeline_chunks(ctx, has_seq ? codes : nullptr, profile, row_bytes, n_pos, chunk_positions, mo->m, [&](int b, int64_t a0, int64_t len) -> int {
         ScanArgs a;
-        if ((rc = check_and_fill(ctx, mo, (const uint8_t *)ctx->pipe_codes[b].p, ctx->pipe_profile[b].p, profile_dtype, len, a))) return rc;
-        a.hits = 1;
-        a.thr_seq = thr_seq;
-        a.thr_struct = thr_struct;
-        a.capacity = shard_cap;
-        a.hit_pos = (int64_t *)ctx->hit_pos.p;
-        a.hit_seq = mo->d_letters ? (float *)ctx->hit_seq.p : nullptr;
-        a.hit_struct = mo->d_struct ? (double *)ctx->hit_struct.p : nullptr;
-        a.hit_count = (unsigned long long *)ctx->count.p;
-        a.hit_shards = HIT_SHARDS;
+        if (int crc = check_and_fill(ctx, mo, (const uint8_t *)ctx->pipe_codes[b].p, ctx->pipe_profile[b].p, profile_dtype, len, a)) return crc;
+        fill_hits(a, sink, has_seq, has_struct, thr_seq, thr_struct);
         a.pos_offset = a0;
-        if ((rc = do_launch(ctx, a, ctx->stream))) return rc;               // asynchronous: the next upload runs beside it
-        HIP_TRY(ctx, hipEventRecord(ctx->pipe_scanned[b], ctx->stream));
-        if (k + 1 < n_chunks && (rc = upload(k + 1))) return rc;
-    }
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->copy_stream));
-    return finish_sorted_hits(ctx, mo->d_letters != nullptr, mo->d_struct != nullptr, n_pos, capacity, shard_cap, hit_pos, hit_seq, hit_struct, n_hits);
+        return do_launch(ctx, a, ctx->stream);
+    });
+    if (rc) return rc;
+    return finish_sorted_hits(ctx, sink, has_seq, has_struct, 0, n_pos, capacity, hit_pos, nullptr, hit_seq, hit_struct, n_hits);
 }
 
 }  // extern "C"

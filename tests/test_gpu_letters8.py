@@ -220,6 +220,27 @@ def test_hits_pair_vs_oracle(ctx, oracle, m):
     b.close()
 
 
+def test_hits_pair_capacity_protocol(ctx):
+    """pfmscan_hits_pair_host: a capacity below the hit count raises with a capacity that suffices, and the call repeated
+    with it returns exactly the hits of the unlimited call"""
+    from rnascan_amd import _lib
+    rng = np.random.default_rng(41)
+    lengths = [int(L) for L in rng.integers(100, 401, size=10)]
+    s1 = _stream(rng, lengths, n_letters=4, case=False)
+    s2 = _stream(rng, lengths)
+    a, b = ctx.motif(_table(rng, 8, n_letters=4), None), ctx.motif(_table(rng, 8), None)
+    full = ctx.hits_pair_host(a, b, s1.codes, s2.codes, 0.0, -4.0)
+    assert len(full[0]) > 100
+    with pytest.raises(_lib.CapacityError) as e:
+        ctx.hits_pair_host(a, b, s1.codes, s2.codes, 0.0, -4.0, capacity=10)
+    assert e.value.required >= len(full[0])
+    again = ctx.hits_pair_host(a, b, s1.codes, s2.codes, 0.0, -4.0, capacity=int(e.value.required))
+    assert np.array_equal(again[0], full[0])
+    assert np.array_equal(again[1].view(np.uint32), full[1].view(np.uint32)) and np.array_equal(again[2], full[2])
+    a.close()
+    b.close()
+
+
 def test_dev_pointer_forms(ctx, oracle):
     """pfmscan_hits_letters_f64_dev / pfmscan_hits_pair_dev on torch-owned device buffers"""
     import torch

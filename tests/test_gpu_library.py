@@ -360,3 +360,26 @@ def test_library_pipeline_host_equals_staged(ctx, oracle, kind):
     with pytest.raises(ValueError):
         ctx.scan_staged(ctx.motif(np.full((3, 8), np.nan)))            # nothing stays staged
     lib.close()
+
+
+def test_library_pipeline_capacity_protocol(ctx):
+    """pfmscan_library_hits_pipeline_host with one work segment per chunk, so that three chunks accumulate into one set of hit
+    buffers: a capacity below the hit count raises with a capacity that suffices, and the call repeated with it returns
+    exactly the hits of the unlimited call"""
+    from rnascan_amd import _lib
+    rng = np.random.default_rng(9)
+    s = rand_stream(rng, 110, 300, 400)
+    assert 2 * 16384 < s.n_pos < 3 * 16384
+    T, P = make_library(rng, 8, 8)
+    lib = ctx.library(T, P)
+    full = ctx.library_hits_pipeline_host(lib, s.codes, s.profile, 14.0, -1e30, chunk_positions=16384)
+    assert len(full[0]) > 100
+    assert (full[0] < 16384).any() and (full[0] >= 2 * 16384).any()          # hits of the first and of the last chunk
+    with pytest.raises(_lib.CapacityError) as ei:
+        ctx.library_hits_pipeline_host(lib, s.codes, s.profile, 14.0, -1e30, chunk_positions=16384, capacity=10)
+    assert ei.value.required >= len(full[0])
+    again = ctx.library_hits_pipeline_host(lib, s.codes, s.profile, 14.0, -1e30, chunk_positions=16384, capacity=ei.value.required)
+    assert np.array_equal(again[0], full[0]) and np.array_equal(again[1], full[1])
+    assert_f32_bits_equal(again[2], full[2])
+    assert np.array_equal(again[3].view(np.uint64), full[3].view(np.uint64))
+    lib.close()

@@ -165,6 +165,34 @@ def test_two_fasta_library_equals_per_pair_hits(ctx, oracle, n, m):
     lib.close()
 
 
+@pytest.mark.parametrize("kind", ["letters", "pair"])
+def test_letter_library_capacity_protocol(ctx, kind):
+    """pfmscan_library_hits_letters_host, both kinds of letter library: a capacity below the hit count raises with a capacity
+    that suffices, and the call repeated with it returns exactly the hits of the unlimited call"""
+    from rnascan_amd import _lib
+    rng = np.random.default_rng(43)
+    a, b = _pair_stream(rng, [int(L) for L in rng.integers(100, 401, size=10)])
+    LT = np.stack([rand_table(rng, 8) for _ in range(8)])
+    ST = np.stack([_table(rng, 8) for _ in range(8)])
+    if kind == "pair":
+        lib = ctx.library(LT, struct_letters=ST)
+        args = (lib, a.codes, b.codes, 8.0, 0.0)
+    else:
+        lib = ctx.library(None, struct_letters=ST)
+        args = (lib, b.codes, None, None, 10.0)
+    full = ctx.library_hits_letters_host(*args)
+    assert len(full[0]) > 100
+    with pytest.raises(_lib.CapacityError) as e:
+        ctx.library_hits_letters_host(*args, capacity=10)
+    assert e.value.required >= len(full[0])
+    again = ctx.library_hits_letters_host(*args, capacity=int(e.value.required))
+    assert np.array_equal(again[0], full[0]) and np.array_equal(again[1], full[1])
+    if kind == "pair":
+        assert np.array_equal(again[2].view(np.uint32), full[2].view(np.uint32))
+    assert np.array_equal(again[3], full[3])
+    lib.close()
+
+
 def test_letter_libraries_through_the_device_entry_point(ctx, oracle):
     """pfmscan_library_hits_letters_dev on torch tensors: unordered hits, total in *d_hit_count"""
     import ctypes

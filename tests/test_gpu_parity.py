@@ -257,6 +257,33 @@ def test_hits_capacity_protocol(ctx, oracle):
     assert np.array_equal(pos, want)
 
 
+def test_hits_capacity_one_shard_overflows_while_the_total_fits(ctx, oracle):
+    """The hit buffers are 32 shards of capacity / 16 + 4096 slots; the workgroup of tile t (4096 windows) appends to shard
+    t mod 32.  Here every hit starts in a tile with t mod 32 == 0, so one shard gets all 16356 of them: a capacity of exactly
+    the hit count holds the total but not that shard, which must raise -- asking for more than the total -- and not return
+    the hits that fitted."""
+    from rnascan_amd import _lib
+    rng = np.random.default_rng(5)
+    m, tile = 8, 4096
+    codes = rng.integers(1, 4, size=4 * 32 * tile + 1000).astype(np.uint8)
+    for t in range(0, 4 * 32, 32):
+        codes[t * tile:(t + 1) * tile] = 0                   # a run of the letter the motif wants, exactly over the tile
+    T = np.full((m, 8), np.nan)
+    T[:, :4] = -1.0
+    T[:, 0] = 1.0
+    motif = ctx.motif(letter_table=T)
+    want_seq = oracle.stream_seq(codes, T)
+    want = oracle.stream_hits(want_seq, None, 7.5, 7.5)
+    assert len(want) == 4 * (tile - m + 1) and (want // tile % 32 == 0).all()
+    assert len(want) > len(want) // 16 + 4096
+    with pytest.raises(_lib.CapacityError) as e:
+        ctx.hits_host(motif, codes, thr_seq=7.5, capacity=len(want))
+    assert e.value.required > len(want)
+    pos, sq, _ = ctx.hits_host(motif, codes, thr_seq=7.5, capacity=e.value.required)
+    assert np.array_equal(pos, want)
+    assert_f32_bits_equal(sq, want_seq[want])
+
+
 def test_no_window_spans_two_records(ctx):
     """separator semantics: every window touching a record end scores NaN"""
     rng = np.random.default_rng(8)

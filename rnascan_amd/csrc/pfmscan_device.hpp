@@ -1,15 +1,18 @@
 // pfmscan_device.hpp -- device-side helpers shared by the kernel translation units (pfmscan_kernels.hip,
-// pfmscan_letters8.hip): workgroup size, vector types, the code-tile stager and the workgroup hit emitter.  Not installed.
+// pfmscan_letters8.hip, pfmscan_library.hip, ...): workgroup size, vector types, the code-tile stager and the workgroup hit
+// emitter.  The hit protocol itself (shards, reservations, the wave hit queues) is pfmscan_hitqueue.hpp.  Not installed.
 #pragma once
 #include <float.h>
 #include <math.h>
 #include <type_traits>
 #include "pfmscan_internal.hpp"
 #include "pfmscan_exact.hpp"
+#include "pfmscan_hitqueue.hpp"
 
 namespace pfmscan {
 
 constexpr int BLOCK = 256;
+static_assert(BLOCK / 64 == HQ_WAVES, "WaveHitQueue is sized for this workgroup");
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 typedef uint16_t u16x2 __attribute__((ext_vector_type(2)));
@@ -120,6 +123,7 @@ __device__ __forceinline__ void emit_hits_block(const uint32_t passmask, PosF po
     __shared__ unsigned long long hb_base;
     __shared__ int hb_wave[BLOCK / 64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const HitShard shard{a.hit_count, a.hit_shards, a.capacity};
     const int cnt = __popc(passmask);
     int incl = cnt;
 #pragma unroll
@@ -137,19 +141,18 @@ __device__ __forceinline__ void emit_hits_block(const uint32_t passmask, PosF po
             hb_wave[w] = run;
             run += t;
         }
-        // sharded counters spread the returning atomics over several words (one word saturates
-        // at ~88 atomics/us: 73k workgroups with hits cost 0.8 ms on a single counter)
-        const int sh = blockIdx.x & (a.hit_shards - 1);
-        hb_base = run ? atomicAdd(a.hit_count + sh * HIT_COUNTER_STRIDE, (unsigned long long)run) : 0ull;
+        // sharded counters spread the returning atomics over several words (73k workgroups with hits cost 0.8 ms on a
+        // single counter)
+        hb_base = run ? shard.reserve((unsigned long long)run) : 0ull;
     }
     __syncthreads();
     if (passmask) {
         unsigned long long slot = hb_base + (unsigned long long)(hb_wave[wave] + incl - cnt);
-        const unsigned long long off = (unsigned long long)(blockIdx.x & (a.hit_shards - 1)) * (unsigned long long)a.capacity;
+        const unsigned long long off = shard.off();
 #pragma unroll
         for (int i = 0; i < N; ++i) {
             if (passmask & (1u << i)) {
-                if ((int64_t)slot < a.capacity) {                 // capacity is per shard
+                if (shard.in_range(slot)) {
                     a.hit_pos[off + slot] = pos_of(i) + a.pos_offset;
                     if (a.hit_seq) a.hit_seq[off + slot] = seq_of(i);
                     if (a.hit_struct) a.hit_struct[off + slot] = st_of(i);
@@ -160,7 +163,5 @@ __device__ __forceinline__ void emit_hits_block(const uint32_t passmask, PosF po
     }
     __syncthreads();                                   // hb_* may be reused by the next call
 }
-
-constexpr int WQ_CAP = 256;                           // hits a wave can park (k_letters_pre / _cred)
 
 }  // namespace pfmscan

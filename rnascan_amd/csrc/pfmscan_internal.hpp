@@ -188,8 +188,8 @@ struct LibArgs {
     int team_first[5];
     int team_ng[4];                       // ng_real per team
     int64_t stride_pairs, stride_letters, stride_pssm, stride_thr;      // in elements of the respective arrays
-    // hits: LIB_SHARDS (or 1) regions of shard_cap slots, counters HIT_COUNTER_STRIDE words apart
-    int64_t shard_cap;
+    // hits: LIB_SHARDS (or 1) regions of `capacity` slots (per shard, as in ScanArgs), counters HIT_COUNTER_STRIDE words apart
+    int64_t capacity;
     int hit_shards;
     int64_t *hit_pos;
     int32_t *hit_motif;
@@ -224,8 +224,8 @@ struct ProfLibArgs {
     const int32_t *finite;                // [n_motifs] 1 = every cell of the motif's PSSM is finite
     int n_motifs, m, motif_base;
     int64_t pos_offset;                   // added to every reported hit position (chunked host pipeline)
-    // hits: hit_shards regions of shard_cap slots, counters HIT_COUNTER_STRIDE words apart (workgroup b -> shard b & (shards-1))
-    int64_t shard_cap;
+    // hits: hit_shards regions of `capacity` slots (per shard), counters HIT_COUNTER_STRIDE words apart (workgroup b -> shard b & (shards-1))
+    int64_t capacity;
     int hit_shards;
     int64_t *hit_pos;
     int32_t *hit_motif;

@@ -254,18 +254,13 @@ __global__ __launch_bounds__(BLOCK) void k_letters_pre(const ScanArgs a)
     constexpr int ROUNDS = (let_iters(NDW) * 4) / W;
     constexpr int LET_TILE = let_tile(NDW);
     constexpr int NW = NDW + 1;                        // code dwords per round: bytes 0 .. W + m - 1 (+1 for the pair)
-    constexpr int NWAVE = BLOCK / 64;
     constexpr int MAXM = (NDW - 1) * 4;                // widest PFM of this instantiation (the launcher picks NDW from m)
     __shared__ __align__(16) double tbl[MAXM * 8];     // sized by the instantiation, not by PFMSCAN_MAX_M: m <= 16 fits 8 workgroups per CU
     __shared__ __align__(16) float ptab[(MAXM / 2) * 16];
     __shared__ __align__(16) uint8_t cbuf[2][LET_TILE + CODE_HALO];
-    __shared__ uint32_t q_pos[NWAVE][WQ_CAP];          // relative to the workgroup's first tile (4 bytes: 22.7 instead of 26.8 KB of LDS)
-    __shared__ float q_sc[NWAVE][WQ_CAP];
-    __shared__ int q_n[NWAVE], snap[2][NWAVE];
-    __shared__ unsigned long long s_base;
+    __shared__ HitQueueLds<float, WQ_CAP, false> hq_lds;            // 22.7 KB of LDS in all (NDW = 9)
     const int m = a.m;
     const int npair = (m + 1) >> 1;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t n_pos = a.n_pos;
     const int ntile = a.tiles_per_block;
     const int64_t first = (int64_t)blockIdx.x * ntile * LET_TILE;
@@ -277,49 +272,15 @@ __global__ __launch_bounds__(BLOCK) void k_letters_pre(const ScanArgs a)
     // (never -0.0), so the exact pass runs whole groups of 4 motif positions
     for (int i = threadIdx.x; i < ((m + 3) & ~3) * 8; i += BLOCK) tbl[i] = i < m * 8 ? a.letter_table[i] : 0.0;
     for (int i = threadIdx.x; i < npair * 16; i += BLOCK) ptab[i] = a.pair_table[i];
-    if (threadIdx.x < NWAVE) q_n[threadIdx.x] = 0;
+    const HitShard shard{a.hit_count, a.hit_shards, a.capacity};
+    WaveHitQueue<float, WQ_CAP, false> hq(hq_lds, a, shard, first);
+    hq.reset();
     cs.park(cbuf[0]);
     if (ntile > 1 && first + LET_TILE < n_pos) cs.fetch(a.codes, first + LET_TILE, n_pos);
     __syncthreads();
 
     const float thr_pre = a.thr_pre;                   // largest float <= thr_seq - pair_eps
     const char *pbytes = (const char *)ptab;
-    const int shard = blockIdx.x & (a.hit_shards - 1);
-    const unsigned long long shard_off = (unsigned long long)shard * (unsigned long long)a.capacity;
-    unsigned long long *counter = a.hit_count + shard * HIT_COUNTER_STRIDE;
-    uint32_t *my_pos = q_pos[wave];
-    float *my_sc = q_sc[wave];
-
-    auto store_hit = [&](unsigned long long slot, int64_t pos, float sc) {
-        if ((int64_t)slot < a.capacity) {             // capacity is per shard
-            a.hit_pos[shard_off + slot] = pos + a.pos_offset;
-            if (a.hit_seq) a.hit_seq[shard_off + slot] = sc;
-            if (a.hit_struct) a.hit_struct[shard_off + slot] = (double)sc;
-        }
-    };
-    // this wave's queue -> global at base; all 64 lanes (LDS operations of one wave execute in order)
-    auto drain = [&](unsigned long long base, int n) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        for (int i = lane; i < n; i += 64) store_hit(base + i, first + (int64_t)my_pos[i], my_sc[i]);
-        if (lane == 0) q_n[wave] = 0;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-    };
-    auto wave_flush = [&]() {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        const int n = __builtin_amdgcn_readfirstlane(q_n[wave]);
-        if (n == 0) return;
-        unsigned long long base = 0;
-        if (lane == 0) base = atomicAdd(counter, (unsigned long long)n);
-        const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)base), hi = __builtin_amdgcn_readfirstlane((uint32_t)(base >> 32));
-        drain(((unsigned long long)hi << 32) | lo, n);
-    };
-
-    int qn_ub = 0;                                     // wave-uniform upper bound of q_n[wave]
     for (int tb = 0; tb < ntile; ++tb) {
         const int64_t tile0 = first + (int64_t)tb * LET_TILE;
         if (tile0 >= n_pos) break;                     // uniform; the previous tile flushed (it was the last)
@@ -359,12 +320,7 @@ __global__ __launch_bounds__(BLOCK) void k_letters_pre(const ScanArgs a)
                 const bool sv = acc[v] > thr_pre;
                 const unsigned long long sb = __ballot(sv);
                 if (sb) {                               // wave-uniform
-                    const int ns = __popcll(sb);
-                    if (qn_ub + ns > WQ_CAP) {
-                        wave_flush();
-                        qn_ub = 0;
-                    }
-                    qn_ub += ns;
+                    hq.ensure_room(__popcll(sb));
                     if (sv) {
                         double sc = 0.0;
 #pragma unroll
@@ -378,39 +334,15 @@ __global__ __launch_bounds__(BLOCK) void k_letters_pre(const ScanArgs a)
                             }
                         }
                         const float f = (float)sc;
-                        if ((double)f > a.thr_seq) {
-                            const int slot = atomicAdd(&q_n[wave], 1);     // LDS
-                            my_pos[slot] = (uint32_t)(tile0 - first) + (uint32_t)(off0 + v);
-                            my_sc[slot] = f;
-                        }
+                        if ((double)f > a.thr_seq) hq.push((uint32_t)(tile0 - first) + (uint32_t)(off0 + v), f);
                     }
                 }
             }
         }
 
-        // tile boundary: publish the next tile's codes and this wave's queue length, ONE barrier
         const bool more = tb + 1 < ntile && tile0 + LET_TILE < n_pos;
-        if (more) cs.park(cbuf[(tb + 1) & 1]);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        if (lane == 0) snap[tb & 1][wave] = q_n[wave];
-        __syncthreads();
-        if (tb + 2 < ntile && tile0 + 2 * (int64_t)LET_TILE < n_pos) cs.fetch(a.codes, tile0 + 2 * (int64_t)LET_TILE, n_pos);
-        int nq[NWAVE], total = 0, most = 0, before = 0;
-#pragma unroll
-        for (int k = 0; k < NWAVE; ++k) {
-            nq[k] = snap[tb & 1][k];
-            if (k < wave) before += nq[k];
-            total += nq[k];
-            most = most > nq[k] ? most : nq[k];
-        }
-        qn_ub = nq[wave];
-        if (most >= WQ_CAP / 2 || (!more && total > 0)) {          // uniform: every thread read the same snapshot
-            if (threadIdx.x == 0) s_base = atomicAdd(counter, (unsigned long long)total);
-            __syncthreads();
-            drain(s_base + (unsigned long long)before, nq[wave]);
-            qn_ub = 0;
-        }
+        hq.tile_boundary(tb, more, [&]() { if (more) cs.park(cbuf[(tb + 1) & 1]); },
+                         [&]() { if (tb + 2 < ntile && tile0 + 2 * (int64_t)LET_TILE < n_pos) cs.fetch(a.codes, tile0 + 2 * (int64_t)LET_TILE, n_pos); });
     }
 }
 
@@ -444,6 +376,9 @@ template <> struct CredEntry<1> { typedef uint32_t type; };
 // score passes is scored right away on the SECOND code stream (a.codes2, a.letter_table2: the structure letters of the same
 // positions, fp64 sum as matrix.py:25-43) and is a hit only when that exceeds a.thr_struct too -- no candidate list, no
 // count read-back, no second launch.  The hit queue carries both scores (half as many slots: combined hits are rarer).
+// (This kernel still spells the hit queue and the survivor hand-over out: moved onto WaveHitQueue / SurvivorQueue of
+// pfmscan_hitqueue.hpp, as k_letters_pre and k_letters_cred8 are, hipcc allocates its registers differently -- 78 -> 83
+// VGPRs for NJ = 5, one wave per SIMD less -- so it keeps the code it was measured with.)
 template <int NJ, bool PAIR>
 __global__ __launch_bounds__(BLOCK) void k_letters_cred(const ScanArgs a, const CredTable ct)
 {

@@ -41,8 +41,6 @@ struct Cred8Table {
     uint32_t d[8][16];                                 // [code][row pair k] = credit of row 2k | credit of row 2k+1 << 16
 };
 
-constexpr int Q8_CAP = 128;                            // hits a wave can park (12 bytes each)
-
 #ifndef CRED8_MIN_WG
 #define CRED8_MIN_WG                                   // A/B builds: -DCRED8_MIN_WG=",4" (tools/build_variant.sh)
 #endif
@@ -66,13 +64,9 @@ __global__ __launch_bounds__(BLOCK CRED8_MIN_WG) void k_letters_cred8(const Scan
     __shared__ __align__(16) double tbl[TROWS * 8];
     __shared__ __align__(16) uint32_t ctab[8 * EDW];
     __shared__ __align__(16) uint8_t cbuf[2][LET_TILE + CODE_HALO];
-    __shared__ __align__(8) double q_sc[NWAVE][Q8_CAP];
-    __shared__ uint32_t q_pos[NWAVE][Q8_CAP];          // positions in both queues are relative to the workgroup's first tile
-    __shared__ uint32_t sv_pos[NWAVE][128];            // survivors of the prefilter waiting for their exact score
-    __shared__ int q_n[NWAVE], snap[2][NWAVE];
-    __shared__ unsigned long long s_base;
+    __shared__ HitQueueLds<double, Q8_CAP, false> hq_lds;            // positions in both queues are relative to the workgroup's first tile
+    __shared__ uint32_t sv_pos[NWAVE][SV_CAP];         // survivors of the prefilter waiting for their exact score
     const int m = a.m;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t n_pos = a.n_pos;
     const int ntile = a.tiles_per_block;
     const int64_t first = (int64_t)blockIdx.x * ntile * LET_TILE;
@@ -91,84 +85,32 @@ __global__ __launch_bounds__(BLOCK CRED8_MIN_WG) void k_letters_cred8(const Scan
     const __attribute__((address_space(4))) uint32_t *ktab =
         (const __attribute__((address_space(4))) uint32_t *)((karg_ptr)__builtin_amdgcn_kernarg_segment_ptr() + sizeof(ScanArgs));
     for (int i = threadIdx.x; i < 8 * EDW; i += BLOCK) ctab[i] = (i % EDW) < NJ ? ktab[(i / EDW) * 16 + (i % EDW)] : 0u;
-    if (threadIdx.x < NWAVE) q_n[threadIdx.x] = 0;
+    const HitShard shard{a.hit_count, a.hit_shards, a.capacity};
+    WaveHitQueue<double, Q8_CAP, false> hq(hq_lds, a, shard, first);
+    SurvivorQueue<decltype(hq)> sq(sv_pos[threadIdx.x >> 6], hq);
+    hq.reset();
     cs.park(cbuf[0]);
     if (ntile > 1 && first + LET_TILE < n_pos) cs.fetch(a.codes, first + LET_TILE, n_pos);
     __syncthreads();
 
     const char *cbytes = (const char *)ctab;
-    const int shard = blockIdx.x & (a.hit_shards - 1);
-    const unsigned long long shard_off = (unsigned long long)shard * (unsigned long long)a.capacity;
-    unsigned long long *counter = a.hit_count + shard * HIT_COUNTER_STRIDE;
-    uint32_t *my_pos = q_pos[wave];
-    double *my_sc = q_sc[wave];
-
-    auto store_hit = [&](unsigned long long slot, int64_t pos, double sc) {
-        if ((int64_t)slot < a.capacity) {             // capacity is per shard
-            a.hit_pos[shard_off + slot] = pos + a.pos_offset;
-            if (a.hit_seq) a.hit_seq[shard_off + slot] = (float)sc;
-            if (a.hit_struct) a.hit_struct[shard_off + slot] = sc;
-        }
-    };
-    // this wave's queue -> global at base; all 64 lanes (LDS operations of one wave execute in order)
-    auto drain = [&](unsigned long long base, int n) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        for (int i = lane; i < n; i += 64) store_hit(base + i, first + (int64_t)my_pos[i], my_sc[i]);
-        if (lane == 0) q_n[wave] = 0;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-    };
-    auto wave_flush = [&]() {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        const int n = __builtin_amdgcn_readfirstlane(q_n[wave]);
-        if (n == 0) return;
-        unsigned long long base = 0;
-        if (lane == 0) base = atomicAdd(counter, (unsigned long long)n);
-        const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)base), hi = __builtin_amdgcn_readfirstlane((uint32_t)(base >> 32));
-        drain(((unsigned long long)hi << 32) | lo, n);
-    };
-
-    int qn_ub = 0;                                     // wave-uniform upper bound of q_n[wave]
-    int sv_n = 0;                                      // wave-uniform length of the survivor queue (< 64 between windows)
-    uint32_t *my_sv = sv_pos[wave];
-    // exact score of survivors [at, at + cnt) of this wave's queue, one per lane (matrix.py:25-43: sequential fp64 sum)
-    auto exact_batch = [&](int at, int cnt) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        if (qn_ub + cnt > Q8_CAP) {                    // room for a hit per lane in the hit queue
-            wave_flush();
-            qn_ub = 0;
-        }
-        qn_ub += cnt;
-        if (lane < cnt) {
-            const int64_t p = first + (int64_t)my_sv[at + lane];
-            const int64_t al = p & ~(int64_t)3;
-            uint32_t raw[NRAW];
+    // exact score of the survivor at stream position p (matrix.py:25-43: sequential fp64 sum); a hit goes to the hit queue
+    auto exact = [&](int64_t p) {
+        const int64_t al = p & ~(int64_t)3;
+        uint32_t raw[NRAW];
 #pragma unroll
-            for (int k = 0; k < NRAW; ++k) raw[k] = load_codes4(a.codes, al + 4 * k, n_pos);
-            double sc = 0.0;
+        for (int k = 0; k < NRAW; ++k) raw[k] = load_codes4(a.codes, al + 4 * k, n_pos);
+        double sc = 0.0;
 #pragma unroll
-            for (int k = 0; k < NRAW - 1; ++k) {
-                const uint32_t cw = __builtin_amdgcn_alignbyte(raw[k + 1], raw[k], (uint32_t)(p & 3));
+        for (int k = 0; k < NRAW - 1; ++k) {
+            const uint32_t cw = __builtin_amdgcn_alignbyte(raw[k + 1], raw[k], (uint32_t)(p & 3));
 #pragma unroll
-                for (int b = 0; b < 4; ++b) {
-                    const int j = 4 * k + b;
-                    if (j < TROWS) sc += tbl[j * 8 + ((cw >> (8 * b)) & 7u)];           // rows m .. 2 NJ - 1 are zeros
-                }
-            }
-            if (sc > a.thr_seq) {                      // fp64 compare: no float32 cast on this path
-                const int slot = atomicAdd(&q_n[wave], 1);     // LDS
-                my_pos[slot] = (uint32_t)(p - first);
-                my_sc[slot] = sc;
+            for (int b = 0; b < 4; ++b) {
+                const int j = 4 * k + b;
+                if (j < TROWS) sc += tbl[j * 8 + ((cw >> (8 * b)) & 7u)];           // rows m .. 2 NJ - 1 are zeros
             }
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
+        if (sc > a.thr_seq) hq.push((uint32_t)(p - first), sc);      // fp64 compare: no float32 cast on this path
     };
     for (int tb = 0; tb < ntile; ++tb) {
         const int64_t tile0 = first + (int64_t)tb * LET_TILE;
@@ -238,52 +180,13 @@ __global__ __launch_bounds__(BLOCK CRED8_MIN_WG) void k_letters_cred8(const Scan
             const u16x2 r = __builtin_bit_cast(u16x2, pk[2 * k + 1]) + __builtin_bit_cast(u16x2, x);
             surv = (surv >> 1) | (__builtin_bit_cast(uint32_t, r) & 0x80008000u);
         }
-        // Survivors -> the wave's queue (positions only; windows past the end hold SEP codes: no credit).  ONE rolled
-        // loop: every pass each lane that still has a survivor hands over its lowest one (an unrolled pass per window
-        // inlined the exact score 17 times: 25 k instructions and 57 spilled SGPRs in the widest instantiation).
-        while (__builtin_amdgcn_ballot_w64(surv != 0)) {
-            const bool sv = surv != 0;
-            const unsigned long long sb = __builtin_amdgcn_ballot_w64(sv);
-            if (sv) {
-                const int b = __builtin_ctz(surv);
-                surv &= surv - 1;
-                const int v = 2 * (b & 7) + (b < 16 ? 1 : 0);
-                my_sv[sv_n + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(sb >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)sb, 0u))] = (uint32_t)(tile0 - first) + (uint32_t)(off0 + v);
-            }
-            sv_n += __popcll(sb);
-            if (sv_n >= 64) {                           // the top 64 get their exact score, the rest stays
-                exact_batch(sv_n - 64, 64);
-                sv_n -= 64;
-            }
-        }
+        // survivors -> the wave's queue (positions only; windows past the end hold SEP codes: no credit)
+        sq.hand_over(surv, (uint32_t)(tile0 - first), off0, [](int b) { return 2 * (b & 7) + (b < 16 ? 1 : 0); }, exact);
 
-        // tile boundary: publish the next tile's codes and this wave's queue length, ONE barrier
         const bool more = tb + 1 < ntile && tile0 + LET_TILE < n_pos;
-        if (!more && sv_n > 0) {                       // last tile of the workgroup: the waiting survivors, then the final flush
-            exact_batch(0, sv_n);
-            sv_n = 0;
-        }
-        if (more) cs.park(cbuf[(tb + 1) & 1]);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        if (lane == 0) snap[tb & 1][wave] = q_n[wave];
-        __syncthreads();
-        if (tb + 2 < ntile && tile0 + 2 * (int64_t)LET_TILE < n_pos) cs.fetch(a.codes, tile0 + 2 * (int64_t)LET_TILE, n_pos);
-        int nq[NWAVE], total = 0, most = 0, before = 0;
-#pragma unroll
-        for (int k = 0; k < NWAVE; ++k) {
-            nq[k] = snap[tb & 1][k];
-            if (k < wave) before += nq[k];
-            total += nq[k];
-            most = most > nq[k] ? most : nq[k];
-        }
-        qn_ub = nq[wave];
-        if (most >= Q8_CAP / 2 || (!more && total > 0)) {          // uniform: every thread read the same snapshot
-            if (threadIdx.x == 0) s_base = atomicAdd(counter, (unsigned long long)total);
-            __syncthreads();
-            drain(s_base + (unsigned long long)before, nq[wave]);
-            qn_ub = 0;
-        }
+        if (!more) sq.finish(exact);                   // last tile of the workgroup: the waiting survivors, then the final flush
+        hq.tile_boundary(tb, more, [&]() { if (more) cs.park(cbuf[(tb + 1) & 1]); },
+                         [&]() { if (tb + 2 < ntile && tile0 + 2 * (int64_t)LET_TILE < n_pos) cs.fetch(a.codes, tile0 + 2 * (int64_t)LET_TILE, n_pos); });
     }
 }
 

@@ -417,7 +417,7 @@ __global__ __launch_bounds__(lib_block(NP)) void k_library(const LibArgs a)
     const int64_t n_pos = a.n_pos;
     const int shard = blockIdx.x & (a.hit_shards - 1);
     unsigned long long *counter = a.hit_count + (size_t)shard * HIT_COUNTER_STRIDE;
-    const unsigned long long shard_off = (unsigned long long)shard * (unsigned long long)a.shard_cap;
+    const unsigned long long shard_off = (unsigned long long)shard * (unsigned long long)a.capacity;
     const lds_cptr pairs_lds = lds_ptr_of(pairs);
 
     // ---- phase B: the top cnt (<= 64) items [first, first + cnt) of this wave's queue, one per lane; items that
@@ -543,11 +543,7 @@ __global__ __launch_bounds__(lib_block(NP)) void k_library(const LibArgs a)
         if (HAS_STRUCT) {
             if (__builtin_amdgcn_ballot_w64(ok)) {
                 if (ok) {
-#ifdef LIB_DIAG_WRAP                                     // timing diagnostic only: the rows come from the first 2^20 positions (cache-resident): WRONG scores
-                    const int64_t ps = p & 0xFFFFF;
-#else
                     const int64_t ps = p;
-#endif
                     if constexpr (std::is_same<PROF_T, uint8_t>::value) {
                         // two-FASTA library: the structure LETTERS of the same window (rnascan.py:416-434 joins the two tables)
                         st = lib_letters2_score<NMP, NP>(reinterpret_cast<const uint8_t *>(a.profile), ps, n_pos, m, pssm, mo);
@@ -575,7 +571,7 @@ __global__ __launch_bounds__(lib_block(NP)) void k_library(const LibArgs a)
             base = ((unsigned long long)hi << 32) | lo;
             if (ok) {
                 const unsigned long long slot = base + __builtin_amdgcn_mbcnt_hi((uint32_t)(hm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)hm, 0u));
-                if ((int64_t)slot < a.shard_cap) {
+                if ((int64_t)slot < a.capacity) {
                     a.hit_pos[shard_off + slot] = p + a.pos_offset;
                     a.hit_motif[shard_off + slot] = motif_base + mo;
                     a.hit_seq[shard_off + slot] = f;
@@ -847,7 +843,7 @@ __global__ __launch_bounds__(lib_block(NR)) void k_library8(const LibArgs a)
     const int ng_real = a.ng_real;
     const int shard = blockIdx.x & (a.hit_shards - 1);
     unsigned long long *counter = a.hit_count + (size_t)shard * HIT_COUNTER_STRIDE;
-    const unsigned long long shard_off = (unsigned long long)shard * (unsigned long long)a.shard_cap;
+    const unsigned long long shard_off = (unsigned long long)shard * (unsigned long long)a.capacity;
     const lds_cptr cred_lds = lds_ptr_of(cred);
 
     // ---- phase B: the top cnt (<= 64) items of this wave's queue, one per lane and ONE motif per lane; what is left of an
@@ -908,7 +904,7 @@ __global__ __launch_bounds__(lib_block(NR)) void k_library8(const LibArgs a)
             base = ((unsigned long long)hi << 32) | lo;
             if (ok) {
                 const unsigned long long slot = base + __builtin_amdgcn_mbcnt_hi((uint32_t)(hm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)hm, 0u));
-                if ((int64_t)slot < a.shard_cap) {
+                if ((int64_t)slot < a.capacity) {
                     a.hit_pos[shard_off + slot] = p + a.pos_offset;
                     a.hit_motif[shard_off + slot] = a.motif_base + mo;
                     if (a.hit_seq) a.hit_seq[shard_off + slot] = (float)sc;

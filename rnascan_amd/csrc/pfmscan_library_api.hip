@@ -546,7 +546,7 @@ static int lib_run(pfmscan_ctx *ctx, pfmscan_library *lib, const uint8_t *d_code
                 a.ng_real = ps.ng_real;
                 a.motif_base = ps.motif_base;
                 a.pos_offset = pos_offset;
-                a.shard_cap = sink.shard_cap;
+                a.capacity = sink.shard_cap;
                 a.hit_shards = sink.shards;
                 a.hit_pos = sink.pos;
                 a.hit_motif = sink.motif;
@@ -572,7 +572,7 @@ static int lib_run(pfmscan_ctx *ctx, pfmscan_library *lib, const uint8_t *d_code
         a.m = lib->m;
         a.motif_base = 0;
         a.pos_offset = pos_offset;
-        a.shard_cap = sink.shard_cap;
+        a.capacity = sink.shard_cap;
         a.hit_shards = sink.shards;
         a.hit_pos = sink.pos;
         a.hit_motif = sink.motif;
@@ -651,7 +651,7 @@ static int lib_run(pfmscan_ctx *ctx, pfmscan_library *lib, const uint8_t *d_code
             a.ng = ps.ng;
             a.motif_base = ps.motif_base;
             a.pos_offset = pos_offset;
-            a.shard_cap = sink.shard_cap;
+            a.capacity = sink.shard_cap;
             a.hit_shards = sink.shards;
             a.hit_pos = sink.pos;
             a.hit_motif = sink.motif;

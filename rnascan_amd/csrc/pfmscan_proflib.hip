@@ -33,6 +33,7 @@
 
 #include "pfmscan_internal.hpp"
 #include "pfmscan_exact.hpp"
+#include "pfmscan_hitqueue.hpp"
 
 namespace pfmscan {
 
@@ -236,21 +237,17 @@ __global__ __launch_bounds__(PL_BLOCK) void k_profile_lib(const ProfLibArgs a)
     if (group == 3) __builtin_amdgcn_s_sleep(3 * PL_STAGGER);
 #endif
 
-    const int shard = blockIdx.x & (a.hit_shards - 1);
-    unsigned long long *counter = a.hit_count + (size_t)shard * HIT_COUNTER_STRIDE;
-    const unsigned long long shard_off = (unsigned long long)shard * (unsigned long long)a.shard_cap;
+    const HitShard shard{a.hit_count, a.hit_shards, a.capacity};
+    const unsigned long long shard_off = shard.off();
     int qn = 0;                                        // wave-uniform queue length
     auto flush = [&]() {
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        unsigned long long base = 0;
-        if (lane == 0) base = atomicAdd(counter, (unsigned long long)qn);
-        const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)base), hi = __builtin_amdgcn_readfirstlane((uint32_t)(base >> 32));
-        base = ((unsigned long long)hi << 32) | lo;
+        const unsigned long long base = shard.reserve_wave(qn);
         for (int i = lane; i < qn; i += 64) {
             const unsigned long long slot = base + (unsigned long long)i;
-            if ((int64_t)slot < a.shard_cap) {         // capacity is per shard
+            if (shard.in_range(slot)) {
                 const uint32_t wm = q_wm[i];
                 a.hit_pos[shard_off + slot] = tile0 + (int64_t)(wm >> 16) + a.pos_offset;
                 a.hit_motif[shard_off + slot] = a.motif_base + (int32_t)(wm & 0xFFFFu);

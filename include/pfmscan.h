@@ -59,7 +59,7 @@
 extern "C" {
 #endif
 
-#define PFMSCAN_ABI_VERSION 12
+#define PFMSCAN_ABI_VERSION 13
 #define PFMSCAN_NCODE   8      /* columns of a letter table */
 #define PFMSCAN_SEP     7      /* separator / foreign-letter code */
 #define PFMSCAN_NSTRUCT 7      /* columns of a structure profile / structure PSSM */
@@ -227,6 +227,42 @@ int pfmscan_hits_staged(pfmscan_ctx *ctx, const pfmscan_motif *motif,
                         double thr_seq, double thr_struct, int64_t capacity,
                         int64_t *hit_pos, float *hit_seq, double *hit_struct,
                         int64_t *n_hits);
+
+/* ---- combined hits with a joint threshold on LogOdds.SeqStruct -----------------------------------
+ * combine() (rnascan.py:416-434) ends the combined table with LogOdds.SeqStruct = LogOdds.Seq + LogOdds.Struct, the sum
+ * of the two PRINTED columns, but only ever filters on each side alone (the two tables it joins were thresholded
+ * separately).  These entry points add the joint filter.  The motif must have BOTH parts (else PFMSCAN_E_BADARG):
+ *   hit <=> seq(p) > thr_seq  and  struct(p) > thr_struct                       (as pfmscan_hits_*; either may be -inf)
+ *           and  (double)round3(seq(p)) + struct(p) > thr_sum                   (strict; a NaN sum never passes)
+ * with round3(x) = np.round(float32 x, 3) = rint(x * 1000f) / 1000f in IEEE float32 -- the printed LogOdds.Seq
+ * (rnascan.py:273) -- and one rounded fp64 addition: exactly the printed LogOdds.SeqStruct of an averaged-structure scan.
+ * A window whose sum lies within a rigorous band of thr_sum is decided on -- and reports -- the structure score taken in
+ * the reference's rounded order, as near thr_struct (csrc/pfmscan_exact.hpp).  thr_sum = -inf gives exactly the hits of
+ * the plain call; NaN is PFMSCAN_E_BADARG.  Hit arrays, count, capacity protocol and ordering: as the pfmscan_hits_*
+ * counterpart.  _dev is ONE fused pass, asynchronous on `stream`, and never synchronises; _staged / _host take the
+ * candidate-then-verify route of pfmscan_hits_staged when thr_seq is finite and selective (the joint filter then runs
+ * in the verify pass); _pipeline_host is one fused pass per chunk. */
+int pfmscan_hits_sum_dev(pfmscan_ctx *ctx, const pfmscan_motif *motif,
+                         const uint8_t *d_codes, const void *d_profile,
+                         int profile_dtype, int64_t n_pos, double thr_seq,
+                         double thr_struct, double thr_sum, int64_t capacity, int64_t *d_hit_pos,
+                         float *d_hit_seq, double *d_hit_struct,
+                         uint64_t *d_hit_count, void *stream);
+int pfmscan_hits_sum_staged(pfmscan_ctx *ctx, const pfmscan_motif *motif,
+                            double thr_seq, double thr_struct, double thr_sum, int64_t capacity,
+                            int64_t *hit_pos, float *hit_seq, double *hit_struct,
+                            int64_t *n_hits);
+int pfmscan_hits_sum_host(pfmscan_ctx *ctx, const pfmscan_motif *motif,
+                          const uint8_t *codes, const void *profile,
+                          int profile_dtype, int64_t n_pos, double thr_seq,
+                          double thr_struct, double thr_sum, int64_t capacity, int64_t *hit_pos,
+                          float *hit_seq, double *hit_struct, int64_t *n_hits);
+int pfmscan_hits_sum_pipeline_host(pfmscan_ctx *ctx, const pfmscan_motif *motif,
+                                   const uint8_t *codes, const void *profile,
+                                   int profile_dtype, int64_t n_pos, int64_t chunk_positions,
+                                   double thr_seq, double thr_struct, double thr_sum, int64_t capacity,
+                                   int64_t *hit_pos, float *hit_seq, double *hit_struct,
+                                   int64_t *n_hits);
 
 /* ---- thresholded hits of a generic-alphabet letter scan, score in fp64 -------------------------
  * (`rnascan -q pfm structs.fa`.)  Replaces `pm.search(seq, threshold=minscore)` (rnascan.py:263) over

@@ -22,7 +22,7 @@ NCODE = 8
 NSTRUCT = 7
 MAX_M = 64            # widest PFM of the tuned kernels and of PFM libraries
 MAX_WIDTH = 4096      # widest PFM accepted (wider than MAX_M: the plain rolled-loop kernel)
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 # every symbol include/pfmscan.h declares (checked by tests/test_abi.py)
 SYMBOLS = [
@@ -43,6 +43,7 @@ SYMBOLS = [
     "pfmscan_dotbracket_annotate_dev", "pfmscan_dotbracket_stage", "pfmscan_dotbracket_annotate_host",
     "pfmscan_average_dev", "pfmscan_average_host", "pfmscan_average_stage", "pfmscan_fragment_ids",
     "pfmscan_profile_colsums_dev", "pfmscan_profile_colsums_host", "pfmscan_profile_colsums_staged",
+    "pfmscan_hits_sum_dev", "pfmscan_hits_sum_staged", "pfmscan_hits_sum_host", "pfmscan_hits_sum_pipeline_host",
 ]
 MAX_COVER = 1024      # largest coverage of a row the averaging accepts
 AVG_OK, AVG_DOTBRACKET, AVG_UNCOVERED, AVG_COVER, AVG_BAD_TABLE = range(5)   # what a rejected averaging names
@@ -121,6 +122,10 @@ def load():
     L.pfmscan_scan_staged.argtypes = [vp, vp, vp, vp]
     L.pfmscan_staged_positions.argtypes = [vp]
     L.pfmscan_hits_staged.argtypes = [vp, vp, dbl, dbl, i64, vp, vp, vp, ctypes.POINTER(i64)]
+    L.pfmscan_hits_sum_dev.argtypes = [vp, vp, vp, vp, i32, i64, dbl, dbl, dbl, i64, vp, vp, vp, vp, vp]
+    L.pfmscan_hits_sum_staged.argtypes = [vp, vp, dbl, dbl, dbl, i64, vp, vp, vp, ctypes.POINTER(i64)]
+    L.pfmscan_hits_sum_host.argtypes = [vp, vp, vp, vp, i32, i64, dbl, dbl, dbl, i64, vp, vp, vp, ctypes.POINTER(i64)]
+    L.pfmscan_hits_sum_pipeline_host.argtypes = [vp, vp, vp, vp, i32, i64, i64, dbl, dbl, dbl, i64, vp, vp, vp, ctypes.POINTER(i64)]
     L.pfmscan_time_scan_dev.argtypes = [vp, vp, vp, vp, i32, i64, vp, vp, vp, i32, i32, ctypes.POINTER(dbl)]
     L.pfmscan_library_create.argtypes = [vp, vp, vp, i32, i32, ctypes.POINTER(vp)]
     L.pfmscan_library_create_letters.argtypes = [vp, vp, vp, i32, i32, ctypes.POINTER(vp)]
@@ -543,9 +548,29 @@ class Context(object):
         self._check(self._L.pfmscan_scan_letters_f64_host(self._h, motif._h, _ptr(codes), codes.size, _ptr(out)))
         return out
 
-    def hits_host(self, motif, codes, profile=None, thr_seq=-np.inf, thr_struct=-np.inf, capacity=None):
+    def hits_sum_host(self, motif, codes, profile, thr_seq, thr_struct, thr_sum, capacity=None):
+        """hits_host with the joint threshold ``LogOdds.SeqStruct > thr_sum`` on the printed sum (pfmscan_hits_sum_host)"""
+        return self.hits_host(motif, codes, profile, thr_seq, thr_struct, capacity, thr_sum=thr_sum)
+
+    def hits_sum_pipeline_host(self, motif, codes, profile, thr_seq, thr_struct, thr_sum, chunk_positions=0, capacity=None):
+        """hits_pipeline_host with the joint threshold on the printed sum (pfmscan_hits_sum_pipeline_host)"""
+        return self.hits_pipeline_host(motif, codes, profile, thr_seq, thr_struct, chunk_positions, capacity, thr_sum=thr_sum)
+
+    def hits_sum_staged(self, motif, thr_seq, thr_struct, thr_sum, capacity=None):
+        """hits_staged with the joint threshold on the printed sum (pfmscan_hits_sum_staged)"""
+        return self.hits_staged(motif, thr_seq, thr_struct, capacity, thr_sum=thr_sum)
+
+    def hits_sum_dev(self, motif, d_codes, d_profile, profile_dtype, n_pos, thr_seq, thr_struct, thr_sum, capacity,
+                     d_hit_pos, d_hit_seq, d_hit_struct, d_hit_count, stream=None):
+        """hits_dev with the joint threshold on the printed sum: one fused pass, asynchronous on ``stream``"""
+        self._check(self._L.pfmscan_hits_sum_dev(self._h, motif._h, _ptr(d_codes), _ptr(d_profile), int(profile_dtype),
+                                                 int(n_pos), float(thr_seq), float(thr_struct), float(thr_sum), int(capacity),
+                                                 _ptr(d_hit_pos), _ptr(d_hit_seq), _ptr(d_hit_struct), _ptr(d_hit_count),
+                                                 _ptr(stream)))
+
+    def hits_host(self, motif, codes, profile=None, thr_seq=-np.inf, thr_struct=-np.inf, capacity=None, thr_sum=None):
         """Thresholded hits sorted by position -> (pos int64[k], seq float32[k], struct float64[k]).
-        Grows the buffer and retries when the first guess was too small."""
+        Grows the buffer and retries when the first guess was too small.  ``thr_sum``: see hits_sum_host."""
         n, codes, profile, dt = _stream_args(motif, codes, profile)
         cap = int(capacity) if capacity is not None else max(1024, n // 64)
         self.scratch_gen += 1
@@ -556,9 +581,14 @@ class Context(object):
             sq = np.empty(cap, dtype=np.float32)
             st = np.empty(cap, dtype=np.float64)
             k = ctypes.c_int64(0)
-            rc = self._L.pfmscan_hits_host(self._h, motif._h, _ptr(codes), _ptr(profile), dt, n,
-                                           float(thr_seq), float(thr_struct), cap,
-                                           _ptr(pos), _ptr(sq), _ptr(st), ctypes.byref(k))
+            if thr_sum is None:
+                rc = self._L.pfmscan_hits_host(self._h, motif._h, _ptr(codes), _ptr(profile), dt, n,
+                                               float(thr_seq), float(thr_struct), cap,
+                                               _ptr(pos), _ptr(sq), _ptr(st), ctypes.byref(k))
+            else:
+                rc = self._L.pfmscan_hits_sum_host(self._h, motif._h, _ptr(codes), _ptr(profile), dt, n,
+                                                   float(thr_seq), float(thr_struct), float(thr_sum), cap,
+                                                   _ptr(pos), _ptr(sq), _ptr(st), ctypes.byref(k))
             if rc == E_CAPACITY and capacity is None:
                 cap = int(k.value)
                 continue
@@ -568,7 +598,7 @@ class Context(object):
             return pos[:k].copy(), (sq[:k].copy() if motif.has_letters else None), (st[:k].copy() if motif.has_struct else None)
 
     def hits_pipeline_host(self, motif, codes, profile=None, thr_seq=-np.inf, thr_struct=-np.inf, chunk_positions=0,
-                           capacity=None):
+                           capacity=None, thr_sum=None):
         """hits_host for streams of any length (numpy arrays or memory maps): chunked, the upload of the next chunk
         overlaps the scan of the current one, device scratch = two chunks.  Same return values as hits_host."""
         n, codes, profile, dt = _stream_args(motif, codes, profile)
@@ -581,9 +611,14 @@ class Context(object):
             sq = np.empty(cap, dtype=np.float32)
             st = np.empty(cap, dtype=np.float64)
             k = ctypes.c_int64(0)
-            rc = self._L.pfmscan_hits_pipeline_host(self._h, motif._h, _ptr(codes), _ptr(profile), dt, n, int(chunk_positions),
-                                                    float(thr_seq), float(thr_struct), cap, _ptr(pos), _ptr(sq), _ptr(st),
-                                                    ctypes.byref(k))
+            if thr_sum is None:
+                rc = self._L.pfmscan_hits_pipeline_host(self._h, motif._h, _ptr(codes), _ptr(profile), dt, n, int(chunk_positions),
+                                                        float(thr_seq), float(thr_struct), cap, _ptr(pos), _ptr(sq), _ptr(st),
+                                                        ctypes.byref(k))
+            else:
+                rc = self._L.pfmscan_hits_sum_pipeline_host(self._h, motif._h, _ptr(codes), _ptr(profile), dt, n, int(chunk_positions),
+                                                            float(thr_seq), float(thr_struct), float(thr_sum), cap, _ptr(pos),
+                                                            _ptr(sq), _ptr(st), ctypes.byref(k))
             if rc == E_CAPACITY and capacity is None:
                 cap = int(k.value)
                 continue
@@ -673,7 +708,7 @@ class Context(object):
         self._check(self._L.pfmscan_scan_staged(self._h, motif._h, _ptr(out_seq), _ptr(out_struct)))
         return out_seq, out_struct
 
-    def hits_staged(self, motif, thr_seq=-np.inf, thr_struct=-np.inf, capacity=None):
+    def hits_staged(self, motif, thr_seq=-np.inf, thr_struct=-np.inf, capacity=None, thr_sum=None):
         n = int(self._L.pfmscan_staged_positions(self._h))
         if n < 0:
             raise ValueError("no stream staged (call stage first)")
@@ -683,8 +718,12 @@ class Context(object):
             sq = np.empty(cap, dtype=np.float32)
             st = np.empty(cap, dtype=np.float64)
             k = ctypes.c_int64(0)
-            rc = self._L.pfmscan_hits_staged(self._h, motif._h, float(thr_seq), float(thr_struct), cap,
-                                             _ptr(pos), _ptr(sq), _ptr(st), ctypes.byref(k))
+            if thr_sum is None:
+                rc = self._L.pfmscan_hits_staged(self._h, motif._h, float(thr_seq), float(thr_struct), cap,
+                                                 _ptr(pos), _ptr(sq), _ptr(st), ctypes.byref(k))
+            else:
+                rc = self._L.pfmscan_hits_sum_staged(self._h, motif._h, float(thr_seq), float(thr_struct), float(thr_sum), cap,
+                                                     _ptr(pos), _ptr(sq), _ptr(st), ctypes.byref(k))
             if rc == E_CAPACITY and capacity is None:
                 cap = int(k.value)
                 continue

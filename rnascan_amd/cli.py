@@ -5,7 +5,7 @@ rnascan/rnascan.py (``getoptions`` :44-105, ``_guess_seq_type`` :114-137,
 ``main`` :490-576).  Extra options only ADD behaviour: ``--device`` picks the
 GPU, ``--pairing`` chooses how averaged-structure columns are paired with the
 structure PFM (see scanner.struct_matrix), ``--profile-dtype`` the device storage
-of the profiles.  ``-c/--cores`` and ``-x/--debug`` are accepted and
+of the profiles, ``--min-seqstruct`` a joint threshold on LogOdds.SeqStruct.  ``-c/--cores`` and ``-x/--debug`` are accepted and
 ignored: there is no process pool, a batch is one kernel launch.
 """
 import argparse
@@ -65,6 +65,11 @@ def getoptions(argv=None):
                      help=("scan on this many GPUs of the node, one process per GPU, records sharded over them (the analogue "
                            "of the reference's -c: its Pool fan-out).  This process then only starts the ranks and waits; "
                            "rank 0 prints the table [1]"))
+    gpu.add_argument("--min-seqstruct", type=float, default=None, dest="min_seqstruct", metavar="T",
+                     help=("combined scans (-p AND -q): additionally keep a row only if its LogOdds.SeqStruct -- the printed sum of "
+                           "the two log-odds -- exceeds T (strict).  -m keeps its meaning and its default: a row still needs "
+                           "seq > m AND struct > m; `-m ' -inf' --min-seqstruct T` thresholds on the sum alone.  With averaged-"
+                           "structure profiles the decision is taken on the GPU.  Match_ID numbers the kept rows [off]"))
     gpu.add_argument("--pairing", choices=["aligned", "positional"], default="aligned",
                      help=("averaged-structure columns vs structure PFM.  'aligned' pairs every profile column with the PFM "
                            "row of the SAME letter -- the evident intent, and what the reference computed on Python 2.  "
@@ -91,6 +96,10 @@ def getoptions(argv=None):
         parser.error("Must specify PFMs with -p and/or -q")
     if args.uniform_background and (args.bg_seq or args.bg_struct):
         parser.error("You cannot set uniform and custom background options at the same time\n")
+    if args.min_seqstruct is not None and not (args.pfm_seq and args.pfm_struct):
+        parser.error("--min-seqstruct thresholds the combined score: it needs both -p and -q")
+    if args.min_seqstruct is not None and args.min_seqstruct != args.min_seqstruct:
+        parser.error("--min-seqstruct: not a number")
     if args.struct_format in FRAGMENT_FORMATS and args.testseq:
         parser.error("--struct-format %s reads a file of fragments: it cannot be used with -t" % args.struct_format)
     return args
@@ -545,12 +554,13 @@ def main(argv=None, engine=None, out=None):
             if prepacked is None:
                 named = load_many(ids) if ps is None else [t for rid in ids for t in load(rid)]
             df = scanner.scan_combined(eng, part, named, seq_pssm, struct_pssm, args.minscore, args.pairing, ptype,
-                                       columns=streaming, prepacked=prepacked)
+                                       columns=streaming, prepacked=prepacked, min_seqstruct=args.min_seqstruct)
             if df is None:
                 if named is None:
                     named = load_many(ids) if ps is None else [t for rid in ids for t in load(rid)]
                 df = scanner.combine(scanner.scan_records(eng, part, seq_pssm, fasta.RNA, args.minscore),
-                                     scanner.scan_profiles(eng, named, struct_pssm, args.minscore, args.pairing, ptype))
+                                     scanner.scan_profiles(eng, named, struct_pssm, args.minscore, args.pairing, ptype),
+                                     args.min_seqstruct)
                 df = df[scanner.COMBINED_COLUMNS]
             return df
 
@@ -571,7 +581,7 @@ def main(argv=None, engine=None, out=None):
                 lambda part: scanner.scan_profiles(eng, part, struct_pssm, args.minscore, args.pairing, ptype),
                 rank, world, dist)
             if rank == 0:
-                final = scanner.combine(seq_results, struct_results)
+                final = scanner.combine(seq_results, struct_results, args.min_seqstruct)
     elif pair_files is not None:
         # sequence FASTA + structure FASTA holding the same records in the same order (rnascan.py:119-123): the letters of
         # both files go to the device as two code streams and a row needs seq > m AND struct > m there (what combine()'s
@@ -584,10 +594,10 @@ def main(argv=None, engine=None, out=None):
 
         def scan_both(part):
             a, b = part
-            df = scanner.scan_pair(eng, a, b, seq_pssm, struct_pssm, args.minscore, columns=streaming)
+            df = scanner.scan_pair(eng, a, b, seq_pssm, struct_pssm, args.minscore, columns=streaming, min_seqstruct=args.min_seqstruct)
             if df is None:                     # e.g. a record whose two strings differ in length: this batch's two tables, joined
                 df = scanner.combine(scanner.scan_records(eng, a, seq_pssm, fasta.RNA, args.minscore),
-                                     scanner.scan_records(eng, b, struct_pssm, fasta.STRUCT, args.minscore))
+                                     scanner.scan_records(eng, b, struct_pssm, fasta.STRUCT, args.minscore), args.min_seqstruct)
                 df = df[scanner.COMBINED_COLUMNS]
             return df
 
@@ -604,7 +614,7 @@ def main(argv=None, engine=None, out=None):
                                        sink=stream_to(scanner.SEQ_COLUMNS) if one_table else None)
         if rank == 0:
             if seq_type == "RNASS":
-                final = scanner.combine(seq_results, struct_results)
+                final = scanner.combine(seq_results, struct_results, args.min_seqstruct)
             elif seq_type == "RNA":
                 final = seq_results
             else:

@@ -268,6 +268,7 @@ int pfmscan::check_and_fill(pfmscan_ctx *ctx, const pfmscan_motif *mo, const uin
     a.struct_band = mo->struct_band;
     a.prio = ctx->tune.prio;
     a.dma_whole = ctx->tune.dma_whole;
+    a.thr_sum = -INFINITY;
     return PFMSCAN_OK;
 }
 
@@ -324,9 +325,9 @@ static HitSink dev_sink(int64_t *d_hit_pos, float *d_hit_seq, double *d_hit_stru
     return {d_hit_pos, nullptr, d_hit_seq, d_hit_struct, reinterpret_cast<unsigned long long *>(d_hit_count), 1, capacity};
 }
 
-int pfmscan_hits_dev(pfmscan_ctx *ctx, const pfmscan_motif *mo, const uint8_t *d_codes, const void *d_profile,
-                     int profile_dtype, int64_t n_pos, double thr_seq, double thr_struct, int64_t capacity,
-                     int64_t *d_hit_pos, float *d_hit_seq, double *d_hit_struct, uint64_t *d_hit_count, void *stream)
+static int hits_dev_impl(pfmscan_ctx *ctx, const pfmscan_motif *mo, const uint8_t *d_codes, const void *d_profile,
+                         int profile_dtype, int64_t n_pos, double thr_seq, double thr_struct, double thr_sum, int64_t capacity,
+                         int64_t *d_hit_pos, float *d_hit_seq, double *d_hit_struct, uint64_t *d_hit_count, void *stream)
 {
     ScanArgs a;
     int rc = check_and_fill(ctx, mo, d_codes, d_profile, profile_dtype, n_pos, a);
@@ -334,20 +335,40 @@ int pfmscan_hits_dev(pfmscan_ctx *ctx, const pfmscan_motif *mo, const uint8_t *d
     if (capacity < 0 || !d_hit_count || (capacity > 0 && !d_hit_pos))
         return fail(ctx, PFMSCAN_E_BADARG, "pfmscan_hits_dev: bad hit buffers");
     if (std::isnan(thr_seq) || std::isnan(thr_struct)) return fail(ctx, PFMSCAN_E_BADARG, "NaN threshold");
-    fill_hits(a, dev_sink(d_hit_pos, d_hit_seq, d_hit_struct, d_hit_count, capacity), mo->d_letters != nullptr, mo->d_struct != nullptr, thr_seq, thr_struct);
+    fill_hits(a, dev_sink(d_hit_pos, d_hit_seq, d_hit_struct, d_hit_count, capacity), mo->d_letters != nullptr, mo->d_struct != nullptr, thr_seq, thr_struct,
+              thr_sum);
     return do_launch(ctx, a, stream);
+}
+
+int pfmscan_hits_dev(pfmscan_ctx *ctx, const pfmscan_motif *mo, const uint8_t *d_codes, const void *d_profile,
+                     int profile_dtype, int64_t n_pos, double thr_seq, double thr_struct, int64_t capacity,
+                     int64_t *d_hit_pos, float *d_hit_seq, double *d_hit_struct, uint64_t *d_hit_count, void *stream)
+{
+    return hits_dev_impl(ctx, mo, d_codes, d_profile, profile_dtype, n_pos, thr_seq, thr_struct, -INFINITY, capacity, d_hit_pos, d_hit_seq,
+                         d_hit_struct, d_hit_count, stream);
+}
+
+// one fused pass (k_profile_sum / k_profile_fixed_sum / k_wide_sum), asynchronous on the caller's stream
+int pfmscan_hits_sum_dev(pfmscan_ctx *ctx, const pfmscan_motif *mo, const uint8_t *d_codes, const void *d_profile,
+                         int profile_dtype, int64_t n_pos, double thr_seq, double thr_struct, double thr_sum, int64_t capacity,
+                         int64_t *d_hit_pos, float *d_hit_seq, double *d_hit_struct, uint64_t *d_hit_count, void *stream)
+{
+    if (int rc = check_sum(ctx, mo, thr_sum)) return rc;
+    return hits_dev_impl(ctx, mo, d_codes, d_profile, profile_dtype, n_pos, thr_seq, thr_struct, thr_sum, capacity, d_hit_pos, d_hit_seq,
+                         d_hit_struct, d_hit_count, stream);
 }
 
 // ---- combined hits, candidate-then-verify ---------------------------------------------
 // One fused pass, or -- when the motif has both parts and the letter threshold is selective --
 // letters pass + structure verification at its hits.  Synchronises `st` when it takes two passes.
+// thr_sum: the joint threshold of pfmscan_hits_sum_* (-inf: none) -- part of the fused pass and of the verify phase
 static int hits_core(pfmscan_ctx *ctx, const pfmscan_motif *mo, const ScanArgs &base, double thr_seq, double thr_struct,
-                     const HitSink &sink, hipStream_t st, bool allow_two_phase)
+                     const HitSink &sink, hipStream_t st, bool allow_two_phase, double thr_sum = -INFINITY)
 {
     const int64_t n_pos = base.n_pos;
     const bool two = allow_two_phase && ctx->tune.two_phase && mo->d_letters && mo->d_struct && !std::isinf(thr_seq) && n_pos > 0;
     ScanArgs fused = base;
-    fill_hits(fused, sink, mo->d_letters != nullptr, mo->d_struct != nullptr, thr_seq, thr_struct);
+    fill_hits(fused, sink, mo->d_letters != nullptr, mo->d_struct != nullptr, thr_seq, thr_struct, thr_sum);
     if (!two) return do_launch(ctx, fused, st);
     // phase 1: letters only (1 B per position) -> candidates.  Measured on C3 (w = 12): letters pass 0.23 ms,
     // verify ~0.1 ms per 1 M candidates (0.3 % of the windows), fused pass 2.1 ms -> two passes pay while
@@ -498,8 +519,8 @@ int pfmscan_scan_letters_f64_host(pfmscan_ctx *ctx, const pfmscan_motif *mo, con
     return PFMSCAN_OK;
 }
 
-int pfmscan_hits_staged(pfmscan_ctx *ctx, const pfmscan_motif *mo, double thr_seq, double thr_struct, int64_t capacity,
-                        int64_t *hit_pos, float *hit_seq, double *hit_struct, int64_t *n_hits)
+static int hits_staged_impl(pfmscan_ctx *ctx, const pfmscan_motif *mo, double thr_seq, double thr_struct, double thr_sum, int64_t capacity,
+                            int64_t *hit_pos, float *hit_seq, double *hit_struct, int64_t *n_hits)
 {
     if (!n_hits) return fail(ctx, PFMSCAN_E_BADARG, "NULL argument");
     int rc = check_staged(ctx, mo);
@@ -515,13 +536,26 @@ int pfmscan_hits_staged(pfmscan_ctx *ctx, const pfmscan_motif *mo, double thr_se
     if ((rc = acquire_sink(ctx, hit_bufs(ctx), HIT_SHARDS, hit_shard_cap(capacity), ctx->stream, sink))) return rc;
     ScanArgs a;
     if ((rc = check_and_fill(ctx, mo, (const uint8_t *)ctx->codes.p, ctx->profile.p, ctx->staged_dtype, n_pos, a))) return rc;
-    if ((rc = hits_core(ctx, mo, a, thr_seq, thr_struct, sink, ctx->stream, true))) return rc;
+    if ((rc = hits_core(ctx, mo, a, thr_seq, thr_struct, sink, ctx->stream, true, thr_sum))) return rc;
     return finish_sorted_hits(ctx, sink, mo->d_letters != nullptr, mo->d_struct != nullptr, 0, n_pos, capacity, hit_pos, nullptr, hit_seq, hit_struct, n_hits);
 }
 
-int pfmscan_hits_host(pfmscan_ctx *ctx, const pfmscan_motif *mo, const uint8_t *codes, const void *profile,
-                      int profile_dtype, int64_t n_pos, double thr_seq, double thr_struct, int64_t capacity,
-                      int64_t *hit_pos, float *hit_seq, double *hit_struct, int64_t *n_hits)
+int pfmscan_hits_staged(pfmscan_ctx *ctx, const pfmscan_motif *mo, double thr_seq, double thr_struct, int64_t capacity,
+                        int64_t *hit_pos, float *hit_seq, double *hit_struct, int64_t *n_hits)
+{
+    return hits_staged_impl(ctx, mo, thr_seq, thr_struct, -INFINITY, capacity, hit_pos, hit_seq, hit_struct, n_hits);
+}
+
+int pfmscan_hits_sum_staged(pfmscan_ctx *ctx, const pfmscan_motif *mo, double thr_seq, double thr_struct, double thr_sum, int64_t capacity,
+                            int64_t *hit_pos, float *hit_seq, double *hit_struct, int64_t *n_hits)
+{
+    if (int rc = check_sum(ctx, mo, thr_sum)) return rc;
+    return hits_staged_impl(ctx, mo, thr_seq, thr_struct, thr_sum, capacity, hit_pos, hit_seq, hit_struct, n_hits);
+}
+
+static int hits_host_impl(pfmscan_ctx *ctx, const pfmscan_motif *mo, const uint8_t *codes, const void *profile,
+                          int profile_dtype, int64_t n_pos, double thr_seq, double thr_struct, double thr_sum, int64_t capacity,
+                          int64_t *hit_pos, float *hit_seq, double *hit_struct, int64_t *n_hits)
 {
     if (!ctx || !mo || !n_hits) return fail(ctx, PFMSCAN_E_BADARG, "NULL argument");
     if (n_pos < 0 || capacity < 0) return fail(ctx, PFMSCAN_E_BADARG, "negative size");
@@ -531,7 +565,22 @@ int pfmscan_hits_host(pfmscan_ctx *ctx, const pfmscan_motif *mo, const uint8_t *
     if (mo->d_struct && !profile) return fail(ctx, PFMSCAN_E_BADARG, "profile is NULL");
     int rc = pfmscan_stage(ctx, mo->d_letters ? codes : nullptr, mo->d_struct ? profile : nullptr, profile_dtype, n_pos);
     if (rc) return rc;
-    return pfmscan_hits_staged(ctx, mo, thr_seq, thr_struct, capacity, hit_pos, hit_seq, hit_struct, n_hits);
+    return hits_staged_impl(ctx, mo, thr_seq, thr_struct, thr_sum, capacity, hit_pos, hit_seq, hit_struct, n_hits);
+}
+
+int pfmscan_hits_host(pfmscan_ctx *ctx, const pfmscan_motif *mo, const uint8_t *codes, const void *profile,
+                      int profile_dtype, int64_t n_pos, double thr_seq, double thr_struct, int64_t capacity,
+                      int64_t *hit_pos, float *hit_seq, double *hit_struct, int64_t *n_hits)
+{
+    return hits_host_impl(ctx, mo, codes, profile, profile_dtype, n_pos, thr_seq, thr_struct, -INFINITY, capacity, hit_pos, hit_seq, hit_struct, n_hits);
+}
+
+int pfmscan_hits_sum_host(pfmscan_ctx *ctx, const pfmscan_motif *mo, const uint8_t *codes, const void *profile,
+                          int profile_dtype, int64_t n_pos, double thr_seq, double thr_struct, double thr_sum, int64_t capacity,
+                          int64_t *hit_pos, float *hit_seq, double *hit_struct, int64_t *n_hits)
+{
+    if (int rc = check_sum(ctx, mo, thr_sum)) return rc;
+    return hits_host_impl(ctx, mo, codes, profile, profile_dtype, n_pos, thr_seq, thr_struct, thr_sum, capacity, hit_pos, hit_seq, hit_struct, n_hits);
 }
 
 // ---- generic-alphabet letter hits in fp64 (structure letter strings: SURVEY 8f N4) ---------------------------

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "pfmscan_hits.hpp"
+#include "pfmscan_exact.hpp"
 
 namespace pfmscan {
 
@@ -30,11 +31,23 @@ int acquire_sink(pfmscan_ctx *ctx, const SinkBufs &b, int shards, int64_t shard_
     return PFMSCAN_OK;
 }
 
-void fill_hits(ScanArgs &a, const HitSink &k, bool has_seq, bool has_struct, double thr_seq, double thr_struct)
+int check_sum(pfmscan_ctx *ctx, const pfmscan_motif *mo, double thr_sum)
+{
+    if (!ctx || !mo) return fail(ctx, PFMSCAN_E_BADARG, "NULL ctx or motif");
+    if (!mo->d_letters || !mo->d_struct)
+        return fail(ctx, PFMSCAN_E_BADARG, "a threshold on LogOdds.SeqStruct needs a motif with a letter table AND a structure PSSM");
+    if (std::isnan(thr_sum)) return fail(ctx, PFMSCAN_E_BADARG, "NaN threshold");
+    return PFMSCAN_OK;
+}
+
+void fill_hits(ScanArgs &a, const HitSink &k, bool has_seq, bool has_struct, double thr_seq, double thr_struct, double thr_sum)
 {
     a.hits = 1;
     a.thr_seq = thr_seq;
     a.thr_struct = thr_struct;
+    a.thr_sum = (has_seq && has_struct) ? thr_sum : -INFINITY;
+    a.sum_band = sum_band(a.struct_band, a.thr_sum);
+    a.sum_margin0 = sum_margin0(a.sum_band);
     a.capacity = k.shard_cap;
     a.hit_pos = k.pos;
     a.hit_seq = has_seq ? k.seq : nullptr;

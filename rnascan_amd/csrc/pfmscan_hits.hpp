@@ -6,6 +6,7 @@
 // appends to shard b & (shards - 1).  A shard that overflowed while the total still fits has dropped hits, so the
 // verdict looks at the fullest shard as well as at the sum.
 #pragma once
+#include <cmath>
 #include <functional>
 
 #include "pfmscan_ctx.hpp"
@@ -58,7 +59,10 @@ inline int64_t pair_cand_shard_cap(int64_t n_pos) { return std::max<int64_t>(n_p
 // grows `b` to `shards` regions of `shard_cap` slots, zeroes the counters on `st` -> sink
 int acquire_sink(pfmscan_ctx *ctx, const SinkBufs &b, int shards, int64_t shard_cap, hipStream_t st, HitSink &sink);
 // the hit fields of `a` from a sink; has_seq / has_struct: which score columns the launch writes
-void fill_hits(ScanArgs &a, const HitSink &k, bool has_seq, bool has_struct, double thr_seq, double thr_struct);
+// thr_sum: the joint threshold on the printed LogOdds.SeqStruct (pfmscan_hits_sum_*; needs both score columns); -inf = none
+void fill_hits(ScanArgs &a, const HitSink &k, bool has_seq, bool has_struct, double thr_seq, double thr_struct, double thr_sum = -INFINITY);
+// the pfmscan_hits_sum_* argument check: both parts, no NaN
+int check_sum(pfmscan_ctx *ctx, const pfmscan_motif *mo, double thr_sum);
 // counters -> host: their sum and the fullest shard.  Synchronises `st`.
 int read_hit_counts(pfmscan_ctx *ctx, const unsigned long long *d_count, int shards, hipStream_t st, uint64_t &total, uint64_t &worst);
 // A sink filled on ctx->stream -> the caller's host arrays, sorted by position (by (position, motif) when the sink has a

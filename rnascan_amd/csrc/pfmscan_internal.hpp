@@ -65,6 +65,10 @@ struct ScanArgs {
     int prio;                    // k_profile: staging instructions at raised wave priority (Tuning::prio)
     int dma_whole;               // k_profile: the last LDS-DMA piece of a region in full (Tuning::dma_whole; default: only the lanes with needed bytes)
     int64_t pos_offset;          // added to every reported hit position (chunked host pipeline: position of the chunk in the stream)
+    // joint threshold on the printed LogOdds.SeqStruct (pfmscan_hits_sum_*; read by the *_sum kernels only, -inf everywhere else)
+    double thr_sum;              // hit <=> ... AND float64(round3(seq)) + struct > thr_sum
+    double sum_band;             // |that sum with the fast structure score - thr_sum| <= sum_band -> the window is scored again (pfmscan_exact.hpp)
+    double sum_margin0;          // constant part of the cheap superset test's margin (sum_maybe)
 };
 
 // Tuning knobs settable through the environment (read once per ctx), so that
@@ -82,6 +86,9 @@ struct Tuning {
     int credits = 1;        // hits over 4-letter alphabets, m <= 32: integer position-keyed prefilter (k_letters_cred) instead of
                             // the fp32 one (k_letters_pre); PFMSCAN_CREDITS=0 for A/B runs and tests
 };
+
+// true when a hits launch carries a joint threshold that can reject a window: the *_sum kernels run (thr_sum = -inf: the plain ones)
+inline bool sum_active(const ScanArgs &a) { return a.hits && a.thr_sum > -__builtin_inf(); }
 
 hipError_t launch_scan(const ScanArgs &a, const Tuning &t, hipStream_t stream, const char **what);
 // pfmscan_letters8.hip: fp64 letter hits through the single-letter integer prefilter (false: not applicable, take the exact

@@ -699,8 +699,9 @@ __device__ __forceinline__ void compute_tile(const PROF_T *prof_lds, const unsig
 
 // one tile per workgroup; overlap comes from several resident workgroups per CU
 // launch bound = the residency the LDS tile allows (4 workgroups/CU at V=5)
-template <int V, bool HAS_SEQ, typename PROF_T, bool FINITE, bool HITS>
-__global__ __launch_bounds__(BLOCK, 4) void k_profile(const ScanArgs a)
+// SUM: the fused hits pass with the joint threshold on LogOdds.SeqStruct (k_profile_sum below)
+template <int V, bool HAS_SEQ, typename PROF_T, bool FINITE, bool HITS, bool SUM>
+__device__ __forceinline__ void profile_body(const ScanArgs &a)
 {
     using L = ProfileLayout<V, PROF_T>;
     extern __shared__ __align__(16) unsigned char smem[];
@@ -725,10 +726,23 @@ __global__ __launch_bounds__(BLOCK, 4) void k_profile(const ScanArgs a)
                                              a.struct_pssm, m, la, acc_st, acc_sq);
     if (HITS) {
         settle_near<V, PROF_T>(a, reinterpret_cast<const PROF_T *>(smem), la, acc_st);
-        emit_tile_hits<V, HAS_SEQ>(a, tile0, la, acc_st, acc_sq);
+        emit_tile_hits<V, HAS_SEQ, SUM, PROF_T>(a, tile0, la, acc_st, acc_sq, reinterpret_cast<const PROF_T *>(smem));
     } else {
         emit_tile_wave<V, HAS_SEQ, PROF_T>(a, tile0, la, acc_st, acc_sq, smem, m);
     }
+}
+
+template <int V, bool HAS_SEQ, typename PROF_T, bool FINITE, bool HITS>
+__global__ __launch_bounds__(BLOCK, 4) void k_profile(const ScanArgs a)
+{
+    profile_body<V, HAS_SEQ, PROF_T, FINITE, HITS, false>(a);
+}
+
+// the fused combined hits pass with the third predicate  LogOdds.SeqStruct > a.thr_sum  (pfmscan_exact.hpp)
+template <int V, typename PROF_T, bool FINITE>
+__global__ __launch_bounds__(BLOCK, 4) void k_profile_sum(const ScanArgs a)
+{
+    profile_body<V, true, PROF_T, FINITE, true, true>(a);
 }
 
 // ---------------------------------------------------------------------------
@@ -827,11 +841,11 @@ __device__ __forceinline__ double struct_score_at_wide(const void *profile, int6
 // shard's CAPACITY spent 70 us launching 74k workgroups that read a count and left.)
 constexpr int STRUCT_AT_MAX_SHARDS = 64;
 
-template <typename PROF_T>
-__global__ __launch_bounds__(BLOCK) void k_struct_at(const ScanArgs a, const int64_t *__restrict__ cand_pos,
-                                                     const float *__restrict__ cand_seq,
-                                                     const unsigned long long *__restrict__ cand_count,
-                                                     const int64_t cand_shard_cap, const int cand_shards)
+template <typename PROF_T, bool SUM>
+__device__ __forceinline__ void struct_at_body(const ScanArgs &a, const int64_t *__restrict__ cand_pos,
+                                               const float *__restrict__ cand_seq,
+                                               const unsigned long long *__restrict__ cand_count,
+                                               const int64_t cand_shard_cap, const int cand_shards)
 {
     __shared__ int chunk_end[STRUCT_AT_MAX_SHARDS];     // inclusive prefix of ceil(n_s / 256)
     __shared__ int64_t shard_n[STRUCT_AT_MAX_SHARDS];
@@ -875,9 +889,37 @@ __global__ __launch_bounds__(BLOCK) void k_struct_at(const ScanArgs a, const int
                 score = struct_window_rounded(reinterpret_cast<const PROF_T *>(a.profile) + p * 7, m, [&](int j, int k) { return pssm[j * 7 + k]; });
             }
             mask = score > a.thr_struct ? 1u : 0u;
+            if constexpr (SUM) {                        // the joint threshold on the printed sum (pfmscan_exact.hpp)
+                if (mask) {
+                    const double *pssm = a.struct_pssm;
+                    const bool ok = sum_passes(sq, score, a.thr_sum, a.sum_band, a.sum_margin0, [&]() {
+                        return struct_window_rounded(reinterpret_cast<const PROF_T *>(a.profile) + p * 7, m, [&](int j, int k) { return pssm[j * 7 + k]; });
+                    });
+                    mask = ok ? 1u : 0u;
+                }
+            }
         }
         emit_hits_block<1>(mask, [&](int) { return p; }, [&](int) { return sq; }, [&](int) { return score; }, a);
     }
+}
+
+template <typename PROF_T>
+__global__ __launch_bounds__(BLOCK) void k_struct_at(const ScanArgs a, const int64_t *__restrict__ cand_pos,
+                                                     const float *__restrict__ cand_seq,
+                                                     const unsigned long long *__restrict__ cand_count,
+                                                     const int64_t cand_shard_cap, const int cand_shards)
+{
+    struct_at_body<PROF_T, false>(a, cand_pos, cand_seq, cand_count, cand_shard_cap, cand_shards);
+}
+
+// k_struct_at with the third predicate  LogOdds.SeqStruct > a.thr_sum  on the candidates that passed the structure threshold
+template <typename PROF_T>
+__global__ __launch_bounds__(BLOCK) void k_struct_at_sum(const ScanArgs a, const int64_t *__restrict__ cand_pos,
+                                                         const float *__restrict__ cand_seq,
+                                                         const unsigned long long *__restrict__ cand_count,
+                                                         const int64_t cand_shard_cap, const int cand_shards)
+{
+    struct_at_body<PROF_T, true>(a, cand_pos, cand_seq, cand_count, cand_shard_cap, cand_shards);
 }
 
 hipError_t launch_struct_at(const ScanArgs &a, const int64_t *cand_pos, const float *cand_seq,
@@ -888,6 +930,15 @@ hipError_t launch_struct_at(const ScanArgs &a, const int64_t *cand_pos, const fl
     if (cand_shards > STRUCT_AT_MAX_SHARDS) return hipErrorInvalidValue;
     const int64_t worst = (cand_shard_cap + BLOCK - 1) / BLOCK * cand_shards;
     const unsigned grid = (unsigned)std::min<int64_t>(worst, 2048);          // 8 workgroups per CU
+    if (sum_active(a)) {
+        if (a.profile_dtype == PFMSCAN_PROFILE_F64)
+            hipLaunchKernelGGL(k_struct_at_sum<double>, dim3(grid), dim3(BLOCK), 0, stream, a, cand_pos, cand_seq, cand_count,
+                               cand_shard_cap, cand_shards);
+        else
+            hipLaunchKernelGGL(k_struct_at_sum<float>, dim3(grid), dim3(BLOCK), 0, stream, a, cand_pos, cand_seq, cand_count,
+                               cand_shard_cap, cand_shards);
+        return hipGetLastError();
+    }
     if (a.profile_dtype == PFMSCAN_PROFILE_F64)
         hipLaunchKernelGGL(k_struct_at<double>, dim3(grid), dim3(BLOCK), 0, stream, a, cand_pos, cand_seq, cand_count,
                            cand_shard_cap, cand_shards);
@@ -1040,9 +1091,25 @@ static hipError_t launch_profile_inst(const ScanArgs &a, hipStream_t stream)
     return hipGetLastError();
 }
 
+template <typename PROF_T, bool FINITE>
+static hipError_t launch_profile_sum_inst(const ScanArgs &a, hipStream_t stream)
+{
+    using L = ProfileLayout<PROFILE_V, PROF_T>;
+    const unsigned grid = (unsigned)((a.n_pos + L::TILE - 1) / L::TILE);
+    const int lds = L::total(a.m, true, 1);
+    auto kern = k_profile_sum<PROFILE_V, PROF_T, FINITE>;
+    static std::atomic<uint64_t> configured{0};     // per instantiation, one bit per device
+    hipError_t e = allow_full_lds(reinterpret_cast<const void *>(kern), configured);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(BLOCK), lds, stream, a);
+    return hipGetLastError();
+}
+
 template <bool HAS_SEQ, typename PROF_T>
 static hipError_t launch_profile_v(const ScanArgs &a, hipStream_t stream)
 {
+    if (HAS_SEQ && sum_active(a))
+        return a.struct_finite ? launch_profile_sum_inst<PROF_T, true>(a, stream) : launch_profile_sum_inst<PROF_T, false>(a, stream);
     if (a.hits) {
         if (a.struct_finite) return launch_profile_inst<HAS_SEQ, PROF_T, true, true>(a, stream);
         return launch_profile_inst<HAS_SEQ, PROF_T, false, true>(a, stream);
@@ -1067,8 +1134,8 @@ static hipError_t launch_profile_t(const ScanArgs &a, hipStream_t stream)
 // straight from global memory (neighbouring threads read neighbouring bytes / rows; the tables through the caches).
 // Same outputs and hit rule as k_letters / k_profile in every mode.  No roofline claim: O(m) dependent loads per window.
 // ---------------------------------------------------------------------------
-template <typename PROF_T>
-__global__ __launch_bounds__(BLOCK) void k_wide(const ScanArgs a)
+template <typename PROF_T, bool SUM>
+__device__ __forceinline__ void wide_body(const ScanArgs &a)
 {
     const int m = a.m;
     const int64_t n_pos = a.n_pos;
@@ -1106,6 +1173,14 @@ __global__ __launch_bounds__(BLOCK) void k_wide(const ScanArgs a)
         }
         if (has_st) pass = pass && (st > a.thr_struct);
         if (has_seq) pass = pass && ((a.f64_hits ? sq : (double)(float)sq) > a.thr_seq);
+        if constexpr (SUM) {                            // the joint threshold on the printed sum (both parts present: the launcher checks)
+            if (pass) {
+                const double *pssm = a.struct_pssm;
+                pass = sum_passes((float)sq, st, a.thr_sum, a.sum_band, a.sum_margin0, [&]() {
+                    return struct_window_rounded(reinterpret_cast<const PROF_T *>(a.profile) + p * 7, m, [&](int j, int k) { return pssm[j * 7 + k]; });
+                });
+            }
+        }
         // a letters-only scan reports its fp64 score in hit_struct (k_letters does), a scan with a structure part the structure score
         emit_hits_block<1>(pass ? 1u : 0u, [&](int) { return p; }, [&](int) { return (float)sq; }, [&](int) { return has_st ? st : sq; }, a);
         return;
@@ -1116,12 +1191,31 @@ __global__ __launch_bounds__(BLOCK) void k_wide(const ScanArgs a)
     if (has_st && a.out_struct) a.out_struct[p] = st;
 }
 
+template <typename PROF_T>
+__global__ __launch_bounds__(BLOCK) void k_wide(const ScanArgs a)
+{
+    wide_body<PROF_T, false>(a);
+}
+
+template <typename PROF_T>
+__global__ __launch_bounds__(BLOCK) void k_wide_sum(const ScanArgs a)
+{
+    wide_body<PROF_T, true>(a);
+}
+
 static hipError_t launch_wide(const ScanArgs &a, hipStream_t stream)
 {
     if ((a.letter_table && !a.codes) || (a.struct_pssm && !a.profile)) return hipErrorInvalidValue;
     hipError_t e = hipSuccess;
     if (!std::getenv("PFMSCAN_WIDE_PLAIN") && launch_wide_letters(a, stream, &e)) return e;      // letters only: the slab kernel
     const unsigned grid = (unsigned)((a.n_pos + BLOCK - 1) / BLOCK);
+    if (sum_active(a) && a.letter_table && a.struct_pssm && !a.f64_hits) {
+        if (a.profile_dtype == PFMSCAN_PROFILE_F64)
+            hipLaunchKernelGGL(k_wide_sum<double>, dim3(grid), dim3(BLOCK), 0, stream, a);
+        else
+            hipLaunchKernelGGL(k_wide_sum<float>, dim3(grid), dim3(BLOCK), 0, stream, a);
+        return hipGetLastError();
+    }
     if (a.struct_pssm && a.profile_dtype == PFMSCAN_PROFILE_F64)
         hipLaunchKernelGGL(k_wide<double>, dim3(grid), dim3(BLOCK), 0, stream, a);
     else

@@ -65,11 +65,9 @@ int pfmscan::pipeline_chunks(pfmscan_ctx *ctx, const uint8_t *codes, const void 
     return PFMSCAN_OK;
 }
 
-extern "C" {
-
-int pfmscan_hits_pipeline_host(pfmscan_ctx *ctx, const pfmscan_motif *mo, const uint8_t *codes, const void *profile,
-                               int profile_dtype, int64_t n_pos, int64_t chunk_positions, double thr_seq, double thr_struct,
-                               int64_t capacity, int64_t *hit_pos, float *hit_seq, double *hit_struct, int64_t *n_hits)
+static int hits_pipeline_impl(pfmscan_ctx *ctx, const pfmscan_motif *mo, const uint8_t *codes, const void *profile,
+                              int profile_dtype, int64_t n_pos, int64_t chunk_positions, double thr_seq, double thr_struct, double thr_sum,
+                              int64_t capacity, int64_t *hit_pos, float *hit_seq, double *hit_struct, int64_t *n_hits)
 {
     if (!ctx || !mo || !n_hits) return fail(ctx, PFMSCAN_E_BADARG, "NULL argument");
     if (n_pos < 0 || capacity < 0) return fail(ctx, PFMSCAN_E_BADARG, "negative size");
@@ -93,12 +91,32 @@ int pfmscan_hits_pipeline_host(pfmscan_ctx *ctx, const pfmscan_motif *mo, const 
     rc = pipeline_chunks(ctx, has_seq ? codes : nullptr, profile, row_bytes, n_pos, chunk_positions, mo->m, [&](int b, int64_t a0, int64_t len) -> int {
         ScanArgs a;
         if (int crc = check_and_fill(ctx, mo, (const uint8_t *)ctx->pipe_codes[b].p, ctx->pipe_profile[b].p, profile_dtype, len, a)) return crc;
-        fill_hits(a, sink, has_seq, has_struct, thr_seq, thr_struct);
+        fill_hits(a, sink, has_seq, has_struct, thr_seq, thr_struct, thr_sum);
         a.pos_offset = a0;
         return do_launch(ctx, a, ctx->stream);
     });
     if (rc) return rc;
     return finish_sorted_hits(ctx, sink, has_seq, has_struct, 0, n_pos, capacity, hit_pos, nullptr, hit_seq, hit_struct, n_hits);
+}
+
+extern "C" {
+
+int pfmscan_hits_pipeline_host(pfmscan_ctx *ctx, const pfmscan_motif *mo, const uint8_t *codes, const void *profile,
+                               int profile_dtype, int64_t n_pos, int64_t chunk_positions, double thr_seq, double thr_struct,
+                               int64_t capacity, int64_t *hit_pos, float *hit_seq, double *hit_struct, int64_t *n_hits)
+{
+    return hits_pipeline_impl(ctx, mo, codes, profile, profile_dtype, n_pos, chunk_positions, thr_seq, thr_struct, -INFINITY, capacity, hit_pos,
+                              hit_seq, hit_struct, n_hits);
+}
+
+// every chunk is one fused launch of the *_sum kernels (as the plain form: no count read-back between chunks)
+int pfmscan_hits_sum_pipeline_host(pfmscan_ctx *ctx, const pfmscan_motif *mo, const uint8_t *codes, const void *profile,
+                                   int profile_dtype, int64_t n_pos, int64_t chunk_positions, double thr_seq, double thr_struct,
+                                   double thr_sum, int64_t capacity, int64_t *hit_pos, float *hit_seq, double *hit_struct, int64_t *n_hits)
+{
+    if (int rc = check_sum(ctx, mo, thr_sum)) return rc;
+    return hits_pipeline_impl(ctx, mo, codes, profile, profile_dtype, n_pos, chunk_positions, thr_seq, thr_struct, thr_sum, capacity, hit_pos,
+                              hit_seq, hit_struct, n_hits);
 }
 
 }  // extern "C"

@@ -218,9 +218,13 @@ __device__ __forceinline__ void emit_tile_wave(const ScanArgs &a, int64_t tile0,
     }
 }
 
-// hits of one tile: the thread's windows that pass the threshold(s) go through the workgroup's hit scan
-template <int V, bool HAS_SEQ>
-__device__ __forceinline__ void emit_tile_hits(const ScanArgs &a, int64_t tile0, int la, double (&acc_st)[V], double (&acc_sq)[V])
+// hits of one tile: the thread's windows that pass the threshold(s) go through the workgroup's hit scan.
+// SUM (the *_sum kernels, pfmscan_hits_sum_*): a window that passed both thresholds must also have its printed
+// LogOdds.SeqStruct above a.thr_sum -- cheap superset test for every such window, the float division, the near band and
+// the re-score from the staged tile (prof_lds) only behind it (pfmscan_exact.hpp)
+template <int V, bool HAS_SEQ, bool SUM = false, typename PROF_T = float>
+__device__ __forceinline__ void emit_tile_hits(const ScanArgs &a, int64_t tile0, int la, double (&acc_st)[V], double (&acc_sq)[V],
+                                               const PROF_T *prof_lds = nullptr)
 {
     const int64_t n_pos = a.n_pos;
     if (tile0 + V * BLOCK + a.m > n_pos) {          // workgroup-uniform: only the last tile(s) of the stream
@@ -234,7 +238,22 @@ __device__ __forceinline__ void emit_tile_hits(const ScanArgs &a, int64_t tile0,
     for (int v = 0; v < V; ++v) {
         bool pass = (tile0 + la + v < n_pos) && (acc_st[v] > a.thr_struct);
         if (HAS_SEQ) pass = pass && ((double)(float)acc_sq[v] > a.thr_seq);
+        if (SUM) pass = pass && sum_maybe((float)acc_sq[v], acc_st[v], a.thr_sum, a.sum_margin0);
         if (pass) mask |= 1u << v;
+    }
+    if constexpr (SUM) {
+        if (mask) {
+            const double *pssm = a.struct_pssm;
+            static_for<0, V>([&](auto vc) __attribute__((always_inline)) {      // (a rolled loop would index acc_st[] at run time)
+                constexpr int v = decltype(vc)::value;
+                if (mask & (1u << v)) {
+                    const bool ok = sum_passes((float)acc_sq[v], acc_st[v], a.thr_sum, a.sum_band, a.sum_margin0, [&]() {
+                        return struct_window_rounded(prof_lds + (la + v) * 7, a.m, [&](int j, int k) { return pssm[j * 7 + k]; });
+                    });
+                    if (!ok) mask &= ~(1u << v);
+                }
+            });
+        }
     }
     emit_hits_block<V>(
         mask, [&](int i) { return tile0 + la + i; }, [&](int i) { return (float)acc_sq[i]; },

@@ -248,8 +248,8 @@ __device__ __forceinline__ void emit_tile_wave_inside(const ScanArgs &a, int64_t
     }
 }
 
-template <int V, int MW, bool HAS_SEQ, typename PROF_T, bool FINITE, bool HITS>
-__global__ __launch_bounds__(BLOCK, 4) void k_profile_fixed(const ScanArgs a)
+template <int V, int MW, bool HAS_SEQ, typename PROF_T, bool FINITE, bool HITS, bool SUM>
+__device__ __forceinline__ void profile_fixed_body(const ScanArgs &a)
 {
     using L = ProfileLayout<V, PROF_T>;
     extern __shared__ __align__(16) unsigned char smem[];
@@ -269,12 +269,50 @@ __global__ __launch_bounds__(BLOCK, 4) void k_profile_fixed(const ScanArgs a)
                                                               la, acc_st, acc_sq);
     if (HITS) {
         settle_near<V, PROF_T>(a, reinterpret_cast<const PROF_T *>(smem), la, acc_st);
-        emit_tile_hits<V, HAS_SEQ>(a, tile0, la, acc_st, acc_sq);      // the fused combined filter: seq > thr && struct > thr
+        // the fused combined filter: seq > thr && struct > thr (SUM: && printed sum > thr_sum)
+        emit_tile_hits<V, HAS_SEQ, SUM, PROF_T>(a, tile0, la, acc_st, acc_sq, reinterpret_cast<const PROF_T *>(smem));
     }
     else if (ends_inside(tile0 + V * BLOCK + MW, a.n_pos))                    // workgroup-uniform: false only for the last tile(s) of the stream
         emit_tile_wave_inside<V, MW, HAS_SEQ, PROF_T>(a, tile0, acc_st, acc_sq, smem);
     else
         emit_tile_wave<V, HAS_SEQ, PROF_T>(a, tile0, la, acc_st, acc_sq, smem, MW);
+}
+
+template <int V, int MW, bool HAS_SEQ, typename PROF_T, bool FINITE, bool HITS>
+__global__ __launch_bounds__(BLOCK, 4) void k_profile_fixed(const ScanArgs a)
+{
+    profile_fixed_body<V, MW, HAS_SEQ, PROF_T, FINITE, HITS, false>(a);
+}
+
+// the fused combined hits pass with the third predicate  LogOdds.SeqStruct > a.thr_sum  (pfmscan_exact.hpp)
+template <int V, int MW, typename PROF_T, bool FINITE>
+__global__ __launch_bounds__(BLOCK, 4) void k_profile_fixed_sum(const ScanArgs a)
+{
+    profile_fixed_body<V, MW, true, PROF_T, FINITE, true, true>(a);
+}
+
+template <int MW, typename PROF_T, bool FINITE>
+static hipError_t launch_fixed_sum_inst(const ScanArgs &a, hipStream_t stream)
+{
+    constexpr int V = PROFILE_V;
+    using L = ProfileLayout<V, PROF_T>;
+    const unsigned grid = (unsigned)((a.n_pos + L::TILE - 1) / L::TILE);
+    const int lds = L::total(MW, true, 1);
+    auto kern = k_profile_fixed_sum<V, MW, PROF_T, FINITE>;
+    static std::atomic<uint64_t> configured{0};     // per instantiation, one bit per device
+    hipError_t e = allow_full_lds(reinterpret_cast<const void *>(kern), configured);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(BLOCK), lds, stream, a);
+    return hipGetLastError();
+}
+
+template <int MW>
+static hipError_t launch_fixed_sum_width(const ScanArgs &a, hipStream_t stream)
+{
+    const bool fin = a.struct_finite != 0;
+    if (a.profile_dtype == PFMSCAN_PROFILE_F64)
+        return fin ? launch_fixed_sum_inst<MW, double, true>(a, stream) : launch_fixed_sum_inst<MW, double, false>(a, stream);
+    return fin ? launch_fixed_sum_inst<MW, float, true>(a, stream) : launch_fixed_sum_inst<MW, float, false>(a, stream);
 }
 
 template <int MW, bool HAS_SEQ, typename PROF_T, bool FINITE, bool HITS>
@@ -334,6 +372,16 @@ bool launch_profile_fixed(const ScanArgs &a, hipStream_t stream, hipError_t *err
     if (const char *v = std::getenv("PFMSCAN_PROFILE_FIXED_MIN")) min_w = std::atoi(v);
     if (a.m < min_w) return false;
     bool taken = true;          // an instantiation may still decline (launch_fixed_inst)
+    if (sum_active(a)) {        // joint threshold: the *_sum instantiation of the width (both parts present: pfmscan_hits_sum_* checks)
+        if (!a.letter_table) return false;
+        switch (a.m) {
+#define FIXED_WIDTH(W) case W: *err = launch_fixed_sum_width<W>(a, stream); return true;
+        FIXED_WIDTH(4) FIXED_WIDTH(5) FIXED_WIDTH(6) FIXED_WIDTH(7) FIXED_WIDTH(8) FIXED_WIDTH(9) FIXED_WIDTH(10) FIXED_WIDTH(11)
+        FIXED_WIDTH(12) FIXED_WIDTH(13) FIXED_WIDTH(14) FIXED_WIDTH(15) FIXED_WIDTH(16) FIXED_WIDTH(17) FIXED_WIDTH(18)
+#undef FIXED_WIDTH
+        default: return false;
+        }
+    }
     switch (a.m) {
 #define FIXED_WIDTH(W) case W: *err = a.hits ? launch_fixed_width<W, true>(a, stream, &taken) : launch_fixed_width<W, false>(a, stream, &taken); return taken;
     FIXED_WIDTH(4) FIXED_WIDTH(5) FIXED_WIDTH(6) FIXED_WIDTH(7) FIXED_WIDTH(8) FIXED_WIDTH(9) FIXED_WIDTH(10) FIXED_WIDTH(11)

@@ -120,6 +120,19 @@ class HipEngine(object):
         self._stage(stream)
         return self.ctx.hits_staged(motif, thr_seq, thr_struct)
 
+    def hits_sum(self, stream, letter_table, struct_pssm, thr_seq, thr_struct, thr_sum, one_shot=True):
+        """``hits`` of a motif with both parts, with the joint threshold decided on the device: a window is kept iff
+        seq > thr_seq AND struct > thr_struct AND float64(round(float32 seq, 3)) + struct > thr_sum -- the printed
+        LogOdds.SeqStruct (pfmscan_hits_sum_*).  Either of the first two may be -inf.  Same staged / pipeline choice as
+        ``hits`` -> (pos, seq, struct)."""
+        motif = self._motif(letter_table, struct_pssm)
+        staged = self._staged is not None and self._staged[0] is stream and self._staged[1] == self.ctx.scratch_gen
+        if one_shot and not staged and stream.n_pos > PIPELINE_MIN:
+            self._staged = None
+            return self.ctx.hits_sum_pipeline_host(motif, stream.codes, stream.profile, thr_seq, thr_struct, thr_sum, PIPELINE_CHUNK)
+        self._stage(stream)
+        return self.ctx.hits_sum_staged(motif, thr_seq, thr_struct, thr_sum)
+
     def profile_colsums(self, stream):
         """per-record column sums of ``stream.profile`` -> float64 [n_records][7] (pfmscan_profile_colsums_*): the counts
         behind the structure background of an averaged-structure input (background.py).  Bit-reproducible: a record's
@@ -509,16 +522,32 @@ COMBINED_COLUMNS = ["Sequence_ID", "Description.Seq", "Motif_ID.Seq", "Start", "
                     "Description.Struct", "Motif_ID.Struct", "Sequence.Struct", "LogOdds.Struct", "LogOdds.SeqStruct"]
 
 
-def combine(seq_results, struct_results):
+def keep_seqstruct(rows, min_seqstruct):
+    """``--min-seqstruct T`` on finished rows (a DataFrame or compact columns): those whose PRINTED LogOdds.SeqStruct
+    exceeds T stay (strict; NaN never passes).  The one host-side form of the filter -- every path that does not decide
+    it on the device (two-FASTA letters mode, -t, the two-tables-plus-join fallbacks, an engine without ``hits_sum``)
+    ends here."""
+    if min_seqstruct is None or rows is None:
+        return rows
+    if isinstance(rows, dict):
+        keep = np.asarray(rows["LogOdds.SeqStruct"], dtype=np.float64) > float(min_seqstruct)
+        return rows if keep.all() else table.select_rows(rows, keep)
+    if not len(rows):
+        return rows
+    keep = rows["LogOdds.SeqStruct"].to_numpy(dtype=np.float64) > float(min_seqstruct)
+    return rows[keep].reset_index(drop=True)
+
+
+def combine(seq_results, struct_results, min_seqstruct=None):
     """rnascan.py:416-434: inner join on (Sequence_ID, Start, End); the combined
-    score is the sum of the two log-odds (float32 + float64 -> float64)."""
+    score is the sum of the two log-odds (float32 + float64 -> float64).  ``min_seqstruct``: keep_seqstruct."""
     result = pd.merge(seq_results, struct_results, on=["Sequence_ID", "Start", "End"])
     result = result.rename(columns={"Description_x": "Description.Seq", "Description_y": "Description.Struct",
                                     "Sequence_x": "Sequence.Seq", "Sequence_y": "Sequence.Struct",
                                     "Motif_ID_x": "Motif_ID.Seq", "Motif_ID_y": "Motif_ID.Struct",
                                     "LogOdds_x": "LogOdds.Seq", "LogOdds_y": "LogOdds.Struct"})
     result["LogOdds.SeqStruct"] = result["LogOdds.Seq"] + result["LogOdds.Struct"]
-    return result
+    return keep_seqstruct(result, min_seqstruct)
 
 
 def pair_motifs(seq_pssm, struct_pssm):
@@ -545,7 +574,7 @@ def pair_motifs(seq_pssm, struct_pssm):
 
 
 def scan_combined(engine, records, named_profiles, seq_pssm, struct_pssm, minscore, pairing="aligned",
-                  profile_dtype=np.float32, columns=False, prepacked=None):
+                  profile_dtype=np.float32, columns=False, prepacked=None, min_seqstruct=None):
     """Sequence PFMs + averaged-structure PFMs in ONE pass per PFM width (configs 3 and 5).
 
     Equivalent to ``combine(scan_main(fasta), scan_main(dir))`` for the records
@@ -554,6 +583,8 @@ def scan_combined(engine, records, named_profiles, seq_pssm, struct_pssm, minsco
     (rnascan.py:422-433 is an inner join of two independently thresholded tables); which pairs
     exist is ``pair_motifs``.  Returns None when the inputs cannot be paired one to one (duplicate ids,
     length mismatch, unpairable libraries); callers then take the two-table path.
+    ``min_seqstruct`` (``--min-seqstruct``): additionally the printed LogOdds.SeqStruct must exceed it, decided on the
+    device when the engine has ``hits_sum``.
 
     ``prepacked`` = (ids, letters, pack.Stream) instead of ``named_profiles``: the profiles of exactly these records,
     in this order, already in stream form (a slice of a packed profile store) -- used as they are when ids and
@@ -575,7 +606,7 @@ def scan_combined(engine, records, named_profiles, seq_pssm, struct_pssm, minsco
             # of the batch (up to 30 GB at 32 x RNASCAN_BATCH_POSITIONS) would change no score and would leave the mapped file
             stream = pack.Stream(batch.codes, prof, batch.offsets, batch.lengths)
             return _scan_combined_stream(engine, stream, batch, list(letters0), pairs_m, seq_pssm, struct_pssm, minscore, pairing,
-                                         columns)
+                                         columns, min_seqstruct)
         named_profiles = [(pids[r], letters0, pst.profile[int(pst.offsets[r]):int(pst.offsets[r] + pst.lengths[r])])
                           for r in range(len(pids))]
     by_id = {}
@@ -599,16 +630,17 @@ def scan_combined(engine, records, named_profiles, seq_pssm, struct_pssm, minsco
             return None
         profs.append(prof)
     stream = pack.Stream(batch.codes, pack.pack(profiles=profs, profile_dtype=profile_dtype).profile, batch.offsets, batch.lengths)
-    return _scan_combined_stream(engine, stream, batch, letters0, pairs_m, seq_pssm, struct_pssm, minscore, pairing, columns)
+    return _scan_combined_stream(engine, stream, batch, letters0, pairs_m, seq_pssm, struct_pssm, minscore, pairing, columns, min_seqstruct)
 
 
-def scan_pair(engine, seq_records, struct_records, seq_pssm, struct_pssm, minscore, columns=False):
+def scan_pair(engine, seq_records, struct_records, seq_pssm, struct_pssm, minscore, columns=False, min_seqstruct=None):
     """Sequence FASTA + structure FASTA in ONE call per motif pair (`rnascan -p .. -q .. seqs.fa structs.fa`,
     rnascan.py:119-123): equivalent to ``combine(scan_main(seqs), scan_main(structs))`` (rnascan.py:416-434) when the
     two batches hold the same records -- same ids in the same order, each id once, same lengths.  The letters of both
     files go to the device as two code streams with the same layout; a window is reported for the motif pair (a, b) iff
     seq_a > minscore AND struct_b > minscore.  Returns None when the batches cannot be paired that way (the caller then
-    makes the two tables and joins them)."""
+    makes the two tables and joins them).  ``min_seqstruct``: the rows are filtered on the printed sum (keep_seqstruct; the
+    structure score of this mode already is the reference-order value)."""
     pairs_m = pair_motifs(seq_pssm, struct_pssm)
     if pairs_m is None:
         return None
@@ -625,10 +657,11 @@ def scan_pair(engine, seq_records, struct_records, seq_pssm, struct_pssm, minsco
     def rows(pos, sq, st, m, seq_ids, struct_ids):
         rec, start = stream.locate(pos)
         lo_seq, lo_st = np.round(sq, 3), _lib.round_decimals(st, 3)       # rnascan.py:273 on a float32 / on a Python float
-        return {"_rec": rec, "Sequence_ID": sb.id_column(rec), "Description.Seq": sb.description_column(rec), "Motif_ID.Seq": seq_ids,
-                "Start": start + 1, "End": start + m, "Sequence.Seq": sb.windows(pos, m), "LogOdds.Seq": lo_seq,
-                "Description.Struct": tb.description_column(rec), "Motif_ID.Struct": struct_ids, "Sequence.Struct": tb.windows(pos, m),
-                "LogOdds.Struct": lo_st, "LogOdds.SeqStruct": lo_seq.astype(np.float64) + lo_st}
+        return keep_seqstruct(
+            {"_rec": rec, "Sequence_ID": sb.id_column(rec), "Description.Seq": sb.description_column(rec), "Motif_ID.Seq": seq_ids,
+             "Start": start + 1, "End": start + m, "Sequence.Seq": sb.windows(pos, m), "LogOdds.Seq": lo_seq,
+             "Description.Struct": tb.description_column(rec), "Motif_ID.Struct": struct_ids, "Sequence.Struct": tb.windows(pos, m),
+             "LogOdds.Struct": lo_st, "LogOdds.SeqStruct": lo_seq.astype(np.float64) + lo_st}, min_seqstruct)
 
     by_width = {}
     for a, b in pairs_m:
@@ -657,9 +690,13 @@ def scan_pair(engine, seq_records, struct_records, seq_pssm, struct_pssm, minsco
     return _finish(tables, COMBINED_COLUMNS, ["Start", "Motif_ID.Seq", "Motif_ID.Struct"], columns)
 
 
-def _scan_combined_stream(engine, stream, batch, letters0, pairs_m, seq_pssm, struct_pssm, minscore, pairing, columns):
-    """the combined hit table of one packed batch (codes + profile rows of the same records)"""
+def _scan_combined_stream(engine, stream, batch, letters0, pairs_m, seq_pssm, struct_pssm, minscore, pairing, columns,
+                          min_seqstruct=None):
+    """the combined hit table of one packed batch (codes + profile rows of the same records).  With ``min_seqstruct`` and an
+    engine that has ``hits_sum`` every pair is one thresholded device call (also at -m ' -inf', and for libraries: one call per
+    pair on the staged stream); otherwise the finished rows are filtered (keep_seqstruct)."""
     thr = float(minscore)
+    on_device = min_seqstruct is not None and hasattr(engine, "hits_sum")
     tables = []
     by_width = {}
     for a, b in pairs_m:
@@ -667,7 +704,16 @@ def _scan_combined_stream(engine, stream, batch, letters0, pairs_m, seq_pssm, st
     for m, group in by_width.items():
         tabs = [seq_pssm[a].letter_table(pack.RNA_LETTERS) for a, _ in group]
         pssms = [struct_matrix(struct_pssm[b], letters0, pairing) for _, b in group]
-        if len(group) > 1 and np.isfinite(thr) and m <= LIBRARY_MAX_M:
+        if on_device:
+            parts = []
+            for k in range(len(group)):
+                pos, sq, st = engine.hits_sum(stream, tabs[k], pssms[k], thr, thr, float(min_seqstruct), one_shot=len(pairs_m) == 1)
+                parts.append((pos, np.full(pos.size, k, dtype=np.int32), sq, st))
+            if len(parts) > 1:                     # (position, pair index) order, as the library kernel gives it
+                pos, mo = np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts])
+                order = np.lexsort((mo, pos))
+                parts = [(pos[order], mo[order], np.concatenate([p[2] for p in parts])[order], np.concatenate([p[3] for p in parts])[order])]
+        elif len(group) > 1 and np.isfinite(thr) and m <= LIBRARY_MAX_M:
             pos, mo, sq, st = engine.library_hits(stream, np.stack(tabs), np.stack(pssms), thr, thr, one_shot=len(by_width) == 1)
             parts = [(pos, mo, sq, st)]
         else:
@@ -678,7 +724,7 @@ def _scan_combined_stream(engine, stream, batch, letters0, pairs_m, seq_pssm, st
         for pos, mo, sq, st in parts:
             rec, start = stream.locate(pos)
             lo_seq = np.round(sq, 3)
-            tables.append({
+            tables.append(keep_seqstruct({
                 "_rec": rec,
                 "Sequence_ID": batch.id_column(rec),
                 "Description.Seq": batch.description_column(rec),
@@ -686,7 +732,7 @@ def _scan_combined_stream(engine, stream, batch, letters0, pairs_m, seq_pssm, st
                 "Sequence.Seq": table.Windows(stream.codes, pos, m, pack.RNA_LETTERS),
                 "LogOdds.Seq": lo_seq, "Description.Struct": "",
                 "Motif_ID.Struct": table.Indexed([b for _, b in group], mo), "Sequence.Struct": ".",
-                "LogOdds.Struct": st, "LogOdds.SeqStruct": lo_seq.astype(np.float64) + st})
+                "LogOdds.Struct": st, "LogOdds.SeqStruct": lo_seq.astype(np.float64) + st}, None if on_device else min_seqstruct))
     # one table: (position, pair index) order = (record, Start, Motif_ID.Seq, Motif_ID.Struct)
     return _finish(tables, COMBINED_COLUMNS, ["Start", "Motif_ID.Seq", "Motif_ID.Struct"], columns)
 

@@ -102,6 +102,24 @@ def _rows(col, a, b):
     return col[a:b]
 
 
+def select_rows(columns, keep):
+    """the rows of compact columns where the boolean array ``keep`` holds, every column in its own kind"""
+    keep = np.asarray(keep, dtype=bool)
+    out = {}
+    for name, col in columns.items():
+        if isinstance(col, Indexed):
+            out[name] = Indexed(col.values, col.index[keep])
+        elif isinstance(col, Spans):
+            out[name] = Spans(col.buffer, col.spans, col.index[keep])
+        elif isinstance(col, Windows):
+            out[name] = Windows(col.codes, col.pos[keep], col.m, col.letters, col.cased)
+        elif column_length(col) is None:
+            out[name] = col
+        else:
+            out[name] = np.asarray(col)[keep]
+    return out
+
+
 def to_frame(columns, order=None):
     """compact columns -> pandas DataFrame (the non-streaming consumers: joins, multi-rank gathers, the API)"""
     import pandas as pd

@@ -59,7 +59,7 @@
 extern "C" {
 #endif
 
-#define PFMSCAN_ABI_VERSION 13
+#define PFMSCAN_ABI_VERSION 14
 #define PFMSCAN_NCODE   8      /* columns of a letter table */
 #define PFMSCAN_SEP     7      /* separator / foreign-letter code */
 #define PFMSCAN_NSTRUCT 7      /* columns of a structure profile / structure PSSM */
@@ -386,6 +386,66 @@ int pfmscan_library_hits_pipeline_host(pfmscan_ctx *ctx, pfmscan_library *lib,
                                        int64_t n_pos, int64_t chunk_positions, const double *thr_seq,
                                        const double *thr_struct, int64_t capacity, int64_t *hit_pos,
                                        int32_t *hit_motif, float *hit_seq, double *hit_struct, int64_t *n_hits);
+
+/* ---- libraries with a joint threshold on LogOdds.SeqStruct: decided in the library kernel ---------------------------------
+ * The joint filter of pfmscan_hits_sum_* -- the printed LogOdds.SeqStruct of combine() (rnascan.py:416-434) -- for every
+ * pair of a multi-PFM library (pfmutil.py:89-133) in ONE pass (k_library<.., SUM>).  The library must have letter tables AND
+ * structure PSSMs and be scanned over profile rows (else PFMSCAN_E_BADARG).  Hit of pair k at window p <=>
+ *   seq_k(p) > thr_seq[k]  and  struct_k(p) > thr_struct[k]  and  (double)round3(seq_k(p)) + struct_k(p) > thr_sum[k]
+ * exactly as pfmscan_hits_sum_* decides it for pair k alone (strict; same near-band re-score, same reported scores).
+ * thr_sum: HOST array of n doubles; NaN is PFMSCAN_E_BADARG; thr_sum[k] = -inf for every k runs the plain kernels and
+ * returns the plain call's hits bit for bit.  thr_seq[k] MAY be -inf here: the kernel's integer prefilter is built for
+ *   thr_eff[k] = max(thr_seq[k], thr_sum[k] - (an upper bound on struct_k) - rounding terms)      (csrc/pfmscan_exact.hpp),
+ * a superset filter -- the exact pass still compares with thr_seq, thr_struct and thr_sum themselves.  The bound is
+ * row_sum_max times the sum of the PSSM's non-negative row maxima; it holds when every profile row a scorable window touches
+ * (every row not under code 7) is finite, non-negative and sums to at most row_sum_max -- what
+ * pfmscan_profile_row_bound_* measures.  A motif with a +inf PSSM cell, or row_sum_max = INFINITY, is not tightened
+ * (thr_eff = thr_seq); a motif whose thr_eff is -inf gives PFMSCAN_E_BADARG with pfmscan_library_hits_*'s message before
+ * anything is written.
+ *   _dev     takes row_sum_max from the CALLER: a promise about the rows (INFINITY promises nothing).  A false promise costs
+ *            hits: windows over rows that break it may be dropped without any error.  Asynchronous under the conditions of
+ *            pfmscan_library_hits_dev (the cached tables are keyed on thr_eff and thr_sum too); reads nothing home.
+ *   _staged, _host  take no promise: they measure the staged stream's row bound themselves (once per staging).
+ * Hit arrays, counts, ordering and the capacity protocol: as the pfmscan_library_hits_* counterpart.  There is no pipeline
+ * form (the bound is needed for the whole stream before its first chunk is scanned), and letter libraries keep filtering
+ * finished rows. */
+int pfmscan_library_hits_sum_dev(pfmscan_ctx *ctx, pfmscan_library *lib,
+                                 const uint8_t *d_codes, const void *d_profile,
+                                 int profile_dtype, int64_t n_pos, const double *thr_seq,
+                                 const double *thr_struct, const double *thr_sum, double row_sum_max,
+                                 int64_t capacity, int64_t *d_hit_pos, int32_t *d_hit_motif,
+                                 float *d_hit_seq, double *d_hit_struct, uint64_t *d_hit_count,
+                                 void *stream);
+int pfmscan_library_hits_sum_staged(pfmscan_ctx *ctx, pfmscan_library *lib,
+                                    const double *thr_seq, const double *thr_struct,
+                                    const double *thr_sum, int64_t capacity, int64_t *hit_pos,
+                                    int32_t *hit_motif, float *hit_seq, double *hit_struct,
+                                    int64_t *n_hits);
+int pfmscan_library_hits_sum_host(pfmscan_ctx *ctx, pfmscan_library *lib,
+                                  const uint8_t *codes, const void *profile, int profile_dtype,
+                                  int64_t n_pos, const double *thr_seq, const double *thr_struct,
+                                  const double *thr_sum, int64_t capacity, int64_t *hit_pos,
+                                  int32_t *hit_motif, float *hit_seq, double *hit_struct,
+                                  int64_t *n_hits);
+/* The row bound of a profile stream: the largest fp64 row sum (columns 0..6 ascending, float32 rows widened first) over the
+ * positions whose code (bits 0-2) is not 7 -- rows under separators and foreign letters are skipped, every window covering one
+ * scores NaN on the sequence side -- or +inf when such a row holds a NaN, an infinite or a negative entry; 0 when no row
+ * counts.  One defined bit pattern (a maximum does not depend on the order).  d_codes may be NULL: every row counts.
+ * _dev writes one double to d_out, asynchronous on `stream`; _staged returns the staged stream's value, cached until the
+ * next pfmscan_stage.  Both keep their per-workgroup partials in scratch the ctx owns (as every entry point does, see the
+ * top of this file): ONE row-bound call in flight per ctx -- a second one on another stream, or a pfmscan_library_hits_sum_staged
+ * / _host beside a _dev call, would share the partials and may return a wrong (too small) bound, which costs hits.  The first
+ * _dev call of a ctx allocates that scratch (a few KB, one synchronous hipMalloc); every later one is asynchronous. */
+int pfmscan_profile_row_bound_dev(pfmscan_ctx *ctx, const uint8_t *d_codes, const void *d_profile,
+                                  int profile_dtype, int64_t n_pos, double *d_out, void *stream);
+int pfmscan_profile_row_bound_staged(pfmscan_ctx *ctx, double *row_sum_max);
+/* Diagnostic (host only, no device needed): thr_eff_out[k] = the letters threshold the prefilter of
+ * pfmscan_library_hits_sum_* is built for (see above): letter_tables [n][m][8], struct_pssms [n][m][7], thr_seq / thr_sum /
+ * thr_eff_out [n].  The letter tables are those of pfmscan_library_create: a 4-letter alphabet, columns 4..7 NaN (else
+ * PFMSCAN_E_BADARG, as for NaN thresholds or a NaN row_sum_max).  Every window whose three predicates hold has (double)seq > thr_eff; tests check that by brute force. */
+int pfmscan_library_sum_thresholds(const double *letter_tables, const double *struct_pssms,
+                                   int n_motifs, int m, const double *thr_seq,
+                                   const double *thr_sum, double row_sum_max, double *thr_eff_out);
 
 /* ---- LETTER libraries: the structure side as letter strings (SURVEY 8f N1 x N4) -----------------------------------
  * The reference scans structure FASTA files (`-q pfm structs.fa`, and `-p pfm -q pfm seqs.fa structs.fa`;

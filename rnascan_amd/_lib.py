@@ -22,7 +22,7 @@ NCODE = 8
 NSTRUCT = 7
 MAX_M = 64            # widest PFM of the tuned kernels and of PFM libraries
 MAX_WIDTH = 4096      # widest PFM accepted (wider than MAX_M: the plain rolled-loop kernel)
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 # every symbol include/pfmscan.h declares (checked by tests/test_abi.py)
 SYMBOLS = [
@@ -44,6 +44,8 @@ SYMBOLS = [
     "pfmscan_average_dev", "pfmscan_average_host", "pfmscan_average_stage", "pfmscan_fragment_ids",
     "pfmscan_profile_colsums_dev", "pfmscan_profile_colsums_host", "pfmscan_profile_colsums_staged",
     "pfmscan_hits_sum_dev", "pfmscan_hits_sum_staged", "pfmscan_hits_sum_host", "pfmscan_hits_sum_pipeline_host",
+    "pfmscan_library_hits_sum_dev", "pfmscan_library_hits_sum_staged", "pfmscan_library_hits_sum_host",
+    "pfmscan_profile_row_bound_dev", "pfmscan_profile_row_bound_staged", "pfmscan_library_sum_thresholds",
 ]
 MAX_COVER = 1024      # largest coverage of a row the averaging accepts
 AVG_OK, AVG_DOTBRACKET, AVG_UNCOVERED, AVG_COVER, AVG_BAD_TABLE = range(5)   # what a rejected averaging names
@@ -138,6 +140,12 @@ def load():
     L.pfmscan_library_hits_dev.argtypes = [vp, vp, vp, vp, i32, i64, vp, vp, i64, vp, vp, vp, vp, vp, vp]
     L.pfmscan_library_hits_staged.argtypes = [vp, vp, vp, vp, i64, vp, vp, vp, vp, ctypes.POINTER(i64)]
     L.pfmscan_library_hits_host.argtypes = [vp, vp, vp, vp, i32, i64, vp, vp, i64, vp, vp, vp, vp, ctypes.POINTER(i64)]
+    L.pfmscan_library_hits_sum_dev.argtypes = [vp, vp, vp, vp, i32, i64, vp, vp, vp, dbl, i64, vp, vp, vp, vp, vp, vp]
+    L.pfmscan_library_hits_sum_staged.argtypes = [vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, ctypes.POINTER(i64)]
+    L.pfmscan_library_hits_sum_host.argtypes = [vp, vp, vp, vp, i32, i64, vp, vp, vp, i64, vp, vp, vp, vp, ctypes.POINTER(i64)]
+    L.pfmscan_profile_row_bound_dev.argtypes = [vp, vp, vp, i32, i64, vp, vp]
+    L.pfmscan_profile_row_bound_staged.argtypes = [vp, ctypes.POINTER(dbl)]
+    L.pfmscan_library_sum_thresholds.argtypes = [vp, vp, i32, i32, vp, vp, dbl, vp]
     L.pfmscan_hits_pipeline_host.argtypes = [vp, vp, vp, vp, i32, i64, i64, dbl, dbl, i64, vp, vp, vp, ctypes.POINTER(i64)]
     L.pfmscan_library_hits_pipeline_host.argtypes = [vp, vp, vp, vp, i32, i64, i64, vp, vp, i64, vp, vp, vp, vp, ctypes.POINTER(i64)]
     L.pfmscan_debug_credit_table.argtypes = [vp, i32, dbl, i32, vp, ctypes.POINTER(dbl)]
@@ -1013,6 +1021,58 @@ class Context(object):
         self.stage(codes if lib.has_letters else None, profile if lib.has_struct else None)
         return self.library_hits_staged(lib, thr_seq, thr_struct, capacity)
 
+    def library_hits_sum_staged(self, lib, thr_seq, thr_struct, thr_sum, capacity=None):
+        """library_hits_staged of a seq + struct library with the joint threshold ``LogOdds.SeqStruct > thr_sum[k]`` on the
+        printed sum, decided in the library kernel (pfmscan_library_hits_sum_staged).  thr_seq may be -inf: ValueError when
+        a motif's effective letters threshold (``library_sum_thresholds``) is -inf too."""
+        n = int(self._L.pfmscan_staged_positions(self._h))
+        if n < 0:
+            raise ValueError("no stream staged (call stage first)")
+        ts, tt = lib.thresholds(thr_seq, thr_struct)
+        tj = np.ascontiguousarray(np.broadcast_to(np.asarray(thr_sum, dtype=np.float64), (lib.n,)))
+        cap = int(capacity) if capacity is not None else max(4096, n // 16)
+        while True:
+            pos = np.empty(cap, dtype=np.int64)
+            mo = np.empty(cap, dtype=np.int32)
+            sq = np.empty(cap, dtype=np.float32)
+            st = np.empty(cap, dtype=np.float64)
+            k = ctypes.c_int64(0)
+            rc = self._L.pfmscan_library_hits_sum_staged(self._h, lib._h, _ptr(ts), _ptr(tt), _ptr(tj), cap, _ptr(pos), _ptr(mo),
+                                                         _ptr(sq), _ptr(st), ctypes.byref(k))
+            if rc == E_CAPACITY and capacity is None:
+                cap = int(k.value)
+                continue
+            self._check(rc, k.value)
+            k = int(k.value)
+            return pos[:k].copy(), mo[:k].copy(), sq[:k].copy(), st[:k].copy()
+
+    def library_hits_sum_host(self, lib, codes, profile, thr_seq, thr_struct, thr_sum, capacity=None):
+        self.stage(codes, profile)
+        return self.library_hits_sum_staged(lib, thr_seq, thr_struct, thr_sum, capacity)
+
+    def library_hits_sum_dev(self, lib, d_codes, d_profile, profile_dtype, n_pos, thr_seq, thr_struct, thr_sum, row_sum_max, capacity,
+                             d_hit_pos, d_hit_motif, d_hit_seq, d_hit_struct, d_hit_count, stream=None):
+        """asynchronous on ``stream``; ``row_sum_max``: the caller's promise about the profile rows (inf: none), see
+        pfmscan_library_hits_sum_dev; hits unordered, *d_hit_count = total (above capacity = incomplete)"""
+        ts, tt = lib.thresholds(thr_seq, thr_struct)
+        tj = np.ascontiguousarray(np.broadcast_to(np.asarray(thr_sum, dtype=np.float64), (lib.n,)))
+        self._check(self._L.pfmscan_library_hits_sum_dev(self._h, lib._h, _ptr(d_codes), _ptr(d_profile), int(profile_dtype),
+                                                         int(n_pos), _ptr(ts), _ptr(tt), _ptr(tj), float(row_sum_max), int(capacity),
+                                                         _ptr(d_hit_pos), _ptr(d_hit_motif), _ptr(d_hit_seq), _ptr(d_hit_struct),
+                                                         _ptr(d_hit_count), _ptr(stream)))
+
+    def profile_row_bound_staged(self):
+        """the staged profile's row bound: the largest fp64 row sum over the rows not under code 7, inf when one of them holds
+        a NaN, infinite or negative entry (pfmscan_profile_row_bound_staged; cached until the next stage)"""
+        v = ctypes.c_double(0.0)
+        self._check(self._L.pfmscan_profile_row_bound_staged(self._h, ctypes.byref(v)))
+        return v.value
+
+    def profile_row_bound_dev(self, d_codes, d_profile, profile_dtype, n_pos, d_out, stream=None):
+        """the same for device arrays: one float64 to ``d_out``, asynchronous on ``stream``"""
+        self._check(self._L.pfmscan_profile_row_bound_dev(self._h, _ptr(d_codes), _ptr(d_profile), int(profile_dtype), int(n_pos),
+                                                          _ptr(d_out), _ptr(stream)))
+
     def library_hits_pipeline_host(self, lib, codes, profile=None, thr_seq=None, thr_struct=None, chunk_positions=0, capacity=None):
         """library_hits_host for host streams of any length (numpy arrays or memory maps): chunked, the upload of the next
         chunk overlaps the scan of the current one, device scratch = two chunks; nothing stays staged"""
@@ -1218,6 +1278,26 @@ def credit_table(letter_table, thr_seq, bits=16):
     if rc != OK:
         raise ValueError("pfmscan_debug_credit_table: bad argument")
     return out, slack.value
+
+
+def library_sum_thresholds(letter_tables, struct_pssms, thr_seq, thr_sum, row_sum_max):
+    """Host-only diagnostic (no device needed): the letters thresholds the library kernel's prefilter is built for under
+    joint thresholds ``thr_sum`` on the printed LogOdds.SeqStruct -> float64 [n].  letter_tables [n][m][8], struct_pssms
+    [n][m][7], thr_seq / thr_sum scalars or [n], ``row_sum_max`` the profile's row bound (inf: nothing is known about the
+    rows -> thr_seq comes back).  Every window that passes all three predicates has float64(seq) > thr_eff."""
+    L = load()
+    T = np.ascontiguousarray(letter_tables, dtype=np.float64)
+    P = np.ascontiguousarray(struct_pssms, dtype=np.float64)
+    if T.ndim != 3 or T.shape[2] != NCODE or P.ndim != 3 or P.shape[2] != NSTRUCT or P.shape[:2] != T.shape[:2]:
+        raise ValueError("letter_tables must be [n][m][8] and struct_pssms [n][m][7]")
+    n, m = T.shape[:2]
+    ts = np.ascontiguousarray(np.broadcast_to(np.asarray(thr_seq, dtype=np.float64), (n,)))
+    tj = np.ascontiguousarray(np.broadcast_to(np.asarray(thr_sum, dtype=np.float64), (n,)))
+    out = np.empty(n, dtype=np.float64)
+    rc = L.pfmscan_library_sum_thresholds(_ptr(T), _ptr(P), n, m, _ptr(ts), _ptr(tj), float(row_sum_max), _ptr(out))
+    if rc != OK:
+        raise ValueError("pfmscan_library_sum_thresholds: bad argument")
+    return out
 
 
 def library8_credits(letter_table, thr):

@@ -119,7 +119,7 @@ void pfmscan_ctx_destroy(pfmscan_ctx *ctx)
                       &ctx->lib_motif, &ctx->lib_seq, &ctx->lib_struct, &ctx->lib_count, &ctx->pipe_codes[0], &ctx->pipe_codes[1],
                       &ctx->pipe_profile[0], &ctx->pipe_profile[1], &ctx->codes2, &ctx->db_in, &ctx->db_out,
                       &ctx->db_tree, &ctx->db_part, &ctx->db_marks, &ctx->db_tiles, &ctx->db_flags,
-                      &ctx->avg_tab, &ctx->avg_blk, &ctx->avg_out, &ctx->bg_tab, &ctx->bg_part, &ctx->bg_blk, &ctx->bg_sums})
+                      &ctx->avg_tab, &ctx->avg_blk, &ctx->avg_out, &ctx->bg_tab, &ctx->bg_part, &ctx->bg_blk, &ctx->bg_sums, &ctx->rb_part})
         release(*b);
     upload_release(ctx);
     place_release_all(ctx);
@@ -449,6 +449,7 @@ int pfmscan_stage(pfmscan_ctx *ctx, const uint8_t *codes, const void *profile, i
     }
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));     // the caller may reuse its buffers
     ctx->staged_n = n_pos;
+    ++ctx->stage_serial;
     ctx->staged_dtype = profile ? profile_dtype : PFMSCAN_PROFILE_NONE;
     ctx->staged_codes = codes != nullptr;
     ctx->staged_profile = profile != nullptr;

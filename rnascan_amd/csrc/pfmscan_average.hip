@@ -393,6 +393,7 @@ int pfmscan_average_stage(pfmscan_ctx *ctx, const uint8_t *codes, int64_t n_pos,
     if (rc) return rc;
     if (n_rows) *n_rows = rows;
     ctx->staged_n = rows;
+    ++ctx->stage_serial;
     ctx->staged_dtype = out_dtype;
     ctx->staged_codes = false;
     ctx->staged_profile = true;

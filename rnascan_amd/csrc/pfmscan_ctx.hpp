@@ -50,6 +50,7 @@ struct pfmscan_ctx {
     DevBuf db_in, db_out, db_tree, db_part, db_marks, db_tiles, db_flags;   // dot-bracket annotation (pfmscan_dotbracket.hip)
     DevBuf avg_tab, avg_blk, avg_out;           // fragment averaging (pfmscan_average.hip): tables + T, verdicts, host rows
     DevBuf bg_tab, bg_part, bg_blk, bg_sums;    // profile column sums (pfmscan_background.hip): record tables, piece sums, verdicts, record sums
+    DevBuf rb_part;                             // profile row bound (pfmscan_rowbound.hip): workgroup partials + the result
     DevBuf pipe_codes[2], pipe_profile[2];      // chunked host pipeline: double-buffered chunk of the stream
     hipEvent_t pipe_copied[2] = {nullptr, nullptr}, pipe_scanned[2] = {nullptr, nullptr};
     // host ranges known to be read-only mappings of files (pfmscan_upload_source_file): the staged uploader preads them
@@ -68,6 +69,10 @@ struct pfmscan_ctx {
     int64_t staged_n = -1;
     int staged_dtype = PFMSCAN_PROFILE_NONE;
     bool staged_codes = false, staged_profile = false, staged_codes2 = false;
+    int64_t stage_serial = 0;                   // counts the stagings: what is cached WITH the staged stream carries the serial it was made for
+    // row bound of the staged profile (pfmscan_profile_row_bound_staged), valid while row_bound_serial == stage_serial
+    double row_bound = 0.0;
+    int64_t row_bound_serial = -1;
     // candidate-then-verify: the last full letters pass was selective -> skip the pilot next time
     bool two_phase_hot = false;
     // pfmscan_place.hip: sets of arrays placed together (PlaceSet *), and a line about the last allocation
@@ -95,6 +100,8 @@ void place_release_all(pfmscan_ctx *ctx);   // pfmscan_place.hip
 // pfmscan_dotbracket.hip: dot-bracket codes d_in -> structure-letter codes d_out on `st` (see pfmscan_dotbracket_annotate_dev)
 int dotbracket_annotate(pfmscan_ctx *ctx, const uint8_t *d_in, uint8_t *d_out, int64_t n, const uint8_t *map,
                         int64_t *d_counts, int64_t *host_counts, int64_t *first_bad, hipStream_t st);
+// pfmscan_rowbound.hip: the row bound of the staged stream (staged_n > 0 with a profile), measured once per staging.  Synchronises ctx->stream.
+int staged_row_bound(pfmscan_ctx *ctx, double *row_sum_max);
 inline bool misaligned(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; }
 
 }  // namespace pfmscan

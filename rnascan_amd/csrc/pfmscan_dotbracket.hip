@@ -643,6 +643,7 @@ int pfmscan_dotbracket_stage(pfmscan_ctx *ctx, const uint8_t *codes, int64_t n_p
     if (rc) return rc;
     if (which == 0) {
         ctx->staged_n = n_pos;
+        ++ctx->stage_serial;
         ctx->staged_dtype = PFMSCAN_PROFILE_NONE;
         ctx->staged_codes = true;
         ctx->staged_profile = false;

@@ -43,6 +43,7 @@
 #pragma once
 #include <float.h>
 #include <math.h>
+#include <algorithm>
 #include <cmath>
 #include <hip/hip_runtime.h>
 
@@ -100,6 +101,95 @@ inline double sum_band(double struct_band_, double thr_sum)
 }
 // host: the constant part of the cheap test's margin (rounded up)
 inline double sum_margin0(double sum_band_) { return (0.0005 + sum_band_) * (1.0 + 0x1p-50); }
+
+// ---- the joint threshold ahead of a LIBRARY's prefilter (pfmscan_library_hits_sum_*) --------------------------------
+// k_library's phase A needs a finite letters threshold for its credit tables; with a joint threshold T_k one follows
+// from an upper bound on the structure score.  Let S be the profile's row bound (pfmscan_profile_row_bound_*: every row
+// a scorable window touches has finite entries >= 0 whose fp64 sum, c ascending, is <= S) and P the motif's PSSM with
+// no +inf cell.
+//   * rows.  The REAL sum of a row's entries is sigma <= s (1 + u)^6 with s its fp64 sum and u = 2^-53 (six rounded
+//     additions of non-negative terms); SUM_ROW_UP = 1 + 2^-50 > (1 + u)^6 gives sigma <= S_up = up(S SUM_ROW_UP).
+//   * one row-dot.  Row j of P with a NaN or -inf cell: the product with that cell is NaN (NaN cell, or entry 0 times
+//     -inf) or -inf, and a sum holding one of them is NaN or -inf, never +inf: nan_to_num gives 0 or -DBL_MAX, both
+//     <= 0.  All cells finite: the real dot is sum_c r_c P_jc <= sigma max(0, max_c P_jc).  With hi_j = max(0, max of the
+//     cells of row j that are neither NaN nor -inf) every row-dot is, in real arithmetic, <= S_up hi_j.
+//   * the window.  U = up(S_up up(sum_j hi_j)) bounds the real score; every operation of the host's evaluation is
+//     rounded UP (next_up after each), so U is at least the real bound.  The score the kernel decides on is a computed
+//     one, fast (F) or re-scored (R): each is a sum of the same <= 7 m products through at most 7 + m roundings and lies
+//     within gamma(8 m) A of the real value, A = sum |r_jc P_jc| <= S_up sum_j max_c |P_jc| (finite cells).
+//     err = up(16 m u S_up sum_j max_c |P_jc|) > gamma(8 m) A covers it for ANY S (struct_band only does for entries up
+//     to STRUCT_ROW_MAX), and no partial sum overflows to +inf while U + err is finite (the positive part of every partial
+//     sum is <= U; an overflow towards -inf only lowers the score).  So  st <= U + max(struct_band, err) =: U + B  for the
+//     structure score that enters the decision.
+//   * the printed sum is fl(z + st), z = float64(round3(f)) <= f + 0.0005 + 3.01 u32 |f| (above; u32 = 2^-24) for
+//     |f| <= ROUND3_SAFE.  f is the float32 of a sequential fp64 sum of m letters: |f| <= Fk (1 + m u)(1 + u32) with
+//     Fk = sum_j max_c |L_jc| (finite cells; a window over a -inf cell scores -inf and is no hit), so
+//     3.01 u32 |f| <= FT = up(ROUND3_C u32 Fk (1 + 2^-20)).
+//     With  e = down(down(down(down(T - U) - B) - 0.0005 (1 + 2^-50)) - FT)  (every subtraction rounded DOWN) a window
+//     with f <= e has, in real arithmetic,  z + st <= e + 0.0005 + FT + U + B <= T,  and rounding to fp64 is monotone and T
+//     is an fp64 number: fl(z + st) <= T, the window is no hit.  So every hit has (double) f > e as well as > thr_seq:
+//         thr_eff = max(thr_seq, e)
+//     is a threshold phase A may build its credits for -- a superset filter: the credits never drop a window with
+//     (double) f > thr (pfmscan_library_api.hip), and phase B decides with the real thr_seq, thr_struct and T.
+//   * no tightening (thr_eff = thr_seq) for a motif with a +inf PSSM cell (no bound), a +inf / NaN letter cell (the
+//     prefilter is off for it anyway), Fk > ROUND3_SAFE (the round3 bound does not hold), S = +inf or NaN (no promise
+//     about the rows), T = -inf, or whenever e comes out NaN.
+constexpr double SUM_ROW_UP = 1.0 + 0x1p-50;
+inline double next_up(double x) { return std::nextafter(x, INFINITY); }
+inline double next_down(double x) { return std::nextafter(x, -INFINITY); }
+
+// host: the pieces of the bound for one motif: letters [m][8] (columns 0..3 count), pssm [m][7]
+struct SumBound {
+    double U = 0.0, B = 0.0, FT = 0.0, Fk = 0.0;
+    bool ok = false;                           // false: one of the switch-off conditions holds
+};
+inline SumBound sum_bound(const double *letters, const double *pssm, int m, double row_sum_max)
+{
+    SumBound b;
+    if (!(row_sum_max >= 0.0) || !(row_sum_max < INFINITY)) return b;
+    double hi_sum = 0.0, abs_sum = 0.0, fk = 0.0;
+    for (int j = 0; j < m; ++j) {
+        double hi = 0.0, mx = 0.0, lmx = 0.0;
+        for (int c = 0; c < 7; ++c) {
+            const double p = pssm[j * 7 + c];
+            if (p == INFINITY) return b;
+            if (std::isnan(p) || p == -INFINITY) continue;
+            hi = std::max(hi, p);
+            mx = std::max(mx, std::fabs(p));
+        }
+        for (int c = 0; c < 4; ++c) {
+            const double l = letters[j * 8 + c];
+            if (std::isnan(l) || l == INFINITY) return b;
+            if (l > -INFINITY) lmx = std::max(lmx, std::fabs(l));
+        }
+        hi_sum = next_up(hi_sum + hi);
+        abs_sum = next_up(abs_sum + mx);
+        fk = next_up(fk + lmx);
+    }
+    if (!(fk <= ROUND3_SAFE)) return b;
+    const double s_up = next_up(row_sum_max * SUM_ROW_UP);
+    b.U = next_up(s_up * hi_sum);
+    const double err = next_up(next_up(16.0 * (double)m * 0x1p-53 * s_up) * abs_sum);
+    b.B = std::max(struct_band(pssm, m), err);
+    b.Fk = fk;
+    b.FT = next_up(next_up(ROUND3_C * 0x1p-24 * (1.0 + 0x1p-20)) * fk);
+    b.ok = true;
+    return b;
+}
+// host: the letters threshold phase A of a library may use for one motif under the joint threshold thr_sum
+inline double sum_thr_eff(const double *letters, const double *pssm, int m, double thr_seq, double thr_sum, double row_sum_max)
+{
+    if (!(thr_sum > -INFINITY)) return thr_seq;
+    if (thr_sum == INFINITY) return INFINITY;              // nothing exceeds +inf
+    const SumBound b = sum_bound(letters, pssm, m, row_sum_max);
+    if (!b.ok) return thr_seq;
+    double e = next_down(thr_sum - b.U);
+    e = next_down(e - b.B);
+    e = next_down(e - 0.0005 * (1.0 + 0x1p-50));
+    e = next_down(e - b.FT);
+    if (std::isnan(e)) return thr_seq;
+    return std::max(thr_seq, e);
+}
 
 // np.round(float32, 3), bit for bit: multiply, rint, divide, each rounded to float32 (no contraction, IEEE division)
 __device__ __forceinline__ float round3(float x)

@@ -203,6 +203,9 @@ struct LibArgs {
     float *hit_seq;
     double *hit_struct;
     unsigned long long *hit_count;
+    // (last: the fields above keep the kernel-argument offsets of the plain kernels)
+    const double *thr_sum;                // null, or [3][nmp] (k_library<.., SUM>): joint thresholds on the printed LogOdds.SeqStruct, their
+                                          // re-score bands (sum_band) and cheap-test margins (sum_margin0), pfmscan_exact.hpp; a team's lie stride_thr on
 };
 size_t lib_group_bytes(int m, int npair, bool has_struct, int np_bucket);   // LDS bytes per motif group of a pass
 size_t lib_queue_bytes(int np_bucket);                          // LDS bytes of the wave queues

@@ -359,7 +359,12 @@ __device__ __forceinline__ int lib_dispatch(const int npair, const int g, const 
 }
 
 // NG = motif groups of the pass, NP = pair rows the code is unrolled for (8 / 16 / 32 for m <= 16 / 32 / 64)
-template <int NG, int NP, typename PROF_T, bool HAS_STRUCT>
+// SUM (pfmscan_library_hits_sum_*; profile rows only): phase B also asks for the printed LogOdds.SeqStruct
+// float64(round3(seq)) + struct > thr_sum[motif] (rnascan.py:416-434; sum_passes in pfmscan_exact.hpp, as k_profile_sum does).
+// The credits of phase A are then built for thr_eff = max(thr_seq, thr_sum - the bound on a structure score), the
+// thresholds phase B compares with are the caller's.  thr_sum and its band and margin stay in global memory: the few
+// lanes that get that far read them, the LDS carve-up and with it the pass layout are those of the plain kernel.
+template <int NG, int NP, typename PROF_T, bool HAS_STRUCT, bool SUM = false>
 __global__ __launch_bounds__(lib_block(NP)) void k_library(const LibArgs a)
 {
     constexpr int LIB_BLOCK = lib_block(NP);
@@ -398,6 +403,7 @@ __global__ __launch_bounds__(lib_block(NP)) void k_library(const LibArgs a)
     const double *g_letters = a.letters + (size_t)team * a.stride_letters;
     const double *g_pssm = HAS_STRUCT ? a.pssm + (size_t)team * a.stride_pssm : nullptr;
     const double *g_thr_seq = a.thr_seq + (size_t)team * a.stride_thr, *g_thr_struct = HAS_STRUCT ? a.thr_struct + (size_t)team * a.stride_thr : nullptr;
+    [[maybe_unused]] const double *g_thr_sum = SUM ? a.thr_sum + (size_t)team * a.stride_thr : nullptr;      // [3][NMP]: thr_sum, sum_band, sum_margin0
     const int motif_base = a.motif_base + team * NMP;
     const int bid = (int)blockIdx.x - team_b0;      // workgroup index inside the team
 
@@ -559,6 +565,15 @@ __global__ __launch_bounds__(lib_block(NP)) void k_library(const LibArgs a)
                                                        [&](int j, int k) { return pssm[((size_t)(j * 4 + (k >> 1)) * NMP + mo) * 2 + (k & 1)]; });
                     }
                     ok = st > thr_t[mo];
+                    if constexpr (SUM) {
+                        if (ok) {
+                            const double *sp = g_thr_sum + mo;
+                            ok = sum_passes(f, st, sp[0], sp[NMP], sp[2 * NMP], [&]() {
+                                return struct_window_rounded(reinterpret_cast<const PROF_T *>(a.profile) + ps * 7, m,
+                                                             [&](int j, int k) { return pssm[((size_t)(j * 4 + (k >> 1)) * NMP + mo) * 2 + (k & 1)]; });
+                            });
+                        }
+                    }
                 }
             }
         }
@@ -722,10 +737,10 @@ int lib_pick_ng(int np_bucket, int want_groups, int max_groups)
     return best;
 }
 
-template <int NG, int NP, typename PROF_T, bool HAS_STRUCT>
+template <int NG, int NP, typename PROF_T, bool HAS_STRUCT, bool SUM = false>
 static hipError_t launch_library_inst(const LibArgs &a, unsigned grid, size_t lds, hipStream_t stream)
 {
-    auto kern = k_library<NG, NP, PROF_T, HAS_STRUCT>;
+    auto kern = k_library<NG, NP, PROF_T, HAS_STRUCT, SUM>;
     static std::atomic<uint64_t> configured{0};     // per instantiation, one bit per device
     hipError_t e = allow_dynamic_lds(reinterpret_cast<const void *>(kern), configured, 160 * 1024);
     if (e != hipSuccess) return e;
@@ -738,6 +753,10 @@ static hipError_t launch_library_ng(const LibArgs &a, unsigned grid, size_t lds,
 {
     if (!a.pssm) return launch_library_inst<NG, NP, float, false>(a, grid, lds, stream);
     if (a.profile_dtype == PROFILE_LETTERS2) return launch_library_inst<NG, NP, uint8_t, true>(a, grid, lds, stream);     // two-FASTA library
+    if (a.thr_sum) {                                     // joint threshold on the printed sum (profile rows)
+        if (a.profile_dtype == PFMSCAN_PROFILE_F64) return launch_library_inst<NG, NP, double, true, true>(a, grid, lds, stream);
+        return launch_library_inst<NG, NP, float, true, true>(a, grid, lds, stream);
+    }
     if (a.profile_dtype == PFMSCAN_PROFILE_F64) return launch_library_inst<NG, NP, double, true>(a, grid, lds, stream);
     return launch_library_inst<NG, NP, float, true>(a, grid, lds, stream);
 }

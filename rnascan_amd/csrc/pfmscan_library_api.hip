@@ -37,7 +37,8 @@ struct LibPass {
     size_t pairs_off = 0;      // uint16 elements into d_pairs
     size_t letters_off = 0;    // doubles into d_letters
     size_t pssm_off = 0;       // doubles into d_pssm
-    size_t thr_off = 0;        // doubles into d_thr: [nmp] seq thresholds, then [nmp] structure thresholds
+    size_t thr_off = 0;        // doubles into d_thr: [nmp] seq thresholds, [nmp] structure thresholds, then (seq + struct libraries over
+                               // profile rows) [3][nmp] joint thresholds, their bands and margins (LibArgs::thr_sum)
 };
 
 // Credits of ONE motif at threshold thr (see the header comment): pairsum [npair][16], out [npair][16].
@@ -126,6 +127,13 @@ struct pfmscan_library {
     std::vector<uint16_t> h_pairs;     // staging of the thresholded credit tables
     std::vector<double> h_thr;
     std::vector<double> cur_seq, cur_struct, eps;   // thresholds the device tables were built for
+    // joint threshold on the printed sum (pfmscan_library_hits_sum_*; seq + struct libraries over profile rows): the host copies
+    // the bound of pfmscan_exact.hpp is computed from, and what the device tables were built for.  cur_eff are the letters
+    // thresholds the CREDITS stand for (thr_seq of a plain call, max(thr_seq, thr_sum - bound) of a sum call): tables are reused only
+    // when they match too, or credits tightened for one call would drop the hits of the next
+    std::vector<double> h_letters, h_pssm;          // [n][m][8], [n][m][7] as handed in
+    std::vector<double> band;                       // [n] struct_band of each motif
+    std::vector<double> cur_eff, cur_sum;
     bool thr_valid = false;
 };
 
@@ -198,8 +206,15 @@ static int create_seq_library(pfmscan_ctx *ctx, const double *letter_tables, con
     lib->np_bucket = lib_np_bucket(m);
     lib->has_struct = struct_pssms != nullptr;
     lib->pair = struct_pssms != nullptr && ncol == 8;
-    if (struct_pssms && ncol == 7)
-        for (int k = 0; k < n_motifs; ++k) lib->struct_band = std::max(lib->struct_band, struct_band(struct_pssms + (size_t)k * m * 7, m));
+    if (struct_pssms && ncol == 7) {
+        lib->band.resize((size_t)n_motifs);
+        for (int k = 0; k < n_motifs; ++k) {
+            lib->band[(size_t)k] = struct_band(struct_pssms + (size_t)k * m * 7, m);
+            lib->struct_band = std::max(lib->struct_band, lib->band[(size_t)k]);
+        }
+        lib->h_letters.assign(letter_tables, letter_tables + (size_t)n_motifs * m * 8);
+        lib->h_pssm.assign(struct_pssms, struct_pssms + (size_t)n_motifs * m * 7);
+    }
     if (struct_pssms && ncol == 7 && !std::getenv("PFMSCAN_FORCE_GENERIC")) {
         lib->all_finite = true;
         for (size_t i = 0; i < (size_t)n_motifs * m * 7 && lib->all_finite; ++i) lib->all_finite = std::isfinite(struct_pssms[i]);
@@ -237,7 +252,7 @@ static int create_seq_library(pfmscan_ctx *ctx, const double *letter_tables, con
         pairs_elems += (size_t)ps.ng * npair * 16 * 8;
         letters_elems += (size_t)m * 4 * ps.nmp;
         pssm_elems += (size_t)m * 8 * ps.nmp;
-        thr_elems += (size_t)2 * ps.nmp;
+        thr_elems += (size_t)5 * ps.nmp;
         base += ps.n_real;
         lib->passes.push_back(ps);
     }
@@ -414,7 +429,9 @@ int pfmscan_library_info(const pfmscan_library *lib, int *n_motifs, int *m, int 
 }  // extern "C"
 
 // (re)build the thresholded credit tables when the thresholds changed; uploads on `st`
-static int lib_set_thresholds(pfmscan_ctx *ctx, pfmscan_library *lib, const double *thr_seq, const double *thr_struct, hipStream_t st)
+// thr_sum (seq + struct libraries over profile rows; null = none): the joint thresholds, row_sum_max the profile's row bound
+static int lib_set_thresholds(pfmscan_ctx *ctx, pfmscan_library *lib, const double *thr_seq, const double *thr_struct, hipStream_t st,
+                              const double *thr_sum = nullptr, double row_sum_max = INFINITY)
 {
     const int n = lib->n, npair = lib->npair;
     if (!lib->has_letters && !lib->letters8) {            // structure-only: the thresholds are the only per-call table
@@ -470,13 +487,20 @@ static int lib_set_thresholds(pfmscan_ctx *ctx, pfmscan_library *lib, const doub
         lib->thr_valid = true;
         return PFMSCAN_OK;
     }
+    std::vector<double> eff(thr_seq, thr_seq + n), tsum((size_t)n, -INFINITY);
     for (int k = 0; k < n; ++k) {
-        if (std::isnan(thr_seq[k]) || (lib->has_struct && std::isnan(thr_struct[k]))) return lib_fail(ctx, PFMSCAN_E_BADARG, "NaN threshold");
-        if (thr_seq[k] == -INFINITY)
+        if (std::isnan(thr_seq[k]) || (lib->has_struct && std::isnan(thr_struct[k])) || (thr_sum && std::isnan(thr_sum[k])))
+            return lib_fail(ctx, PFMSCAN_E_BADARG, "NaN threshold");
+        if (thr_sum) {
+            tsum[(size_t)k] = thr_sum[k];
+            eff[(size_t)k] = sum_thr_eff(lib->h_letters.data() + (size_t)k * lib->m * 8, lib->h_pssm.data() + (size_t)k * lib->m * 7, lib->m,
+                                         thr_seq[k], thr_sum[k], row_sum_max);
+        }
+        if (eff[(size_t)k] == -INFINITY)
             return lib_fail(ctx, PFMSCAN_E_BADARG, "library hits need a finite sequence threshold (every window would be a hit; use the all-scores entry points)");
     }
     if (lib->thr_valid && std::equal(thr_seq, thr_seq + n, lib->cur_seq.begin()) &&
-        (!lib->has_struct || std::equal(thr_struct, thr_struct + n, lib->cur_struct.begin())))
+        (!lib->has_struct || std::equal(thr_struct, thr_struct + n, lib->cur_struct.begin())) && eff == lib->cur_eff && tsum == lib->cur_sum)
         return PFMSCAN_OK;
     HIP_TRY(ctx, hipStreamSynchronize(st));              // an earlier upload may still read the staging vectors
     lib->thr_valid = false;
@@ -492,12 +516,20 @@ static int lib_set_thresholds(pfmscan_ctx *ctx, pfmscan_library *lib, const doub
             if (l >= ps.n_real) {                         // padding motif: all credits 0, never flagged
                 lib->h_thr[ps.thr_off + l] = INFINITY;
                 lib->h_thr[ps.thr_off + ps.nmp + l] = INFINITY;
+                lib->h_thr[ps.thr_off + 2 * ps.nmp + l] = INFINITY;
                 continue;
             }
             const int k = ps.motif_base + l;
             lib->h_thr[ps.thr_off + l] = thr_seq[k];
             lib->h_thr[ps.thr_off + ps.nmp + l] = lib->has_struct ? thr_struct[k] : -INFINITY;
-            lib->eps[k] = build_credits(lib->pairsum.data() + (size_t)k * npair * 16, npair, thr_seq[k], cr.data(), bits);
+            if (thr_sum) {
+                const double sb = sum_band(lib->band[(size_t)k], thr_sum[k]);
+                lib->h_thr[ps.thr_off + 2 * ps.nmp + l] = thr_sum[k];
+                lib->h_thr[ps.thr_off + 3 * ps.nmp + l] = sb;
+                lib->h_thr[ps.thr_off + 4 * ps.nmp + l] = sum_margin0(sb);
+            }
+            // the credits stand for eff[k] (= thr_seq[k] without a joint threshold); phase B compares with the thresholds above
+            lib->eps[k] = build_credits(lib->pairsum.data() + (size_t)k * npair * 16, npair, eff[(size_t)k], cr.data(), bits);
             for (int t = 0; t < npair; ++t)               // kernel layout [pair row][group][entry][4 dwords]
                 for (int i = 0; i < 16; ++i) {
                     uint32_t *entry = words + ps.pairs_off / 2 + (((size_t)t * ps.ng + g) * 16 + i) * 4;
@@ -512,6 +544,8 @@ static int lib_set_thresholds(pfmscan_ctx *ctx, pfmscan_library *lib, const doub
     HIP_TRY(ctx, hipMemcpyAsync(lib->d_thr, lib->h_thr.data(), lib->thr_elems * 8, hipMemcpyHostToDevice, st));
     lib->cur_seq.assign(thr_seq, thr_seq + n);
     if (lib->has_struct) lib->cur_struct.assign(thr_struct, thr_struct + n);
+    lib->cur_eff = eff;
+    lib->cur_sum = tsum;
     lib->thr_valid = true;
     return PFMSCAN_OK;
 }
@@ -520,7 +554,7 @@ constexpr int64_t LIB_SEG = (int64_t)1 << LIB_SEG_SHIFT;        // windows per w
 
 // every pass of the library over [0, n_pos); asynchronous on `st`
 static int lib_run(pfmscan_ctx *ctx, pfmscan_library *lib, const uint8_t *d_codes, const void *d_profile, int profile_dtype,
-                   int64_t n_pos, const HitSink &sink, hipStream_t st, int64_t pos_offset = 0)
+                   int64_t n_pos, const HitSink &sink, hipStream_t st, int64_t pos_offset = 0, bool sum = false)
 {
     if (lib->letters8) {
         // generic-alphabet letter library: its passes one after the other (each re-reads only the 1-byte codes)
@@ -643,6 +677,7 @@ static int lib_run(pfmscan_ctx *ctx, pfmscan_library *lib, const uint8_t *d_code
             a.pssm = lib->has_struct ? lib->d_pssm + ps.pssm_off : nullptr;
             a.thr_seq = lib->d_thr + ps.thr_off;
             a.thr_struct = lib->d_thr + ps.thr_off + ps.nmp;
+            a.thr_sum = sum ? lib->d_thr + ps.thr_off + 2 * ps.nmp : nullptr;
             a.struct_finite = lib->all_finite ? 1 : 0;
             a.struct_band = lib->struct_band;
             a.m = lib->m;
@@ -762,12 +797,26 @@ __global__ __launch_bounds__(PACK_BLOCK) void k_lib_pack(const int64_t *__restri
 
 }  // namespace pfmscan
 
-extern "C" {
+// the pfmscan_library_hits_sum_* argument check; *any = some motif has a joint threshold that can reject a window (none: the plain
+// kernels run, as for an infinite thr_sum of pfmscan_hits_sum_*)
+static int lib_check_sum(pfmscan_ctx *ctx, const pfmscan_library *lib, const double *thr_sum, bool *any)
+{
+    if (!ctx || !lib) return lib_fail(ctx, PFMSCAN_E_BADARG, "NULL ctx or library");
+    if (!lib->has_letters || !lib->has_struct || lib->pair || lib->letters8)
+        return lib_fail(ctx, PFMSCAN_E_BADARG, "a threshold on LogOdds.SeqStruct needs a library of letter tables AND structure PSSMs over profile rows");
+    if (!thr_sum) return lib_fail(ctx, PFMSCAN_E_BADARG, "threshold arrays are NULL");
+    *any = false;
+    for (int k = 0; k < lib->n; ++k) {
+        if (std::isnan(thr_sum[k])) return lib_fail(ctx, PFMSCAN_E_BADARG, "NaN threshold");
+        *any = *any || thr_sum[k] > -INFINITY;
+    }
+    return PFMSCAN_OK;
+}
 
-int pfmscan_library_hits_dev(pfmscan_ctx *ctx, pfmscan_library *lib, const uint8_t *d_codes, const void *d_profile,
-                             int profile_dtype, int64_t n_pos, const double *thr_seq, const double *thr_struct, int64_t capacity,
-                             int64_t *d_hit_pos, int32_t *d_hit_motif, float *d_hit_seq, double *d_hit_struct,
-                             uint64_t *d_hit_count, void *stream)
+static int library_hits_dev_impl(pfmscan_ctx *ctx, pfmscan_library *lib, const uint8_t *d_codes, const void *d_profile,
+                                 int profile_dtype, int64_t n_pos, const double *thr_seq, const double *thr_struct, const double *thr_sum,
+                                 double row_sum_max, int64_t capacity, int64_t *d_hit_pos, int32_t *d_hit_motif, float *d_hit_seq,
+                                 double *d_hit_struct, uint64_t *d_hit_count, void *stream)
 {
     int rc = lib_check(ctx, lib, d_codes, d_profile, profile_dtype, n_pos, thr_seq, thr_struct);
     if (rc) return rc;
@@ -776,10 +825,10 @@ int pfmscan_library_hits_dev(pfmscan_ctx *ctx, pfmscan_library *lib, const uint8
     if (misaligned(d_codes) || misaligned(d_profile)) return lib_fail(ctx, PFMSCAN_E_BADSHAPE, "stream base pointers must be 16-byte aligned");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-    if ((rc = lib_set_thresholds(ctx, lib, thr_seq, thr_struct, st))) return rc;
+    if ((rc = lib_set_thresholds(ctx, lib, thr_seq, thr_struct, st, thr_sum, row_sum_max))) return rc;
     HitSink sink;
     if ((rc = lib_acquire(ctx, lib, capacity, n_pos, st, sink))) return rc;
-    if ((rc = lib_run(ctx, lib, d_codes, d_profile, profile_dtype, n_pos, sink, st))) return rc;
+    if ((rc = lib_run(ctx, lib, d_codes, d_profile, profile_dtype, n_pos, sink, st, 0, thr_sum != nullptr))) return rc;
     int64_t *starts = lib_starts(sink);
     hipLaunchKernelGGL(k_lib_prefix, dim3(1), dim3(PACK_BLOCK), 0, st, sink.count, LIB_SHARDS, sink.shard_cap, capacity, starts,
                        reinterpret_cast<unsigned long long *>(d_hit_count));
@@ -794,9 +843,11 @@ int pfmscan_library_hits_dev(pfmscan_ctx *ctx, pfmscan_library *lib, const uint8
     return PFMSCAN_OK;
 }
 
-int pfmscan_library_hits_staged(pfmscan_ctx *ctx, pfmscan_library *lib, const double *thr_seq, const double *thr_struct,
-                                int64_t capacity, int64_t *hit_pos, int32_t *hit_motif, float *hit_seq, double *hit_struct,
-                                int64_t *n_hits)
+// thr_sum null: the plain scan.  Otherwise the row bound of the staged profile is measured (once per staging) unless no
+// motif's joint threshold can reject anything.
+static int library_hits_staged_impl(pfmscan_ctx *ctx, pfmscan_library *lib, const double *thr_seq, const double *thr_struct,
+                                    const double *thr_sum, int64_t capacity, int64_t *hit_pos, int32_t *hit_motif, float *hit_seq,
+                                    double *hit_struct, int64_t *n_hits)
 {
     if (!n_hits) return lib_fail(ctx, PFMSCAN_E_BADARG, "NULL argument");
     if (!ctx || !lib) return lib_fail(ctx, PFMSCAN_E_BADARG, "NULL ctx or library");
@@ -816,11 +867,85 @@ int pfmscan_library_hits_staged(pfmscan_ctx *ctx, pfmscan_library *lib, const do
     if (capacity > 0 && (!hit_pos || !hit_motif)) return lib_fail(ctx, PFMSCAN_E_BADARG, "hit_pos / hit_motif is NULL");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    if ((rc = lib_set_thresholds(ctx, lib, thr_seq, thr_struct, st))) return rc;
+    double row_sum_max = INFINITY;
+    if (thr_sum && (rc = staged_row_bound(ctx, &row_sum_max))) return rc;
+    if ((rc = lib_set_thresholds(ctx, lib, thr_seq, thr_struct, st, thr_sum, row_sum_max))) return rc;
     HitSink sink;
     if ((rc = lib_acquire(ctx, lib, capacity, n_pos, st, sink))) return rc;
-    if ((rc = lib_run(ctx, lib, (const uint8_t *)ctx->codes.p, second, ctx->staged_dtype, n_pos, sink, st))) return rc;
+    if ((rc = lib_run(ctx, lib, (const uint8_t *)ctx->codes.p, second, ctx->staged_dtype, n_pos, sink, st, 0, thr_sum != nullptr))) return rc;
     return finish_sorted_hits(ctx, sink, lib->has_letters, lib->has_struct, lib->n, n_pos, capacity, hit_pos, hit_motif, hit_seq, hit_struct, n_hits);
+}
+
+extern "C" {
+
+int pfmscan_library_hits_dev(pfmscan_ctx *ctx, pfmscan_library *lib, const uint8_t *d_codes, const void *d_profile,
+                             int profile_dtype, int64_t n_pos, const double *thr_seq, const double *thr_struct, int64_t capacity,
+                             int64_t *d_hit_pos, int32_t *d_hit_motif, float *d_hit_seq, double *d_hit_struct,
+                             uint64_t *d_hit_count, void *stream)
+{
+    return library_hits_dev_impl(ctx, lib, d_codes, d_profile, profile_dtype, n_pos, thr_seq, thr_struct, nullptr, INFINITY, capacity, d_hit_pos,
+                                 d_hit_motif, d_hit_seq, d_hit_struct, d_hit_count, stream);
+}
+
+// k_library<.., SUM>: one pass for all motifs, asynchronous on the caller's stream; row_sum_max is the caller's promise about the rows
+int pfmscan_library_hits_sum_dev(pfmscan_ctx *ctx, pfmscan_library *lib, const uint8_t *d_codes, const void *d_profile,
+                                 int profile_dtype, int64_t n_pos, const double *thr_seq, const double *thr_struct, const double *thr_sum,
+                                 double row_sum_max, int64_t capacity, int64_t *d_hit_pos, int32_t *d_hit_motif, float *d_hit_seq,
+                                 double *d_hit_struct, uint64_t *d_hit_count, void *stream)
+{
+    bool any = false;
+    if (int rc = lib_check_sum(ctx, lib, thr_sum, &any)) return rc;
+    if (std::isnan(row_sum_max)) return lib_fail(ctx, PFMSCAN_E_BADARG, "NaN row_sum_max (INFINITY promises nothing)");
+    return library_hits_dev_impl(ctx, lib, d_codes, d_profile, profile_dtype, n_pos, thr_seq, thr_struct, any ? thr_sum : nullptr, row_sum_max,
+                                 capacity, d_hit_pos, d_hit_motif, d_hit_seq, d_hit_struct, d_hit_count, stream);
+}
+
+int pfmscan_library_hits_staged(pfmscan_ctx *ctx, pfmscan_library *lib, const double *thr_seq, const double *thr_struct,
+                                int64_t capacity, int64_t *hit_pos, int32_t *hit_motif, float *hit_seq, double *hit_struct,
+                                int64_t *n_hits)
+{
+    return library_hits_staged_impl(ctx, lib, thr_seq, thr_struct, nullptr, capacity, hit_pos, hit_motif, hit_seq, hit_struct, n_hits);
+}
+
+int pfmscan_library_hits_sum_staged(pfmscan_ctx *ctx, pfmscan_library *lib, const double *thr_seq, const double *thr_struct,
+                                    const double *thr_sum, int64_t capacity, int64_t *hit_pos, int32_t *hit_motif, float *hit_seq,
+                                    double *hit_struct, int64_t *n_hits)
+{
+    bool any = false;
+    if (int rc = lib_check_sum(ctx, lib, thr_sum, &any)) return rc;
+    return library_hits_staged_impl(ctx, lib, thr_seq, thr_struct, any ? thr_sum : nullptr, capacity, hit_pos, hit_motif, hit_seq, hit_struct, n_hits);
+}
+
+int pfmscan_library_hits_sum_host(pfmscan_ctx *ctx, pfmscan_library *lib, const uint8_t *codes, const void *profile, int profile_dtype,
+                                  int64_t n_pos, const double *thr_seq, const double *thr_struct, const double *thr_sum, int64_t capacity,
+                                  int64_t *hit_pos, int32_t *hit_motif, float *hit_seq, double *hit_struct, int64_t *n_hits)
+{
+    bool any = false;
+    if (int rc = lib_check_sum(ctx, lib, thr_sum, &any)) return rc;
+    if (!n_hits) return lib_fail(ctx, PFMSCAN_E_BADARG, "NULL argument");
+    if (n_pos < 0 || capacity < 0) return lib_fail(ctx, PFMSCAN_E_BADARG, "negative size");
+    *n_hits = 0;
+    if (n_pos == 0) return PFMSCAN_OK;
+    if (!codes) return lib_fail(ctx, PFMSCAN_E_BADARG, "codes is NULL");
+    if (!profile) return lib_fail(ctx, PFMSCAN_E_BADARG, "profile is NULL");
+    if (int rc = pfmscan_stage(ctx, codes, profile, profile_dtype, n_pos)) return rc;
+    return library_hits_staged_impl(ctx, lib, thr_seq, thr_struct, any ? thr_sum : nullptr, capacity, hit_pos, hit_motif, hit_seq, hit_struct, n_hits);
+}
+
+// host only, no device: the letters thresholds phase A's credits are built for under joint thresholds (sum_thr_eff, pfmscan_exact.hpp)
+int pfmscan_library_sum_thresholds(const double *letter_tables, const double *struct_pssms, int n_motifs, int m, const double *thr_seq,
+                                   const double *thr_sum, double row_sum_max, double *thr_eff_out)
+{
+    if (!letter_tables || !struct_pssms || !thr_seq || !thr_sum || !thr_eff_out || n_motifs < 1 || m < 1 || m > PFMSCAN_MAX_M || std::isnan(row_sum_max))
+        return PFMSCAN_E_BADARG;
+    for (int k = 0; k < n_motifs; ++k)
+        if (std::isnan(thr_seq[k]) || std::isnan(thr_sum[k])) return PFMSCAN_E_BADARG;
+    for (int64_t i = 0; i < (int64_t)n_motifs * m; ++i)       // a 4-letter alphabet, as pfmscan_library_create asks: the bound on |seq| reads columns 0..3
+        for (int c = 4; c < 8; ++c)
+            if (!std::isnan(letter_tables[i * 8 + c])) return PFMSCAN_E_BADARG;
+    for (int k = 0; k < n_motifs; ++k)
+        thr_eff_out[k] = sum_thr_eff(letter_tables + (size_t)k * m * 8, struct_pssms + (size_t)k * m * 7, m, thr_seq[k], thr_sum[k], row_sum_max);
+    return PFMSCAN_OK;
 }
 
 int pfmscan_library_hits_letters_dev(pfmscan_ctx *ctx, pfmscan_library *lib, const uint8_t *d_codes, const uint8_t *d_codes2,

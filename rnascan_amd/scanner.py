@@ -148,6 +148,17 @@ class HipEngine(object):
         return self.ctx.profile_colsums_host(stream.profile, stream.offsets, stream.lengths)
 
 
+def _library(self, T, P):
+    """the device tables of a library (letter tables and / or structure PSSMs), kept across batches until another one is asked for"""
+    key = ((T if T is not None else P).shape, None if T is None else T.tobytes(), None if P is None else P.tobytes())
+    if self._library is None or self._library[0] != key:
+        if self._library is not None:
+            self._library[1].close()
+            self._library = None
+        self._library = (key, self.ctx.library(T, P))
+    return self._library[1]
+
+
 def _library_hits(self, stream, letter_tables, struct_pssms, thr_seq, thr_struct=None, one_shot=True):
     """hits of EVERY motif of a library in one pass over the stream: letter_tables [n][m][8] or None,
     struct_pssms [n][m][7] or None, thresholds scalar or [n] -> (pos, motif index, seq float32 | None,
@@ -155,24 +166,42 @@ def _library_hits(self, stream, letter_tables, struct_pssms, thr_seq, thr_struct
     k_profile_lib (the profile is read once, whatever the library's size)."""
     T = None if letter_tables is None else np.ascontiguousarray(letter_tables, dtype=np.float64)
     P = None if struct_pssms is None else np.ascontiguousarray(struct_pssms, dtype=np.float64)
-    key = ((T if T is not None else P).shape, None if T is None else T.tobytes(), None if P is None else P.tobytes())
-    if self._library is None or self._library[0] != key:
-        if self._library is not None:
-            self._library[1].close()
-            self._library = None
-        self._library = (key, self.ctx.library(T, P))
+    lib = _library(self, T, P)
     staged = self._staged is not None and self._staged[0] is stream and self._staged[1] == self.ctx.scratch_gen
     if one_shot and not staged and stream.n_pos > PIPELINE_MIN:
         # a long stream that only this library will scan (a memory-mapped profile store + the codes of its records):
         # chunked, upload beside scan, two chunks of device scratch
         self._staged = None
-        return self.ctx.library_hits_pipeline_host(self._library[1], stream.codes if T is not None else None,
+        return self.ctx.library_hits_pipeline_host(lib, stream.codes if T is not None else None,
                                                    stream.profile if P is not None else None, thr_seq, thr_struct, PIPELINE_CHUNK)
     self._stage(stream)
-    return self.ctx.library_hits_staged(self._library[1], thr_seq, thr_struct)
+    return self.ctx.library_hits_staged(lib, thr_seq, thr_struct)
 
 
 HipEngine.library_hits = _library_hits
+
+
+def _library_sum_thresholds(self, stream, letter_tables, struct_pssms, thr_seq, thr_sum):
+    """the letters thresholds ``library_hits_sum`` would build its prefilter for on ``stream`` -> float64 [n]; -inf where the
+    joint threshold gives no finite one (then that call raises).  Stages the stream and measures its row bound."""
+    self._stage(stream)
+    return _lib.library_sum_thresholds(letter_tables, struct_pssms, thr_seq, thr_sum, self.ctx.profile_row_bound_staged())
+
+
+def _library_hits_sum(self, stream, letter_tables, struct_pssms, thr_seq, thr_struct, thr_sum):
+    """``library_hits`` of a seq + struct library with the joint threshold of ``hits_sum`` per pair, decided in the library
+    kernel in one pass (pfmscan_library_hits_sum_staged): pair k keeps a window iff seq > thr_seq AND struct > thr_struct AND
+    float64(round(float32 seq, 3)) + struct > thr_sum[k].  thr_seq may be -inf as long as ``library_sum_thresholds`` is
+    finite for every pair.  The stream is staged (there is no pipeline form: the row bound is needed before the first chunk)."""
+    T = np.ascontiguousarray(letter_tables, dtype=np.float64)
+    P = np.ascontiguousarray(struct_pssms, dtype=np.float64)
+    lib = _library(self, T, P)
+    self._stage(stream)
+    return self.ctx.library_hits_sum_staged(lib, thr_seq, thr_struct, thr_sum)
+
+
+HipEngine.library_sum_thresholds = _library_sum_thresholds
+HipEngine.library_hits_sum = _library_hits_sum
 
 
 def _library_hits_letters(self, stream, seq_tables, struct_tables, thr_seq, thr_struct):
@@ -693,8 +722,9 @@ def scan_pair(engine, seq_records, struct_records, seq_pssm, struct_pssm, minsco
 def _scan_combined_stream(engine, stream, batch, letters0, pairs_m, seq_pssm, struct_pssm, minscore, pairing, columns,
                           min_seqstruct=None):
     """the combined hit table of one packed batch (codes + profile rows of the same records).  With ``min_seqstruct`` and an
-    engine that has ``hits_sum`` every pair is one thresholded device call (also at -m ' -inf', and for libraries: one call per
-    pair on the staged stream); otherwise the finished rows are filtered (keep_seqstruct)."""
+    engine that has ``hits_sum`` every pair is one thresholded device call (also at -m ' -inf'); a library of pairs of one
+    width is ONE call of the library kernel (``library_hits_sum``) when the joint threshold gives every pair a finite letters
+    threshold, else one call per pair on the staged stream.  Otherwise the finished rows are filtered (keep_seqstruct)."""
     thr = float(minscore)
     on_device = min_seqstruct is not None and hasattr(engine, "hits_sum")
     tables = []
@@ -704,7 +734,15 @@ def _scan_combined_stream(engine, stream, batch, letters0, pairs_m, seq_pssm, st
     for m, group in by_width.items():
         tabs = [seq_pssm[a].letter_table(pack.RNA_LETTERS) for a, _ in group]
         pssms = [struct_matrix(struct_pssm[b], letters0, pairing) for _, b in group]
-        if on_device:
+        in_library = on_device and len(group) > 1 and m <= LIBRARY_MAX_M and hasattr(engine, "library_hits_sum") and \
+            hasattr(engine, "library_sum_thresholds")
+        if in_library:
+            # every pair in ONE pass of the library kernel, when the joint threshold gives each a finite letters threshold
+            T, P = np.stack(tabs), np.stack(pssms)
+            in_library = bool(np.all(np.isfinite(engine.library_sum_thresholds(stream, T, P, thr, float(min_seqstruct)))))
+        if in_library:
+            parts = [engine.library_hits_sum(stream, T, P, thr, thr, float(min_seqstruct))]
+        elif on_device:
             parts = []
             for k in range(len(group)):
                 pos, sq, st = engine.hits_sum(stream, tabs[k], pssms[k], thr, thr, float(min_seqstruct), one_shot=len(pairs_m) == 1)

@@ -59,7 +59,7 @@
 extern "C" {
 #endif
 
-#define PFMSCAN_ABI_VERSION 14
+#define PFMSCAN_ABI_VERSION 15
 #define PFMSCAN_NCODE   8      /* columns of a letter table */
 #define PFMSCAN_SEP     7      /* separator / foreign-letter code */
 #define PFMSCAN_NSTRUCT 7      /* columns of a structure profile / structure PSSM */
@@ -68,6 +68,7 @@ extern "C" {
                                   any width (_pwm.c:34-68, rnascan.py:302-307).  Above PFMSCAN_MAX_M: letters-only scans run a
                                   slab-tiled kernel (the table through LDS 64 rows at a time), scans with a structure part the
                                   profile kernel up to 180 rows and a plain one-thread-per-window kernel beyond -- same results */
+#define PFMSCAN_SITE_GROUP 4096 /* most hits of one group of the site profiles (pfmscan_site_groups) */
 
 #define PFMSCAN_OK          0
 #define PFMSCAN_E_BADARG   -1  /* NULL / negative / inconsistent argument   -> ValueError */
@@ -665,6 +666,70 @@ int pfmscan_profile_colsums_host(pfmscan_ctx *ctx, const void *profile, int prof
                                  int64_t *first_bad);
 int pfmscan_profile_colsums_staged(pfmscan_ctx *ctx, const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec,
                                    double *sums, int64_t *first_bad);
+
+/* ---- site profiles: profile rows and letters summed under aligned hit windows ---------------------------------------
+ * What the sites of a motif look like: the structural context under the hits of a sequence motif, the same over
+ * flanks (the meta-profile), and the counts a site PFM is made from.  The reference builds its averaged profiles by
+ * counting aligned context letters (average_structure.py:28-42) and normalising per position (pfmutil.py:136-151);
+ * summing the profile rows under aligned hit windows is the same operation on hits.
+ * Inputs: a packed stream (codes and / or profile rows [n_pos][7], float32 or float64), its record table rec_off /
+ * rec_len (as pfmscan_profile_colsums_*), a hit list hit_pos[0..n_hits): stream positions of window starts, STRICTLY
+ * ascending, every window [pos, pos + m) inside ONE record; width m >= 1, flank F >= 0, W = m + 2 F <=
+ * PFMSCAN_MAX_WIDTH (else PFMSCAN_E_BADSHAPE).
+ * Columns: column j in [0, W) of hit h is stream row x = hit_pos[h] - F + j.  It COUNTS only if x lies inside the hit's
+ *   record; flank columns that hang over a record end are skipped, not read.
+ * Groups: the hits of one record, in order, are cut into groups of at most PFMSCAN_SITE_GROUP hits, anchored at the
+ *   record's first hit: a group is a function of that record's hits alone, whatever batch, chunk or rank holds it.
+ * Per group the device produces
+ *   sums   double [W][7] (with a profile): sums[j][c] = the sum of (double) profile[x][c] over the group's hits whose
+ *          column j counts; float32 rows are widened first;
+ *   counts uint32 [W][8] (with codes): counts[j][k] = the number of those hits with min(codes[x], 7) == k; bin 7 is a
+ *          foreign letter inside the record.  The sum over k of counts[j][k] is the number of hits whose column j counts.
+ * Order of additions inside a group (only additions, no FMA; a function of the group alone): wave v of a workgroup's
+ *   four waves starts every cell at 0.0 and adds the group's hits v, v + 4, v + 8, ... in ascending order, skipping a
+ *   hit whose column does not count; the group's cell is ((w0 + w1) + w2) + w3.  tests/sites_rules.py restates this in
+ *   numpy and the kernels equal it bit for bit.  No atomics: the same input gives the same bits on every run.
+ * The caller adds the groups of all records, batches and ranks with math.fsum per cell (exactly rounded, so independent
+ *   of how the hits were cut) and the counts as int64; the site PFM's row j is sums[j][.] / (the row's sum), the letter
+ *   row counts[j][letter] / (the sum over the alphabet's letters).
+ * Rejection: a NaN, +-inf or negative profile cell UNDER A COUNTED COLUMN OF A HIT makes the result meaningless:
+ *   PFMSCAN_E_BADARG, *first_bad = the smallest flat element index row * 7 + column among the cells touched; the sums
+ *   are not to be used.  The same cell under no hit (or under a skipped flank column) is no error.  *first_bad = -1 on
+ *   success and for every other error.
+ *
+ * pfmscan_site_groups: host only, no ctx (no message is left: the return code says it all).  Checks the record table
+ *   (offsets and lengths >= 0, every record behind the one before it and its separator), that the hits ascend strictly
+ *   and that every window lies inside one record: PFMSCAN_E_BADARG otherwise.  Fills grp_first [*n_grp + 1] (indices
+ *   into hit_pos, the last one n_hits) and grp_rec [*n_grp].  capacity: room for that many groups (grp_first holds one
+ *   entry more); PFMSCAN_E_CAPACITY with *n_grp = what suffices when there are more (nothing was written).
+ * _dev: every buffer is a device buffer (d_codes or d_profile may be NULL, and with it d_counts / d_sums; d_profile
+ *   8-byte aligned).  d_sums [n_grp][W][7], d_counts [n_grp][W][8].  The groups are the caller's: any table whose groups
+ *   are at most PFMSCAN_SITE_GROUP hits of one record each and cover the hits in order is taken, one that is not (or hits
+ *   that do not ascend, a window that leaves its record, a record outside the stream) gives PFMSCAN_E_BADARG with
+ *   *first_bad = -1, decided on the device without a load outside the buffers.  Asynchronous on `stream` (NULL: the
+ *   ctx's) except for the verdict: `stream` is synchronised once.  Device scratch (8 bytes per group) belongs to the ctx.
+ * _staged: the stream that pfmscan_stage / pfmscan_average_stage left on the device (use_codes / use_profile say which
+ *   parts to sum); hits, tables and outputs on the host.  It cuts the groups itself: capacity = the groups the outputs
+ *   hold (grp_rec [capacity], sums [capacity][W][7], counts [capacity][W][8]), PFMSCAN_E_CAPACITY with *n_grp set when
+ *   there are more.
+ * _host: a host stream of ANY length (a numpy array or a mapped packed store; through the ctx's upload mode), cut at
+ *   record boundaries into pieces of at most 2^24 rows (PFMSCAN_SITES_CHUNK in the environment overrides; a longer
+ *   record is a piece of its own; a piece no hit lies in is not uploaded); the upload of piece k + 1 runs beside the
+ *   sums of piece k in two alternating buffers.  Leaves the staged stream alone.  Otherwise as _staged. */
+int pfmscan_site_groups(const int64_t *hit_pos, int64_t n_hits, const int64_t *rec_off, const int64_t *rec_len,
+                        int64_t n_rec, int32_t m, int64_t capacity, int64_t *grp_first, int64_t *grp_rec, int64_t *n_grp);
+int pfmscan_site_sums_dev(pfmscan_ctx *ctx, const uint8_t *d_codes, const void *d_profile, int profile_dtype, int64_t n_pos,
+                          const int64_t *d_hit_pos, int64_t n_hits, const int64_t *d_grp_first, const int64_t *d_grp_rec,
+                          int64_t n_grp, const int64_t *d_rec_off, const int64_t *d_rec_len, int64_t n_rec, int32_t m,
+                          int32_t flank, double *d_sums, uint32_t *d_counts, int64_t *first_bad, void *stream);
+int pfmscan_site_sums_staged(pfmscan_ctx *ctx, int use_codes, int use_profile, const int64_t *hit_pos, int64_t n_hits,
+                             const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec, int32_t m, int32_t flank,
+                             int64_t capacity, int64_t *grp_rec, double *sums, uint32_t *counts, int64_t *n_grp,
+                             int64_t *first_bad);
+int pfmscan_site_sums_host(pfmscan_ctx *ctx, const uint8_t *codes, const void *profile, int profile_dtype, int64_t n_pos,
+                           const int64_t *hit_pos, int64_t n_hits, const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec,
+                           int32_t m, int32_t flank, int64_t capacity, int64_t *grp_rec, double *sums, uint32_t *counts,
+                           int64_t *n_grp, int64_t *first_bad);
 
 /* ---- host ingest and output (no device needed; no context: errors via pfmscan_last_error(NULL)) ---------------
  * The two pieces of host work that dwarf the kernel at scale, in native code.

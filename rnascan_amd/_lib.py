@@ -22,7 +22,7 @@ NCODE = 8
 NSTRUCT = 7
 MAX_M = 64            # widest PFM of the tuned kernels and of PFM libraries
 MAX_WIDTH = 4096      # widest PFM accepted (wider than MAX_M: the plain rolled-loop kernel)
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 # every symbol include/pfmscan.h declares (checked by tests/test_abi.py)
 SYMBOLS = [
@@ -46,7 +46,9 @@ SYMBOLS = [
     "pfmscan_hits_sum_dev", "pfmscan_hits_sum_staged", "pfmscan_hits_sum_host", "pfmscan_hits_sum_pipeline_host",
     "pfmscan_library_hits_sum_dev", "pfmscan_library_hits_sum_staged", "pfmscan_library_hits_sum_host",
     "pfmscan_profile_row_bound_dev", "pfmscan_profile_row_bound_staged", "pfmscan_library_sum_thresholds",
+    "pfmscan_site_groups", "pfmscan_site_sums_dev", "pfmscan_site_sums_staged", "pfmscan_site_sums_host",
 ]
+SITE_GROUP = 4096     # most hits of one group of the site profiles
 MAX_COVER = 1024      # largest coverage of a row the averaging accepts
 AVG_OK, AVG_DOTBRACKET, AVG_UNCOVERED, AVG_COVER, AVG_BAD_TABLE = range(5)   # what a rejected averaging names
 TSV_CONST, TSV_I64, TSV_F32, TSV_F64, TSV_INDEXED, TSV_FIXED, TSV_WINDOW, TSV_SPAN = range(8)
@@ -167,6 +169,13 @@ def load():
     L.pfmscan_profile_colsums_dev.argtypes = [vp, vp, i32, i64, vp, vp, i64, vp, ctypes.POINTER(i64), vp]
     L.pfmscan_profile_colsums_host.argtypes = [vp, vp, i32, i64, vp, vp, i64, vp, ctypes.POINTER(i64)]
     L.pfmscan_profile_colsums_staged.argtypes = [vp, vp, vp, i64, vp, ctypes.POINTER(i64)]
+    L.pfmscan_site_groups.argtypes = [vp, i64, vp, vp, i64, i32, i64, vp, vp, ctypes.POINTER(i64)]
+    L.pfmscan_site_sums_dev.argtypes = [vp, vp, vp, i32, i64, vp, i64, vp, vp, i64, vp, vp, i64, i32, i32, vp, vp,
+                                        ctypes.POINTER(i64), vp]
+    L.pfmscan_site_sums_staged.argtypes = [vp, i32, i32, vp, i64, vp, vp, i64, i32, i32, i64, vp, vp, vp, ctypes.POINTER(i64),
+                                           ctypes.POINTER(i64)]
+    L.pfmscan_site_sums_host.argtypes = [vp, vp, vp, i32, i64, vp, i64, vp, vp, i64, i32, i32, i64, vp, vp, vp,
+                                         ctypes.POINTER(i64), ctypes.POINTER(i64)]
     L.pfmscan_count_bytes.argtypes = [vp, i64, vp, i32]
     L.pfmscan_place_alloc.argtypes = [vp, i32, vp, vp, i32]
     L.pfmscan_place_free.argtypes = [vp, vp]
@@ -241,6 +250,32 @@ def _raise(L, ctx, rc, n_hits=None):
 # ---------------------------------------------------------------------------
 # host ingest / output (no device, no context)
 # ---------------------------------------------------------------------------
+def site_groups(pos, offsets, lengths, m):
+    """the groups of a sorted hit list (pfmscan_site_groups, include/pfmscan.h) -> (grp_first int64 [n_grp + 1], grp_rec
+    int64 [n_grp]).  ValueError when the hits do not ascend strictly, a window [pos, pos + m) does not lie inside one
+    record, or the record table is broken."""
+    L = load()
+    pos = np.ascontiguousarray(pos, dtype=np.int64)
+    off = np.ascontiguousarray(offsets, dtype=np.int64)
+    ln = np.ascontiguousarray(lengths, dtype=np.int64)
+    if pos.ndim != 1 or off.ndim != 1 or off.shape != ln.shape:
+        raise ValueError("positions, offsets and lengths must be one-dimensional, the last two of the same size")
+    n = ctypes.c_int64(0)
+    first = np.zeros(1, dtype=np.int64)
+    rc = L.pfmscan_site_groups(_ptr(pos), pos.size, _ptr(off), _ptr(ln), off.size, int(m), 0, _ptr(first), None, ctypes.byref(n))
+    if rc == E_CAPACITY:
+        first = np.zeros(n.value + 1, dtype=np.int64)
+        rec = np.zeros(n.value, dtype=np.int64)
+        rc = L.pfmscan_site_groups(_ptr(pos), pos.size, _ptr(off), _ptr(ln), off.size, int(m), n.value, _ptr(first), _ptr(rec),
+                                   ctypes.byref(n))
+    else:
+        rec = np.zeros(0, dtype=np.int64)
+    if rc != 0:
+        raise ValueError("site groups: the hits must ascend strictly and every window of width %d must lie inside one record "
+                         "of a record table whose records ascend, each behind the separator of the one before" % int(m))
+    return first, rec
+
+
 def fasta_index(buf, threads=0):
     """uint8 array of FASTA bytes -> (hdr_off, hdr_len, seq_off, seq_end, n_letters), int64 [n_records] each."""
     L = load()
@@ -904,6 +939,74 @@ class Context(object):
                                                  PROFILE_F32 if np.dtype(dtype) == np.float32 else PROFILE_F64, int(n_pos),
                                                  _ptr(addr(d_offsets)), _ptr(addr(d_lengths)), int(n_rec), _ptr(addr(d_sums)),
                                                  ctypes.byref(bad), _ptr(stream))
+        self._colsums_check(rc, bad)
+
+    # -- site profiles: rows and letters summed under hit windows (include/pfmscan.h) ---------------------------
+    site_groups = staticmethod(site_groups)
+
+    def _site_call(self, fn, pos, offsets, lengths, m, flank, want_counts, want_sums):
+        """the capacity protocol of the _staged / _host forms: fn(pos, off, ln, capacity, grp_rec, sums, counts, n, bad) -> rc"""
+        pos = np.ascontiguousarray(pos, dtype=np.int64)
+        off, ln = self._colsums_tables(offsets, lengths)
+        W = int(m) + 2 * int(flank)
+        cap = max(1, min(pos.size, off.size + pos.size // SITE_GROUP))
+        while True:
+            grp_rec = np.zeros(cap, dtype=np.int64)
+            sums = np.zeros((cap, W, NSTRUCT), dtype=np.float64) if want_sums else None
+            counts = np.zeros((cap, W, NCODE), dtype=np.uint32) if want_counts else None
+            n, bad = ctypes.c_int64(0), ctypes.c_int64(-1)
+            rc = fn(pos, off, ln, cap, grp_rec, sums, counts, n, bad)
+            if rc == E_CAPACITY and n.value > cap:
+                cap = int(n.value)
+                continue
+            self._colsums_check(rc, bad)
+            k = int(n.value)
+            return grp_rec[:k], (None if sums is None else sums[:k]), (None if counts is None else counts[:k])
+
+    def site_sums_staged(self, pos, offsets, lengths, m, flank=0, letters=True, profile=True):
+        """group sums / counts under the hits ``pos`` of the staged stream -> (grp_rec, sums float64 [n_grp][W][7] | None,
+        counts uint32 [n_grp][W][8] | None).  ValueError (``.element``) for a NaN, infinite or negative cell under a hit"""
+        def fn(pos, off, ln, cap, grp_rec, sums, counts, n, bad):
+            return self._L.pfmscan_site_sums_staged(self._h, int(bool(letters)), int(bool(profile)), _ptr(pos), pos.size, _ptr(off),
+                                                    _ptr(ln), off.size, int(m), int(flank), cap, _ptr(grp_rec), _ptr(sums),
+                                                    _ptr(counts), ctypes.byref(n), ctypes.byref(bad))
+        return self._site_call(fn, pos, offsets, lengths, m, flank, letters, profile)
+
+    def site_sums_host(self, codes, profile, pos, offsets, lengths, m, flank=0):
+        """the same for a packed host stream of any length (numpy arrays or a mapped store); either part may be None"""
+        n_pos = None
+        dt = PROFILE_NONE
+        if codes is not None:
+            codes = np.ascontiguousarray(codes, dtype=np.uint8)
+            n_pos = codes.size
+        if profile is not None:
+            if profile.dtype not in (np.float32, np.float64) or profile.ndim != 2 or profile.shape[1] != NSTRUCT:
+                raise ValueError("profile must be float32 or float64 [n_pos][7]")
+            profile = np.ascontiguousarray(profile)
+            dt = PROFILE_F32 if profile.dtype == np.float32 else PROFILE_F64
+            if n_pos is not None and n_pos != profile.shape[0]:
+                raise ValueError("codes and profile differ in length")
+            n_pos = profile.shape[0]
+        if n_pos is None:
+            raise ValueError("neither codes nor a profile")
+        self._upload_mode_for(codes, profile)
+
+        def fn(pos, off, ln, cap, grp_rec, sums, counts, n, bad):
+            return self._L.pfmscan_site_sums_host(self._h, _ptr(codes), _ptr(profile), dt, n_pos, _ptr(pos), pos.size, _ptr(off),
+                                                  _ptr(ln), off.size, int(m), int(flank), cap, _ptr(grp_rec), _ptr(sums),
+                                                  _ptr(counts), ctypes.byref(n), ctypes.byref(bad))
+        return self._site_call(fn, pos, offsets, lengths, m, flank, codes is not None, profile is not None)
+
+    def site_sums_dev(self, d_codes, d_profile, dtype, n_pos, d_pos, n_hits, d_grp_first, d_grp_rec, n_grp, d_offsets, d_lengths,
+                      n_rec, m, flank, d_sums, d_counts, stream=None):
+        """device buffers (raw addresses or objects with data_ptr()); asynchronous on `stream` except for the verdict"""
+        addr = lambda a: None if a is None else (a.data_ptr() if hasattr(a, "data_ptr") else a)   # noqa: E731
+        bad = ctypes.c_int64(-1)
+        rc = self._L.pfmscan_site_sums_dev(self._h, _ptr(addr(d_codes)), _ptr(addr(d_profile)),
+                                           PROFILE_F32 if np.dtype(dtype) == np.float32 else PROFILE_F64, int(n_pos),
+                                           _ptr(addr(d_pos)), int(n_hits), _ptr(addr(d_grp_first)), _ptr(addr(d_grp_rec)), int(n_grp),
+                                           _ptr(addr(d_offsets)), _ptr(addr(d_lengths)), int(n_rec), int(m), int(flank),
+                                           _ptr(addr(d_sums)), _ptr(addr(d_counts)), ctypes.byref(bad), _ptr(stream))
         self._colsums_check(rc, bad)
 
     # -- generic-alphabet letter hits in fp64; two code streams ---------------------------------

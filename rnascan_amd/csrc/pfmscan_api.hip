@@ -119,7 +119,8 @@ void pfmscan_ctx_destroy(pfmscan_ctx *ctx)
                       &ctx->lib_motif, &ctx->lib_seq, &ctx->lib_struct, &ctx->lib_count, &ctx->pipe_codes[0], &ctx->pipe_codes[1],
                       &ctx->pipe_profile[0], &ctx->pipe_profile[1], &ctx->codes2, &ctx->db_in, &ctx->db_out,
                       &ctx->db_tree, &ctx->db_part, &ctx->db_marks, &ctx->db_tiles, &ctx->db_flags,
-                      &ctx->avg_tab, &ctx->avg_blk, &ctx->avg_out, &ctx->bg_tab, &ctx->bg_part, &ctx->bg_blk, &ctx->bg_sums, &ctx->rb_part})
+                      &ctx->avg_tab, &ctx->avg_blk, &ctx->avg_out, &ctx->bg_tab, &ctx->bg_part, &ctx->bg_blk, &ctx->bg_sums, &ctx->rb_part,
+                      &ctx->site_tab, &ctx->site_blk, &ctx->site_sums, &ctx->site_counts})
         release(*b);
     upload_release(ctx);
     place_release_all(ctx);

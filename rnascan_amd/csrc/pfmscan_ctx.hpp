@@ -50,6 +50,7 @@ struct pfmscan_ctx {
     DevBuf db_in, db_out, db_tree, db_part, db_marks, db_tiles, db_flags;   // dot-bracket annotation (pfmscan_dotbracket.hip)
     DevBuf avg_tab, avg_blk, avg_out;           // fragment averaging (pfmscan_average.hip): tables + T, verdicts, host rows
     DevBuf bg_tab, bg_part, bg_blk, bg_sums;    // profile column sums (pfmscan_background.hip): record tables, piece sums, verdicts, record sums
+    DevBuf site_tab, site_blk, site_sums, site_counts;   // site profiles (pfmscan_sites.hip): hit / group / record tables, verdict keys, group sums, group counts
     DevBuf rb_part;                             // profile row bound (pfmscan_rowbound.hip): workgroup partials + the result
     DevBuf pipe_codes[2], pipe_profile[2];      // chunked host pipeline: double-buffered chunk of the stream
     hipEvent_t pipe_copied[2] = {nullptr, nullptr}, pipe_scanned[2] = {nullptr, nullptr};

@@ -147,6 +147,22 @@ class HipEngine(object):
             return self.ctx.profile_colsums_staged(stream.offsets, stream.lengths)
         return self.ctx.profile_colsums_host(stream.profile, stream.offsets, stream.lengths)
 
+    def site_sums(self, stream, pos, m, flank=0, letters=True, profile=True):
+        """profile rows and letters of ``stream`` summed under the hit windows [pos, pos + m) and ``flank`` columns either
+        side, per group of at most 4096 hits of a record (pfmscan_site_sums_*, include/pfmscan.h) -> (grp_rec,
+        sums float64 [n_grp][W][7] | None, counts uint32 [n_grp][W][8] | None).  Bit-reproducible: a group's cells depend
+        on that record's hits alone.  Staged when ``stream`` is the staged stream, else the chunked upload-beside-sum
+        pipeline, which leaves the staged stream alone.  ValueError with ``element`` (flat index row * 7 + column) when
+        a NaN, infinite or negative cell lies under a hit."""
+        letters = bool(letters) and stream.codes is not None
+        profile = bool(profile) and stream.profile is not None
+        if not letters and not profile:
+            raise ValueError("the stream has neither the codes nor the profile asked for")
+        if self._staged is not None and self._staged[0] is stream and self._staged[1] == self.ctx.scratch_gen:
+            return self.ctx.site_sums_staged(pos, stream.offsets, stream.lengths, m, flank, letters, profile)
+        return self.ctx.site_sums_host(stream.codes if letters else None, stream.profile if profile else None, pos,
+                                       stream.offsets, stream.lengths, m, flank)
+
 
 def _library(self, T, P):
     """the device tables of a library (letter tables and / or structure PSSMs), kept across batches until another one is asked for"""

@@ -1,0 +1,465 @@
+"""Site profiles: what the sites of a motif look like.
+
+``rnascan -p .. -q .. seqs.fa avgdir/`` prints where a motif pair hits; this module answers the next question: the
+structural context (and the letters) under those hits, and over ``--flank`` columns either side of them -- the
+meta-profile -- summed over all sites and normalised per position.  That is also what a structure PFM is made from: the
+reference builds its averaged profiles by counting aligned context letters (average_structure.py:28-42) and normalising
+per position (``norm_pfm``, pfmutil.py:136-151); summing the profile rows under aligned hit windows is the same
+operation on hits.  With ``--flank 0`` the output is a PFM that ``-p`` / ``-q`` read, which closes the loop
+fold -> average -> background -> scan -> site PFM -> scan again.
+
+    column j of a hit at stream position p   row p - F + j of the hit's record, j in [0, W), W = m + 2 F; columns that
+                                             hang over a record end are skipped (coverage n[j] counts the others)
+    S[j][c]       the sum of profile[row][c] over the hits whose column j counts
+    counts[j][k]  the number of those hits whose letter there is k (A, C, G, U; anything else is foreign)
+    structure PFM row j = S[j][c] / sum over c of S[j][c]            (norm_pfm: columns BEHLMRT, summed left to right)
+    letter PFM    row j = counts[j][letter] / sum over A, C, G, U     (foreign letters excluded, and reported)
+
+The sums are made on the GPU per GROUP of at most 4096 hits of a record (``HipEngine.site_sums``: a fixed order of
+additions inside a group, see include/pfmscan.h) and the groups are combined here with ``math.fsum``, which is exactly
+rounded: the result has the same bits whatever the batch size, the pipeline chunk, the upload mode, the input form and
+the number of ranks.  Profile columns are matched to letters by NAME, file by file for a directory.
+"""
+import argparse
+import math
+import os
+import sys
+
+import numpy as np
+
+from . import fasta, pack, shard, store
+
+STRUCT_ORDER = pack.STRUCT_COLUMNS         # column order of the structure PFMs this writes (the shipped PFMs': BEHLMRT)
+SEQ_ORDER = pack.RNA_LETTERS               # ... and of the sequence PFMs (ACGU); code k of a stream is SEQ_ORDER[k]
+
+
+class SitesError(ValueError):
+    """a cell under a site from which no profile can be computed; ``record``, ``position`` (1-based) and ``letter`` say where"""
+
+    def __init__(self, record, position, letter, value):
+        ValueError.__init__(self, "Averaged-structure profile %s holds %r at position %d, column %s, under a site: no site "
+                                  "profile can be computed from it (fix the profile)" % (record, value, position, letter))
+        self.record, self.position, self.letter, self.value = record, position, letter, value
+
+    def __reduce__(self):            # ranks hand it to each other (combine): rebuilt from its four fields
+        return (SitesError, (self.record, self.position, self.letter, self.value))
+
+
+class InputError(ValueError):
+    """inputs no site profile can be read from (the message says which record or file and why)"""
+
+
+class Rows(object):
+    """what one rank collected: group sums float64 [n][W][7] (columns in STRUCT_ORDER) or None, letter counts int64
+    [W][8] or None, coverage int64 [W], the number of hits"""
+
+    def __init__(self, W, profile=True, letters=True):
+        self.W = W
+        self.sums = [] if profile else None
+        self.counts = np.zeros((W, 8), dtype=np.int64) if letters else None
+        self.coverage = np.zeros(W, dtype=np.int64)
+        self.hits = 0
+
+    def packed(self):
+        sums = None
+        if self.sums is not None:
+            sums = np.concatenate(self.sums) if self.sums else np.zeros((0, self.W, 7), dtype=np.float64)
+        return sums, self.counts, self.coverage, self.hits
+
+
+def coverage(stream, pos, m, flank):
+    """n[j], int64 [W]: the number of hits whose column j lies inside the hit's record, from positions and record bounds"""
+    W = m + 2 * flank
+    pos = np.asarray(pos, dtype=np.int64)
+    if pos.size == 0:
+        return np.zeros(W, dtype=np.int64)
+    rec, start = stream.locate(pos)
+    # column j counts iff 0 <= start - flank + j < length: per hit a run [lo, hi) of columns
+    lo = np.clip(flank - start, 0, W)
+    hi = np.clip(stream.lengths[rec] - start + flank, 0, W)
+    edge = np.zeros(W + 1, dtype=np.int64)
+    np.add.at(edge, lo, 1)
+    np.add.at(edge, hi, -1)
+    return np.cumsum(edge[:-1])
+
+
+def accumulate(engine, rows, stream, ids, letters_of, pos, m, flank=0):
+    """add the sites ``pos`` (sorted stream positions of windows of width m) of one packed batch to ``rows``.
+    ``letters_of(record index in the batch)`` -> that record's profile column letters (for messages);
+    the batch's columns are ``letters_of(0)`` and are put into STRUCT_ORDER by name."""
+    pos = np.asarray(pos, dtype=np.int64)
+    if pos.size == 0:
+        return
+    try:
+        _, sums, counts = engine.site_sums(stream, pos, m, flank, letters=rows.counts is not None, profile=rows.sums is not None)
+    except ValueError as e:
+        at = getattr(e, "element", None)
+        if at is None:
+            raise
+        row, col = divmod(int(at), 7)
+        rec, start = stream.locate(np.asarray([row]))
+        rec = int(rec[0])
+        raise SitesError(ids[rec], int(start[0]) + 1, letters_of(rec)[col], float(stream.profile[row, col]))
+    if rows.sums is not None:
+        cols = list(letters_of(0))
+        if sorted(cols) != sorted(STRUCT_ORDER):
+            raise InputError("averaged-structure columns %s are not the seven structure letters %s" % (cols, STRUCT_ORDER))
+        if cols != list(STRUCT_ORDER):
+            sums = sums[:, :, [cols.index(c) for c in STRUCT_ORDER]]
+        rows.sums.append(np.ascontiguousarray(sums))
+    if rows.counts is not None:
+        rows.counts += counts.astype(np.int64).sum(axis=0)
+    rows.coverage += coverage(stream, pos, m, flank)
+    rows.hits += int(pos.size)
+
+
+def _portable(e):
+    """an exception another rank can rebuild"""
+    import pickle
+    try:
+        pickle.loads(pickle.dumps(e))
+        return e
+    except Exception:
+        return RuntimeError("%s: %s" % (type(e).__name__, e))
+
+
+def combine(rows, rank=0, world=1, dist=None, failure=None):
+    """the ranks' rows -> (S float64 [W][7] | None, counts int64 [W][8] | None, coverage int64 [W], hits), the same on
+    every rank.  The rows are exchanged once over the process group, host side; a rank that failed hands its exception
+    over instead (``failure``), and every rank raises the one of the lowest rank (shares are contiguous and in rank
+    order: for a rejected cell that is the earliest in input order).  Then math.fsum per cell over every group."""
+    if world > 1:
+        shares = [None] * world
+        dist.all_gather_object(shares, (None if failure is None else _portable(failure), None if failure is not None else rows.packed()))
+        for bad, _ in shares:
+            if bad is not None:
+                raise bad
+        parts = [s for _, s in shares]
+    else:
+        if failure is not None:
+            raise failure
+        parts = [rows.packed()]
+    W = rows.W
+    S = counts = None
+    if parts[0][0] is not None:
+        groups = np.concatenate([p[0] for p in parts])
+        S = np.zeros((W, 7), dtype=np.float64)
+        flat = np.ascontiguousarray(groups.reshape(groups.shape[0], W * 7).T)
+        for e in range(W * 7):
+            S[e // 7, e % 7] = math.fsum(flat[e].tolist())
+    if parts[0][1] is not None:
+        counts = np.sum([p[1] for p in parts], axis=0, dtype=np.int64)
+    cov = np.sum([p[2] for p in parts], axis=0, dtype=np.int64)
+    return S, counts, cov, int(sum(p[3] for p in parts))
+
+
+def site_pfms(S, counts):
+    """(structure PFM float64 [W][7] in STRUCT_ORDER | None, letter PFM float64 [W][4] in SEQ_ORDER | None, foreign
+    letters int64 [W] | None).  A row without mass is an error that names the column."""
+    struct = seq = foreign = None
+    if S is not None:
+        total = np.zeros(S.shape[0], dtype=np.float64)
+        for c in range(7):                         # norm_pfm (pfmutil.py:136-151): 0 + B + E + ... left to right
+            total = total + S[:, c]
+        empty = np.flatnonzero(~(total > 0))
+        if empty.size:
+            raise InputError("column %d of the site profile has no structure mass under any site (every site skips it, or "
+                             "the profile rows there are zero): it cannot be normalised" % int(empty[0]))
+        struct = S / total[:, None]
+    if counts is not None:
+        known = counts[:, :len(SEQ_ORDER)]
+        total = known.sum(axis=1)
+        empty = np.flatnonzero(total == 0)
+        if empty.size:
+            raise InputError("column %d of the site profile has no nucleotide under any site: it cannot be normalised" % int(empty[0]))
+        seq = known / total[:, None].astype(np.float64)
+        foreign = counts[:, len(SEQ_ORDER):].sum(axis=1)
+    return struct, seq, foreign
+
+
+def write_pfm(path, letters, matrix):
+    """the PFM text format ``-p`` / ``-q`` read: header PO + letters, one row per position, every number in the shortest
+    form that reads back to the same float64 (the native table writer, pfmscan_tsv_format)"""
+    from . import table
+    matrix = np.asarray(matrix)
+    with open(path, "w") as out:
+        w = table.TsvWriter(out, ["PO"] + list(letters), match_id=False)
+        cols = {"PO": np.arange(matrix.shape[0], dtype=np.int64)}
+        for k, c in enumerate(letters):
+            cols[c] = np.ascontiguousarray(matrix[:, k])
+        w.write_chunk(cols, matrix.shape[0])
+        w.close()
+
+
+def write_counts(path, S, counts, cov, hits):
+    """PREFIX.counts.txt: per column the coverage, the raw structure sums and the integer letter counts (N = foreign)"""
+    from . import table
+    names, cols = ["PO", "Sites", "Coverage"], {"PO": np.arange(cov.size, dtype=np.int64), "Sites": np.full(cov.size, hits, dtype=np.int64),
+                                                "Coverage": cov}
+    if S is not None:
+        for k, c in enumerate(STRUCT_ORDER):
+            names.append("Sum." + c)
+            cols["Sum." + c] = np.ascontiguousarray(S[:, k])
+    if counts is not None:
+        for k, c in enumerate(SEQ_ORDER):
+            names.append("Count." + c)
+            cols["Count." + c] = np.ascontiguousarray(counts[:, k])
+        names.append("Count.N")
+        cols["Count.N"] = counts[:, len(SEQ_ORDER):].sum(axis=1)
+    with open(path, "w") as out:
+        w = table.TsvWriter(out, names, match_id=False)
+        w.write_chunk(cols, cov.size)
+        w.close()
+
+
+# ---------------------------------------------------------------------------
+# hit selection: exactly rnascan's
+# ---------------------------------------------------------------------------
+def select(engine, stream, m, letter_table, struct_pssm, minscore, min_seqstruct=None):
+    """the stream positions ``rnascan`` reports for this motif (pair) with the same -m / --min-seqstruct: the same
+    engine.hits / hits_sum calls as scanner._scan_combined_stream, scan_records and _scan_profile_stream make"""
+    from . import scanner
+    thr = float(minscore)
+    both = letter_table is not None and struct_pssm is not None
+    if both and min_seqstruct is not None and hasattr(engine, "hits_sum"):
+        pos, _, _ = engine.hits_sum(stream, letter_table, struct_pssm, thr, thr, float(min_seqstruct))
+        return pos
+    pos, sq, st = scanner._select(engine, stream, m, letter_table, struct_pssm, thr if letter_table is not None else -np.inf,
+                                  thr if struct_pssm is not None else -np.inf)
+    if both and min_seqstruct is not None:
+        keep = np.round(sq, 3).astype(np.float64) + st > float(min_seqstruct)
+        pos = pos[keep]
+    return pos
+
+
+def getoptions(argv=None):
+    desc = ("Site profiles: the averaged-structure rows (and the nucleotides) under the hits rnascan would report with the same "
+            "options, summed over all sites and normalised per position.  Writes PREFIX.struct.txt (structure PFM over "
+            "W = width + 2 x flank columns), PREFIX.seq.txt (sequence PFM; only with a FASTA) and PREFIX.counts.txt (raw "
+            "sums, integer counts, coverage and number of sites per column).")
+    parser = argparse.ArgumentParser(prog="python -m rnascan_amd.sites", description=desc)
+    parser.add_argument("inputs", metavar="INPUT", nargs="+",
+                        help="seqs.fa avgdir_or_store/ (with -p), or avgdir_or_store/ alone (with -q only)")
+    parser.add_argument("-p", "--pfm_seq", dest="pfm_seq", type=str, help="Sequence PFM (the first motif of a multi-PFM file)")
+    parser.add_argument("-q", "--pfm_struct", dest="pfm_struct", type=str, help="Structure PFM (the first motif of a multi-PFM file)")
+    parser.add_argument("-C", "--pseudocount", type=float, dest="pseudocount", default=0, help="Pseudocount for normalizing PFM. [%(default)s]")
+    parser.add_argument("-m", "--minscore", type=float, dest="minscore", default=6, help="Minimum score for motif hits. [%(default)s]")
+    parser.add_argument("--min-seqstruct", type=float, default=None, dest="min_seqstruct", metavar="T",
+                        help="with -p AND -q: additionally keep a site only if its LogOdds.SeqStruct exceeds T, as rnascan does [off]")
+    parser.add_argument("--flank", type=int, default=0, metavar="F",
+                        help=("also sum F columns either side of every site; columns that hang over a record end are skipped.  "
+                              "NOTE: only --flank 0 writes a PFM of the motif's width that -q / -p accept as the motif it came from; "
+                              "with F > 0 the files are a profile plot over the flanks, not a PFM for -q [%(default)s]"))
+    parser.add_argument("-u", "--uniformbg", action="store_true", default=False, dest="uniform_background",
+                        help="Use uniform background for calculating log-odds [%(default)s]")
+    parser.add_argument("-b", "--bg_seq", default=None, dest="bg_seq", help="File of pre-computed background probabilities for sequences")
+    parser.add_argument("-B", "--bg_struct", default=None, dest="bg_struct", help="File of pre-computed background probabilities for structure")
+    parser.add_argument("--pairing", choices=["aligned", "positional"], default="aligned", help="as rnascan's [%(default)s]")
+    parser.add_argument("--profile-dtype", choices=["auto", "float64", "float32"], default="float64", help="as rnascan's [%(default)s]")
+    parser.add_argument("--device", type=int, default=int(os.environ.get("RNASCAN_DEVICE", "0")), help="HIP device index [%(default)s]")
+    parser.add_argument("--gpus", type=int, default=None, help="one process per GPU, records sharded over them, as rnascan's [1]")
+    parser.add_argument("-o", "--output", dest="prefix", required=True, metavar="PREFIX", help="prefix of the files written")
+    args = parser.parse_args(argv)
+    if not (args.pfm_seq or args.pfm_struct):
+        parser.error("Must specify PFMs with -p and/or -q")
+    if args.uniform_background and (args.bg_seq or args.bg_struct):
+        parser.error("You cannot set uniform and custom background options at the same time\n")
+    if args.min_seqstruct is not None and not (args.pfm_seq and args.pfm_struct):
+        parser.error("--min-seqstruct thresholds the combined score: it needs both -p and -q")
+    if args.min_seqstruct is not None and args.min_seqstruct != args.min_seqstruct:
+        parser.error("--min-seqstruct: not a number")
+    if args.flank < 0:
+        parser.error("--flank must be at least 0")
+    if args.pfm_seq and len(args.inputs) != 2:
+        parser.error("with -p give the sequence FASTA and the averaged-structure directory or store")
+    if not args.pfm_seq and len(args.inputs) != 1:
+        parser.error("with -q alone give the averaged-structure directory or store only")
+    args.fastafiles = list(args.inputs)
+    args.testseq, args.bgonly = None, False
+    return args
+
+
+class _Profiles(object):
+    """the averaged-structure input (directory or packed store) as records: ids, lengths (weights for a directory), and
+    ``runs(a, b)`` -> [(ids, column letters, pack.Stream without codes)] of records [a, b): one run for a store, one per
+    stretch of files with the same column order for a directory (columns are matched by name, file by file)"""
+
+    def __init__(self, source, dtype, order=None):
+        self.store = store.ProfileStore(source) if store.is_store(source) else None
+        self.dtype = dtype
+        self.at = None                             # with ``order``: index of the FASTA's record k among the profiles
+        if self.store is not None:
+            self.ids = list(self.store.ids)
+            self.lengths = self.store.lengths
+        else:
+            files = fasta.list_profiles(source)
+            if len(files) == 0:
+                raise IOError("No averaged structure files found")
+            self.files = files
+            self.ids = [sid for sid, _ in files]
+            self.lengths = np.asarray([os.path.getsize(path) // 64 + 1 for _, path in files], dtype=np.int64)
+        if order is not None:                      # the FASTA's records in the FASTA's order, one profile each
+            where = {}
+            for i, sid in enumerate(self.ids):
+                if sid in where:
+                    raise InputError("record %s has more than one averaged-structure profile" % sid)
+                where[sid] = i
+            missing = [sid for sid in order if sid not in where]
+            if missing:
+                raise InputError("record %s of the FASTA has no averaged-structure profile" % missing[0])
+            if len(where) != len(order):
+                extra = sorted(set(where) - set(order))
+                raise InputError("averaged-structure profile %s has no record in the FASTA" % extra[0])
+            self.at = [where[sid] for sid in order]
+            if self.at == list(range(len(order))):
+                self.at = None
+            else:
+                self.ids = list(order)
+                self.lengths = self.lengths[self.at]
+
+    def runs(self, a, b):
+        if self.store is not None:
+            ps = self.store
+            if self.at is None:
+                st = ps.stream(a, b)
+            else:
+                st = pack.pack(profiles=[ps.profile[int(ps.offsets[i]):int(ps.offsets[i] + ps.lengths[i])] for i in self.at[a:b]],
+                               profile_dtype=ps.dtype)
+            prof = st.profile
+            if prof.dtype == np.float64 and np.dtype(self.dtype) == np.float32:
+                prof = np.asarray(prof, dtype=np.float32)
+            return [(self.ids[a:b], list(ps.letters), pack.Stream(None, prof, st.offsets, st.lengths))]
+        idx = list(range(a, b)) if self.at is None else self.at[a:b]
+        parsed = fasta.read_profiles([self.files[i][1] for i in idx])
+        out, k = [], 0
+        while k < len(parsed):
+            e = k + 1
+            while e < len(parsed) and list(parsed[e][0]) == list(parsed[k][0]):
+                e += 1
+            st = pack.pack(profiles=[p for _, p in parsed[k:e]], profile_dtype=self.dtype)
+            out.append((self.ids[a + k:a + e], list(parsed[k][0]), st))
+            k = e
+        return out
+
+
+def collect(engine, args, seq_pssm, struct_pssm, rank=0, world=1):
+    """this rank's Rows: its share of the records, batch by batch, sites selected as rnascan selects its hits"""
+    from . import cli, scanner
+    seq_id, seq_pm = scanner._first_motif(seq_pssm) if seq_pssm else (None, None)
+    st_id, st_pm = scanner._first_motif(struct_pssm) if struct_pssm else (None, None)
+    if seq_pm is not None and st_pm is not None and seq_pm.length != st_pm.length:
+        raise InputError("the sequence PFM is %d positions wide and the structure PFM %d: they share no site" % (seq_pm.length, st_pm.length))
+    m = (seq_pm or st_pm).length
+    W = m + 2 * args.flank
+    from ._lib import MAX_WIDTH
+    if W > MAX_WIDTH:
+        raise InputError("width %d + 2 x flank %d exceeds %d columns (PFMSCAN_MAX_WIDTH, include/pfmscan.h)" % (m, args.flank, MAX_WIDTH))
+    source = args.fastafiles[-1]
+    stored = store.ProfileStore(source).dtype if store.is_store(source) else None
+    ptype = cli.profile_type(args, struct_pssm, stored) if struct_pssm else (np.dtype(args.profile_dtype).type if args.profile_dtype != "auto" else np.float64)
+    tab = seq_pm.letter_table(pack.RNA_LETTERS) if seq_pm is not None else None
+    rows = Rows(W, profile=True, letters=seq_pm is not None)
+    if seq_pm is not None:
+        recs = fasta.open_lazy(args.fastafiles[0])
+        if len(set(recs.ids)) != len(recs):
+            seen = set()
+            dup = next(i for i in recs.ids if i in seen or seen.add(i))
+            raise InputError("record %s occurs more than once in the FASTA" % dup)
+        profiles = _Profiles(source, ptype, order=list(recs.ids))
+        lengths = recs.lengths
+    else:
+        recs = None
+        profiles = _Profiles(source, ptype)
+        lengths = profiles.lengths
+    lo, hi = shard.partition(lengths, world)[rank]
+    for a, b in (shard.batches(lengths, lo, hi, shard.batch_positions()) if hi > lo else []):
+        at = a
+        for ids, cols, pst in profiles.runs(a, b):
+            n = len(ids)
+            stream = pst
+            if recs is not None:
+                batch = scanner._RnaBatch(recs[at:at + n])
+                if not np.array_equal(batch.lengths, pst.lengths):
+                    r = int(np.flatnonzero(batch.lengths != pst.lengths)[0])
+                    raise InputError("record %s is %d letters long but its averaged-structure profile has %d rows" %
+                                     (ids[r], int(batch.lengths[r]), int(pst.lengths[r])))
+                stream = pack.Stream(batch.codes, pst.profile, batch.offsets, batch.lengths)
+            P = scanner.struct_matrix(st_pm, cols, args.pairing) if st_pm is not None else None
+            pos = select(engine, stream, m, tab, P, args.minscore, args.min_seqstruct)
+            accumulate(engine, rows, stream, ids, lambda r, cols=cols: cols, pos, m, args.flank)
+            at += n
+    return rows, m
+
+
+def gather(engine, args, seq_pssm, struct_pssm, rank=0, world=1, dist=None):
+    """``collect`` on this rank, then ``combine`` over the ranks -> (S, counts, coverage, hits), the same on every rank; a
+    rank whose share fails hands its exception over and every rank raises the one of the lowest rank"""
+    rows, failure = None, None
+    try:
+        rows, _ = collect(engine, args, seq_pssm, struct_pssm, rank, world)
+    except Exception as e:
+        if world == 1:
+            raise
+        failure = e
+        rows = Rows(1)
+    return combine(rows, rank, world, dist, failure)
+
+
+def main(argv=None, engine=None):
+    from . import background, cli, scanner
+    args = getoptions(argv)
+    if engine is None:
+        from . import launch
+        world, must_spawn = launch.resolve_world(args.gpus)
+        if must_spawn:
+            pkg_parent = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+            path = os.pathsep.join([pkg_parent] + [p for p in os.environ.get("PYTHONPATH", "").split(os.pathsep) if p])
+            rc, _ = launch.spawn_ranks(world, [sys.executable, "-m", "rnascan_amd.sites"] + list(sys.argv[1:] if argv is None else argv),
+                                       extra_env={"PYTHONPATH": path})
+            return rc
+    own = engine is None
+    rank, world, dist = cli._init_distributed(args)
+    if engine is None:
+        engine = scanner.HipEngine(args.device)
+    try:
+        seq_pssm = struct_pssm = None
+        source = args.fastafiles[-1]
+        if not os.path.isdir(source):
+            raise InputError("%s is neither a directory of structure.<id>.txt files nor a packed profile store" % source)
+        if args.pfm_seq:
+            bg = fasta.load_background(args.bg_seq, args.uniform_background, args.fastafiles[0], fasta.RNA, True)
+            seq_pssm = cli.load_motif(args.pfm_seq, args.pseudocount, fasta.RNA, bg)
+        if args.pfm_struct:
+            if not args.bg_struct and not args.uniform_background:
+                bg = background.profile_background(engine, source, rank, world, dist, True)
+            else:
+                bg = fasta.load_background(args.bg_struct, args.uniform_background, source, fasta.STRUCT, True)
+            struct_pssm = cli.load_motif(args.pfm_struct, args.pseudocount, fasta.STRUCT, bg)
+        S, counts, cov, hits = gather(engine, args, seq_pssm, struct_pssm, rank, world, dist)
+        fasta.eprint("Found %d sites" % hits)
+        if hits == 0:
+            fasta.eprint("No site passes the thresholds: nothing to profile, no files written")
+            return 1
+        struct, seq, foreign = site_pfms(S, counts)
+        if foreign is not None and int(foreign.sum()):
+            fasta.eprint("Foreign letters under the sites, left out of the sequence PFM: %d (per column: %s)" %
+                         (int(foreign.sum()), " ".join(str(int(x)) for x in foreign)))
+        if rank == 0:
+            write_pfm(args.prefix + ".struct.txt", STRUCT_ORDER, struct)
+            if seq is not None:
+                write_pfm(args.prefix + ".seq.txt", SEQ_ORDER, seq)
+            write_counts(args.prefix + ".counts.txt", S, counts, cov, hits)
+        if dist is not None:
+            dist.barrier()
+        return 0
+    except (SitesError, InputError, background.BackgroundError, background.InputError) as e:
+        if rank == 0:
+            fasta.eprint(str(e))
+        return 1
+    finally:
+        if own:
+            engine.close()
+
+
+if __name__ == "__main__":
+    sys.exit(main())

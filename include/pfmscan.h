@@ -59,7 +59,7 @@
 extern "C" {
 #endif
 
-#define PFMSCAN_ABI_VERSION 15
+#define PFMSCAN_ABI_VERSION 16
 #define PFMSCAN_NCODE   8      /* columns of a letter table */
 #define PFMSCAN_SEP     7      /* separator / foreign-letter code */
 #define PFMSCAN_NSTRUCT 7      /* columns of a structure profile / structure PSSM */
@@ -69,6 +69,7 @@ extern "C" {
                                   slab-tiled kernel (the table through LDS 64 rows at a time), scans with a structure part the
                                   profile kernel up to 180 rows and a plain one-thread-per-window kernel beyond -- same results */
 #define PFMSCAN_SITE_GROUP 4096 /* most hits of one group of the site profiles (pfmscan_site_groups) */
+#define PFMSCAN_SITE_LIMBS 66   /* 64-bit limbs of one cell of a long accumulator (pfmscan_site_sums_lib_*) */
 
 #define PFMSCAN_OK          0
 #define PFMSCAN_E_BADARG   -1  /* NULL / negative / inconsistent argument   -> ValueError */
@@ -730,6 +731,78 @@ int pfmscan_site_sums_host(pfmscan_ctx *ctx, const uint8_t *codes, const void *p
                            const int64_t *hit_pos, int64_t n_hits, const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec,
                            int32_t m, int32_t flank, int64_t capacity, int64_t *grp_rec, double *sums, uint32_t *counts,
                            int64_t *n_grp, int64_t *first_bad);
+
+/* ---- site profiles of a library: exact per-motif sums in one pass -----------------------------------------------------
+ * The site profile of EVERY motif of a multi-PFM library of one width m, from one pass over the stream: what
+ * pfmscan_site_sums_* + math.fsum give for each motif alone, bit for bit, without bringing the group rows home.
+ * Hit list: (hit_pos, hit_motif) over the n_motifs motifs.  The _dev form and pfmscan_site_groups_lib take it
+ *   MOTIF-MAJOR: hit_motif does not descend, inside one motif the positions ascend strictly, every window
+ *   [pos, pos + m) lies inside one record.  Columns, flank F, W = m + 2 F <= PFMSCAN_MAX_WIDTH, "a column counts" and
+ *   the rejection rule are those of pfmscan_site_sums_* above.
+ * Groups: the groups of motif k are what pfmscan_site_groups gives for motif k's hit list alone: at most
+ *   PFMSCAN_SITE_GROUP consecutive hits of one (motif, record), anchored at that pair's first hit.
+ * Group cell: as above -- lane-wave v of four starts at 0.0 and adds hits v, v + 4, ... in ascending order, the group's
+ *   cell is ((w0 + w1) + w2) + w3; only additions, float32 rows widened first (tests/sites_rules.py).
+ * Per-motif sum: for motif k and cell e = 7 j + c the LONG ACCUMULATOR holds EXACTLY the integer
+ *   A = sum over the groups of motif k of (group cell value / 2^-1074); the values are finite and >= 0.
+ *   Layout: uint64 acc[n_motifs][PFMSCAN_SITE_LIMBS][W * 7], A = sum over i of acc[k][i][e] * 2^(32 i).  Limbs are the
+ *   slow index inside a motif: the 64 lanes of a wave (consecutive cells) add to contiguous addresses.
+ *   A double v > 0 with exponent field E and fraction f: M = f, b = 0 if E == 0 (subnormal), else M = f | 2^52,
+ *   b = E - 1; x = M << (b mod 32) < 2^85; its three 32-bit pieces are added to limbs b / 32, b / 32 + 1, b / 32 + 2.
+ *   DBL_MAX reaches limb 65, hence 66 limbs.  Zero pieces and v == 0 add nothing.  (rnascan_amd/csrc/pfmscan_superacc.hpp,
+ *   shared by host and device; tests/sites_lib_rules.py restates it in Python ints.)
+ *   Integer additions do not depend on their order: the limbs are the same for every schedule, so the device adds
+ *   with 64-bit integer atomics and the bits still do not depend on how the work was cut.  No float atomics.
+ *   Headroom: a call adds fewer than 2^31 groups of fewer than 2^32 per limb: a RAW limb stays below 2^63.  An
+ *   accumulator is NORMALISED when every limb but the top one is below 2^32; the top limb has room for 2^46 values of
+ *   DBL_MAX.
+ *   Rounding: pfmscan_site_acc_round takes A * 2^-1074 to the nearest double, ties to even, +inf beyond DBL_MAX: a
+ *   motif's S[j][c] is bit for bit math.fsum over its group rows.
+ * Counts: uint64 counts[n_motifs][W][8], the integer sums of the per-group counts.  Coverage comes from positions and
+ *   record bounds on the host, per motif.
+ * Rejection: a NaN, +-inf or negative cell under a counted column of a hit of ANY motif: PFMSCAN_E_BADARG, *first_bad
+ *   = the smallest flat element index touched.  NOTE the difference from one pfmscan_site_sums_* run per motif, which
+ *   fails only for the motifs whose hits touch the cell.  A group cell that overflows to +inf from finite cells:
+ *   PFMSCAN_E_BADARG with *first_bad = -1 and a message that says so; a non-finite value is never decomposed.
+ *
+ * Host only, no ctx, no message (the return code says it all):
+ * pfmscan_site_groups_lib: checks the motif-major list (motif indices in [0, n_motifs)) and the record table and cuts
+ *   the groups: grp_first [*n_grp + 1] (indices into the list), grp_rec, grp_motif [*n_grp].  Capacity protocol and
+ *   return codes of pfmscan_site_groups.
+ * pfmscan_site_order_lib: order[i] = index, in the given list, of hit i of the motif-major list: a STABLE counting sort
+ *   by motif, so a list in (position, motif) order -- as pfmscan_library_hits_* return hits -- becomes motif-major.
+ *   An index outside [0, n_motifs): PFMSCAN_E_BADARG.
+ * pfmscan_site_acc_add: dst (normalised) += src (raw or normalised) for n_acc accumulators of n_words_per_limb words
+ *   per limb each (n_motifs and W * 7); dst is normalised again.  PFMSCAN_E_BADSHAPE if a top limb overflows.
+ * pfmscan_site_acc_round: acc (raw or normalised) [n_acc][LIMBS][n_cells] -> out double [n_acc][n_cells].
+ * pfmscan_site_acc_from_doubles: acc_one_cell [LIMBS] = the RAW sum of n < 2^31 values, each finite and >= 0
+ *   (PFMSCAN_E_BADARG otherwise), by the device's decomposition.
+ *
+ * _dev: every buffer is a device buffer; the tables are the caller's (pfmscan_site_groups_lib makes them).  Zeroes
+ *   d_acc [n_motifs][LIMBS][W * 7] / d_counts [n_motifs][W][8] itself and leaves this call's RAW sums there.  A table
+ *   that is broken (groups that do not cover the hits in order, an empty group or one of more than PFMSCAN_SITE_GROUP
+ *   hits, grp_motif descending or outside [0, n_motifs), positions not ascending inside a motif, a window outside its
+ *   group's record, a record outside the stream): PFMSCAN_E_BADARG, *first_bad = -1, decided on the device without a
+ *   load or an add outside the buffers.  Asynchronous on `stream` except for the verdict's one synchronise.  Device
+ *   scratch (8 bytes per four groups) belongs to the ctx.
+ * _staged: the staged stream; hits on the host AS pfmscan_library_hits_* RETURN THEM (any order that is ascending in
+ *   position inside each motif); it reorders, cuts the groups and returns NORMALISED accumulators acc / counts on the host.
+ * There is no pipeline (_host) form: the caller stages, as for pfmscan_library_hits_sum_staged. */
+int pfmscan_site_groups_lib(const int64_t *hit_pos, const int32_t *hit_motif, int64_t n_hits, int32_t n_motifs,
+                            const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec, int32_t m, int64_t capacity,
+                            int64_t *grp_first, int64_t *grp_rec, int64_t *grp_motif, int64_t *n_grp);
+int pfmscan_site_order_lib(const int64_t *hit_pos, const int32_t *hit_motif, int64_t n_hits, int32_t n_motifs, int64_t *order);
+int pfmscan_site_acc_add(uint64_t *dst, const uint64_t *src, int64_t n_acc, int64_t n_words_per_limb);
+int pfmscan_site_acc_round(const uint64_t *acc, int64_t n_acc, int64_t n_cells, double *out);
+int pfmscan_site_acc_from_doubles(const double *values, int64_t n, uint64_t *acc_one_cell);
+int pfmscan_site_sums_lib_dev(pfmscan_ctx *ctx, const uint8_t *d_codes, const void *d_profile, int profile_dtype, int64_t n_pos,
+                              const int64_t *d_hit_pos, int64_t n_hits, const int64_t *d_grp_first, const int64_t *d_grp_rec,
+                              const int64_t *d_grp_motif, int64_t n_grp, const int64_t *d_rec_off, const int64_t *d_rec_len,
+                              int64_t n_rec, int32_t n_motifs, int32_t m, int32_t flank, uint64_t *d_acc, uint64_t *d_counts,
+                              int64_t *first_bad, void *stream);
+int pfmscan_site_sums_lib_staged(pfmscan_ctx *ctx, int use_codes, int use_profile, const int64_t *hit_pos, const int32_t *hit_motif,
+                                 int64_t n_hits, const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec, int32_t n_motifs,
+                                 int32_t m, int32_t flank, uint64_t *acc, uint64_t *counts, int64_t *first_bad);
 
 /* ---- host ingest and output (no device needed; no context: errors via pfmscan_last_error(NULL)) ---------------
  * The two pieces of host work that dwarf the kernel at scale, in native code.

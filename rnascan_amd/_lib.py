@@ -22,7 +22,7 @@ NCODE = 8
 NSTRUCT = 7
 MAX_M = 64            # widest PFM of the tuned kernels and of PFM libraries
 MAX_WIDTH = 4096      # widest PFM accepted (wider than MAX_M: the plain rolled-loop kernel)
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 # every symbol include/pfmscan.h declares (checked by tests/test_abi.py)
 SYMBOLS = [
@@ -47,8 +47,11 @@ SYMBOLS = [
     "pfmscan_library_hits_sum_dev", "pfmscan_library_hits_sum_staged", "pfmscan_library_hits_sum_host",
     "pfmscan_profile_row_bound_dev", "pfmscan_profile_row_bound_staged", "pfmscan_library_sum_thresholds",
     "pfmscan_site_groups", "pfmscan_site_sums_dev", "pfmscan_site_sums_staged", "pfmscan_site_sums_host",
+    "pfmscan_site_groups_lib", "pfmscan_site_order_lib", "pfmscan_site_acc_add", "pfmscan_site_acc_round",
+    "pfmscan_site_acc_from_doubles", "pfmscan_site_sums_lib_dev", "pfmscan_site_sums_lib_staged",
 ]
 SITE_GROUP = 4096     # most hits of one group of the site profiles
+SITE_LIMBS = 66       # 64-bit limbs of one cell of a long accumulator (site profiles of a library)
 MAX_COVER = 1024      # largest coverage of a row the averaging accepts
 AVG_OK, AVG_DOTBRACKET, AVG_UNCOVERED, AVG_COVER, AVG_BAD_TABLE = range(5)   # what a rejected averaging names
 TSV_CONST, TSV_I64, TSV_F32, TSV_F64, TSV_INDEXED, TSV_FIXED, TSV_WINDOW, TSV_SPAN = range(8)
@@ -176,6 +179,14 @@ def load():
                                            ctypes.POINTER(i64)]
     L.pfmscan_site_sums_host.argtypes = [vp, vp, vp, i32, i64, vp, i64, vp, vp, i64, i32, i32, i64, vp, vp, vp,
                                          ctypes.POINTER(i64), ctypes.POINTER(i64)]
+    L.pfmscan_site_groups_lib.argtypes = [vp, vp, i64, i32, vp, vp, i64, i32, i64, vp, vp, vp, ctypes.POINTER(i64)]
+    L.pfmscan_site_order_lib.argtypes = [vp, vp, i64, i32, vp]
+    L.pfmscan_site_acc_add.argtypes = [vp, vp, i64, i64]
+    L.pfmscan_site_acc_round.argtypes = [vp, i64, i64, vp]
+    L.pfmscan_site_acc_from_doubles.argtypes = [vp, i64, vp]
+    L.pfmscan_site_sums_lib_dev.argtypes = [vp, vp, vp, i32, i64, vp, i64, vp, vp, vp, i64, vp, vp, i64, i32, i32, i32, vp, vp,
+                                            ctypes.POINTER(i64), vp]
+    L.pfmscan_site_sums_lib_staged.argtypes = [vp, i32, i32, vp, vp, i64, vp, vp, i64, i32, i32, i32, vp, vp, ctypes.POINTER(i64)]
     L.pfmscan_count_bytes.argtypes = [vp, i64, vp, i32]
     L.pfmscan_place_alloc.argtypes = [vp, i32, vp, vp, i32]
     L.pfmscan_place_free.argtypes = [vp, vp]
@@ -274,6 +285,85 @@ def site_groups(pos, offsets, lengths, m):
         raise ValueError("site groups: the hits must ascend strictly and every window of width %d must lie inside one record "
                          "of a record table whose records ascend, each behind the separator of the one before" % int(m))
     return first, rec
+
+
+def site_groups_lib(pos, motif, n_motifs, offsets, lengths, m):
+    """the per-motif groups of a MOTIF-MAJOR hit list (pfmscan_site_groups_lib, include/pfmscan.h) -> (grp_first int64
+    [n_grp + 1], grp_rec int64 [n_grp], grp_motif int64 [n_grp]).  ValueError for a list that is not motif-major, a motif
+    index outside [0, n_motifs), a window outside its record or a broken record table."""
+    L = load()
+    pos = np.ascontiguousarray(pos, dtype=np.int64)
+    motif = np.ascontiguousarray(motif, dtype=np.int32)
+    off = np.ascontiguousarray(offsets, dtype=np.int64)
+    ln = np.ascontiguousarray(lengths, dtype=np.int64)
+    if pos.ndim != 1 or pos.shape != motif.shape or off.ndim != 1 or off.shape != ln.shape:
+        raise ValueError("positions and motifs, offsets and lengths must be one-dimensional and pairwise of the same size")
+    n = ctypes.c_int64(0)
+    first = np.zeros(1, dtype=np.int64)
+    rec = mot = np.zeros(0, dtype=np.int64)
+    args = (_ptr(pos), _ptr(motif), pos.size, int(n_motifs), _ptr(off), _ptr(ln), off.size, int(m))
+    rc = L.pfmscan_site_groups_lib(*args, 0, _ptr(first), None, None, ctypes.byref(n))
+    if rc == E_CAPACITY:
+        first = np.zeros(n.value + 1, dtype=np.int64)
+        rec = np.zeros(n.value, dtype=np.int64)
+        mot = np.zeros(n.value, dtype=np.int64)
+        rc = L.pfmscan_site_groups_lib(*args, n.value, _ptr(first), _ptr(rec), _ptr(mot), ctypes.byref(n))
+    if rc != 0:
+        raise ValueError("site groups: the hit list must be motif-major with motif indices in [0, %d), ascend strictly inside a "
+                         "motif, and every window of width %d must lie inside one record of a valid record table" % (int(n_motifs), int(m)))
+    return first, rec, mot
+
+
+def site_order_lib(pos, motif, n_motifs):
+    """the stable permutation that makes a (position, motif)-ordered hit list motif-major (pfmscan_site_order_lib) -> int64 [n]"""
+    L = load()
+    pos = np.ascontiguousarray(pos, dtype=np.int64)
+    motif = np.ascontiguousarray(motif, dtype=np.int32)
+    if pos.ndim != 1 or pos.shape != motif.shape:
+        raise ValueError("positions and motifs must be one-dimensional and of the same size")
+    order = np.zeros(pos.size, dtype=np.int64)
+    if L.pfmscan_site_order_lib(_ptr(pos), _ptr(motif), pos.size, int(n_motifs), _ptr(order)) != 0:
+        raise ValueError("site order: a motif index lies outside [0, %d)" % int(n_motifs))
+    return order
+
+
+def site_acc_from_doubles(values):
+    """RAW long accumulator uint64 [SITE_LIMBS] of one cell: the exact sum of finite values >= 0 (pfmscan_site_acc_from_doubles)"""
+    L = load()
+    values = np.ascontiguousarray(values, dtype=np.float64).ravel()
+    acc = np.zeros(SITE_LIMBS, dtype=np.uint64)
+    if L.pfmscan_site_acc_from_doubles(_ptr(values), values.size, _ptr(acc)) != 0:
+        raise ValueError("site accumulator: every value must be finite and at least 0")
+    return acc
+
+
+def site_acc_add(dst, src):
+    """dst (normalised, uint64 [..][SITE_LIMBS][n], C-contiguous, changed in place) += src (raw or normalised, same shape);
+    dst is normalised again (pfmscan_site_acc_add).  Returns dst."""
+    L = load()
+    src = np.ascontiguousarray(src, dtype=np.uint64)
+    if not (isinstance(dst, np.ndarray) and dst.dtype == np.uint64 and dst.flags.c_contiguous and dst.flags.writeable):
+        raise ValueError("dst must be a writable C-contiguous uint64 array")
+    if dst.shape != src.shape or dst.ndim < 2 or dst.shape[-2] != SITE_LIMBS:
+        raise ValueError("accumulators are uint64 [..][%d][n] of the same shape" % SITE_LIMBS)
+    n_acc = int(np.prod(dst.shape[:-2], dtype=np.int64))
+    rc = L.pfmscan_site_acc_add(_ptr(dst), _ptr(src), n_acc, dst.shape[-1])
+    if rc != 0:
+        raise OverflowError("site accumulator: the top limb overflows")
+    return dst
+
+
+def site_acc_round(acc):
+    """uint64 [..][SITE_LIMBS][n] (raw or normalised) -> float64 [..][n]: A * 2^-1074 to the nearest double, ties to even,
+    +inf beyond DBL_MAX (pfmscan_site_acc_round)"""
+    L = load()
+    acc = np.ascontiguousarray(acc, dtype=np.uint64)
+    if acc.ndim < 2 or acc.shape[-2] != SITE_LIMBS:
+        raise ValueError("accumulators are uint64 [..][%d][n]" % SITE_LIMBS)
+    out = np.zeros(acc.shape[:-2] + acc.shape[-1:], dtype=np.float64)
+    if L.pfmscan_site_acc_round(_ptr(acc), int(np.prod(acc.shape[:-2], dtype=np.int64)), acc.shape[-1], _ptr(out)) != 0:
+        raise ValueError("site accumulator: bad shape")
+    return out
 
 
 def fasta_index(buf, threads=0):
@@ -1007,6 +1097,42 @@ class Context(object):
                                            _ptr(addr(d_pos)), int(n_hits), _ptr(addr(d_grp_first)), _ptr(addr(d_grp_rec)), int(n_grp),
                                            _ptr(addr(d_offsets)), _ptr(addr(d_lengths)), int(n_rec), int(m), int(flank),
                                            _ptr(addr(d_sums)), _ptr(addr(d_counts)), ctypes.byref(bad), _ptr(stream))
+        self._colsums_check(rc, bad)
+
+    # -- site profiles of a library: exact per-motif sums (include/pfmscan.h) --------------------------------------
+    def site_sums_lib_staged(self, pos, motif, n_motifs, offsets, lengths, m, flank=0, letters=True, profile=True):
+        """per-motif long accumulators under the hits (pos, motif) -- as the library scans return them -- of the staged
+        stream -> (acc uint64 [n_motifs][SITE_LIMBS][W * 7] normalised | None, counts uint64 [n_motifs][W][8] | None).
+        ValueError (``.element``) for a NaN, infinite or negative cell under a hit of any motif"""
+        pos = np.ascontiguousarray(pos, dtype=np.int64)
+        motif = np.ascontiguousarray(motif, dtype=np.int32)
+        if pos.ndim != 1 or pos.shape != motif.shape:
+            raise ValueError("positions and motifs must be one-dimensional and of the same size")
+        off, ln = self._colsums_tables(offsets, lengths)
+        W, n_motifs = int(m) + 2 * int(flank), int(n_motifs)
+        if n_motifs < 0 or W < 1 or W > MAX_WIDTH:
+            raise ValueError("site sums: a negative number of motifs, or width + 2 x flank outside [1, PFMSCAN_MAX_WIDTH]")
+        acc = np.zeros((n_motifs, SITE_LIMBS, W * NSTRUCT), dtype=np.uint64) if profile else None
+        counts = np.zeros((n_motifs, W, NCODE), dtype=np.uint64) if letters else None
+        bad = ctypes.c_int64(-1)
+        rc = self._L.pfmscan_site_sums_lib_staged(self._h, int(bool(letters)), int(bool(profile)), _ptr(pos), _ptr(motif), pos.size,
+                                                  _ptr(off), _ptr(ln), off.size, n_motifs, int(m), int(flank), _ptr(acc),
+                                                  _ptr(counts), ctypes.byref(bad))
+        self._colsums_check(rc, bad)
+        return acc, counts
+
+    def site_sums_lib_dev(self, d_codes, d_profile, dtype, n_pos, d_pos, n_hits, d_grp_first, d_grp_rec, d_grp_motif, n_grp,
+                          d_offsets, d_lengths, n_rec, n_motifs, m, flank, d_acc, d_counts, stream=None):
+        """device buffers (raw addresses or objects with data_ptr()); zeroes d_acc / d_counts and leaves RAW sums there;
+        asynchronous on `stream` except for the verdict"""
+        addr = lambda a: None if a is None else (a.data_ptr() if hasattr(a, "data_ptr") else a)   # noqa: E731
+        bad = ctypes.c_int64(-1)
+        rc = self._L.pfmscan_site_sums_lib_dev(self._h, _ptr(addr(d_codes)), _ptr(addr(d_profile)),
+                                               PROFILE_F32 if np.dtype(dtype) == np.float32 else PROFILE_F64, int(n_pos),
+                                               _ptr(addr(d_pos)), int(n_hits), _ptr(addr(d_grp_first)), _ptr(addr(d_grp_rec)),
+                                               _ptr(addr(d_grp_motif)), int(n_grp), _ptr(addr(d_offsets)), _ptr(addr(d_lengths)),
+                                               int(n_rec), int(n_motifs), int(m), int(flank), _ptr(addr(d_acc)), _ptr(addr(d_counts)),
+                                               ctypes.byref(bad), _ptr(stream))
         self._colsums_check(rc, bad)
 
     # -- generic-alphabet letter hits in fp64; two code streams ---------------------------------

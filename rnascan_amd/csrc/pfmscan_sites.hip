@@ -38,7 +38,7 @@
 #include <string>
 #include <vector>
 
-#include "pfmscan_ctx.hpp"
+#include "pfmscan_sites.hpp"
 
 using namespace pfmscan;
 
@@ -48,8 +48,6 @@ constexpr int SITE_BLOCK = 256;
 constexpr int SITE_WAVES = SITE_BLOCK / 64;
 constexpr int SITE_AHEAD = 4;                    // hits of a wave whose cells are loaded together
 constexpr int SITE_CHECK_BLOCK = 256;
-constexpr int SITE_VERDICT_BLOCK = 1024;
-constexpr int64_t SITE_NONE = INT64_MAX;
 
 struct SiteArgs {
     int64_t n_pos;                               // rows / codes of the stream buffer
@@ -65,26 +63,6 @@ struct SiteArgs {
 
 template <typename T> struct SiteCell { using Acc = double; static constexpr int CS = 7; };
 template <> struct SiteCell<uint8_t> { using Acc = uint32_t; static constexpr int CS = 8; };
-
-__device__ inline int64_t site_block_min(int64_t v, int64_t *sh)
-{
-    const int t = threadIdx.x;
-    sh[t] = v;
-    __syncthreads();
-    for (int s = blockDim.x / 2; s > 0; s >>= 1) {
-        if (t < s) sh[t] = min(sh[t], sh[t + s]);
-        __syncthreads();
-    }
-    const int64_t m = sh[0];
-    __syncthreads();
-    return m;
-}
-
-// record (off, len), off already relative to the buffer, lies inside it
-__device__ inline bool site_inside(int64_t off, int64_t len, int64_t n_pos)
-{
-    return off >= 0 && len >= 0 && off <= n_pos && len <= n_pos - off;
-}
 
 __global__ __launch_bounds__(SITE_CHECK_BLOCK) void k_site_check(SiteArgs a, int64_t *__restrict__ blk)
 {
@@ -217,32 +195,6 @@ __global__ __launch_bounds__(SITE_BLOCK) void k_site_sums(SiteArgs a, const T *_
     }
 }
 
-// verdict[0] = the smallest bad flat element index, verdict[1] = the first lane of k_site_check that found a broken table
-__global__ __launch_bounds__(SITE_VERDICT_BLOCK) void k_site_verdict(const int64_t *__restrict__ blk_cells, int64_t n_cells,
-                                                                    const int64_t *__restrict__ blk_check, int64_t n_check,
-                                                                    int64_t *__restrict__ verdict)
-{
-    __shared__ int64_t sh[SITE_VERDICT_BLOCK];
-    int64_t m = SITE_NONE;
-    for (int64_t i = threadIdx.x; i < n_cells; i += SITE_VERDICT_BLOCK) m = min(m, blk_cells[i]);
-    m = site_block_min(m, sh);
-    if (threadIdx.x == 0) verdict[0] = m;
-    m = SITE_NONE;
-    for (int64_t i = threadIdx.x; i < n_check; i += SITE_VERDICT_BLOCK) m = min(m, blk_check[i]);
-    m = site_block_min(m, sh);
-    if (threadIdx.x == 0) verdict[1] = m;
-}
-
-int site_shape(pfmscan_ctx *ctx, bool rows, int dtype, int32_t m, int32_t flank)
-{
-    if (rows && dtype != PFMSCAN_PROFILE_F32 && dtype != PFMSCAN_PROFILE_F64)
-        return fail(ctx, PFMSCAN_E_BADARG, "site sums: profile_dtype must be PFMSCAN_PROFILE_F32 or F64");
-    if (m < 1 || flank < 0) return fail(ctx, PFMSCAN_E_BADARG, "site sums: the width must be at least 1 and the flank at least 0");
-    if ((int64_t)m + 2 * (int64_t)flank > PFMSCAN_MAX_WIDTH)
-        return fail(ctx, PFMSCAN_E_BADSHAPE, "site sums: width + 2 x flank exceeds PFMSCAN_MAX_WIDTH");
-    return PFMSCAN_OK;
-}
-
 int64_t site_check_blocks(int64_t n_hits, int64_t n_grp) { return (std::max(n_hits, n_grp) + SITE_CHECK_BLOCK - 1) / SITE_CHECK_BLOCK; }
 // int64 words of scratch one launch set needs: a key per group, a key per check workgroup
 size_t site_blk_words(int64_t n_hits, int64_t n_grp) { return (size_t)(n_grp + site_check_blocks(n_hits, n_grp)); }
@@ -271,21 +223,6 @@ int site_launch(pfmscan_ctx *ctx, const SiteArgs &a, const uint8_t *d_codes, con
     hipLaunchKernelGGL(k_site_verdict, dim3(1), dim3(SITE_VERDICT_BLOCK), 0, st, blk, rows ? a.n_grp : 0, blk_check, nb_check,
                        d_verdict);
     HIP_TRY(ctx, hipGetLastError());
-    return PFMSCAN_OK;
-}
-
-// v[0..1] as k_site_verdict wrote them -> status; cell_base is added to the reported element index
-int site_verdict(pfmscan_ctx *ctx, const int64_t *v, int64_t cell_base, int64_t *first_bad)
-{
-    if (v[1] != SITE_NONE)
-        return fail(ctx, PFMSCAN_E_BADARG, "site sums: the group table does not cover the hits in order, a hit's window leaves "
-                                           "the record of its group, or a record lies outside the stream");
-    if (v[0] != SITE_NONE) {
-        const int64_t at = cell_base + v[0];
-        if (first_bad) *first_bad = at;
-        return fail(ctx, PFMSCAN_E_BADARG, "site sums: row " + std::to_string(at / 7) + ", column " + std::to_string(at % 7) +
-                                               " under a hit is NaN, infinite or negative");
-    }
     return PFMSCAN_OK;
 }
 
@@ -370,6 +307,30 @@ int site_upload_tables(pfmscan_ctx *ctx, const int64_t *hit_pos, int64_t n_hits,
 }
 
 }  // namespace
+
+int pfmscan::site_shape(pfmscan_ctx *ctx, bool rows, int dtype, int32_t m, int32_t flank)
+{
+    if (rows && dtype != PFMSCAN_PROFILE_F32 && dtype != PFMSCAN_PROFILE_F64)
+        return fail(ctx, PFMSCAN_E_BADARG, "site sums: profile_dtype must be PFMSCAN_PROFILE_F32 or F64");
+    if (m < 1 || flank < 0) return fail(ctx, PFMSCAN_E_BADARG, "site sums: the width must be at least 1 and the flank at least 0");
+    if ((int64_t)m + 2 * (int64_t)flank > PFMSCAN_MAX_WIDTH)
+        return fail(ctx, PFMSCAN_E_BADSHAPE, "site sums: width + 2 x flank exceeds PFMSCAN_MAX_WIDTH");
+    return PFMSCAN_OK;
+}
+
+int pfmscan::site_verdict(pfmscan_ctx *ctx, const int64_t *v, int64_t cell_base, int64_t *first_bad)
+{
+    if (v[1] != SITE_NONE)
+        return fail(ctx, PFMSCAN_E_BADARG, "site sums: the group table does not cover the hits in order, a hit's window leaves "
+                                           "the record of its group, or a record lies outside the stream");
+    if (v[0] != SITE_NONE) {
+        const int64_t at = cell_base + v[0];
+        if (first_bad) *first_bad = at;
+        return fail(ctx, PFMSCAN_E_BADARG, "site sums: row " + std::to_string(at / 7) + ", column " + std::to_string(at % 7) +
+                                               " under a hit is NaN, infinite or negative");
+    }
+    return PFMSCAN_OK;
+}
 
 extern "C" {
 

@@ -163,6 +163,21 @@ class HipEngine(object):
         return self.ctx.site_sums_host(stream.codes if letters else None, stream.profile if profile else None, pos,
                                        stream.offsets, stream.lengths, m, flank)
 
+    def site_sums_library(self, stream, pos, motif, n_motifs, m, flank=0, letters=True, profile=True):
+        """the site sums of EVERY motif of a library of width m in one pass: hits (pos, motif index) as ``library_hits`` /
+        ``library_hits_sum`` return them -> (acc uint64 [n_motifs][66][W * 7] | None, counts uint64 [n_motifs][W][8] | None):
+        per motif and cell the exact integer sum of its group cells (pfmscan_site_sums_lib_staged, include/pfmscan.h);
+        ``_lib.site_acc_add`` merges batches and ranks, ``_lib.site_acc_round`` gives what math.fsum over that motif's
+        group rows gives.  The stream is staged unless it already is (the library scans leave it staged: one staging
+        serves the hits call and this one); there is no pipeline form.  ValueError with ``element`` when a NaN, infinite
+        or negative cell lies under a hit of any motif."""
+        letters = bool(letters) and stream.codes is not None
+        profile = bool(profile) and stream.profile is not None
+        if not letters and not profile:
+            raise ValueError("the stream has neither the codes nor the profile asked for")
+        self._stage(stream)
+        return self.ctx.site_sums_lib_staged(pos, motif, n_motifs, stream.offsets, stream.lengths, m, flank, letters, profile)
+
 
 def _library(self, T, P):
     """the device tables of a library (letter tables and / or structure PSSMs), kept across batches until another one is asked for"""

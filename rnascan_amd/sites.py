@@ -19,6 +19,11 @@ The sums are made on the GPU per GROUP of at most 4096 hits of a record (``HipEn
 additions inside a group, see include/pfmscan.h) and the groups are combined here with ``math.fsum``, which is exactly
 rounded: the result has the same bits whatever the batch size, the pipeline chunk, the upload mode, the input form and
 the number of ranks.  Profile columns are matched to letters by NAME, file by file for a directory.
+
+``--all-motifs``: one profile per motif (pair) of multi-PFM files from ONE pass per PFM width.  The hits come from the library
+kernels, and the group rows are not brought home: the GPU adds them per motif into exact integer accumulators
+(``HipEngine.site_sums_library``; 66 limbs of 64 bits per cell, include/pfmscan.h), which are merged over batches and ranks
+and rounded once -- per motif the bits of the ``math.fsum`` above.
 """
 import argparse
 import math
@@ -180,19 +185,28 @@ def site_pfms(S, counts):
 def write_pfm(path, letters, matrix):
     """the PFM text format ``-p`` / ``-q`` read: header PO + letters, one row per position, every number in the shortest
     form that reads back to the same float64 (the native table writer, pfmscan_tsv_format)"""
+    with open(path, "w") as out:
+        _pfm_to(out, letters, matrix)
+
+
+def _pfm_to(out, letters, matrix):
     from . import table
     matrix = np.asarray(matrix)
-    with open(path, "w") as out:
-        w = table.TsvWriter(out, ["PO"] + list(letters), match_id=False)
-        cols = {"PO": np.arange(matrix.shape[0], dtype=np.int64)}
-        for k, c in enumerate(letters):
-            cols[c] = np.ascontiguousarray(matrix[:, k])
-        w.write_chunk(cols, matrix.shape[0])
-        w.close()
+    w = table.TsvWriter(out, ["PO"] + list(letters), match_id=False)
+    cols = {"PO": np.arange(matrix.shape[0], dtype=np.int64)}
+    for k, c in enumerate(letters):
+        cols[c] = np.ascontiguousarray(matrix[:, k])
+    w.write_chunk(cols, matrix.shape[0])
+    w.close()
 
 
 def write_counts(path, S, counts, cov, hits):
     """PREFIX.counts.txt: per column the coverage, the raw structure sums and the integer letter counts (N = foreign)"""
+    with open(path, "w") as out:
+        _counts_to(out, S, counts, cov, hits)
+
+
+def _counts_to(out, S, counts, cov, hits):
     from . import table
     names, cols = ["PO", "Sites", "Coverage"], {"PO": np.arange(cov.size, dtype=np.int64), "Sites": np.full(cov.size, hits, dtype=np.int64),
                                                 "Coverage": cov}
@@ -206,26 +220,25 @@ def write_counts(path, S, counts, cov, hits):
             cols["Count." + c] = np.ascontiguousarray(counts[:, k])
         names.append("Count.N")
         cols["Count.N"] = counts[:, len(SEQ_ORDER):].sum(axis=1)
-    with open(path, "w") as out:
-        w = table.TsvWriter(out, names, match_id=False)
-        w.write_chunk(cols, cov.size)
-        w.close()
+    w = table.TsvWriter(out, names, match_id=False)
+    w.write_chunk(cols, cov.size)
+    w.close()
 
 
 # ---------------------------------------------------------------------------
 # hit selection: exactly rnascan's
 # ---------------------------------------------------------------------------
-def select(engine, stream, m, letter_table, struct_pssm, minscore, min_seqstruct=None):
+def select(engine, stream, m, letter_table, struct_pssm, minscore, min_seqstruct=None, one_shot=True):
     """the stream positions ``rnascan`` reports for this motif (pair) with the same -m / --min-seqstruct: the same
     engine.hits / hits_sum calls as scanner._scan_combined_stream, scan_records and _scan_profile_stream make"""
     from . import scanner
     thr = float(minscore)
     both = letter_table is not None and struct_pssm is not None
     if both and min_seqstruct is not None and hasattr(engine, "hits_sum"):
-        pos, _, _ = engine.hits_sum(stream, letter_table, struct_pssm, thr, thr, float(min_seqstruct))
+        pos, _, _ = engine.hits_sum(stream, letter_table, struct_pssm, thr, thr, float(min_seqstruct), one_shot=one_shot)
         return pos
     pos, sq, st = scanner._select(engine, stream, m, letter_table, struct_pssm, thr if letter_table is not None else -np.inf,
-                                  thr if struct_pssm is not None else -np.inf)
+                                  thr if struct_pssm is not None else -np.inf, one_shot=one_shot)
     if both and min_seqstruct is not None:
         keep = np.round(sq, 3).astype(np.float64) + st > float(min_seqstruct)
         pos = pos[keep]
@@ -240,12 +253,16 @@ def getoptions(argv=None):
     parser = argparse.ArgumentParser(prog="python -m rnascan_amd.sites", description=desc)
     parser.add_argument("inputs", metavar="INPUT", nargs="+",
                         help="seqs.fa avgdir_or_store/ (with -p), or avgdir_or_store/ alone (with -q only)")
-    parser.add_argument("-p", "--pfm_seq", dest="pfm_seq", type=str, help="Sequence PFM (the first motif of a multi-PFM file)")
-    parser.add_argument("-q", "--pfm_struct", dest="pfm_struct", type=str, help="Structure PFM (the first motif of a multi-PFM file)")
+    parser.add_argument("-p", "--pfm_seq", dest="pfm_seq", type=str, help="Sequence PFM (the first motif of a multi-PFM file; every motif with --all-motifs)")
+    parser.add_argument("-q", "--pfm_struct", dest="pfm_struct", type=str, help="Structure PFM (the first motif of a multi-PFM file; every motif with --all-motifs)")
     parser.add_argument("-C", "--pseudocount", type=float, dest="pseudocount", default=0, help="Pseudocount for normalizing PFM. [%(default)s]")
     parser.add_argument("-m", "--minscore", type=float, dest="minscore", default=6, help="Minimum score for motif hits. [%(default)s]")
     parser.add_argument("--min-seqstruct", type=float, default=None, dest="min_seqstruct", metavar="T",
                         help="with -p AND -q: additionally keep a site only if its LogOdds.SeqStruct exceeds T, as rnascan does [off]")
+    parser.add_argument("--all-motifs", action="store_true", default=False, dest="all_motifs",
+                        help=("one site profile per motif (pair) of multi-PFM files, pairs as rnascan pairs them, in one pass per "
+                              "width: PREFIX.struct.txt / PREFIX.seq.txt become multi-PFM libraries that -q / -p read, "
+                              "PREFIX.counts.txt gets a leading Motif column [off]"))
     parser.add_argument("--flank", type=int, default=0, metavar="F",
                         help=("also sum F columns either side of every site; columns that hang over a record end are skipped.  "
                               "NOTE: only --flank 0 writes a PFM of the motif's width that -q / -p accept as the motif it came from; "
@@ -405,6 +422,258 @@ def gather(engine, args, seq_pssm, struct_pssm, rank=0, world=1, dist=None):
     return combine(rows, rank, world, dist, failure)
 
 
+# ---------------------------------------------------------------------------
+# --all-motifs: one profile per motif (pair) of multi-PFM files
+# ---------------------------------------------------------------------------
+ACC_LIMIT = 1 << 31                           # bytes of the long accumulators of one width group
+
+
+def motif_pairs(seq_pssm, struct_pssm):
+    """[(sequence id | None, structure id | None)] in output order: scanner.pair_motifs' pairs, or every motif of the one file"""
+    from . import scanner
+    if seq_pssm and struct_pssm:
+        pairs = scanner.pair_motifs(seq_pssm, struct_pssm)
+        if pairs is None:
+            raise InputError("the two PFM libraries differ in size and share no motif id: their motifs cannot be paired")
+        return pairs
+    one = seq_pssm or struct_pssm
+    ids = sorted(one.keys()) if len(one) > 1 else list(one.keys())
+    return [(i, None) for i in ids] if seq_pssm else [(None, i) for i in ids]
+
+
+def pair_id(a, b):
+    if b is None or a == b:
+        return a
+    return b if a is None else "%s__%s" % (a, b)
+
+
+def select_library(engine, stream, m, tabs, pssms, minscore, min_seqstruct=None):
+    """(pos, motif index) in (position, motif index) order: for every motif (pair) of one width the positions ``rnascan``
+    reports with the same options -- the same library_hits / library_hits_sum / per-pair calls and conditions as
+    scanner._scan_combined_stream, scan_records and _scan_profile_stream.  The stream is left staged for the sums."""
+    from . import scanner
+    thr = float(minscore)
+    n = len(tabs if tabs is not None else pssms)
+    both = tabs is not None and pssms is not None
+    wide = n > 1 and m <= scanner.LIBRARY_MAX_M
+    T = None if tabs is None else np.stack(tabs)
+    P = None if pssms is None else np.stack(pssms)
+    if both:
+        on_device = min_seqstruct is not None and hasattr(engine, "hits_sum")
+        in_library = on_device and wide and hasattr(engine, "library_hits_sum") and hasattr(engine, "library_sum_thresholds")
+        if in_library:
+            in_library = bool(np.all(np.isfinite(engine.library_sum_thresholds(stream, T, P, thr, float(min_seqstruct)))))
+        if in_library:
+            pos, mo, _, _ = engine.library_hits_sum(stream, T, P, thr, thr, float(min_seqstruct))
+            return pos, mo
+        if not on_device and wide and np.isfinite(thr):
+            pos, mo, sq, st = engine.library_hits(stream, T, P, thr, thr, one_shot=False)
+            if min_seqstruct is not None:
+                keep = np.round(sq, 3).astype(np.float64) + st > float(min_seqstruct)
+                pos, mo = pos[keep], mo[keep]
+            return pos, mo
+    elif wide and np.isfinite(thr) and hasattr(engine, "library_hits"):
+        if tabs is not None:
+            pos, mo, _, _ = engine.library_hits(stream, T, None, thr, one_shot=False)
+        else:
+            pos, mo, _, _ = engine.library_hits(stream, None, P, None, thr, one_shot=False)
+            rec, start = stream.locate(pos)         # no codes -> no separators: drop windows that run over a record end
+            ok = start + m <= stream.lengths[rec]
+            pos, mo = pos[ok], mo[ok]
+        return pos, mo
+    parts = [select(engine, stream, m, None if tabs is None else tabs[k], None if pssms is None else pssms[k], minscore,
+                    min_seqstruct, one_shot=False) for k in range(n)]
+    pos = np.concatenate(parts) if parts else np.zeros(0, dtype=np.int64)
+    mo = np.concatenate([np.full(p.size, k, dtype=np.int32) for k, p in enumerate(parts)]) if parts else np.zeros(0, dtype=np.int32)
+    order = np.lexsort((mo, pos))
+    return pos[order], mo[order]
+
+
+class LibraryRows(object):
+    """what one rank collected for the n motifs of one width: normalised long accumulators uint64 [n][66][W * 7] (cells in
+    STRUCT_ORDER) or None, letter counts int64 [n][W][8] or None, coverage int64 [n][W], hits int64 [n]"""
+
+    def __init__(self, n, W, letters=True):
+        from ._lib import SITE_LIMBS
+        self.acc = np.zeros((n, SITE_LIMBS, W * 7), dtype=np.uint64)
+        self.counts = np.zeros((n, W, 8), dtype=np.int64) if letters else None
+        self.coverage = np.zeros((n, W), dtype=np.int64)
+        self.hits = np.zeros(n, dtype=np.int64)
+
+    def add(self, other):
+        from . import _lib
+        _lib.site_acc_add(self.acc, other.acc)
+        if self.counts is not None:
+            self.counts += other.counts
+        self.coverage += other.coverage
+        self.hits += other.hits
+
+
+def accumulate_library(engine, rows, stream, ids, cols, pos, mo, m, flank=0):
+    """add the sites (pos, motif index) of one packed batch to ``rows``; ``cols``: the batch's profile column letters"""
+    from . import _lib
+    n, W = rows.hits.size, rows.coverage.shape[1]
+    if pos.size == 0:
+        return
+    try:
+        acc, counts = engine.site_sums_library(stream, pos, mo, n, m, flank, letters=rows.counts is not None, profile=True)
+    except ValueError as e:
+        at = getattr(e, "element", None)
+        if at is None:
+            raise
+        row, col = divmod(int(at), 7)
+        rec, start = stream.locate(np.asarray([row]))
+        rec = int(rec[0])
+        raise SitesError(ids[rec], int(start[0]) + 1, cols[col], float(stream.profile[row, col]))
+    cols = list(cols)
+    if sorted(cols) != sorted(STRUCT_ORDER):
+        raise InputError("averaged-structure columns %s are not the seven structure letters %s" % (cols, STRUCT_ORDER))
+    if cols != list(STRUCT_ORDER):
+        acc = acc.reshape(n, acc.shape[1], W, 7)[..., [cols.index(c) for c in STRUCT_ORDER]].reshape(n, acc.shape[1], W * 7)
+    _lib.site_acc_add(rows.acc, np.ascontiguousarray(acc))
+    if rows.counts is not None:
+        rows.counts += counts.astype(np.int64)
+    for k in range(n):
+        mine = pos[mo == k]
+        rows.coverage[k] += coverage(stream, mine, m, flank)
+        rows.hits[k] += mine.size
+
+
+def collect_library(engine, args, seq_pssm, struct_pssm, rank=0, world=1):
+    """this rank's {width: LibraryRows} and the pairs of every width [(width, [pair])], in pair order"""
+    from . import cli, scanner
+    from ._lib import MAX_WIDTH, SITE_LIMBS
+    by_width = {}
+    for a, b in motif_pairs(seq_pssm, struct_pssm):
+        by_width.setdefault((seq_pssm[a] if a is not None else struct_pssm[b]).length, []).append((a, b))
+    if not by_width:
+        raise InputError("no sequence PFM is as wide as the structure PFM it is paired with: they share no site")
+    for m, group in by_width.items():
+        W = m + 2 * args.flank
+        if W > MAX_WIDTH:
+            raise InputError("width %d + 2 x flank %d exceeds %d columns (PFMSCAN_MAX_WIDTH, include/pfmscan.h)" % (m, args.flank, MAX_WIDTH))
+        if len(group) * W * 7 * SITE_LIMBS * 8 > ACC_LIMIT:
+            raise InputError("the %d motifs of width %d need %d bytes of accumulators at --flank %d, more than %d: lower --flank or "
+                             "split the library" % (len(group), m, len(group) * W * 7 * SITE_LIMBS * 8, args.flank, ACC_LIMIT))
+    source = args.fastafiles[-1]
+    stored = store.ProfileStore(source).dtype if store.is_store(source) else None
+    ptype = cli.profile_type(args, struct_pssm, stored) if struct_pssm else (np.dtype(args.profile_dtype).type if args.profile_dtype != "auto" else np.float64)
+    rows = dict((m, LibraryRows(len(group), m + 2 * args.flank, letters=seq_pssm is not None)) for m, group in by_width.items())
+    if seq_pssm is not None:
+        recs = fasta.open_lazy(args.fastafiles[0])
+        if len(set(recs.ids)) != len(recs):
+            seen = set()
+            dup = next(i for i in recs.ids if i in seen or seen.add(i))
+            raise InputError("record %s occurs more than once in the FASTA" % dup)
+        profiles = _Profiles(source, ptype, order=list(recs.ids))
+        lengths = recs.lengths
+    else:
+        recs = None
+        profiles = _Profiles(source, ptype)
+        lengths = profiles.lengths
+    lo, hi = shard.partition(lengths, world)[rank]
+    for a, b in (shard.batches(lengths, lo, hi, shard.batch_positions()) if hi > lo else []):
+        at = a
+        for ids, cols, pst in profiles.runs(a, b):
+            n = len(ids)
+            stream = pst
+            if recs is not None:
+                batch = scanner._RnaBatch(recs[at:at + n])
+                if not np.array_equal(batch.lengths, pst.lengths):
+                    r = int(np.flatnonzero(batch.lengths != pst.lengths)[0])
+                    raise InputError("record %s is %d letters long but its averaged-structure profile has %d rows" %
+                                     (ids[r], int(batch.lengths[r]), int(pst.lengths[r])))
+                stream = pack.Stream(batch.codes, pst.profile, batch.offsets, batch.lengths)
+            for m, group in by_width.items():
+                tabs = [seq_pssm[x].letter_table(pack.RNA_LETTERS) for x, _ in group] if seq_pssm else None
+                pssms = [scanner.struct_matrix(struct_pssm[y], cols, args.pairing) for _, y in group] if struct_pssm else None
+                pos, mo = select_library(engine, stream, m, tabs, pssms, args.minscore, args.min_seqstruct)
+                accumulate_library(engine, rows[m], stream, ids, cols, pos, mo, m, args.flank)
+            at += n
+    return rows, list(by_width.items())
+
+
+def gather_library(engine, args, seq_pssm, struct_pssm, rank=0, world=1, dist=None):
+    """``collect_library`` on this rank, the ranks' accumulators exchanged once and added (integer sums: any order gives
+    the same limbs), rounded once -> [(pair, S float64 [W][7], counts | None, coverage, hits)] in pair order, the same on
+    every rank; failures are handed over as in ``combine``"""
+    from . import _lib
+    rows, groups, failure = None, None, None
+    try:
+        rows, groups = collect_library(engine, args, seq_pssm, struct_pssm, rank, world)
+    except Exception as e:
+        if world == 1:
+            raise
+        failure = e
+    if world > 1:
+        shares = [None] * world
+        dist.all_gather_object(shares, (None if failure is None else _portable(failure), rows))
+        for bad, _ in shares:
+            if bad is not None:
+                raise bad
+        rows = shares[0][1]
+        for _, other in shares[1:]:
+            for m in rows:
+                rows[m].add(other[m])
+    out = []
+    for m, group in groups:
+        r = rows[m]
+        W = r.coverage.shape[1]
+        S = _lib.site_acc_round(r.acc).reshape(len(group), W, 7)
+        for k, pair in enumerate(group):
+            out.append((pair, S[k], None if r.counts is None else r.counts[k], r.coverage[k], int(r.hits[k])))
+    order = dict((pair, i) for i, pair in enumerate(motif_pairs(seq_pssm, struct_pssm)))
+    out.sort(key=lambda x: order[x[0]])
+    return out
+
+
+def write_library(args, results, rank=0):
+    """the three files of --all-motifs; a motif without a site or with a column that cannot be normalised is named on
+    stderr and left out of the PFM files.  -> exit code"""
+    import io
+    struct_txt, seq_txt, counts_txt = io.StringIO(), io.StringIO(), io.StringIO()
+    written, have_seq = 0, False
+    for (a, b), S, counts, cov, hits in results:
+        name = pair_id(a, b)
+        one = io.StringIO()
+        _counts_to(one, S, counts, cov, hits)
+        lines = one.getvalue().splitlines(True)
+        if not counts_txt.tell():
+            counts_txt.write("Motif\t" + lines[0])
+        for ln in lines[1:]:
+            counts_txt.write(name + "\t" + ln)
+        if hits == 0:
+            fasta.eprint("Motif %s: no site passes the thresholds, left out" % name)
+            continue
+        try:
+            struct, seq, foreign = site_pfms(S, counts)
+        except InputError as e:
+            fasta.eprint("Motif %s: %s, left out" % (name, e))
+            continue
+        if foreign is not None and int(foreign.sum()):
+            fasta.eprint("Motif %s: foreign letters under the sites, left out of the sequence PFM: %d (per column: %s)" %
+                         (name, int(foreign.sum()), " ".join(str(int(x)) for x in foreign)))
+        struct_txt.write("#%s\n#" % name)
+        _pfm_to(struct_txt, STRUCT_ORDER, struct)
+        struct_txt.write("\n")
+        if seq is not None:
+            have_seq = True
+            seq_txt.write("#%s\n#" % name)
+            _pfm_to(seq_txt, SEQ_ORDER, seq)
+            seq_txt.write("\n")
+        written += 1
+    fasta.eprint("Wrote the site profiles of %d of %d motifs" % (written, len(results)))
+    if written == 0:
+        fasta.eprint("No motif has a site profile: no files written")
+        return 1
+    if rank == 0:
+        for suffix, text in ((".struct.txt", struct_txt), (".seq.txt", seq_txt if have_seq else None), (".counts.txt", counts_txt)):
+            if text is not None:
+                with open(args.prefix + suffix, "w") as out:
+                    out.write(text.getvalue())
+    return 0
+
+
 def main(argv=None, engine=None):
     from . import background, cli, scanner
     args = getoptions(argv)
@@ -435,6 +704,11 @@ def main(argv=None, engine=None):
             else:
                 bg = fasta.load_background(args.bg_struct, args.uniform_background, source, fasta.STRUCT, True)
             struct_pssm = cli.load_motif(args.pfm_struct, args.pseudocount, fasta.STRUCT, bg)
+        if args.all_motifs:
+            rc = write_library(args, gather_library(engine, args, seq_pssm, struct_pssm, rank, world, dist), rank)
+            if dist is not None:
+                dist.barrier()
+            return rc
         S, counts, cov, hits = gather(engine, args, seq_pssm, struct_pssm, rank, world, dist)
         fasta.eprint("Found %d sites" % hits)
         if hits == 0:

@@ -59,7 +59,7 @@
 extern "C" {
 #endif
 
-#define PFMSCAN_ABI_VERSION 16
+#define PFMSCAN_ABI_VERSION 17
 #define PFMSCAN_NCODE   8      /* columns of a letter table */
 #define PFMSCAN_SEP     7      /* separator / foreign-letter code */
 #define PFMSCAN_NSTRUCT 7      /* columns of a structure profile / structure PSSM */
@@ -318,6 +318,64 @@ int pfmscan_hits_pair_host(pfmscan_ctx *ctx, const pfmscan_motif *motif_seq,
                            int64_t capacity, int64_t *hit_pos, float *hit_seq, double *hit_struct,
                            int64_t *n_hits);
 
+/* ---- two code streams with a joint threshold on the printed LogOdds.SeqStruct -----------------
+ * (`rnascan -p pfm -q pfm seqs.fa structs.fa --min-seqstruct T`.)  In this mode BOTH printed columns are rounded to three
+ * places before combine() adds them (rnascan.py:273, :416-434): LogOdds.Seq is np.round of a float32, LogOdds.Struct is
+ * Python's round(x, 3) of a double.  Arguments of pfmscan_hits_pair_* plus thr_sum:
+ *   hit <=> seq(p) > thr_seq  and  struct(p) > thr_struct                      (as pfmscan_hits_pair_*; either may be -inf;
+ *                                                                               NaN and -inf scores never pass)
+ *           and  (double) round3(seq(p)) + round3d(struct(p))  >  thr_sum      (strict; one rounded fp64 addition)
+ * with round3 as in pfmscan_hits_sum_* and round3d(x) = round(x, 3) of a double, bit for bit what pfmscan_round_decimals
+ * gives (csrc/pfmscan_exact.hpp).  The reported scores are the unrounded ones, as from pfmscan_hits_pair_*.  thr_sum = -inf
+ * gives exactly the hits of the plain call; NaN is PFMSCAN_E_BADARG.
+ * Where it is decided (rnascan.py:273, :416-434):  a finite thr_seq takes the routes of pfmscan_hits_pair_dev with the
+ * predicate in the exact stage (k_letters_cred<.., PAIR, SUM>: one launch, no synchronisation; else a letters pass and
+ * k_letters_at<SUM>, which synchronises `stream` in between, exactly where pfmscan_hits_pair_dev may).  thr_seq = -inf with a
+ * finite thr_sum is ONE asynchronous launch: for widths up to 32 an integer prefilter adds the credits of BOTH streams into one
+ * 16-bit sum with the joint threshold folded in and only its survivors get the two exact sums (k_pair_cred_sum); wider PFMs,
+ * tables with a +inf cell and thresholds that more than 1/32 of the windows would survive take both exact letter sums of every
+ * window (k_pair_sum_dense).  A finite thr_seq too dense for the sequence credits alone tries the joint credits before the two launches.
+ * Hit arrays, count, capacity protocol and ordering: as the pfmscan_hits_pair_* counterpart. */
+int pfmscan_hits_pair_sum_dev(pfmscan_ctx *ctx, const pfmscan_motif *motif_seq,
+                              const pfmscan_motif *motif_struct, const uint8_t *d_codes,
+                              const uint8_t *d_codes2, int64_t n_pos, double thr_seq,
+                              double thr_struct, double thr_sum, int64_t capacity,
+                              int64_t *d_hit_pos, float *d_hit_seq, double *d_hit_struct,
+                              uint64_t *d_hit_count, void *stream);
+int pfmscan_hits_pair_sum_staged(pfmscan_ctx *ctx, const pfmscan_motif *motif_seq,
+                                 const pfmscan_motif *motif_struct, double thr_seq,
+                                 double thr_struct, double thr_sum, int64_t capacity,
+                                 int64_t *hit_pos, float *hit_seq, double *hit_struct,
+                                 int64_t *n_hits);
+int pfmscan_hits_pair_sum_host(pfmscan_ctx *ctx, const pfmscan_motif *motif_seq,
+                               const pfmscan_motif *motif_struct, const uint8_t *codes,
+                               const uint8_t *codes2, int64_t n_pos, double thr_seq,
+                               double thr_struct, double thr_sum, int64_t capacity,
+                               int64_t *hit_pos, float *hit_seq, double *hit_struct,
+                               int64_t *n_hits);
+/* The route the last pfmscan_hits_pair_sum_* call of this ctx took (NONE: thr_sum was -inf, or no such call yet). */
+#define PFMSCAN_PAIR_ROUTE_NONE      0
+#define PFMSCAN_PAIR_ROUTE_FUSED     1   /* k_letters_cred<.., PAIR, SUM>: one launch */
+#define PFMSCAN_PAIR_ROUTE_TWO_PHASE 2   /* sequence letters pass, then k_letters_at<SUM> at its hits */
+#define PFMSCAN_PAIR_ROUTE_DENSE     3   /* k_pair_sum_dense: both exact sums of every window */
+#define PFMSCAN_PAIR_ROUTE_CREDITS   4   /* k_pair_cred_sum: one integer credit sum over both streams, exact sums for its survivors */
+int pfmscan_pair_sum_route(const pfmscan_ctx *ctx);
+/* Diagnostics (host only, no ctx): out[i] = round3d(in[i]) as the kernels compute it (rnascan.py:273 on a Python float);
+ * and the two steps of the joint decision for n windows that passed both single thresholds: maybe[i] = the cheap superset
+ * test, passes[i] = the exact predicate behind it (0 / 1), *margin0 = the constant part of the test's margin for thr_sum. */
+int pfmscan_debug_round3d(const double *in, int64_t n, double *out);
+/* The joint credit tables k_pair_cred_sum uses for one pair ([m][8] tables, m <= 32) and one thr_sum: credits_seq /
+ * credits_struct uint16 [m][8] (the joint threshold folded into row 0 of credits_seq; "bit 15 of the sum over both clear" =>
+ * the printed sum cannot exceed thr_sum), *quantum and *slack in score units (slack = 2 m quanta, one-sided), *thr_joint =
+ * thr_sum minus the margin of the cheap test, *survive = the predicted share of surviving windows for uniform letters,
+ * *mode 1: used; 2: dense (survive > 1/32: the exact kernel instead); 3: switched off (+inf cell, letters beyond ROUND3_SAFE,
+ * non-finite quantum: quantum = slack = inf, credits 0). */
+int pfmscan_debug_pair_credits(const double *letters_seq, const double *letters_struct, int m, double thr_sum,
+                               uint16_t *credits_seq, uint16_t *credits_struct, double *quantum, double *slack,
+                               double *thr_joint, double *survive, int *mode);
+int pfmscan_debug_pair_sum_test(const float *seq, const double *st, int64_t n, double thr_sum,
+                                uint8_t *maybe, uint8_t *passes, double *margin0);
+
 /* ---- multi-PFM libraries: every motif in ONE pass (BASELINE config 5) ----------
  * The reference loads one PFM file per run (load_motif, rnascan.py:217-218), scans only the first
  * motif of its dict (rnascan.py:262) and would re-read every sequence and profile per motif,
@@ -482,6 +540,25 @@ int pfmscan_library_hits_letters_host(pfmscan_ctx *ctx, pfmscan_library *lib,
                                       const double *thr_seq, const double *thr_struct, int64_t capacity,
                                       int64_t *hit_pos, int32_t *hit_motif, float *hit_seq,
                                       double *hit_struct, int64_t *n_hits);
+/* Two-FASTA LIBRARIES with joint thresholds (rnascan.py:273, :416-434): pfmscan_library_hits_letters_dev / _host for a library made
+ * by pfmscan_library_create_letters with both parts, plus thr_sum [n] (one T per pair; all -inf = the plain call).  The predicate
+ * of pfmscan_hits_pair_sum_* sits in phase B of the one-pass library kernel (k_library<.., uint8_t, true, SUM>); phase A's credits
+ * are built for thr_eff[k] = max(thr_seq[k], thr_sum[k] - U2[k] - margins), U2 = the sum of the row maxima of the pair's structure
+ * table, so thr_seq[k] may be -inf as long as thr_eff[k] is finite (else PFMSCAN_E_BADARG: scan that pair with
+ * pfmscan_hits_pair_sum_*).  pfmscan_library_letters_sum_thresholds (host only): tables [n][m][8] and thresholds -> thr_eff [n],
+ * -inf where the route is closed (a +inf cell in the structure table or a +inf / NaN letter cell beside thr_seq = -inf, thr_sum = -inf). */
+int pfmscan_library_hits_letters_sum_dev(pfmscan_ctx *ctx, pfmscan_library *lib, const uint8_t *d_codes,
+                                         const uint8_t *d_codes2, int64_t n_pos, const double *thr_seq,
+                                         const double *thr_struct, const double *thr_sum, int64_t capacity,
+                                         int64_t *d_hit_pos, int32_t *d_hit_motif, float *d_hit_seq,
+                                         double *d_hit_struct, uint64_t *d_hit_count, void *stream);
+int pfmscan_library_hits_letters_sum_host(pfmscan_ctx *ctx, pfmscan_library *lib, const uint8_t *codes,
+                                          const uint8_t *codes2, int64_t n_pos, const double *thr_seq,
+                                          const double *thr_struct, const double *thr_sum, int64_t capacity,
+                                          int64_t *hit_pos, int32_t *hit_motif, float *hit_seq,
+                                          double *hit_struct, int64_t *n_hits);
+int pfmscan_library_letters_sum_thresholds(const double *letter_tables, const double *struct_tables, int n_motifs,
+                                           int m, const double *thr_seq, const double *thr_sum, double *thr_eff);
 
 /* Diagnostics (host only, no device needed): the unsigned two-letter credit table the prefilters use for ONE motif
  * (letter_table double [m][8], 4-letter alphabet) at threshold thr_seq: credits uint16 [ceil(m/2)][16], entry index

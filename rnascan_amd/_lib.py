@@ -22,7 +22,7 @@ NCODE = 8
 NSTRUCT = 7
 MAX_M = 64            # widest PFM of the tuned kernels and of PFM libraries
 MAX_WIDTH = 4096      # widest PFM accepted (wider than MAX_M: the plain rolled-loop kernel)
-ABI_VERSION = 16
+ABI_VERSION = 17
 
 # every symbol include/pfmscan.h declares (checked by tests/test_abi.py)
 SYMBOLS = [
@@ -49,7 +49,11 @@ SYMBOLS = [
     "pfmscan_site_groups", "pfmscan_site_sums_dev", "pfmscan_site_sums_staged", "pfmscan_site_sums_host",
     "pfmscan_site_groups_lib", "pfmscan_site_order_lib", "pfmscan_site_acc_add", "pfmscan_site_acc_round",
     "pfmscan_site_acc_from_doubles", "pfmscan_site_sums_lib_dev", "pfmscan_site_sums_lib_staged",
+    "pfmscan_hits_pair_sum_dev", "pfmscan_hits_pair_sum_staged", "pfmscan_hits_pair_sum_host", "pfmscan_pair_sum_route",
+    "pfmscan_debug_round3d", "pfmscan_debug_pair_sum_test", "pfmscan_debug_pair_credits",
+    "pfmscan_library_hits_letters_sum_dev", "pfmscan_library_hits_letters_sum_host", "pfmscan_library_letters_sum_thresholds",
 ]
+PAIR_ROUTE_NONE, PAIR_ROUTE_FUSED, PAIR_ROUTE_TWO_PHASE, PAIR_ROUTE_DENSE, PAIR_ROUTE_CREDITS = range(5)   # Context.pair_sum_route()
 SITE_GROUP = 4096     # most hits of one group of the site profiles
 SITE_LIMBS = 66       # 64-bit limbs of one cell of a long accumulator (site profiles of a library)
 MAX_COVER = 1024      # largest coverage of a row the averaging accepts
@@ -207,6 +211,16 @@ def load():
     L.pfmscan_hits_pair_staged.argtypes = [vp, vp, vp, dbl, dbl, i64, vp, vp, vp, ctypes.POINTER(i64)]
     L.pfmscan_hits_pair_host.argtypes = [vp, vp, vp, vp, vp, i64, dbl, dbl, i64, vp, vp, vp, ctypes.POINTER(i64)]
     L.pfmscan_round_decimals.argtypes = [vp, i64, i32, vp, i32]
+    L.pfmscan_hits_pair_sum_dev.argtypes = [vp, vp, vp, vp, vp, i64, dbl, dbl, dbl, i64, vp, vp, vp, vp, vp]
+    L.pfmscan_hits_pair_sum_staged.argtypes = [vp, vp, vp, dbl, dbl, dbl, i64, vp, vp, vp, ctypes.POINTER(i64)]
+    L.pfmscan_hits_pair_sum_host.argtypes = [vp, vp, vp, vp, vp, i64, dbl, dbl, dbl, i64, vp, vp, vp, ctypes.POINTER(i64)]
+    L.pfmscan_pair_sum_route.argtypes = [vp]
+    L.pfmscan_debug_round3d.argtypes = [vp, i64, vp]
+    L.pfmscan_library_hits_letters_sum_dev.argtypes = [vp, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp]
+    L.pfmscan_library_hits_letters_sum_host.argtypes = [vp, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, vp, ctypes.POINTER(i64)]
+    L.pfmscan_library_letters_sum_thresholds.argtypes = [vp, vp, i32, i32, vp, vp, vp]
+    L.pfmscan_debug_pair_credits.argtypes = [vp, vp, i32, dbl, vp, vp] + [ctypes.POINTER(dbl)] * 4 + [ctypes.POINTER(i32)]
+    L.pfmscan_debug_pair_sum_test.argtypes = [vp, vp, i64, dbl, vp, vp, ctypes.POINTER(dbl)]
     L.pfmscan_tsv_format.argtypes = [ctypes.POINTER(TsvColumn), i32, i64, i64, vp, i64, ctypes.POINTER(i64), vp, ctypes.POINTER(i32), i32]
     for name in SYMBOLS:          # every other entry point returns a status
         if name not in ("pfmscan_ctx_destroy", "pfmscan_motif_destroy", "pfmscan_last_error", "pfmscan_library_destroy",
@@ -491,6 +505,69 @@ def round_decimals(values, decimals=3, threads=0):
     if rc != OK:
         _raise(L, None, rc)
     return out
+
+
+def debug_round3d(values):
+    """Host-only diagnostic: ``round(float(x), 3)`` for every x as the joint-threshold kernels compute it (round3d of
+    csrc/pfmscan_exact.hpp: no strings) -> float64 array"""
+    L = load()
+    a = np.ascontiguousarray(values, dtype=np.float64)
+    out = np.empty_like(a)
+    if L.pfmscan_debug_round3d(_ptr(a), a.size, _ptr(out)) != OK:
+        raise ValueError("pfmscan_debug_round3d: bad argument")
+    return out
+
+
+def library_letters_sum_thresholds(seq_tables, struct_tables, thr_seq, thr_sum):
+    """Host-only (no device needed): the letters thresholds the two-FASTA library kernel's prefilter is built for under joint
+    thresholds ``thr_sum`` -> float64 [n]; -inf where the route is closed for that pair.  seq_tables / struct_tables [n][m][8],
+    thr_seq / thr_sum scalars or [n]"""
+    L = load()
+    T = np.ascontiguousarray(seq_tables, dtype=np.float64)
+    S = np.ascontiguousarray(struct_tables, dtype=np.float64)
+    if T.ndim != 3 or T.shape[2] != NCODE or T.shape != S.shape:
+        raise ValueError("both table arrays must be [n][m][8]")
+    n = T.shape[0]
+    ts = np.ascontiguousarray(np.broadcast_to(np.asarray(thr_seq, dtype=np.float64), (n,)))
+    tj = np.ascontiguousarray(np.broadcast_to(np.asarray(thr_sum, dtype=np.float64), (n,)))
+    out = np.empty(n, dtype=np.float64)
+    if L.pfmscan_library_letters_sum_thresholds(_ptr(T), _ptr(S), n, T.shape[1], _ptr(ts), _ptr(tj), _ptr(out)) != OK:
+        raise ValueError("pfmscan_library_letters_sum_thresholds: bad argument")
+    return out
+
+
+def debug_pair_credits(letters_seq, letters_struct, thr_sum):
+    """Host-only diagnostic: the joint credit tables of k_pair_cred_sum for one pair ([m][8] tables, m <= 32) at thr_sum
+    -> dict(seq uint16 [m][8], struct uint16 [m][8], quantum, slack, thr_joint, survive, mode)"""
+    L = load()
+    A = np.ascontiguousarray(letters_seq, dtype=np.float64)
+    B = np.ascontiguousarray(letters_struct, dtype=np.float64)
+    if A.ndim != 2 or A.shape[1] != NCODE or A.shape != B.shape:
+        raise ValueError("both letter tables must be [m][8]")
+    c1, c2 = np.zeros(A.shape, dtype=np.uint16), np.zeros(A.shape, dtype=np.uint16)
+    q, sl, tj, sv = (ctypes.c_double(0.0) for _ in range(4))
+    mode = ctypes.c_int32(0)
+    rc = L.pfmscan_debug_pair_credits(_ptr(A), _ptr(B), A.shape[0], float(thr_sum), _ptr(c1), _ptr(c2), ctypes.byref(q), ctypes.byref(sl),
+                                      ctypes.byref(tj), ctypes.byref(sv), ctypes.byref(mode))
+    if rc != OK:
+        raise ValueError("pfmscan_debug_pair_credits: bad argument")
+    return {"seq": c1, "struct": c2, "quantum": q.value, "slack": sl.value, "thr_joint": tj.value, "survive": sv.value, "mode": mode.value}
+
+
+def debug_pair_sum_test(seq, st, thr_sum):
+    """Host-only diagnostic: the joint decision of pfmscan_hits_pair_sum_* for windows with float32 sequence scores ``seq``
+    and fp64 structure scores ``st`` that passed both single thresholds -> (maybe bool[n]: the cheap superset test,
+    passes bool[n]: the exact predicate behind it, margin0)"""
+    L = load()
+    f = np.ascontiguousarray(seq, dtype=np.float32)
+    s = np.ascontiguousarray(st, dtype=np.float64)
+    if f.shape != s.shape:
+        raise ValueError("seq and st must have the same shape")
+    maybe, passes = np.zeros(f.size, dtype=np.uint8), np.zeros(f.size, dtype=np.uint8)
+    m0 = ctypes.c_double(0.0)
+    if L.pfmscan_debug_pair_sum_test(_ptr(f), _ptr(s), f.size, float(thr_sum), _ptr(maybe), _ptr(passes), ctypes.byref(m0)) != OK:
+        raise ValueError("pfmscan_debug_pair_sum_test: bad argument")
+    return maybe.astype(bool).reshape(f.shape), passes.astype(bool).reshape(f.shape), m0.value
 
 
 TSV_MAX_PIECES = 16
@@ -1190,6 +1267,60 @@ class Context(object):
         self.stage_codes2(codes2)
         return self.hits_pair_staged(motif_seq, motif_struct, thr_seq, thr_struct, capacity)
 
+    def hits_pair_sum_staged(self, motif_seq, motif_struct, thr_seq, thr_struct, thr_sum, capacity=None):
+        """hits_pair_staged with the joint threshold on the printed sum: additionally
+        float64(np.round(seq, 3)) + round(struct, 3) > thr_sum, decided on the device (rnascan.py:273, :416-434)
+        -> (pos int64[k] sorted, seq float32[k], struct float64[k])"""
+        n = int(self._L.pfmscan_staged_positions(self._h))
+        if n < 0:
+            raise ValueError("no stream staged (call stage first)")
+        cap = int(capacity) if capacity is not None else max(1024, n // 64)
+        while True:
+            pos = np.empty(cap, dtype=np.int64)
+            sq = np.empty(cap, dtype=np.float32)
+            st = np.empty(cap, dtype=np.float64)
+            k = ctypes.c_int64(0)
+            rc = self._L.pfmscan_hits_pair_sum_staged(self._h, motif_seq._h, motif_struct._h, float(thr_seq), float(thr_struct),
+                                                      float(thr_sum), cap, _ptr(pos), _ptr(sq), _ptr(st), ctypes.byref(k))
+            if rc == E_CAPACITY and capacity is None:
+                cap = int(k.value)
+                continue
+            self._check(rc, k.value)
+            k = int(k.value)
+            return pos[:k].copy(), sq[:k].copy(), st[:k].copy()
+
+    def hits_pair_sum_host(self, motif_seq, motif_struct, codes, codes2, thr_seq, thr_struct, thr_sum, capacity=None):
+        """one call of pfmscan_hits_pair_sum_host (stages both streams itself)"""
+        codes = np.ascontiguousarray(codes, dtype=np.uint8)
+        codes2 = np.ascontiguousarray(codes2, dtype=np.uint8)
+        if codes.size != codes2.size:
+            raise ValueError("the two code streams must have the same length")
+        cap = int(capacity) if capacity is not None else max(1024, codes.size // 64)
+        while True:
+            pos = np.empty(cap, dtype=np.int64)
+            sq = np.empty(cap, dtype=np.float32)
+            st = np.empty(cap, dtype=np.float64)
+            k = ctypes.c_int64(0)
+            rc = self._L.pfmscan_hits_pair_sum_host(self._h, motif_seq._h, motif_struct._h, _ptr(codes), _ptr(codes2), codes.size,
+                                                    float(thr_seq), float(thr_struct), float(thr_sum), cap, _ptr(pos), _ptr(sq),
+                                                    _ptr(st), ctypes.byref(k))
+            if rc == E_CAPACITY and capacity is None:
+                cap = int(k.value)
+                continue
+            self._check(rc, k.value)
+            k = int(k.value)
+            return pos[:k].copy(), sq[:k].copy(), st[:k].copy()
+
+    def hits_pair_sum_dev(self, motif_seq, motif_struct, d_codes, d_codes2, n_pos, thr_seq, thr_struct, thr_sum, capacity,
+                          d_hit_pos, d_hit_seq, d_hit_struct, d_hit_count, stream=None):
+        self._check(self._L.pfmscan_hits_pair_sum_dev(self._h, motif_seq._h, motif_struct._h, _ptr(d_codes), _ptr(d_codes2), int(n_pos),
+                                                      float(thr_seq), float(thr_struct), float(thr_sum), int(capacity), _ptr(d_hit_pos),
+                                                      _ptr(d_hit_seq), _ptr(d_hit_struct), _ptr(d_hit_count), _ptr(stream)))
+
+    def pair_sum_route(self):
+        """PAIR_ROUTE_* of the last hits_pair_sum_* call (NONE: thr_sum was -inf, or a plain hits_pair_* call came after)"""
+        return int(self._L.pfmscan_pair_sum_route(self._h))
+
     def hits_letters_f64_dev(self, motif, d_codes, n_pos, thr, capacity, d_hit_pos, d_hit_score, d_hit_count, stream=None):
         self._check(self._L.pfmscan_hits_letters_f64_dev(self._h, motif._h, _ptr(d_codes), int(n_pos), float(thr), int(capacity),
                                                          _ptr(d_hit_pos), _ptr(d_hit_score), _ptr(d_hit_count), _ptr(stream)))
@@ -1222,6 +1353,43 @@ class Context(object):
         if lib.has_letters:
             self.stage_codes2(codes2)
         return self.library_hits_staged(lib, thr_seq, thr_struct, capacity)
+
+    def library_hits_letters_sum_dev(self, lib, d_codes, d_codes2, n_pos, thr_seq, thr_struct, thr_sum, capacity,
+                                     d_hit_pos, d_hit_motif, d_hit_seq, d_hit_struct, d_hit_count, stream=None):
+        """two-FASTA library with joint thresholds on device-resident code streams: asynchronous on ``stream``; hits unordered"""
+        ts, tt = lib.thresholds(thr_seq, thr_struct)
+        tj = np.ascontiguousarray(np.broadcast_to(np.asarray(thr_sum, dtype=np.float64), (lib.n,)))
+        self._check(self._L.pfmscan_library_hits_letters_sum_dev(self._h, lib._h, _ptr(d_codes), _ptr(d_codes2), int(n_pos), _ptr(ts), _ptr(tt),
+                                                                 _ptr(tj), int(capacity), _ptr(d_hit_pos), _ptr(d_hit_motif), _ptr(d_hit_seq),
+                                                                 _ptr(d_hit_struct), _ptr(d_hit_count), _ptr(stream)))
+
+    def library_hits_letters_sum_host(self, lib, codes, codes2, thr_seq, thr_struct, thr_sum, capacity=None):
+        """hits of a two-FASTA library (Library(letter_tables, struct_letters=...)) with the joint threshold of hits_pair_sum per
+        pair (scalar or [n]), decided in the one-pass library kernel -> (pos, motif, seq float32, struct float64) sorted by
+        (position, motif index); stages both streams"""
+        codes = np.ascontiguousarray(codes, dtype=np.uint8)
+        codes2 = np.ascontiguousarray(codes2, dtype=np.uint8)
+        if codes.size != codes2.size:
+            raise ValueError("the two code streams must have the same length")
+        ts, tt = lib.thresholds(thr_seq, thr_struct)
+        tj = np.ascontiguousarray(np.broadcast_to(np.asarray(thr_sum, dtype=np.float64), (lib.n,)))
+        self.scratch_gen += 1
+        self._staged_n = -1
+        cap = int(capacity) if capacity is not None else max(4096, codes.size // 16)
+        while True:
+            pos = np.empty(cap, dtype=np.int64)
+            mo = np.empty(cap, dtype=np.int32)
+            sq = np.empty(cap, dtype=np.float32)
+            st = np.empty(cap, dtype=np.float64)
+            k = ctypes.c_int64(0)
+            rc = self._L.pfmscan_library_hits_letters_sum_host(self._h, lib._h, _ptr(codes), _ptr(codes2), codes.size, _ptr(ts), _ptr(tt), _ptr(tj),
+                                                               cap, _ptr(pos), _ptr(mo), _ptr(sq), _ptr(st), ctypes.byref(k))
+            if rc == E_CAPACITY and capacity is None:
+                cap = int(k.value)
+                continue
+            self._check(rc, k.value)
+            k = int(k.value)
+            return pos[:k].copy(), mo[:k].copy(), sq[:k].copy(), st[:k].copy()
 
     def library_hits_staged(self, lib, thr_seq, thr_struct=None, capacity=None):
         """hits of every motif of ``lib`` over the staged stream, sorted by (position, motif index)

@@ -69,7 +69,8 @@ def getoptions(argv=None):
                      help=("combined scans (-p AND -q): additionally keep a row only if its LogOdds.SeqStruct -- the printed sum of "
                            "the two log-odds -- exceeds T (strict).  -m keeps its meaning and its default: a row still needs "
                            "seq > m AND struct > m; `-m ' -inf' --min-seqstruct T` thresholds on the sum alone.  With averaged-"
-                           "structure profiles the decision is taken on the GPU.  Match_ID numbers the kept rows [off]"))
+                           "structure profiles and with two FASTA files the decision is taken on the GPU, for single pairs and for "
+                           "libraries of pairs.  Match_ID numbers the kept rows [off]"))
     gpu.add_argument("--pairing", choices=["aligned", "positional"], default="aligned",
                      help=("averaged-structure columns vs structure PFM.  'aligned' pairs every profile column with the PFM "
                            "row of the SAME letter -- the evident intent, and what the reference computed on Python 2.  "

@@ -650,8 +650,13 @@ int pfmscan_hits_letters_f64_host(pfmscan_ctx *ctx, const pfmscan_motif *mo, con
 // Phase 1: the sequence letters pass over everything (any of the letters hits kernels) -> candidates in the ctx's
 // candidate buffers; phase 2: k_letters_at scores the structure letters at the candidates only.  The candidate buffers
 // start at 1/32 of the windows; a denser threshold is retried once with the exact sizes the counters reported.
+// thr_sum: the joint threshold of pfmscan_hits_pair_sum_* on the printed sum (-inf: none).  It is decided where the second
+// score appears: in the exact stage of the one-launch kernel, in k_letters_at -- or, when thr_seq = -inf leaves the
+// sequence letters nothing to select with, over both exact sums of every window (k_pair_sum_dense), which is also the
+// route of thr_seq = -inf for every width.  ctx->pair_sum_route remembers which one ran.
 static int pair_core(pfmscan_ctx *ctx, const pfmscan_motif *mo_seq, const pfmscan_motif *mo_st, const uint8_t *d_codes,
-                     const uint8_t *d_codes2, int64_t n_pos, double thr_seq, double thr_struct, const HitSink &sink, hipStream_t st)
+                     const uint8_t *d_codes2, int64_t n_pos, double thr_seq, double thr_struct, const HitSink &sink, hipStream_t st,
+                     double thr_sum = -INFINITY)
 {
     int rc;
     ScanArgs a1, a2;
@@ -659,6 +664,37 @@ static int pair_core(pfmscan_ctx *ctx, const pfmscan_motif *mo_seq, const pfmsca
     if ((rc = check_and_fill(ctx, mo_st, d_codes2, nullptr, PFMSCAN_PROFILE_NONE, n_pos, a2))) return rc;
     a1.struct_pssm = a2.struct_pssm = nullptr;
     a1.profile = a2.profile = nullptr;
+    const bool sum = thr_sum > -INFINITY;
+    const double margin0 = pair_sum_margin0(thr_sum);
+    ctx->pair_sum_route = PFMSCAN_PAIR_ROUTE_NONE;
+    // the joint integer prefilter (both streams' credits in one sum) where it applies, else both exact sums of every window
+    auto joint = [&](bool dense_too, bool &done) -> int {
+        done = false;
+        ScanArgs f = a1;
+        fill_hits(f, sink, true, true, thr_seq, thr_struct);
+        f.codes2 = d_codes2;
+        f.letter_table2 = mo_st->d_letters;
+        f.thr_sum = thr_sum;
+        f.sum_margin0 = margin0;
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        hipError_t e0 = hipSuccess;
+        if (launch_pair_cred_sum(f, mo_st->h_letters, &mo_seq->pair_cred, ctx->tune, st, &e0)) {
+            if (e0 != hipSuccess) return fail_hip(ctx, e0, "launch k_pair_cred_sum");
+            ctx->pair_sum_route = PFMSCAN_PAIR_ROUTE_CREDITS;
+            done = true;
+            return PFMSCAN_OK;
+        }
+        if (!dense_too) return PFMSCAN_OK;
+        e0 = launch_pair_sum_dense(f, st);
+        if (e0 != hipSuccess) return fail_hip(ctx, e0, "launch k_pair_sum_dense");
+        ctx->pair_sum_route = PFMSCAN_PAIR_ROUTE_DENSE;
+        done = true;
+        return PFMSCAN_OK;
+    };
+    if (sum && thr_seq == -INFINITY) {
+        bool done;
+        return joint(true, done);
+    }
     // the usual case -- a selective finite threshold on a PFM up to 32 wide -- is ONE launch: the integer-prefiltered letters
     // kernel verifies the second stream for its own survivors (k_letters_cred<.., PAIR>); PFMSCAN_PAIR_TWO_PHASE=1: A/B
     if (!std::getenv("PFMSCAN_PAIR_TWO_PHASE")) {
@@ -666,13 +702,25 @@ static int pair_core(pfmscan_ctx *ctx, const pfmscan_motif *mo_seq, const pfmsca
         fill_hits(f, sink, true, true, thr_seq, thr_struct);
         f.codes2 = d_codes2;
         f.letter_table2 = mo_st->d_letters;
+        if (sum) {
+            f.thr_sum = thr_sum;
+            f.sum_margin0 = margin0;
+        }
         hipError_t e1 = hipSuccess;
         HIP_TRY(ctx, hipSetDevice(ctx->device));
         if (launch_letters_cred(f, ctx->tune, st, &e1)) {
             if (e1 != hipSuccess) return fail_hip(ctx, e1, "launch k_letters_cred (pair)");
+            if (sum) ctx->pair_sum_route = PFMSCAN_PAIR_ROUTE_FUSED;
             return PFMSCAN_OK;
         }
     }
+    if (sum && std::isfinite(thr_sum) && !std::getenv("PFMSCAN_PAIR_TWO_PHASE")) {
+        // a thr_seq too dense for the sequence credits alone: the joint credits may still be sparse
+        bool done;
+        if ((rc = joint(false, done))) return rc;
+        if (done) return PFMSCAN_OK;
+    }
+    if (sum) ctx->pair_sum_route = PFMSCAN_PAIR_ROUTE_TWO_PHASE;
     HitSink cs;
     int64_t shard_cap = pair_cand_shard_cap(n_pos);
     uint64_t n_cand = 0, worst = 0;
@@ -688,6 +736,10 @@ static int pair_core(pfmscan_ctx *ctx, const pfmscan_motif *mo_seq, const pfmsca
     }
     if (n_cand == 0) return PFMSCAN_OK;
     fill_hits(a2, sink, true, true, thr_seq, thr_struct);
+    if (sum) {
+        a2.thr_sum = thr_sum;
+        a2.sum_margin0 = margin0;
+    }
     hipError_t e = launch_letters_at(a2, cs.pos, cs.seq, cs.count, cs.shards, cs.shard_cap, st);
     if (e != hipSuccess) return fail_hip(ctx, e, "launch k_letters_at");
     return PFMSCAN_OK;
@@ -704,19 +756,77 @@ static int check_pair(pfmscan_ctx *ctx, const pfmscan_motif *mo_seq, const pfmsc
     return PFMSCAN_OK;
 }
 
-int pfmscan_hits_pair_dev(pfmscan_ctx *ctx, const pfmscan_motif *mo_seq, const pfmscan_motif *mo_st, const uint8_t *d_codes,
-                          const uint8_t *d_codes2, int64_t n_pos, double thr_seq, double thr_struct, int64_t capacity,
-                          int64_t *d_hit_pos, float *d_hit_seq, double *d_hit_struct, uint64_t *d_hit_count, void *stream)
+static int pair_dev_impl(pfmscan_ctx *ctx, const pfmscan_motif *mo_seq, const pfmscan_motif *mo_st, const uint8_t *d_codes,
+                         const uint8_t *d_codes2, int64_t n_pos, double thr_seq, double thr_struct, double thr_sum, int64_t capacity,
+                         int64_t *d_hit_pos, float *d_hit_seq, double *d_hit_struct, uint64_t *d_hit_count, void *stream)
 {
     int rc = check_pair(ctx, mo_seq, mo_st, thr_seq, thr_struct);
     if (rc) return rc;
+    if (std::isnan(thr_sum)) return fail(ctx, PFMSCAN_E_BADARG, "NaN threshold");
     if (n_pos < 0) return fail(ctx, PFMSCAN_E_BADARG, "negative n_pos");
     if (capacity < 0 || !d_hit_count || (capacity > 0 && !d_hit_pos)) return fail(ctx, PFMSCAN_E_BADARG, "pfmscan_hits_pair_dev: bad hit buffers");
     if (n_pos == 0) return PFMSCAN_OK;
     if (!d_codes || !d_codes2) return fail(ctx, PFMSCAN_E_BADARG, "codes is NULL");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const HitSink sink = dev_sink(d_hit_pos, d_hit_seq, d_hit_struct, d_hit_count, capacity);
-    return pair_core(ctx, mo_seq, mo_st, d_codes, d_codes2, n_pos, thr_seq, thr_struct, sink, stream ? (hipStream_t)stream : ctx->stream);
+    return pair_core(ctx, mo_seq, mo_st, d_codes, d_codes2, n_pos, thr_seq, thr_struct, sink, stream ? (hipStream_t)stream : ctx->stream,
+                     thr_sum);
+}
+
+int pfmscan_hits_pair_dev(pfmscan_ctx *ctx, const pfmscan_motif *mo_seq, const pfmscan_motif *mo_st, const uint8_t *d_codes,
+                          const uint8_t *d_codes2, int64_t n_pos, double thr_seq, double thr_struct, int64_t capacity,
+                          int64_t *d_hit_pos, float *d_hit_seq, double *d_hit_struct, uint64_t *d_hit_count, void *stream)
+{
+    return pair_dev_impl(ctx, mo_seq, mo_st, d_codes, d_codes2, n_pos, thr_seq, thr_struct, -INFINITY, capacity, d_hit_pos, d_hit_seq,
+                         d_hit_struct, d_hit_count, stream);
+}
+
+// rnascan.py:273, :416-434: the printed LogOdds.SeqStruct of the two-FASTA mode, thresholded where the scores are made
+int pfmscan_hits_pair_sum_dev(pfmscan_ctx *ctx, const pfmscan_motif *mo_seq, const pfmscan_motif *mo_st, const uint8_t *d_codes,
+                              const uint8_t *d_codes2, int64_t n_pos, double thr_seq, double thr_struct, double thr_sum,
+                              int64_t capacity, int64_t *d_hit_pos, float *d_hit_seq, double *d_hit_struct, uint64_t *d_hit_count,
+                              void *stream)
+{
+    return pair_dev_impl(ctx, mo_seq, mo_st, d_codes, d_codes2, n_pos, thr_seq, thr_struct, thr_sum, capacity, d_hit_pos, d_hit_seq,
+                         d_hit_struct, d_hit_count, stream);
+}
+
+int pfmscan_pair_sum_route(const pfmscan_ctx *ctx) { return ctx ? ctx->pair_sum_route : PFMSCAN_PAIR_ROUTE_NONE; }
+
+int pfmscan_debug_pair_credits(const double *letters_seq, const double *letters_struct, int m, double thr_sum, uint16_t *credits_seq,
+                               uint16_t *credits_struct, double *quantum, double *slack, double *thr_joint, double *survive, int *mode)
+{
+    if (!letters_seq || !letters_struct || !credits_seq || !credits_struct || m < 1 || m > 32 || std::isnan(thr_sum)) return PFMSCAN_E_BADARG;
+    PairCred pc;
+    build_pair_credits(letters_seq, letters_struct, m, thr_sum, &pc);
+    std::memcpy(credits_seq, pc.cr, sizeof(uint16_t) * 8 * m);
+    std::memcpy(credits_struct, pc.cr + 8 * m, sizeof(uint16_t) * 8 * m);
+    if (quantum) *quantum = pc.quantum;
+    if (slack) *slack = pc.slack;
+    if (thr_joint) *thr_joint = pc.thr_joint;
+    if (survive) *survive = pc.survive;
+    if (mode) *mode = pc.mode;
+    return PFMSCAN_OK;
+}
+
+int pfmscan_debug_round3d(const double *in, int64_t n, double *out)
+{
+    if (n < 0 || (n > 0 && (!in || !out))) return PFMSCAN_E_BADARG;
+    for (int64_t i = 0; i < n; ++i) out[i] = round3d(in[i]);
+    return PFMSCAN_OK;
+}
+
+int pfmscan_debug_pair_sum_test(const float *seq, const double *st, int64_t n, double thr_sum, uint8_t *maybe, uint8_t *passes,
+                                double *margin0)
+{
+    if (std::isnan(thr_sum) || n < 0 || (n > 0 && (!seq || !st || !maybe || !passes))) return PFMSCAN_E_BADARG;
+    const double m0 = pair_sum_margin0(thr_sum);
+    for (int64_t i = 0; i < n; ++i) {
+        maybe[i] = pair_sum_maybe(seq[i], st[i], thr_sum, m0) ? 1 : 0;
+        passes[i] = pair_sum_passes(seq[i], st[i], thr_sum, m0) ? 1 : 0;
+    }
+    if (margin0) *margin0 = m0;
+    return PFMSCAN_OK;
 }
 
 int pfmscan_stage_codes2(pfmscan_ctx *ctx, const uint8_t *codes2, int64_t n_pos)
@@ -737,13 +847,14 @@ int pfmscan_stage_codes2(pfmscan_ctx *ctx, const uint8_t *codes2, int64_t n_pos)
     return PFMSCAN_OK;
 }
 
-int pfmscan_hits_pair_staged(pfmscan_ctx *ctx, const pfmscan_motif *mo_seq, const pfmscan_motif *mo_st, double thr_seq,
-                             double thr_struct, int64_t capacity, int64_t *hit_pos, float *hit_seq, double *hit_struct,
-                             int64_t *n_hits)
+static int pair_staged_impl(pfmscan_ctx *ctx, const pfmscan_motif *mo_seq, const pfmscan_motif *mo_st, double thr_seq,
+                            double thr_struct, double thr_sum, int64_t capacity, int64_t *hit_pos, float *hit_seq, double *hit_struct,
+                            int64_t *n_hits)
 {
     if (!n_hits) return fail(ctx, PFMSCAN_E_BADARG, "NULL argument");
     int rc = check_pair(ctx, mo_seq, mo_st, thr_seq, thr_struct);
     if (rc) return rc;
+    if (std::isnan(thr_sum)) return fail(ctx, PFMSCAN_E_BADARG, "NaN threshold");
     if (ctx->staged_n < 0 || !ctx->staged_codes || !ctx->staged_codes2)
         return fail(ctx, PFMSCAN_E_BADARG, "two code streams must be staged (pfmscan_stage + pfmscan_stage_codes2)");
     if (capacity < 0) return fail(ctx, PFMSCAN_E_BADARG, "negative size");
@@ -755,9 +866,23 @@ int pfmscan_hits_pair_staged(pfmscan_ctx *ctx, const pfmscan_motif *mo_seq, cons
     HitSink sink;
     if ((rc = acquire_sink(ctx, hit_bufs(ctx), HIT_SHARDS, hit_shard_cap(capacity), ctx->stream, sink))) return rc;
     if ((rc = pair_core(ctx, mo_seq, mo_st, (const uint8_t *)ctx->codes.p, (const uint8_t *)ctx->codes2.p, n_pos, thr_seq, thr_struct,
-                        sink, ctx->stream)))
+                        sink, ctx->stream, thr_sum)))
         return rc;
     return finish_sorted_hits(ctx, sink, true, true, 0, n_pos, capacity, hit_pos, nullptr, hit_seq, hit_struct, n_hits);
+}
+
+int pfmscan_hits_pair_staged(pfmscan_ctx *ctx, const pfmscan_motif *mo_seq, const pfmscan_motif *mo_st, double thr_seq,
+                             double thr_struct, int64_t capacity, int64_t *hit_pos, float *hit_seq, double *hit_struct,
+                             int64_t *n_hits)
+{
+    return pair_staged_impl(ctx, mo_seq, mo_st, thr_seq, thr_struct, -INFINITY, capacity, hit_pos, hit_seq, hit_struct, n_hits);
+}
+
+int pfmscan_hits_pair_sum_staged(pfmscan_ctx *ctx, const pfmscan_motif *mo_seq, const pfmscan_motif *mo_st, double thr_seq,
+                                 double thr_struct, double thr_sum, int64_t capacity, int64_t *hit_pos, float *hit_seq,
+                                 double *hit_struct, int64_t *n_hits)
+{
+    return pair_staged_impl(ctx, mo_seq, mo_st, thr_seq, thr_struct, thr_sum, capacity, hit_pos, hit_seq, hit_struct, n_hits);
 }
 
 int pfmscan_hits_pair_host(pfmscan_ctx *ctx, const pfmscan_motif *mo_seq, const pfmscan_motif *mo_st, const uint8_t *codes,
@@ -773,6 +898,22 @@ int pfmscan_hits_pair_host(pfmscan_ctx *ctx, const pfmscan_motif *mo_seq, const 
     if (rc) return rc;
     if ((rc = pfmscan_stage_codes2(ctx, codes2, n_pos))) return rc;
     return pfmscan_hits_pair_staged(ctx, mo_seq, mo_st, thr_seq, thr_struct, capacity, hit_pos, hit_seq, hit_struct, n_hits);
+}
+
+int pfmscan_hits_pair_sum_host(pfmscan_ctx *ctx, const pfmscan_motif *mo_seq, const pfmscan_motif *mo_st, const uint8_t *codes,
+                               const uint8_t *codes2, int64_t n_pos, double thr_seq, double thr_struct, double thr_sum,
+                               int64_t capacity, int64_t *hit_pos, float *hit_seq, double *hit_struct, int64_t *n_hits)
+{
+    if (!ctx || !mo_seq || !mo_st || !n_hits) return fail(ctx, PFMSCAN_E_BADARG, "NULL argument");
+    if (n_pos < 0 || capacity < 0) return fail(ctx, PFMSCAN_E_BADARG, "negative size");
+    *n_hits = 0;
+    if (std::isnan(thr_sum)) return fail(ctx, PFMSCAN_E_BADARG, "NaN threshold");
+    if (n_pos == 0) return PFMSCAN_OK;
+    if (!codes || !codes2) return fail(ctx, PFMSCAN_E_BADARG, "codes is NULL");
+    int rc = pfmscan_stage(ctx, codes, nullptr, PFMSCAN_PROFILE_NONE, n_pos);
+    if (rc) return rc;
+    if ((rc = pfmscan_stage_codes2(ctx, codes2, n_pos))) return rc;
+    return pfmscan_hits_pair_sum_staged(ctx, mo_seq, mo_st, thr_seq, thr_struct, thr_sum, capacity, hit_pos, hit_seq, hit_struct, n_hits);
 }
 
 // ---- the reference's native entry point ------------------------------------------

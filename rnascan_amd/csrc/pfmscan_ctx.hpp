@@ -17,6 +17,7 @@ struct pfmscan_motif {
     mutable pfmscan::CredCache cred_cache;
     double *h_letters = nullptr;   // host copy of the letter table [m][8] (m <= 32): operand of k_letters_cred8's credits
     mutable pfmscan::Cred8Cache cred8_cache;
+    mutable pfmscan::PairCred pair_cred;   // k_pair_cred_sum's tables for the last (structure motif, thr_sum) this sequence motif met
     double *d_struct = nullptr;    // [m][7]
     int m = 0;
     int struct_finite = 0;
@@ -76,6 +77,8 @@ struct pfmscan_ctx {
     int64_t row_bound_serial = -1;
     // candidate-then-verify: the last full letters pass was selective -> skip the pilot next time
     bool two_phase_hot = false;
+    // which route the last pfmscan_hits_pair_sum_* call with a finite thr_sum took (PFMSCAN_PAIR_ROUTE_*)
+    int pair_sum_route = 0;
     // pfmscan_place.hip: sets of arrays placed together (PlaceSet *), and a line about the last allocation
     std::vector<void *> place_sets;
     std::vector<void *> place_retired;        // freed sets kept mapped for the next request of the same sizes

@@ -191,13 +191,21 @@ inline double sum_thr_eff(const double *letters, const double *pssm, int m, doub
     return std::max(thr_seq, e);
 }
 
-// np.round(float32, 3), bit for bit: multiply, rint, divide, each rounded to float32 (no contraction, IEEE division)
-__device__ __forceinline__ float round3(float x)
+// np.round(float32, 3), bit for bit: multiply, rint, divide, each rounded to float32 (no contraction, IEEE division).  ONE
+// function for both sides: the device spells the multiply and the divide with the round-to-nearest intrinsics, the host's plain
+// operators are IEEE float32 already; rintf on either side (round to nearest even, the mode both run in).
+__host__ __device__ __forceinline__ float round3(float x)
 {
 #pragma clang fp contract(off)
+#if defined(__HIP_DEVICE_COMPILE__)
     const float y = __fmul_rn(x, 1000.0f);
     const float r = rintf(y);
     return __fdiv_rn(r, 1000.0f);
+#else
+    const float y = x * 1000.0f;
+    const float r = rintf(y);
+    return r / 1000.0f;
+#endif
 }
 
 // false only when the printed sum cannot exceed thr_sum, whichever structure score (fast or re-scored) ends up in it
@@ -223,6 +231,110 @@ __device__ __forceinline__ bool sum_passes(float seq, double &st, double thr_sum
         s = z + st;
     }
     return s > thr_sum;
+}
+
+// ---- the joint threshold of the two-FASTA mode (pfmscan_hits_pair_sum_*) ---------------------------------------------
+// Both scores are letter sums here and BOTH printed columns are rounded (scan_pair.rows; rnascan.py:273, :416-434):
+//     printed(p) = fl( (double) round3(f) + round3d(st) ),   f = float32 of the sequence sum, st = the fp64 structure sum.
+// There is no near band and no re-score: st already is the reference-order value.
+//
+// round3d(x) = Python's round(x, 3) of a double = the double nearest to the 3-digit decimal nearest to the EXACT binary
+// value, ties to even (float.__round__ goes through dtoa / strtod; pfmscan_round_decimals is the host's form of it).
+// Without strings, for |fl(1000 x)| < 2^52:  y = fl(1000 x) and e = fma(x, 1000, -y) give the product exactly, y + e
+// with |e| <= ulp(y) / 2;  r = rint(y);  t = y - r is exact and a multiple of ulp(y) <= 1/2.  When |t| < 1/2, y is at least
+// ulp(y) away from the nearest half-integer and |e| <= ulp(y) / 2 cannot carry the product to or across it: r is the
+// product's nearest integer too.  When |t| = 1/2, y IS the half-integer and the sign of e alone says on which side the
+// product lies: t = +1/2 with e > 0 -> r + 1, t = -1/2 with e < 0 -> r - 1, e = 0 -> an exact tie, and rint chose the even
+// one.  r / 1000 is then ONE correctly rounded division of two exact integers.  From 2^52 on (and for inf / NaN) x comes
+// back unchanged, as from pfmscan_round_decimals.
+__host__ __device__ inline double round3d(double x)
+{
+#pragma clang fp contract(off)
+    const double y = x * 1000.0;
+    if (!(fabs(y) < 0x1p52)) return x;
+    const double e = fma(x, 1000.0, -y);
+    double r = rint(y);
+    const double t = y - r;
+    if (t == 0.5 && e > 0.0) r += 1.0;
+    else if (t == -0.5 && e < 0.0) r -= 1.0;
+    return r / 1000.0;
+}
+
+// Cheap superset test ahead of the two roundings and the division: a window goes on only if
+//     fl( fl((double) f + st) + mg ) > thr_sum,   mg = margin0 + ROUND3_C u32 |f| + 2^-50 |st|      (u32 = 2^-24, u = 2^-53).
+// Why no window whose printed sum passes fails it.  fl(z + s3) > T with T a double implies z + s3 > T in real numbers
+// (rounding is monotone).  z = (double) round3(f) <= f + 0.0005 + 3.01 u32 |f| for |f| <= ROUND3_SAFE (head of this file);
+// s3 = fl(r / 1000) with |r / 1000 - st| <= 0.0005, so s3 <= st + 0.0005 + u (|st| + 0.0005); a = fl(f + st) >= f + st -
+// u (|f| + |st|).  Together  a + M > T  with  M = 0.001 + 3.01 u32 |f| + u |f| + 2 u |st| + 2^-63.  The computed mg (two FMAs,
+// each within 2^-53 relative) exceeds M by at least 0.001 (2^-50 - 2^-52) - 2^-63 + 2^-50 |T| + 0.98 u32 |f| + 2^-51 |st|
+// (margin0 = up(up(0.001 (1 + 2^-50)) + up(2^-50 |T|)), pair_sum_margin0), so a + mg > T + 2^-50 |T| >= T + 2 ulp(T) in
+// real numbers and its rounding is still > T.  Beyond ROUND3_SAFE (and for +inf) the test is skipped, not trusted.
+inline double pair_sum_margin0(double thr_sum)
+{
+    if (!std::isfinite(thr_sum)) return 0.0;
+    return next_up(next_up(0.001 * (1.0 + 0x1p-50)) + next_up(0x1p-50 * std::fabs(thr_sum)));
+}
+// host: an upper bound Mmax on (printed-sum margin + the roundings of the test's two additions) for EVERY window of one pair, so
+// that a hit has (double) f + st > thr_sum - Mmax in real numbers: Mmax = 0.0010001 + 4.01 * 2^-24 F1 + 2^-48 (F1 + F2 + |thr_sum|)
+// with F1 / F2 = sum_j max_c |cell| of the sequence / structure table over finite cells (|f| <= F1 (1 + 2^-23), |st| <= F2 (1 + m 2^-53));
+// every operation rounded up.  The joint credits of k_pair_cred_sum and thr_eff of a two-FASTA library both start from it.
+inline double pair_joint_margin(double F1, double F2, double thr_sum)
+{
+    double M = next_up(0.0010001 + next_up(4.01 * 0x1p-24 * F1));
+    return next_up(M + next_up(0x1p-48 * next_up(next_up(F1 + F2) + std::fabs(thr_sum))));
+}
+// host: the letters threshold phase A of a TWO-FASTA library may use for one pair under the joint threshold thr_sum
+// (pfmscan_library_hits_letters_sum_*).  The structure score is a letter sum here: st <= U2 = the sequential fp64 sum, j ascending,
+// of the row maxima of table2 over finite cells -- the very sum the kernel takes for the window that holds those letters, so U2 is
+// ATTAINED (rounding is monotone: a window with smaller cells sums to no more), not merely a bound.  A hit has
+// (double) f + st > thr_sum - Mmax (pair_joint_margin), hence (double) f > e = down(down(thr_sum - Mmax) - U2), and
+//     thr_eff = max(thr_seq, e)
+// is a superset threshold for the credits; phase B decides with the caller's thr_seq, thr_struct and thr_sum.  No tightening
+// (thr_eff = thr_seq) with a +inf cell in table2 (no bound), a +inf / NaN cell in the letter columns of table1 (the prefilter is
+// off for it anyway), letters beyond ROUND3_SAFE, thr_sum = -inf, or when e comes out NaN.  A row of table2 without a finite cell
+// makes every window -inf / NaN: it adds nothing to U2.
+inline double pair_thr_eff(const double *table1, const double *table2, int m, double thr_seq, double thr_sum)
+{
+    if (!(thr_sum > -INFINITY)) return thr_seq;
+    if (thr_sum == INFINITY) return INFINITY;
+    double F1 = 0.0, F2 = 0.0, U2 = 0.0;
+    for (int j = 0; j < m; ++j) {
+        double mx1 = 0.0, mx2 = 0.0, hi = -INFINITY;
+        for (int c = 0; c < 4; ++c) {
+            const double l = table1[j * 8 + c];
+            if (std::isnan(l) || l == INFINITY) return thr_seq;
+            if (l > -INFINITY) mx1 = std::max(mx1, std::fabs(l));
+        }
+        for (int c = 0; c < 8; ++c) {
+            const double v = table2[j * 8 + c];
+            if (v == INFINITY) return thr_seq;
+            if (std::isfinite(v)) {
+                mx2 = std::max(mx2, std::fabs(v));
+                hi = std::max(hi, v);
+            }
+        }
+        F1 = next_up(F1 + mx1);
+        F2 = next_up(F2 + mx2);
+        if (hi > -INFINITY) U2 = U2 + hi;              // the kernel's own order and rounding
+    }
+    if (!(F1 <= ROUND3_SAFE)) return thr_seq;
+    const double e = next_down(next_down(thr_sum - pair_joint_margin(F1, F2, thr_sum)) - U2);
+    if (std::isnan(e)) return thr_seq;
+    return std::max(thr_seq, e);
+}
+__host__ __device__ inline bool pair_sum_maybe(float f, double st, double thr_sum, double margin0)
+{
+#pragma clang fp contract(off)
+    const double x = (double)f;
+    const double mg = fma(fabs(st), 0x1p-50, fma(fabs(x), ROUND3_C * 0x1p-24, margin0));
+    return !(fabs(x) <= ROUND3_SAFE) || ((x + st) + mg > thr_sum);
+}
+// The third predicate for a window that already passed f > thr_seq AND st > thr_struct (so neither is NaN or -inf).
+__host__ __device__ inline bool pair_sum_passes(float f, double st, double thr_sum, double margin0)
+{
+#pragma clang fp contract(off)
+    if (!pair_sum_maybe(f, st, thr_sum, margin0)) return false;
+    return (double)round3(f) + round3d(st) > thr_sum;
 }
 
 }  // namespace pfmscan

@@ -23,6 +23,17 @@ struct Cred8Cache {
     uint16_t cr[32 * 8];
 };
 
+// the joint credit tables of one (sequence PFM, structure-letter PFM) pair at one thr_sum (pfmscan_pairsum.hip), kept with the
+// sequence motif: rows 0 .. m-1 the sequence side, m .. 2m-1 the structure side, [row][code]
+struct PairCred {
+    int mode = 0;                // 0: nothing cached; 1: k_pair_cred_sum with cr; 2: dense; 3: no integer prefilter possible
+    int m = 0;
+    double thr_sum = __builtin_nan("");
+    double thr_joint = 0.0, quantum = 0.0, slack = 0.0, survive = 0.0;
+    uint16_t cr[64 * 8];
+    double key2[32 * 8];         // the structure table the credits were built for
+};
+
 struct ScanArgs {
     const uint8_t *codes;        // [n_pos] device, may be null when the motif has no letter table
     const void *profile;         // [n_pos][7] float or double, device, may be null
@@ -97,6 +108,13 @@ bool launch_letters_cred8(const ScanArgs &a, const Tuning &t, hipStream_t stream
 // pfmscan_kernels.hip: the integer-prefiltered hits kernel of 4-letter alphabets (false: not applicable -- dense threshold,
 // +inf cells, width > 32); with a.codes2 / a.letter_table2 set it verifies the second stream in the same launch
 bool launch_letters_cred(const ScanArgs &a, const Tuning &t, hipStream_t stream, hipError_t *err);
+// pfmscan_pairsum.hip: both exact letter sums of every window and the joint predicate of pfmscan_hits_pair_sum_* (a.codes2 /
+// a.letter_table2 = the structure side, a.thr_sum, a.sum_margin0 = pair_sum_margin0); any width up to PFMSCAN_MAX_WIDTH
+hipError_t launch_pair_sum_dense(const ScanArgs &a, hipStream_t stream);
+// ... and the integer prefilter in front of them for widths up to 32 (a.h_letters = the sequence table on the host, h_letters2 the
+// structure table; false: not applicable -- width, a switched-off prefilter, a predicted survivor rate above 1/32)
+void build_pair_credits(const double *L1, const double *L2, int m, double thr_sum, PairCred *pc);
+bool launch_pair_cred_sum(const ScanArgs &a, const double *h_letters2, PairCred *cache, const Tuning &t, hipStream_t stream, hipError_t *err);
 // letters-only scans of PFMs wider than PFMSCAN_MAX_M: codes in LDS, the table streamed through LDS in 64-row slabs
 bool launch_wide_letters(const ScanArgs &a, hipStream_t stream, hipError_t *err);
 bool launch_profile_fixed(const ScanArgs &a, hipStream_t stream, hipError_t *err);     // pfmscan_profile_fixed.hip

@@ -379,7 +379,10 @@ template <> struct CredEntry<1> { typedef uint32_t type; };
 // (This kernel still spells the hit queue and the survivor hand-over out: moved onto WaveHitQueue / SurvivorQueue of
 // pfmscan_hitqueue.hpp, as k_letters_pre and k_letters_cred8 are, hipcc allocates its registers differently -- 78 -> 83
 // VGPRs for NJ = 5, one wave per SIMD less -- so it keeps the code it was measured with.)
-template <int NJ, bool PAIR>
+// SUM (with PAIR): the joint threshold of pfmscan_hits_pair_sum_* -- a window that passed both single thresholds is a hit only
+// when its PRINTED sum exceeds a.thr_sum too (pair_sum_passes, pfmscan_exact.hpp; a.sum_margin0 = pair_sum_margin0).  A
+// compile-time flag: the PAIR = false / PAIR = true instantiations keep their code and their registers.
+template <int NJ, bool PAIR, bool SUM = false>
 __global__ __launch_bounds__(BLOCK) void k_letters_cred(const ScanArgs a, const CredTable ct)
 {
     constexpr int W = 16;                              // windows per lane = one round per tile
@@ -503,6 +506,7 @@ __global__ __launch_bounds__(BLOCK) void k_letters_cred(const ScanArgs a, const 
                     for (int b = 0; b < 4; ++b) st += tbl2[(4 * k + b) * 8 + ((cw >> (8 * b)) & 7u)];      // rows m .. 4 NJ - 1 are zeros
                 }
                 ok = st > a.thr_struct;
+                if (SUM && ok) ok = pair_sum_passes(f, st, a.thr_sum, a.sum_margin0);
             }
             if (ok) {
                 const int slot = atomicAdd(&q_n[wave], 1);     // LDS
@@ -1023,11 +1027,14 @@ bool launch_letters_cred(const ScanArgs &a, const Tuning &t, hipStream_t stream,
     b.tiles_per_block = walk_tiles(ntiles, t);
     if (t.tiles_per_block > 0) b.tiles_per_block = t.tiles_per_block;
     const unsigned g = (unsigned)((ntiles + b.tiles_per_block - 1) / b.tiles_per_block);
-#define CRED_CASE(N) case N: if (b.codes2) hipLaunchKernelGGL((k_letters_cred<N, true>), dim3(g), dim3(BLOCK), 0, stream, b, ct); \
+    const bool sum = b.codes2 && b.thr_sum > -INFINITY;       // pfmscan_hits_pair_sum_*: the third predicate in the exact stage
+#define CRED_CASE(N) case N: if (sum) hipLaunchKernelGGL((k_letters_cred<N, true, true>), dim3(g), dim3(BLOCK), 0, stream, b, ct); \
+                             else if (b.codes2) hipLaunchKernelGGL((k_letters_cred<N, true>), dim3(g), dim3(BLOCK), 0, stream, b, ct); \
                              else hipLaunchKernelGGL((k_letters_cred<N, false>), dim3(g), dim3(BLOCK), 0, stream, b, ct); break;
     switch (nj) {
     CRED_CASE(1) CRED_CASE(2) CRED_CASE(3) CRED_CASE(4) CRED_CASE(5) CRED_CASE(6) CRED_CASE(7)
-    default: if (b.codes2) hipLaunchKernelGGL((k_letters_cred<8, true>), dim3(g), dim3(BLOCK), 0, stream, b, ct);
+    default: if (sum) hipLaunchKernelGGL((k_letters_cred<8, true, true>), dim3(g), dim3(BLOCK), 0, stream, b, ct);
+             else if (b.codes2) hipLaunchKernelGGL((k_letters_cred<8, true>), dim3(g), dim3(BLOCK), 0, stream, b, ct);
              else hipLaunchKernelGGL((k_letters_cred<8, false>), dim3(g), dim3(BLOCK), 0, stream, b, ct);
              break;
     }

@@ -291,8 +291,11 @@ bool launch_letters_cred8(const ScanArgs &a, const Tuning &t, hipStream_t stream
 // the sum exceeds a.thr_struct (rnascan.py:263 on the structure side; combine() then joins the two tables,
 // rnascan.py:422-423).  a.codes / a.letter_table are the second stream and its table here.
 // ---------------------------------------------------------------------------
+// SUM: the joint threshold of pfmscan_hits_pair_sum_* on the candidates that passed the structure threshold
+// (pair_sum_passes, pfmscan_exact.hpp; a.sum_margin0 = pair_sum_margin0).
 constexpr int LETTERS_AT_MAX_SHARDS = 64;
 
+template <bool SUM>
 __global__ __launch_bounds__(BLOCK) void k_letters_at(const ScanArgs a, const int64_t *__restrict__ cand_pos,
                                                       const float *__restrict__ cand_seq,
                                                       const unsigned long long *__restrict__ cand_count,
@@ -340,7 +343,9 @@ __global__ __launch_bounds__(BLOCK) void k_letters_at(const ScanArgs a, const in
                 const uint32_t code = p + j < n_pos ? (uint32_t)a.codes[p + j] & 7u : (uint32_t)PFMSCAN_SEP;
                 score += tab[j * 8 + code];
             }
-            mask = score > a.thr_struct ? 1u : 0u;
+            bool ok = score > a.thr_struct;
+            if (SUM && ok) ok = pair_sum_passes(sq, score, a.thr_sum, a.sum_margin0);
+            mask = ok ? 1u : 0u;
         }
         emit_hits_block<1>(mask, [&](int) { return p; }, [&](int) { return sq; }, [&](int) { return score; }, a);
     }
@@ -354,8 +359,12 @@ hipError_t launch_letters_at(const ScanArgs &a, const int64_t *cand_pos, const f
     if (cand_shards > LETTERS_AT_MAX_SHARDS || !a.codes || !a.letter_table) return hipErrorInvalidValue;
     const int64_t worst = (cand_shard_cap + BLOCK - 1) / BLOCK * cand_shards;
     const unsigned grid = (unsigned)std::min<int64_t>(worst, 2048);          // 8 workgroups per CU
-    hipLaunchKernelGGL(k_letters_at, dim3(grid), dim3(BLOCK), 0, stream, a, cand_pos, cand_seq, cand_count, cand_shard_cap,
-                       cand_shards);
+    if (a.thr_sum > -INFINITY)
+        hipLaunchKernelGGL(k_letters_at<true>, dim3(grid), dim3(BLOCK), 0, stream, a, cand_pos, cand_seq, cand_count, cand_shard_cap,
+                           cand_shards);
+    else
+        hipLaunchKernelGGL(k_letters_at<false>, dim3(grid), dim3(BLOCK), 0, stream, a, cand_pos, cand_seq, cand_count, cand_shard_cap,
+                           cand_shards);
     return hipGetLastError();
 }
 

@@ -359,7 +359,7 @@ __device__ __forceinline__ int lib_dispatch(const int npair, const int g, const 
 }
 
 // NG = motif groups of the pass, NP = pair rows the code is unrolled for (8 / 16 / 32 for m <= 16 / 32 / 64)
-// SUM (pfmscan_library_hits_sum_*; profile rows only): phase B also asks for the printed LogOdds.SeqStruct
+// SUM (pfmscan_library_hits_sum_*, and pfmscan_library_hits_letters_sum_* for PROF_T = uint8_t): phase B also asks for the printed LogOdds.SeqStruct
 // float64(round3(seq)) + struct > thr_sum[motif] (rnascan.py:416-434; sum_passes in pfmscan_exact.hpp, as k_profile_sum does).
 // The credits of phase A are then built for thr_eff = max(thr_seq, thr_sum - the bound on a structure score), the
 // thresholds phase B compares with are the caller's.  thr_sum and its band and margin stay in global memory: the few
@@ -568,10 +568,15 @@ __global__ __launch_bounds__(lib_block(NP)) void k_library(const LibArgs a)
                     if constexpr (SUM) {
                         if (ok) {
                             const double *sp = g_thr_sum + mo;
-                            ok = sum_passes(f, st, sp[0], sp[NMP], sp[2 * NMP], [&]() {
-                                return struct_window_rounded(reinterpret_cast<const PROF_T *>(a.profile) + ps * 7, m,
-                                                             [&](int j, int k) { return pssm[((size_t)(j * 4 + (k >> 1)) * NMP + mo) * 2 + (k & 1)]; });
-                            });
+                            if constexpr (std::is_same<PROF_T, uint8_t>::value) {
+                                // two-FASTA library: st is the letter sum itself, both printed columns are rounded (pfmscan_hits_pair_sum_*)
+                                ok = pair_sum_passes(f, st, sp[0], sp[2 * NMP]);
+                            } else {
+                                ok = sum_passes(f, st, sp[0], sp[NMP], sp[2 * NMP], [&]() {
+                                    return struct_window_rounded(reinterpret_cast<const PROF_T *>(a.profile) + ps * 7, m,
+                                                                 [&](int j, int k) { return pssm[((size_t)(j * 4 + (k >> 1)) * NMP + mo) * 2 + (k & 1)]; });
+                                });
+                            }
                         }
                     }
                 }
@@ -752,7 +757,10 @@ template <int NG, int NP>
 static hipError_t launch_library_ng(const LibArgs &a, unsigned grid, size_t lds, hipStream_t stream)
 {
     if (!a.pssm) return launch_library_inst<NG, NP, float, false>(a, grid, lds, stream);
-    if (a.profile_dtype == PROFILE_LETTERS2) return launch_library_inst<NG, NP, uint8_t, true>(a, grid, lds, stream);     // two-FASTA library
+    if (a.profile_dtype == PROFILE_LETTERS2) {           // two-FASTA library; with joint thresholds on the printed sum (pfmscan_library_hits_letters_sum_*)
+        if (a.thr_sum) return launch_library_inst<NG, NP, uint8_t, true, true>(a, grid, lds, stream);
+        return launch_library_inst<NG, NP, uint8_t, true>(a, grid, lds, stream);
+    }
     if (a.thr_sum) {                                     // joint threshold on the printed sum (profile rows)
         if (a.profile_dtype == PFMSCAN_PROFILE_F64) return launch_library_inst<NG, NP, double, true, true>(a, grid, lds, stream);
         return launch_library_inst<NG, NP, float, true, true>(a, grid, lds, stream);

@@ -215,6 +215,10 @@ static int create_seq_library(pfmscan_ctx *ctx, const double *letter_tables, con
         lib->h_letters.assign(letter_tables, letter_tables + (size_t)n_motifs * m * 8);
         lib->h_pssm.assign(struct_pssms, struct_pssms + (size_t)n_motifs * m * 7);
     }
+    if (struct_pssms && ncol == 8) {                     // two-FASTA library: the host copies thr_eff of a joint threshold is computed from
+        lib->h_letters.assign(letter_tables, letter_tables + (size_t)n_motifs * m * 8);
+        lib->h_pssm.assign(struct_pssms, struct_pssms + (size_t)n_motifs * m * 8);
+    }
     if (struct_pssms && ncol == 7 && !std::getenv("PFMSCAN_FORCE_GENERIC")) {
         lib->all_finite = true;
         for (size_t i = 0; i < (size_t)n_motifs * m * 7 && lib->all_finite; ++i) lib->all_finite = std::isfinite(struct_pssms[i]);
@@ -493,8 +497,10 @@ static int lib_set_thresholds(pfmscan_ctx *ctx, pfmscan_library *lib, const doub
             return lib_fail(ctx, PFMSCAN_E_BADARG, "NaN threshold");
         if (thr_sum) {
             tsum[(size_t)k] = thr_sum[k];
-            eff[(size_t)k] = sum_thr_eff(lib->h_letters.data() + (size_t)k * lib->m * 8, lib->h_pssm.data() + (size_t)k * lib->m * 7, lib->m,
-                                         thr_seq[k], thr_sum[k], row_sum_max);
+            eff[(size_t)k] = lib->pair ? pair_thr_eff(lib->h_letters.data() + (size_t)k * lib->m * 8, lib->h_pssm.data() + (size_t)k * lib->m * 8,
+                                                      lib->m, thr_seq[k], thr_sum[k])
+                                       : sum_thr_eff(lib->h_letters.data() + (size_t)k * lib->m * 8, lib->h_pssm.data() + (size_t)k * lib->m * 7, lib->m,
+                                                     thr_seq[k], thr_sum[k], row_sum_max);
         }
         if (eff[(size_t)k] == -INFINITY)
             return lib_fail(ctx, PFMSCAN_E_BADARG, "library hits need a finite sequence threshold (every window would be a hit; use the all-scores entry points)");
@@ -523,10 +529,10 @@ static int lib_set_thresholds(pfmscan_ctx *ctx, pfmscan_library *lib, const doub
             lib->h_thr[ps.thr_off + l] = thr_seq[k];
             lib->h_thr[ps.thr_off + ps.nmp + l] = lib->has_struct ? thr_struct[k] : -INFINITY;
             if (thr_sum) {
-                const double sb = sum_band(lib->band[(size_t)k], thr_sum[k]);
+                const double sb = lib->pair ? 0.0 : sum_band(lib->band[(size_t)k], thr_sum[k]);      // letter sums: no near band
                 lib->h_thr[ps.thr_off + 2 * ps.nmp + l] = thr_sum[k];
                 lib->h_thr[ps.thr_off + 3 * ps.nmp + l] = sb;
-                lib->h_thr[ps.thr_off + 4 * ps.nmp + l] = sum_margin0(sb);
+                lib->h_thr[ps.thr_off + 4 * ps.nmp + l] = lib->pair ? pair_sum_margin0(thr_sum[k]) : sum_margin0(sb);
             }
             // the credits stand for eff[k] (= thr_seq[k] without a joint threshold); phase B compares with the thresholds above
             lib->eps[k] = build_credits(lib->pairsum.data() + (size_t)k * npair * 16, npair, eff[(size_t)k], cr.data(), bits);
@@ -799,10 +805,11 @@ __global__ __launch_bounds__(PACK_BLOCK) void k_lib_pack(const int64_t *__restri
 
 // the pfmscan_library_hits_sum_* argument check; *any = some motif has a joint threshold that can reject a window (none: the plain
 // kernels run, as for an infinite thr_sum of pfmscan_hits_sum_*)
-static int lib_check_sum(pfmscan_ctx *ctx, const pfmscan_library *lib, const double *thr_sum, bool *any)
+static int lib_check_sum(pfmscan_ctx *ctx, const pfmscan_library *lib, const double *thr_sum, bool *any, bool pair = false)
 {
     if (!ctx || !lib) return lib_fail(ctx, PFMSCAN_E_BADARG, "NULL ctx or library");
-    if (!lib->has_letters || !lib->has_struct || lib->pair || lib->letters8)
+    if (pair && !lib->pair) return lib_fail(ctx, PFMSCAN_E_BADARG, "not a two-FASTA library (pfmscan_library_create_letters with both parts)");
+    if (!lib->has_letters || !lib->has_struct || lib->pair != pair || lib->letters8)
         return lib_fail(ctx, PFMSCAN_E_BADARG, "a threshold on LogOdds.SeqStruct needs a library of letter tables AND structure PSSMs over profile rows");
     if (!thr_sum) return lib_fail(ctx, PFMSCAN_E_BADARG, "threshold arrays are NULL");
     *any = false;
@@ -868,7 +875,7 @@ static int library_hits_staged_impl(pfmscan_ctx *ctx, pfmscan_library *lib, cons
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     double row_sum_max = INFINITY;
-    if (thr_sum && (rc = staged_row_bound(ctx, &row_sum_max))) return rc;
+    if (thr_sum && !lib->pair && (rc = staged_row_bound(ctx, &row_sum_max))) return rc;
     if ((rc = lib_set_thresholds(ctx, lib, thr_seq, thr_struct, st, thr_sum, row_sum_max))) return rc;
     HitSink sink;
     if ((rc = lib_acquire(ctx, lib, capacity, n_pos, st, sink))) return rc;
@@ -973,6 +980,48 @@ int pfmscan_library_hits_letters_host(pfmscan_ctx *ctx, pfmscan_library *lib, co
     if (rc) return rc;
     if (lib->pair && (rc = pfmscan_stage_codes2(ctx, codes2, n_pos))) return rc;
     return pfmscan_library_hits_staged(ctx, lib, thr_seq, thr_struct, capacity, hit_pos, hit_motif, hit_seq, hit_struct, n_hits);
+}
+
+// rnascan.py:273, :416-434: two-FASTA libraries with joint thresholds on the printed LogOdds.SeqStruct, decided in k_library phase B
+int pfmscan_library_hits_letters_sum_dev(pfmscan_ctx *ctx, pfmscan_library *lib, const uint8_t *d_codes, const uint8_t *d_codes2,
+                                         int64_t n_pos, const double *thr_seq, const double *thr_struct, const double *thr_sum,
+                                         int64_t capacity, int64_t *d_hit_pos, int32_t *d_hit_motif, float *d_hit_seq, double *d_hit_struct,
+                                         uint64_t *d_hit_count, void *stream)
+{
+    bool any = false;
+    if (int rc = lib_check_sum(ctx, lib, thr_sum, &any, true)) return rc;
+    return library_hits_dev_impl(ctx, lib, d_codes, (const void *)d_codes2, PFMSCAN_PROFILE_NONE, n_pos, thr_seq, thr_struct, any ? thr_sum : nullptr,
+                                 INFINITY, capacity, d_hit_pos, d_hit_motif, d_hit_seq, d_hit_struct, d_hit_count, stream);
+}
+
+// rnascan.py:273, :416-434
+int pfmscan_library_hits_letters_sum_host(pfmscan_ctx *ctx, pfmscan_library *lib, const uint8_t *codes, const uint8_t *codes2, int64_t n_pos,
+                                          const double *thr_seq, const double *thr_struct, const double *thr_sum, int64_t capacity,
+                                          int64_t *hit_pos, int32_t *hit_motif, float *hit_seq, double *hit_struct, int64_t *n_hits)
+{
+    bool any = false;
+    if (int rc = lib_check_sum(ctx, lib, thr_sum, &any, true)) return rc;
+    if (!n_hits) return lib_fail(ctx, PFMSCAN_E_BADARG, "NULL argument");
+    if (n_pos < 0 || capacity < 0) return lib_fail(ctx, PFMSCAN_E_BADARG, "negative size");
+    *n_hits = 0;
+    if (n_pos == 0) return PFMSCAN_OK;
+    if (!codes || !codes2) return lib_fail(ctx, PFMSCAN_E_BADARG, "codes is NULL");
+    int rc = pfmscan_stage(ctx, codes, nullptr, PFMSCAN_PROFILE_NONE, n_pos);
+    if (rc) return rc;
+    if ((rc = pfmscan_stage_codes2(ctx, codes2, n_pos))) return rc;
+    return library_hits_staged_impl(ctx, lib, thr_seq, thr_struct, any ? thr_sum : nullptr, capacity, hit_pos, hit_motif, hit_seq, hit_struct, n_hits);
+}
+
+// host only, no device (rnascan.py:273, :416-434): the letters thresholds phase A's credits are built for (pair_thr_eff, pfmscan_exact.hpp)
+int pfmscan_library_letters_sum_thresholds(const double *letter_tables, const double *struct_tables, int n_motifs, int m, const double *thr_seq,
+                                           const double *thr_sum, double *thr_eff_out)
+{
+    if (!letter_tables || !struct_tables || !thr_seq || !thr_sum || !thr_eff_out || n_motifs < 1 || m < 1 || m > PFMSCAN_MAX_M) return PFMSCAN_E_BADARG;
+    for (int k = 0; k < n_motifs; ++k)
+        if (std::isnan(thr_seq[k]) || std::isnan(thr_sum[k])) return PFMSCAN_E_BADARG;
+    for (int k = 0; k < n_motifs; ++k)
+        thr_eff_out[k] = pair_thr_eff(letter_tables + (size_t)k * m * 8, struct_tables + (size_t)k * m * 8, m, thr_seq[k], thr_sum[k]);
+    return PFMSCAN_OK;
 }
 
 // The library twin of pfmscan_hits_pipeline_host: a HOST-resident stream of any length through pipeline_chunks

@@ -104,6 +104,17 @@ class HipEngine(object):
             self._staged2 = stream
         return self.ctx.hits_pair_staged(mo_seq, mo_st, thr_seq, thr_struct)
 
+    def hits_pair_sum(self, stream, seq_table, struct_table, thr_seq, thr_struct, thr_sum):
+        """``hits_pair`` with the joint threshold of ``--min-seqstruct`` decided on the device: additionally the PRINTED
+        LogOdds.SeqStruct, float64(np.round(seq, 3)) + round(struct, 3) (rnascan.py:273, :416-434), must exceed thr_sum.
+        Either single threshold may be -inf -> (pos, seq float32, struct float64), unrounded scores"""
+        mo_seq, mo_st = self._motif(seq_table, None), self._motif(struct_table, None)
+        self._stage(stream)
+        if self._staged2 is not stream:
+            self.ctx.stage_codes2(stream.codes2)
+            self._staged2 = stream
+        return self.ctx.hits_pair_sum_staged(mo_seq, mo_st, thr_seq, thr_struct, thr_sum)
+
     def hits(self, stream, letter_table=None, struct_pssm=None, thr_seq=-np.inf, thr_struct=-np.inf, one_shot=True):
         """positions (sorted) whose scores exceed the thresholds -> (pos, seq | None, struct | None).
         A stream that is not on the device yet and is longer than PIPELINE_MIN positions (a memory-mapped profile store,
@@ -256,6 +267,33 @@ def _library_hits_letters(self, stream, seq_tables, struct_tables, thr_seq, thr_
 
 
 HipEngine.library_hits_letters = _library_hits_letters
+
+
+def _library_letters_sum_thresholds(self, seq_tables, struct_tables, thr_seq, thr_sum):
+    """the letters thresholds ``library_hits_letters_sum`` would build its prefilter for -> float64 [n]; -inf where the joint
+    threshold gives a pair no finite one (then that call raises: scan such a group pair by pair with ``hits_pair_sum``)"""
+    return _lib.library_letters_sum_thresholds(seq_tables, struct_tables, thr_seq, thr_sum)
+
+
+def _library_hits_letters_sum(self, stream, seq_tables, struct_tables, thr_seq, thr_struct, thr_sum):
+    """``library_hits_letters`` of a two-FASTA library with the joint threshold of ``hits_pair_sum`` per pair, decided in the
+    library kernel in one pass (pfmscan_library_hits_letters_sum_host; rnascan.py:273, :416-434).  thr_seq may be -inf as long
+    as ``library_letters_sum_thresholds`` is finite for every pair.  -> (pos, pair index, seq float32, struct float64)"""
+    T = np.ascontiguousarray(seq_tables, dtype=np.float64)
+    S = np.ascontiguousarray(struct_tables, dtype=np.float64)
+    key = ("letters", S.shape, T.tobytes(), S.tobytes())
+    if self._library is None or self._library[0] != key:
+        if self._library is not None:
+            self._library[1].close()
+            self._library = None
+        self._library = (key, self.ctx.library(T, struct_letters=S))
+    self._staged = None                                 # the call stages both streams itself
+    self._staged2 = None
+    return self.ctx.library_hits_letters_sum_host(self._library[1], stream.codes, stream.codes2, thr_seq, thr_struct, thr_sum)
+
+
+HipEngine.library_letters_sum_thresholds = _library_letters_sum_thresholds
+HipEngine.library_hits_letters_sum = _library_hits_letters_sum
 
 
 def _first_motif(pssm):
@@ -699,8 +737,11 @@ def scan_pair(engine, seq_records, struct_records, seq_pssm, struct_pssm, minsco
     two batches hold the same records -- same ids in the same order, each id once, same lengths.  The letters of both
     files go to the device as two code streams with the same layout; a window is reported for the motif pair (a, b) iff
     seq_a > minscore AND struct_b > minscore.  Returns None when the batches cannot be paired that way (the caller then
-    makes the two tables and joins them).  ``min_seqstruct``: the rows are filtered on the printed sum (keep_seqstruct; the
-    structure score of this mode already is the reference-order value)."""
+    makes the two tables and joins them).  ``min_seqstruct``: with an engine that has ``hits_pair_sum`` every pair that is
+    scanned by itself is ONE thresholded device call that decides the printed sum as well, and a width group of several pairs
+    is one call of the library kernel (``library_hits_letters_sum``) when the joint threshold gives every pair a finite letters
+    threshold, else one call per pair; ``rows`` still runs keep_seqstruct over what comes back (it finds nothing to drop there, and
+    it is the filter of engines without these methods)."""
     pairs_m = pair_motifs(seq_pssm, struct_pssm)
     if pairs_m is None:
         return None
@@ -713,6 +754,7 @@ def scan_pair(engine, seq_records, struct_records, seq_pssm, struct_pssm, minsco
     stream = pack.Stream(sb.codes, None, sb.offsets, sb.lengths, codes2=tb.codes)
     thr = float(minscore)
     tables = []
+    on_device = min_seqstruct is not None and hasattr(engine, "hits_pair_sum") and not np.isnan(float(min_seqstruct))
 
     def rows(pos, sq, st, m, seq_ids, struct_ids):
         rec, start = stream.locate(pos)
@@ -727,7 +769,17 @@ def scan_pair(engine, seq_records, struct_records, seq_pssm, struct_pssm, minsco
     for a, b in pairs_m:
         by_width.setdefault(seq_pssm[a].length, []).append((a, b))
     for m, group in by_width.items():
-        if len(group) > 1 and np.isfinite(thr) and m <= LIBRARY_MAX_M and hasattr(engine, "library_hits_letters"):
+        if on_device and len(group) > 1 and m <= LIBRARY_MAX_M and hasattr(engine, "library_hits_letters_sum") and \
+                hasattr(engine, "library_letters_sum_thresholds"):
+            # every pair of this width in ONE pass with the joint threshold decided in the library kernel, also at -m ' -inf', when
+            # it gives every pair a finite letters threshold; else the group goes pair by pair through hits_pair_sum below
+            T = np.stack([seq_pssm[a].letter_table(pack.RNA_LETTERS) for a, _ in group])
+            S = np.stack([struct_pssm[b].letter_table(fasta.STRUCT) for _, b in group])
+            if np.all(np.isfinite(engine.library_letters_sum_thresholds(T, S, thr, float(min_seqstruct)))):
+                pos, mo, sq, st = engine.library_hits_letters_sum(stream, T, S, thr, thr, float(min_seqstruct))
+                tables.append(rows(pos, sq, st, m, table.Indexed([a for a, _ in group], mo), table.Indexed([b for _, b in group], mo)))
+                continue
+        elif len(group) > 1 and np.isfinite(thr) and m <= LIBRARY_MAX_M and hasattr(engine, "library_hits_letters"):
             # two libraries (RNAcompete-S style): every pair of this width in ONE pass (k_library over the sequences, the
             # structure letters of its survivors); (position, pair index) order = (record, Start, Motif_ID.Seq, Motif_ID.Struct)
             T = np.stack([seq_pssm[a].letter_table(pack.RNA_LETTERS) for a, _ in group])
@@ -738,7 +790,10 @@ def scan_pair(engine, seq_records, struct_records, seq_pssm, struct_pssm, minsco
         for a, b in group:
             tab_seq = seq_pssm[a].letter_table(pack.RNA_LETTERS)
             tab_st = struct_pssm[b].letter_table(fasta.STRUCT)
-            if np.isneginf(thr) or not hasattr(engine, "hits_pair"):
+            if on_device:
+                # both single thresholds AND the printed sum in one device call, also at -m ' -inf' (rnascan.py:273, :416-434)
+                pos, sq, st = engine.hits_pair_sum(stream, tab_seq, tab_st, thr, thr, float(min_seqstruct))
+            elif np.isneginf(thr) or not hasattr(engine, "hits_pair"):
                 # every window with two finite scores is a row: all scores of both sides, the same strict `>` on the host
                 sq, _ = engine.scan(stream, tab_seq, None)
                 st = engine.scan_letters_f64(pack.Stream(tb.codes, None, tb.offsets, tb.lengths), tab_st)

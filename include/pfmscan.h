@@ -59,7 +59,7 @@
 extern "C" {
 #endif
 
-#define PFMSCAN_ABI_VERSION 17
+#define PFMSCAN_ABI_VERSION 18
 #define PFMSCAN_NCODE   8      /* columns of a letter table */
 #define PFMSCAN_SEP     7      /* separator / foreign-letter code */
 #define PFMSCAN_NSTRUCT 7      /* columns of a structure profile / structure PSSM */
@@ -408,6 +408,13 @@ void pfmscan_library_destroy(pfmscan_library *lib);
  * +inf / NaN log-odds sums runs without prefilter); any pointer may be NULL */
 int pfmscan_library_info(const pfmscan_library *lib, int *n_motifs, int *m, int *n_passes,
                          int *motifs_per_pass, double *max_eps);
+/* How the last scan of this library ran, through any pfmscan_library_hits* form (all three 0 before the first scan):
+ * *n_launches = the scan kernel's launches (a chunked or > 2^31-position scan: over all chunks / spans),
+ * *n_team_launches = those that ran several passes of a seq + struct library side by side as teams of one launch (long
+ * streams only; 0 for structure-only and letter libraries), *max_teams = the most passes in one launch (1: one after the
+ * other).  Host only; any pointer may be NULL. */
+int pfmscan_library_last_launches(const pfmscan_library *lib, int *n_launches, int *n_team_launches,
+                                  int *max_teams);
 /* Device-resident form, asynchronous on `stream` WHILE THE THRESHOLDS REPEAT: a
  * call whose thresholds differ from the previous call's on this library (the
  * first call included) synchronises `stream` once before it rewrites the
@@ -418,7 +425,10 @@ int pfmscan_library_info(const pfmscan_library *lib, int *n_motifs, int *m, int 
  *   d_hit_pos int64 [capacity], d_hit_motif int32 [capacity] (motif index 0..n-1),
  *   d_hit_seq float [capacity] or NULL, d_hit_struct double [capacity] or NULL,
  *   d_hit_count: one uint64 (need not be zeroed); afterwards the TOTAL number of hits.  A value
- *   above capacity means the hit arrays are incomplete: call again with at least that capacity. */
+ *   above capacity means the hit arrays are incomplete: call again with at least that capacity (the value
+ *   is then the total or more: the hit arrays are 256 regions that must each hold their part, and hits
+ *   that crowd into some of them -- the passes of a large library differ in their hit counts -- need more
+ *   room than their number). */
 int pfmscan_library_hits_dev(pfmscan_ctx *ctx, pfmscan_library *lib,
                              const uint8_t *d_codes, const void *d_profile,
                              int profile_dtype, int64_t n_pos, const double *thr_seq,

@@ -22,7 +22,7 @@ NCODE = 8
 NSTRUCT = 7
 MAX_M = 64            # widest PFM of the tuned kernels and of PFM libraries
 MAX_WIDTH = 4096      # widest PFM accepted (wider than MAX_M: the plain rolled-loop kernel)
-ABI_VERSION = 17
+ABI_VERSION = 18
 
 # every symbol include/pfmscan.h declares (checked by tests/test_abi.py)
 SYMBOLS = [
@@ -52,6 +52,7 @@ SYMBOLS = [
     "pfmscan_hits_pair_sum_dev", "pfmscan_hits_pair_sum_staged", "pfmscan_hits_pair_sum_host", "pfmscan_pair_sum_route",
     "pfmscan_debug_round3d", "pfmscan_debug_pair_sum_test", "pfmscan_debug_pair_credits",
     "pfmscan_library_hits_letters_sum_dev", "pfmscan_library_hits_letters_sum_host", "pfmscan_library_letters_sum_thresholds",
+    "pfmscan_library_last_launches",
 ]
 PAIR_ROUTE_NONE, PAIR_ROUTE_FUSED, PAIR_ROUTE_TWO_PHASE, PAIR_ROUTE_DENSE, PAIR_ROUTE_CREDITS = range(5)   # Context.pair_sum_route()
 SITE_GROUP = 4096     # most hits of one group of the site profiles
@@ -215,6 +216,7 @@ def load():
     L.pfmscan_hits_pair_sum_staged.argtypes = [vp, vp, vp, dbl, dbl, dbl, i64, vp, vp, vp, ctypes.POINTER(i64)]
     L.pfmscan_hits_pair_sum_host.argtypes = [vp, vp, vp, vp, vp, i64, dbl, dbl, dbl, i64, vp, vp, vp, ctypes.POINTER(i64)]
     L.pfmscan_pair_sum_route.argtypes = [vp]
+    L.pfmscan_library_last_launches.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i32)]
     L.pfmscan_debug_round3d.argtypes = [vp, i64, vp]
     L.pfmscan_library_hits_letters_sum_dev.argtypes = [vp, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp]
     L.pfmscan_library_hits_letters_sum_host.argtypes = [vp, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, vp, ctypes.POINTER(i64)]
@@ -1645,6 +1647,13 @@ class Library(object):
                                                       ctypes.byref(per), ctypes.byref(eps)))
         return {"n_motifs": n.value, "m": m.value, "passes": npass.value, "motifs_per_pass": per.value,
                 "max_prefilter_eps": eps.value}
+
+    def last_launches(self):
+        """how the last scan of this library ran (pfmscan_library_last_launches): its kernel launches, how many of them ran
+        several passes side by side as teams, the most passes in one launch; all 0 before the first scan"""
+        n, teams, most = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        self._ctx._check(self._L.pfmscan_library_last_launches(self._h, ctypes.byref(n), ctypes.byref(teams), ctypes.byref(most)))
+        return {"n_launches": n.value, "n_team_launches": teams.value, "max_teams": most.value}
 
     def close(self):
         if getattr(self, "_h", None) and getattr(self._ctx, "_h", None):

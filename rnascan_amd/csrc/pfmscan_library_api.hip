@@ -135,6 +135,8 @@ struct pfmscan_library {
     std::vector<double> band;                       // [n] struct_band of each motif
     std::vector<double> cur_eff, cur_sum;
     bool thr_valid = false;
+    // the kernel launches of the last scan (pfmscan_library_last_launches): all of them, those with teams, the most teams in one
+    int last_launches = 0, last_team_launches = 0, last_max_teams = 0;
 };
 
 static int lib_fail(pfmscan_ctx *ctx, int code, const std::string &msg) { return fail(ctx, code, msg); }
@@ -430,6 +432,15 @@ int pfmscan_library_info(const pfmscan_library *lib, int *n_motifs, int *m, int 
     return PFMSCAN_OK;
 }
 
+int pfmscan_library_last_launches(const pfmscan_library *lib, int *n_launches, int *n_team_launches, int *max_teams)
+{
+    if (!lib) return PFMSCAN_E_BADARG;
+    if (n_launches) *n_launches = lib->last_launches;
+    if (n_team_launches) *n_team_launches = lib->last_team_launches;
+    if (max_teams) *max_teams = lib->last_max_teams;
+    return PFMSCAN_OK;
+}
+
 }  // extern "C"
 
 // (re)build the thresholded credit tables when the thresholds changed; uploads on `st`
@@ -558,6 +569,14 @@ static int lib_set_thresholds(pfmscan_ctx *ctx, pfmscan_library *lib, const doub
 
 constexpr int64_t LIB_SEG = (int64_t)1 << LIB_SEG_SHIFT;        // windows per work segment (segment s -> workgroup s mod grid, shard s mod 256)
 
+// what pfmscan_library_last_launches reports: one kernel launch of `n_teams` passes side by side (1: a pass alone)
+static void lib_note_launch(pfmscan_library *lib, int n_teams)
+{
+    ++lib->last_launches;
+    if (n_teams > 1) ++lib->last_team_launches;
+    lib->last_max_teams = std::max(lib->last_max_teams, n_teams);
+}
+
 // every pass of the library over [0, n_pos); asynchronous on `st`
 static int lib_run(pfmscan_ctx *ctx, pfmscan_library *lib, const uint8_t *d_codes, const void *d_profile, int profile_dtype,
                    int64_t n_pos, const HitSink &sink, hipStream_t st, int64_t pos_offset = 0, bool sum = false)
@@ -595,6 +614,7 @@ static int lib_run(pfmscan_ctx *ctx, pfmscan_library *lib, const uint8_t *d_code
                 a.hit_count = sink.count;
                 hipError_t e = launch_library8(a, ctx->n_cu, st);
                 if (e != hipSuccess) return fail_hip(ctx, e, "launch k_library8");
+                lib_note_launch(lib, 1);
             }
         return PFMSCAN_OK;
     }
@@ -620,6 +640,7 @@ static int lib_run(pfmscan_ctx *ctx, pfmscan_library *lib, const uint8_t *d_code
         a.hit_count = sink.count;
         hipError_t e = launch_profile_library(a, st);
         if (e != hipSuccess) return fail_hip(ctx, e, "launch k_profile_lib");
+        lib_note_launch(lib, 1);
         return PFMSCAN_OK;
     }
     // Teams: up to four consecutive passes SIDE BY SIDE in one launch, each on a share of the workgroups, all walking the
@@ -701,6 +722,7 @@ static int lib_run(pfmscan_ctx *ctx, pfmscan_library *lib, const uint8_t *d_code
             a.hit_count = sink.count;
             hipError_t e = launch_library(a, ctx->n_cu, st);
             if (e != hipSuccess) return fail_hip(ctx, e, "launch k_library");
+            lib_note_launch(lib, (int)nt);
         }
     }
     return PFMSCAN_OK;
@@ -734,8 +756,10 @@ static int lib_check(pfmscan_ctx *ctx, const pfmscan_library *lib, const uint8_t
 }
 
 // the ctx's library hit buffers sized for `capacity` hits of a scan of n_pos positions, counters zeroed on `st`
-static int lib_acquire(pfmscan_ctx *ctx, const pfmscan_library *lib, int64_t capacity, int64_t n_pos, hipStream_t st, HitSink &sink)
+// (a scan begins here: the launch figures of pfmscan_library_last_launches start over)
+static int lib_acquire(pfmscan_ctx *ctx, pfmscan_library *lib, int64_t capacity, int64_t n_pos, hipStream_t st, HitSink &sink)
 {
+    lib->last_launches = lib->last_team_launches = lib->last_max_teams = 0;
     return acquire_sink(ctx, lib_bufs(ctx), LIB_SHARDS, lib_shard_cap(capacity, n_pos, lib_work_unit(lib)), st, sink);
 }
 
@@ -744,17 +768,21 @@ namespace pfmscan {
 
 constexpr int PACK_BLOCK = 256;
 
-// starts[s] = exclusive prefix of min(count_s, shard_cap); *out_count = total hits (capacity + 1 at least when a shard
-// overflowed although the total fits, so that the caller sees "incomplete" exactly when something was dropped)
+// starts[s] = exclusive prefix of min(count_s, shard_cap); *out_count = total hits -- or, when they do not fit or a shard
+// overflowed although the total fits, a capacity above `capacity` at which every shard fits (the fullest shard times all of
+// them, as finish_sorted_hits asks): the caller sees "incomplete" exactly when something was dropped, and a second call with
+// that capacity is complete.  (Teams put the workgroups of one pass on neighbouring shards: a pass with most of the hits
+// fills its share of the shards only, and "capacity + 1" asked for room that was no more than before.)
 __global__ __launch_bounds__(PACK_BLOCK) void k_lib_prefix(const unsigned long long *__restrict__ counts, int shards,
                                                            int64_t shard_cap, int64_t capacity, int64_t *__restrict__ starts,
                                                            unsigned long long *__restrict__ out_count)
 {
     __shared__ int64_t held[LIB_SHARDS];
-    __shared__ unsigned long long total_s;
+    __shared__ unsigned long long total_s, worst_s;
     __shared__ int over_s;
     if (threadIdx.x == 0) {
         total_s = 0;
+        worst_s = 0;
         over_s = 0;
     }
     __syncthreads();
@@ -762,6 +790,7 @@ __global__ __launch_bounds__(PACK_BLOCK) void k_lib_prefix(const unsigned long l
         const unsigned long long n = counts[(size_t)s * HIT_COUNTER_STRIDE];
         held[s] = (int64_t)n < shard_cap ? (int64_t)n : shard_cap;
         atomicAdd(&total_s, n);
+        atomicMax(&worst_s, n);
         if ((int64_t)n > shard_cap) atomicOr(&over_s, 1);
     }
     __syncthreads();
@@ -773,7 +802,10 @@ __global__ __launch_bounds__(PACK_BLOCK) void k_lib_prefix(const unsigned long l
         }
         starts[shards] = run;
         unsigned long long t = total_s;
-        if (over_s && (int64_t)t <= capacity) t = (unsigned long long)capacity + 1;
+        if (over_s || (int64_t)t > capacity) {
+            if (worst_s * (unsigned long long)shards > t) t = worst_s * (unsigned long long)shards;
+            if ((int64_t)t <= capacity) t = (unsigned long long)capacity + 1;      // (cannot happen: an overflowed shard holds more than capacity / shards)
+        }
         *out_count = t;
     }
 }

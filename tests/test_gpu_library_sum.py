@@ -102,7 +102,7 @@ def same_bits(a, b):
 
 # ---- hit sets ---------------------------------------------------------------------------------------------------------------
 # (n, m): one and two groups of 12 motifs (10-bit credits), 16-bit credits (m = 18), the wide buckets (33, 64), several
-# passes / teams (130 x 12)
+# passes (130 x 12; one after the other: teams need a long stream, test_gpu_library_teams.py)
 SHAPES = [(2, 12), (13, 12), (25, 8), (9, 18), (10, 33), (10, 64), (130, 12)]
 
 

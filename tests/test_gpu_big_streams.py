@@ -2,7 +2,8 @@
 but the entry points take an int64 n_pos and must not wrap): the scores and hits of the last 3 M positions -- across the 2^31
 border -- equal the oracle's on that slice (window scores do not depend on what lies before the window: _pwm.c:34-68,
 matrix.py:25-43), and a window planted at the very end is found at its 64-bit position.  Letters side only: a profile of
-that length is 60 GB.  The library form of this test is in test_gpu_library.py."""
+that length is 60 GB -- the structure side, the libraries and the two-stream kernels at this length are in
+test_gpu_past_2_31.py.  The library form of this test is in test_gpu_library.py."""
 import numpy as np
 import pytest
 

@@ -59,7 +59,7 @@
 extern "C" {
 #endif
 
-#define PFMSCAN_ABI_VERSION 18
+#define PFMSCAN_ABI_VERSION 19
 #define PFMSCAN_NCODE   8      /* columns of a letter table */
 #define PFMSCAN_SEP     7      /* separator / foreign-letter code */
 #define PFMSCAN_NSTRUCT 7      /* columns of a structure profile / structure PSSM */
@@ -70,6 +70,7 @@ extern "C" {
                                   profile kernel up to 180 rows and a plain one-thread-per-window kernel beyond -- same results */
 #define PFMSCAN_SITE_GROUP 4096 /* most hits of one group of the site profiles (pfmscan_site_groups) */
 #define PFMSCAN_SITE_LIMBS 66   /* 64-bit limbs of one cell of a long accumulator (pfmscan_site_sums_lib_*) */
+#define PFMSCAN_SITE_JOINT_COLS 64 /* columns of one LDS tile of the letter-pair counts (pfmscan_site_joint_*) */
 
 #define PFMSCAN_OK          0
 #define PFMSCAN_E_BADARG   -1  /* NULL / negative / inconsistent argument   -> ValueError */
@@ -890,6 +891,47 @@ int pfmscan_site_sums_lib_dev(pfmscan_ctx *ctx, const uint8_t *d_codes, const vo
 int pfmscan_site_sums_lib_staged(pfmscan_ctx *ctx, int use_codes, int use_profile, const int64_t *hit_pos, const int32_t *hit_motif,
                                  int64_t n_hits, const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec, int32_t n_motifs,
                                  int32_t m, int32_t flank, uint64_t *acc, uint64_t *counts, int64_t *first_bad);
+
+/* ---- site profiles on letter streams: letter and letter-pair counts under hits ------------------------------------------
+ * The sites of motifs scanned over LETTER strings (`-p seqs.fa`, `-q structs.fa`, `-p -q seqs.fa structs.fa`): the
+ * structure side is a code stream, not a profile, so the site PFM is the reference's own PFM builder on the hit windows --
+ * struct_pfm_from_aligned counts the letters of aligned windows per position (average_structure.py:28-42) and norm_pfm
+ * divides each row by its sum (pfmutil.py:136-151).  With two streams both letters of every position are known, and one
+ * table serves every mode:
+ *   joint  uint64 [n_motifs][W][8][8]      W = m + 2 F <= PFMSCAN_MAX_WIDTH (else PFMSCAN_E_BADSHAPE)
+ *   joint[k][j][a][b] = the number of hits of motif k whose column j counts and has (codes[x] & 7) == a and
+ *                       (codes2[x] & 7) == b,  x = hit_pos - F + j.
+ * "A column counts" is what it is for pfmscan_site_sums_*: row x lies inside the hit's record; a flank column that hangs
+ *   over a record end is skipped and not read.  The code is taken & 7, not min(code, 7): structure streams keep the
+ *   input's case in bit 3 and a lower-case letter counts as its letter (the scores ignore the case, matrix.py:31); index 7
+ *   is a foreign letter inside the record.  A stream that is absent (NULL / not used) has index 0 everywhere.
+ * The marginals are the two count tables (struct_pfm_from_aligned's counts for the second stream), the sum over a column's
+ *   cells its coverage: no second output.  Integer counting is exact and independent of order, so the device adds with
+ *   LDS atomics and 64-bit integer global atomics and the table is a function of the input alone; no float atomics.
+ * Hit list: (hit_pos, hit_motif) over n_motifs motifs of width m; hit_motif NULL: one motif (n_motifs >= 1).  Every
+ *   window [pos, pos + m) lies inside ONE record of the record table rec_off / rec_len (records ascending, each behind
+ *   the separator of the one before, as pfmscan_profile_colsums_*).  A hit's record is found ON THE DEVICE by binary
+ *   search of rec_off: there are no group tables.
+ * _dev: every buffer is a device buffer (d_codes or d_codes2 may be NULL, not both); the list is MOTIF-MAJOR (hit_motif
+ *   does not descend), as for pfmscan_site_sums_lib_dev.  Zeroes d_joint itself.  A position outside the stream, a
+ *   window that leaves its record, a motif index outside [0, n_motifs) or a motif smaller than the one before:
+ *   PFMSCAN_E_BADARG, decided on the device without a load or an add outside the buffers; the table is then not to be
+ *   used.  Asynchronous on `stream` (NULL: the ctx's) except for the verdict: `stream` is synchronised once.  Device
+ *   scratch (8 bytes per workgroup) belongs to the ctx.  A workgroup owns a slice of the list (PFMSCAN_SITE_JOINT_SLICE in
+ *   the environment overrides its length; the table does not depend on it) and counts PFMSCAN_SITE_JOINT_COLS columns at
+ *   a time in LDS.
+ * _staged: the stream that pfmscan_stage (use_codes) and pfmscan_stage_codes2 (use_codes2) left on the device; hits and
+ *   record table on the host, the hits AS pfmscan_library_hits_* RETURN THEM ((position, motif) order; reordered with
+ *   pfmscan_site_order_lib); joint comes home.
+ * There is no pipeline (_host) form: a FASTA code stream is one byte per position and every letter scan stages it anyway,
+ *   so the stream the hits came from is still on the device when they are counted. */
+int pfmscan_site_joint_dev(pfmscan_ctx *ctx, const uint8_t *d_codes, const uint8_t *d_codes2, int64_t n_pos,
+                           const int64_t *d_hit_pos, const int32_t *d_hit_motif, int64_t n_hits, const int64_t *d_rec_off,
+                           const int64_t *d_rec_len, int64_t n_rec, int32_t n_motifs, int32_t m, int32_t flank, uint64_t *d_joint,
+                           void *stream);
+int pfmscan_site_joint_staged(pfmscan_ctx *ctx, int use_codes, int use_codes2, const int64_t *hit_pos, const int32_t *hit_motif,
+                              int64_t n_hits, const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec, int32_t n_motifs,
+                              int32_t m, int32_t flank, uint64_t *joint);
 
 /* ---- host ingest and output (no device needed; no context: errors via pfmscan_last_error(NULL)) ---------------
  * The two pieces of host work that dwarf the kernel at scale, in native code.

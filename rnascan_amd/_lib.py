@@ -22,7 +22,7 @@ NCODE = 8
 NSTRUCT = 7
 MAX_M = 64            # widest PFM of the tuned kernels and of PFM libraries
 MAX_WIDTH = 4096      # widest PFM accepted (wider than MAX_M: the plain rolled-loop kernel)
-ABI_VERSION = 18
+ABI_VERSION = 19
 
 # every symbol include/pfmscan.h declares (checked by tests/test_abi.py)
 SYMBOLS = [
@@ -53,10 +53,12 @@ SYMBOLS = [
     "pfmscan_debug_round3d", "pfmscan_debug_pair_sum_test", "pfmscan_debug_pair_credits",
     "pfmscan_library_hits_letters_sum_dev", "pfmscan_library_hits_letters_sum_host", "pfmscan_library_letters_sum_thresholds",
     "pfmscan_library_last_launches",
+    "pfmscan_site_joint_dev", "pfmscan_site_joint_staged",
 ]
 PAIR_ROUTE_NONE, PAIR_ROUTE_FUSED, PAIR_ROUTE_TWO_PHASE, PAIR_ROUTE_DENSE, PAIR_ROUTE_CREDITS = range(5)   # Context.pair_sum_route()
 SITE_GROUP = 4096     # most hits of one group of the site profiles
 SITE_LIMBS = 66       # 64-bit limbs of one cell of a long accumulator (site profiles of a library)
+SITE_JOINT_COLS = 64  # columns of one LDS tile of the letter-pair counts (PFMSCAN_SITE_JOINT_COLS)
 MAX_COVER = 1024      # largest coverage of a row the averaging accepts
 AVG_OK, AVG_DOTBRACKET, AVG_UNCOVERED, AVG_COVER, AVG_BAD_TABLE = range(5)   # what a rejected averaging names
 TSV_CONST, TSV_I64, TSV_F32, TSV_F64, TSV_INDEXED, TSV_FIXED, TSV_WINDOW, TSV_SPAN = range(8)
@@ -192,6 +194,8 @@ def load():
     L.pfmscan_site_sums_lib_dev.argtypes = [vp, vp, vp, i32, i64, vp, i64, vp, vp, vp, i64, vp, vp, i64, i32, i32, i32, vp, vp,
                                             ctypes.POINTER(i64), vp]
     L.pfmscan_site_sums_lib_staged.argtypes = [vp, i32, i32, vp, vp, i64, vp, vp, i64, i32, i32, i32, vp, vp, ctypes.POINTER(i64)]
+    L.pfmscan_site_joint_dev.argtypes = [vp, vp, vp, i64, vp, vp, i64, vp, vp, i64, i32, i32, i32, vp, vp]
+    L.pfmscan_site_joint_staged.argtypes = [vp, i32, i32, vp, vp, i64, vp, vp, i64, i32, i32, i32, vp]
     L.pfmscan_count_bytes.argtypes = [vp, i64, vp, i32]
     L.pfmscan_place_alloc.argtypes = [vp, i32, vp, vp, i32]
     L.pfmscan_place_free.argtypes = [vp, vp]
@@ -1213,6 +1217,36 @@ class Context(object):
                                                int(n_rec), int(n_motifs), int(m), int(flank), _ptr(addr(d_acc)), _ptr(addr(d_counts)),
                                                ctypes.byref(bad), _ptr(stream))
         self._colsums_check(rc, bad)
+
+    # -- site profiles on letter streams: letter-pair counts under hits (include/pfmscan.h) ---------------------------
+    def site_joint_staged(self, pos, motif, n_motifs, offsets, lengths, m, flank=0, first=True, second=True):
+        """letter-pair counts under the hits (pos, motif) -- as the library scans return them; motif None: one motif -- of
+        the staged code streams -> uint64 [n_motifs][W][8][8]: cell [k][j][a][b] counts the hits of motif k whose column j
+        lies inside the hit's record with code a in the staged codes (``first``) and code b in the staged codes2
+        (``second``), both taken & 7; a stream that is not used has index 0.  ValueError for a hit outside the stream,
+        a window that leaves its record or a motif index that is no motif"""
+        pos = np.ascontiguousarray(pos, dtype=np.int64)
+        if motif is not None:
+            motif = np.ascontiguousarray(motif, dtype=np.int32)
+        if pos.ndim != 1 or (motif is not None and pos.shape != motif.shape):
+            raise ValueError("positions and motifs must be one-dimensional and of the same size")
+        off, ln = self._colsums_tables(offsets, lengths)
+        W, n_motifs = int(m) + 2 * int(flank), int(n_motifs)
+        if n_motifs < 0 or W < 1 or W > MAX_WIDTH:
+            raise ValueError("site joint: a negative number of motifs, or width + 2 x flank outside [1, PFMSCAN_MAX_WIDTH]")
+        joint = np.zeros((n_motifs, W, NCODE, NCODE), dtype=np.uint64)
+        self._check(self._L.pfmscan_site_joint_staged(self._h, int(bool(first)), int(bool(second)), _ptr(pos), _ptr(motif), pos.size,
+                                                      _ptr(off), _ptr(ln), off.size, n_motifs, int(m), int(flank), _ptr(joint)))
+        return joint
+
+    def site_joint_dev(self, d_codes, d_codes2, n_pos, d_pos, d_motif, n_hits, d_offsets, d_lengths, n_rec, n_motifs, m, flank,
+                       d_joint, stream=None):
+        """device buffers (raw addresses or objects with data_ptr(); d_codes, d_codes2 or d_motif may be None): the hit list
+        is motif-major; zeroes d_joint uint64 [n_motifs][W][8][8] itself; asynchronous on `stream` except for the verdict"""
+        addr = lambda a: None if a is None else (a.data_ptr() if hasattr(a, "data_ptr") else a)   # noqa: E731
+        self._check(self._L.pfmscan_site_joint_dev(self._h, _ptr(addr(d_codes)), _ptr(addr(d_codes2)), int(n_pos), _ptr(addr(d_pos)),
+                                                   _ptr(addr(d_motif)), int(n_hits), _ptr(addr(d_offsets)), _ptr(addr(d_lengths)),
+                                                   int(n_rec), int(n_motifs), int(m), int(flank), _ptr(addr(d_joint)), _ptr(stream)))
 
     # -- generic-alphabet letter hits in fp64; two code streams ---------------------------------
     def hits_letters_f64_staged(self, motif, thr, capacity=None):

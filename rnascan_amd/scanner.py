@@ -189,6 +189,25 @@ class HipEngine(object):
         self._stage(stream)
         return self.ctx.site_sums_lib_staged(pos, motif, n_motifs, stream.offsets, stream.lengths, m, flank, letters, profile)
 
+    def site_joint(self, stream, pos, motif, n_motifs, m, flank=0, first=True, second=True):
+        """the letter and letter-pair counts under the hits of EVERY motif of width m over LETTER streams: hits (pos, motif
+        index) as the library scans return them, ``motif=None``: one motif -> uint64 [n_motifs][W][8][8]; cell [k][j][a][b]
+        counts the hits of motif k whose column j lies inside the hit's record and holds code a in ``stream.codes``
+        (``first``) and code b in ``stream.codes2`` (``second``), both & 7 (a lower-case structure letter counts as its
+        letter; 7 is foreign); a stream left out has index 0 (pfmscan_site_joint_staged, include/pfmscan.h).  The marginals
+        are the two count tables, a column's sum its coverage.  Exact integers: batches and ranks simply add.  The stream
+        is staged unless it already is, ``codes2`` included (as ``hits_pair`` does: one staging serves the hits call and
+        this one); there is no pipeline form."""
+        first = bool(first) and stream.codes is not None
+        second = bool(second) and getattr(stream, "codes2", None) is not None
+        if not first and not second:
+            raise ValueError("the stream has neither of the code streams asked for")
+        self._stage(stream)
+        if second and self._staged2 is not stream:
+            self.ctx.stage_codes2(stream.codes2)
+            self._staged2 = stream
+        return self.ctx.site_joint_staged(pos, motif, n_motifs, stream.offsets, stream.lengths, m, flank, first, second)
+
 
 def _library(self, T, P):
     """the device tables of a library (letter tables and / or structure PSSMs), kept across batches until another one is asked for"""

@@ -24,6 +24,14 @@ the number of ranks.  Profile columns are matched to letters by NAME, file by fi
 kernels, and the group rows are not brought home: the GPU adds them per motif into exact integer accumulators
 (``HipEngine.site_sums_library``; 66 limbs of 64 bits per cell, include/pfmscan.h), which are merged over batches and ranks
 and rounded once -- per motif the bits of the ``math.fsum`` above.
+
+FASTA inputs (the last input is a file): ``-p seqs.fa``, ``-q structs.fa``, ``-p -q seqs.fa structs.fa`` and ``-p seqs.fa
+structs.fa`` (the sequence motif's hits with the structure letters under them).  The structure side is then a letter
+string and the site PFM is the reference's own PFM builder on the hit windows: ``struct_pfm_from_aligned`` counts letters
+per position (average_structure.py:28-42), ``norm_pfm`` divides each row by its sum (pfmutil.py:136-151).  The GPU counts
+letter PAIRS per column (``HipEngine.site_joint``: uint64 [n][W][8][8], include/pfmscan.h); the letter counts of either
+stream are the table's marginals, the coverage its column sums, and with two files PREFIX.joint.txt shows which nucleotide
+sits in which structural context.  Integers: batches and ranks add, the bytes do not depend on how the input was cut.
 """
 import argparse
 import math
@@ -249,10 +257,15 @@ def getoptions(argv=None):
     desc = ("Site profiles: the averaged-structure rows (and the nucleotides) under the hits rnascan would report with the same "
             "options, summed over all sites and normalised per position.  Writes PREFIX.struct.txt (structure PFM over "
             "W = width + 2 x flank columns), PREFIX.seq.txt (sequence PFM; only with a FASTA) and PREFIX.counts.txt (raw "
-            "sums, integer counts, coverage and number of sites per column).")
+            "sums, integer counts, coverage and number of sites per column).  On FASTA inputs alone the structure side is a "
+            "letter string: the letters under the hits are counted instead, and with two files PREFIX.joint.txt holds the "
+            "nucleotide x structure letter counts per column.")
     parser = argparse.ArgumentParser(prog="python -m rnascan_amd.sites", description=desc)
     parser.add_argument("inputs", metavar="INPUT", nargs="+",
-                        help="seqs.fa avgdir_or_store/ (with -p), or avgdir_or_store/ alone (with -q only)")
+                        help=("seqs.fa avgdir_or_store/ (with -p), or avgdir_or_store/ alone (with -q only); or FASTA inputs as "
+                              "rnascan takes them: seqs.fa (-p), structs.fa (-q), seqs.fa structs.fa (-p -q, or -p alone: the "
+                              "sequence motif's sites with the structure letters under them), which also write PREFIX.joint.txt "
+                              "(nucleotide x structure letter counts per column) when there are two files"))
     parser.add_argument("-p", "--pfm_seq", dest="pfm_seq", type=str, help="Sequence PFM (the first motif of a multi-PFM file; every motif with --all-motifs)")
     parser.add_argument("-q", "--pfm_struct", dest="pfm_struct", type=str, help="Structure PFM (the first motif of a multi-PFM file; every motif with --all-motifs)")
     parser.add_argument("-C", "--pseudocount", type=float, dest="pseudocount", default=0, help="Pseudocount for normalizing PFM. [%(default)s]")
@@ -273,6 +286,8 @@ def getoptions(argv=None):
     parser.add_argument("-B", "--bg_struct", default=None, dest="bg_struct", help="File of pre-computed background probabilities for structure")
     parser.add_argument("--pairing", choices=["aligned", "positional"], default="aligned", help="as rnascan's [%(default)s]")
     parser.add_argument("--profile-dtype", choices=["auto", "float64", "float32"], default="float64", help="as rnascan's [%(default)s]")
+    parser.add_argument("--struct-format", choices=["auto", "letters", "dotbracket"], default="auto", dest="struct_format",
+                        help="a structure FASTA: as rnascan's, without the fragment formats [%(default)s]")
     parser.add_argument("--device", type=int, default=int(os.environ.get("RNASCAN_DEVICE", "0")), help="HIP device index [%(default)s]")
     parser.add_argument("--gpus", type=int, default=None, help="one process per GPU, records sharded over them, as rnascan's [1]")
     parser.add_argument("-o", "--output", dest="prefix", required=True, metavar="PREFIX", help="prefix of the files written")
@@ -287,10 +302,12 @@ def getoptions(argv=None):
         parser.error("--min-seqstruct: not a number")
     if args.flank < 0:
         parser.error("--flank must be at least 0")
-    if args.pfm_seq and len(args.inputs) != 2:
-        parser.error("with -p give the sequence FASTA and the averaged-structure directory or store")
+    if args.pfm_seq and args.pfm_struct and len(args.inputs) != 2:
+        parser.error("with -p and -q give the sequence FASTA and the averaged-structure directory, store or structure FASTA")
+    if args.pfm_seq and (len(args.inputs) > 2 or (len(args.inputs) == 1 and os.path.isdir(args.inputs[0]))):
+        parser.error("with -p give the sequence FASTA and the averaged-structure directory or store (or FASTA files alone)")
     if not args.pfm_seq and len(args.inputs) != 1:
-        parser.error("with -q alone give the averaged-structure directory or store only")
+        parser.error("with -q alone give the averaged-structure directory or store (or the structure FASTA) only")
     args.fastafiles = list(args.inputs)
     args.testseq, args.bgonly = None, False
     return args
@@ -674,6 +691,354 @@ def write_library(args, results, rank=0):
     return 0
 
 
+# ---------------------------------------------------------------------------
+# FASTA inputs: the structure side is a letter string; letter and letter-pair counts
+# ---------------------------------------------------------------------------
+STRUCT_CODES = [pack.STRUCT_LETTERS.index(c) for c in STRUCT_ORDER]      # code of a structure stream per column of STRUCT_ORDER
+JOINT_NAMES = ["%s.%s" % (a, b) for a in SEQ_ORDER for b in STRUCT_ORDER]  # the 28 known cells: nucleotide major
+
+
+def select_letters(engine, stream, m, seq_tabs, struct_tabs, minscore, min_seqstruct=None):
+    """(pos, motif index) in (position, motif index) order: for every motif (pair) of one width the positions ``rnascan``
+    reports on FASTA inputs with the same options -- the same engine calls under the same conditions as
+    scanner.scan_records (one kind of table: ``seq_tabs`` over the nucleotides of ``stream.codes``, or ``struct_tabs`` over
+    the structure letters of ``stream.codes``) and scanner.scan_pair (both: nucleotides in ``stream.codes``, structure
+    letters in ``stream.codes2``).  The stream is left staged for the counts wherever the call allows it."""
+    from . import _lib, scanner
+    thr = float(minscore)
+    n = len(seq_tabs if seq_tabs is not None else struct_tabs)
+    finite = bool(np.isfinite(thr))
+    if struct_tabs is None:                                    # scan_records, nucleotides
+        if n > 1 and finite and m <= scanner.LIBRARY_MAX_M:
+            pos, mo, _, _ = engine.library_hits(stream, np.stack(seq_tabs), None, thr, one_shot=False)
+            return pos, mo
+        parts = [scanner._select(engine, stream, m, t, None, thr, -np.inf, one_shot=False)[0] for t in seq_tabs]
+    elif seq_tabs is None:                                     # scan_records, a generic alphabet: fp64 scores
+        if n > 1 and finite and m <= scanner.LETTER_LIBRARY_MAX_M and hasattr(engine, "library_hits_letters"):
+            pos, mo, _, _ = engine.library_hits_letters(stream, None, np.stack(struct_tabs), None, thr)
+            return pos, mo
+        parts = [scanner._select_letters_f64(engine, stream, m, t, thr)[0] for t in struct_tabs]
+    else:                                                      # scan_pair
+        on_device = min_seqstruct is not None and hasattr(engine, "hits_pair_sum") and not np.isnan(float(min_seqstruct))
+
+        def kept(pos, mo, sq, st):                             # scan_pair's rows(): keep_seqstruct on the PRINTED sum
+            if min_seqstruct is not None:
+                keep = np.round(sq, 3).astype(np.float64) + _lib.round_decimals(st, 3) > float(min_seqstruct)
+                pos, mo = pos[keep], (None if mo is None else mo[keep])
+            return pos, mo
+
+        if on_device and n > 1 and m <= scanner.LIBRARY_MAX_M and hasattr(engine, "library_hits_letters_sum") and \
+                hasattr(engine, "library_letters_sum_thresholds"):
+            T, S = np.stack(seq_tabs), np.stack(struct_tabs)
+            if np.all(np.isfinite(engine.library_letters_sum_thresholds(T, S, thr, float(min_seqstruct)))):
+                return kept(*engine.library_hits_letters_sum(stream, T, S, thr, thr, float(min_seqstruct)))
+        elif n > 1 and finite and m <= scanner.LIBRARY_MAX_M and hasattr(engine, "library_hits_letters"):
+            return kept(*engine.library_hits_letters(stream, np.stack(seq_tabs), np.stack(struct_tabs), thr, thr))
+        parts = []
+        for tab_seq, tab_st in zip(seq_tabs, struct_tabs):
+            if on_device:
+                pos, sq, st = engine.hits_pair_sum(stream, tab_seq, tab_st, thr, thr, float(min_seqstruct))
+            elif np.isneginf(thr) or not hasattr(engine, "hits_pair"):
+                sq, _ = engine.scan(stream, tab_seq, None)
+                st = engine.scan_letters_f64(pack.Stream(stream.codes2, None, stream.offsets, stream.lengths), tab_st)
+                pos = np.flatnonzero(stream.window_mask(m) & (sq.astype(np.float64) > thr) & (st > thr))
+                sq, st = sq[pos], st[pos]
+            else:
+                pos, sq, st = engine.hits_pair(stream, tab_seq, tab_st, thr, thr)
+            parts.append(kept(pos, None, sq, st)[0])
+    pos = np.concatenate(parts) if parts else np.zeros(0, dtype=np.int64)
+    mo = np.concatenate([np.full(p.size, k, dtype=np.int32) for k, p in enumerate(parts)]) if parts else np.zeros(0, dtype=np.int32)
+    order = np.lexsort((mo, pos))
+    return pos[order], mo[order]
+
+
+class LetterRows(object):
+    """what one rank collected on FASTA inputs for the n motifs (pairs) of one width: joint int64 [n][W][8][8] -- cell
+    [a][b]: nucleotide code a (SEQ_ORDER, 7 foreign), structure code b (pack.STRUCT_LETTERS, 7 foreign); the index of a
+    stream that is absent is 0 -- and hits int64 [n]"""
+
+    def __init__(self, n, W):
+        self.joint = np.zeros((n, W, 8, 8), dtype=np.int64)
+        self.hits = np.zeros(n, dtype=np.int64)
+
+    def add(self, other):
+        self.joint += other.joint
+        self.hits += other.hits
+
+
+def paired_fastas(seq_fasta, struct_fasta):
+    """(LazyFasta of the sequences, LazyFasta of the structure strings) of two files that hold the same ids in the same
+    order, each once, with equal lengths; anything else is an InputError that names the first offending record (the
+    counts need both letters of every position: there is no join fallback here)"""
+    recs, srecs = fasta.open_lazy(seq_fasta), fasta.open_lazy(struct_fasta)
+    ids, sids = list(recs.ids), list(srecs.ids)
+    seen = set()
+    for k, sid in enumerate(ids):
+        if sid in seen:
+            raise InputError("record %s occurs more than once in %s" % (sid, seq_fasta))
+        seen.add(sid)
+        if k >= len(sids):
+            raise InputError("record %s of %s has no record in %s" % (sid, seq_fasta, struct_fasta))
+        if sids[k] != sid:
+            raise InputError("record %s of %s is paired by position with record %s of %s: the two files must hold the same ids "
+                             "in the same order" % (sid, seq_fasta, sids[k], struct_fasta))
+    if len(sids) > len(ids):
+        raise InputError("record %s of %s has no record in %s" % (sids[len(ids)], struct_fasta, seq_fasta))
+    a, b = np.asarray(recs.lengths, dtype=np.int64), np.asarray(srecs.lengths, dtype=np.int64)
+    if not np.array_equal(a, b):
+        r = int(np.flatnonzero(a != b)[0])
+        raise InputError("record %s is %d letters long but its structure string has %d" % (ids[r], int(a[r]), int(b[r])))
+    return recs, srecs
+
+
+def collect_letters(engine, args, seq_pssm, struct_pssm, rank=0, world=1):
+    """this rank's {width: LetterRows} and the pairs of every width [(width, [pair])]: its share of the records, batch by
+    batch, sites selected as rnascan selects its hits (select_letters), counted by ``engine.site_joint``"""
+    from . import scanner
+    from ._lib import MAX_WIDTH
+    two = len(args.fastafiles) == 2
+    if args.all_motifs:
+        pairs = motif_pairs(seq_pssm, struct_pssm)
+    else:
+        a = scanner._first_motif(seq_pssm)[0] if seq_pssm else None
+        b = scanner._first_motif(struct_pssm)[0] if struct_pssm else None
+        if a is not None and b is not None and seq_pssm[a].length != struct_pssm[b].length:
+            raise InputError("the sequence PFM is %d positions wide and the structure PFM %d: they share no site" %
+                             (seq_pssm[a].length, struct_pssm[b].length))
+        pairs = [(a, b)]
+    by_width = {}
+    for a, b in pairs:
+        by_width.setdefault((seq_pssm[a] if a is not None else struct_pssm[b]).length, []).append((a, b))
+    if not by_width:
+        raise InputError("no sequence PFM is as wide as the structure PFM it is paired with: they share no site")
+    for m, group in by_width.items():
+        W = m + 2 * args.flank
+        if W > MAX_WIDTH:
+            raise InputError("width %d + 2 x flank %d exceeds %d columns (PFMSCAN_MAX_WIDTH, include/pfmscan.h)" % (m, args.flank, MAX_WIDTH))
+        if len(group) * W * 64 * 8 > ACC_LIMIT:
+            raise InputError("the %d motifs of width %d need %d bytes of letter-pair counts at --flank %d, more than %d: lower --flank "
+                             "or split the library" % (len(group), m, len(group) * W * 64 * 8, args.flank, ACC_LIMIT))
+    rows = dict((m, LetterRows(len(group), m + 2 * args.flank)) for m, group in by_width.items())
+    if two:
+        recs, srecs = paired_fastas(args.fastafiles[0], args.fastafiles[1])
+    else:
+        recs, srecs = fasta.open_lazy(args.fastafiles[0]), None
+    lengths = recs.lengths
+    lo, hi = shard.partition(lengths, world)[rank]
+    for a, b in (shard.batches(lengths, lo, hi, shard.batch_positions()) if hi > lo else []):
+        if two:
+            sb, tb = scanner._RnaBatch(recs[a:b]), scanner._RnaBatch(srecs[a:b], fasta.STRUCT)
+            if not np.array_equal(sb.lengths, tb.lengths):
+                r = int(np.flatnonzero(sb.lengths != tb.lengths)[0])
+                raise InputError("record %s is %d letters long but its structure string has %d" %
+                                 (sb.ids[r], int(sb.lengths[r]), int(tb.lengths[r])))
+            stream = pack.Stream(sb.codes, None, sb.offsets, sb.lengths, codes2=tb.codes)
+        else:
+            sb = scanner._RnaBatch(recs[a:b], None if seq_pssm else fasta.STRUCT)
+            stream = pack.Stream(sb.codes, None, sb.offsets, sb.lengths)
+        for m, group in by_width.items():
+            tabs = [seq_pssm[x].letter_table(pack.RNA_LETTERS) for x, _ in group] if seq_pssm else None
+            stabs = [struct_pssm[y].letter_table(fasta.STRUCT) for _, y in group] if struct_pssm else None
+            pos, mo = select_letters(engine, stream, m, tabs, stabs, args.minscore, args.min_seqstruct)
+            if pos.size == 0:
+                continue
+            n = len(group)
+            J = engine.site_joint(stream, pos, None if n == 1 else mo, n, m, args.flank, first=True, second=two).astype(np.int64)
+            if not two and not seq_pssm:                       # the one stream holds the structure letters
+                J = J.transpose(0, 1, 3, 2)
+            rows[m].joint += J
+            rows[m].hits += np.bincount(mo, minlength=n).astype(np.int64)
+    return rows, list(by_width.items())
+
+
+def gather_letters(engine, args, seq_pssm, struct_pssm, rank=0, world=1, dist=None):
+    """``collect_letters`` on this rank, the ranks' integer tables exchanged once and added -> [(pair, joint int64
+    [W][8][8], hits)] in pair order, the same on every rank; failures are handed over as in ``combine``"""
+    rows, groups, failure = None, None, None
+    try:
+        rows, groups = collect_letters(engine, args, seq_pssm, struct_pssm, rank, world)
+    except Exception as e:
+        if world == 1:
+            raise
+        failure = e
+    if world > 1:
+        shares = [None] * world
+        dist.all_gather_object(shares, (None if failure is None else _portable(failure), rows))
+        for bad, _ in shares:
+            if bad is not None:
+                raise bad
+        rows = shares[0][1]
+        for _, other in shares[1:]:
+            for m in rows:
+                rows[m].add(other[m])
+    out = []
+    for m, group in groups:
+        for k, pair in enumerate(group):
+            out.append((pair, rows[m].joint[k], int(rows[m].hits[k])))
+    if args.all_motifs:
+        order = dict((pair, i) for i, pair in enumerate(motif_pairs(seq_pssm, struct_pssm)))
+        out.sort(key=lambda x: order[x[0]])
+    return out
+
+
+def letter_tables(J, has_seq, has_struct):
+    """joint int64 [W][8][8] -> (S float64 [W][7] in STRUCT_ORDER | None: the structure letter counts, as float64 for
+    ``site_pfms``; nucleotide counts int64 [W][8] | None; structure counts int64 [W][8] by code | None; coverage int64 [W])"""
+    seq_counts = J.sum(axis=2) if has_seq else None
+    struct_counts = J.sum(axis=1) if has_struct else None
+    S = struct_counts[:, STRUCT_CODES].astype(np.float64) if has_struct else None
+    return S, seq_counts, struct_counts, J.sum(axis=(1, 2))
+
+
+def mutual_information(cells):
+    """the mutual information, in bits, of a column's 4 x 7 table of known cells (Python ints): math.fsum of
+    p_ab log2(p_ab / (p_a p_b)) over the non-zero cells, p = counts / their total; 0.0 for an empty column"""
+    total = sum(sum(row) for row in cells)
+    if total == 0:
+        return 0.0
+    pa = [sum(row) / total for row in cells]
+    pb = [sum(row[b] for row in cells) / total for b in range(len(cells[0]))]
+    return math.fsum((c / total) * math.log2((c / total) / (pa[a] * pb[b]))
+                     for a, row in enumerate(cells) for b, c in enumerate(row) if c)
+
+
+def _letter_counts_to(out, seq_counts, struct_counts, cov, hits):
+    """PREFIX.counts.txt on FASTA inputs: coverage and the integer letter counts of the streams present (N / X = foreign)"""
+    from . import table
+    names = ["PO", "Sites", "Coverage"]
+    cols = {"PO": np.arange(cov.size, dtype=np.int64), "Sites": np.full(cov.size, hits, dtype=np.int64), "Coverage": np.ascontiguousarray(cov)}
+    if seq_counts is not None:
+        for k, c in enumerate(SEQ_ORDER):
+            names.append("Count." + c)
+            cols["Count." + c] = np.ascontiguousarray(seq_counts[:, k])
+        names.append("Count.N")
+        cols["Count.N"] = seq_counts[:, len(SEQ_ORDER):].sum(axis=1)
+    if struct_counts is not None:
+        for k, c in zip(STRUCT_CODES, STRUCT_ORDER):
+            names.append("Count." + c)
+            cols["Count." + c] = np.ascontiguousarray(struct_counts[:, k])
+        names.append("Count.X")
+        cols["Count.X"] = np.ascontiguousarray(struct_counts[:, 7])
+    w = table.TsvWriter(out, names, match_id=False)
+    w.write_chunk(cols, cov.size)
+    w.close()
+
+
+def _joint_to(out, J):
+    """PREFIX.joint.txt: per column the 28 known cells A.B A.E ... U.T (nucleotide major, STRUCT_ORDER minor) and MI"""
+    from . import table
+    known = J[:, :len(SEQ_ORDER)][:, :, STRUCT_CODES]
+    cols = {"PO": np.arange(J.shape[0], dtype=np.int64)}
+    for i, name in enumerate(JOINT_NAMES):
+        cols[name] = np.ascontiguousarray(known[:, i // len(STRUCT_ORDER), i % len(STRUCT_ORDER)])
+    cols["MI"] = np.asarray([mutual_information(known[j].tolist()) for j in range(J.shape[0])], dtype=np.float64)
+    w = table.TsvWriter(out, ["PO"] + JOINT_NAMES + ["MI"], match_id=False)
+    w.write_chunk(cols, J.shape[0])
+    w.close()
+
+
+def _report_foreign(prefix, seq_counts, struct_counts):
+    for counts, first, what, pfm in ((seq_counts, len(SEQ_ORDER), "letters", "sequence"), (struct_counts, 7, "structure characters", "structure")):
+        if counts is None:
+            continue
+        foreign = counts[:, first:].sum(axis=1)
+        if int(foreign.sum()):
+            msg = "foreign %s under the sites, left out of the %s PFM: %d (per column: %s)" % \
+                (what, pfm, int(foreign.sum()), " ".join(str(int(x)) for x in foreign))
+            fasta.eprint(prefix + msg if prefix else msg[0].upper() + msg[1:])
+
+
+def write_letters(args, results, has_seq, has_struct, rank=0):
+    """the files of the FASTA route (.struct.txt / .seq.txt for the streams present, .joint.txt with both, .counts.txt).
+    With --all-motifs a motif without a site or with a column that cannot be normalised is named on stderr and left out
+    of the PFM files, as ``write_library`` does; for one motif either is the run's failure.  -> exit code"""
+    import io
+    if not args.all_motifs:
+        _, J, hits = results[0]
+        fasta.eprint("Found %d sites" % hits)
+        if hits == 0:
+            fasta.eprint("No site passes the thresholds: nothing to profile, no files written")
+            return 1
+        S, seq_counts, struct_counts, cov = letter_tables(J, has_seq, has_struct)
+        struct, seq, _ = site_pfms(S, seq_counts)
+        _report_foreign("", seq_counts, struct_counts)
+        if rank == 0:
+            if struct is not None:
+                write_pfm(args.prefix + ".struct.txt", STRUCT_ORDER, struct)
+            if seq is not None:
+                write_pfm(args.prefix + ".seq.txt", SEQ_ORDER, seq)
+            if has_seq and has_struct:
+                with open(args.prefix + ".joint.txt", "w") as out:
+                    _joint_to(out, J)
+            with open(args.prefix + ".counts.txt", "w") as out:
+                _letter_counts_to(out, seq_counts, struct_counts, cov, hits)
+        return 0
+    texts = dict((suffix, io.StringIO()) for suffix in (".struct.txt", ".seq.txt", ".joint.txt", ".counts.txt"))
+    written = 0
+
+    def tagged(text, name, one):                               # a leading Motif column
+        lines = one.getvalue().splitlines(True)
+        if not text.tell():
+            text.write("Motif\t" + lines[0])
+        for ln in lines[1:]:
+            text.write(name + "\t" + ln)
+
+    for (a, b), J, hits in results:
+        name = pair_id(a, b)
+        S, seq_counts, struct_counts, cov = letter_tables(J, has_seq, has_struct)
+        one = io.StringIO()
+        _letter_counts_to(one, seq_counts, struct_counts, cov, hits)
+        tagged(texts[".counts.txt"], name, one)
+        if has_seq and has_struct:
+            one = io.StringIO()
+            _joint_to(one, J)
+            tagged(texts[".joint.txt"], name, one)
+        if hits == 0:
+            fasta.eprint("Motif %s: no site passes the thresholds, left out" % name)
+            continue
+        try:
+            struct, seq, _ = site_pfms(S, seq_counts)
+        except InputError as e:
+            fasta.eprint("Motif %s: %s, left out" % (name, e))
+            continue
+        _report_foreign("Motif %s: " % name, seq_counts, struct_counts)
+        for suffix, letters, matrix in ((".struct.txt", STRUCT_ORDER, struct), (".seq.txt", SEQ_ORDER, seq)):
+            if matrix is not None:
+                texts[suffix].write("#%s\n#" % name)
+                _pfm_to(texts[suffix], letters, matrix)
+                texts[suffix].write("\n")
+        written += 1
+    fasta.eprint("Wrote the site profiles of %d of %d motifs" % (written, len(results)))
+    if written == 0:
+        fasta.eprint("No motif has a site profile: no files written")
+        return 1
+    if rank == 0:
+        for suffix, text in texts.items():
+            if text.tell():
+                with open(args.prefix + suffix, "w") as out:
+                    out.write(text.getvalue())
+    return 0
+
+
+def main_letters(engine, args, rank=0, world=1, dist=None):
+    """the FASTA route of ``main``: inputs and backgrounds as cli.main takes them for the same command line"""
+    from . import cli
+    two = len(args.fastafiles) == 2
+    if two and (not os.path.isfile(args.fastafiles[0]) or not args.pfm_seq):
+        raise InputError("with two FASTA files give the sequence FASTA first and its PFM with -p (a structure PFM with -q is optional)")
+    # a dot-bracket structure FASTA is annotated first and replaced by its letters (cli.struct_input)
+    cli.struct_input(args, "RNASS" if two else ("RNA" if args.pfm_seq else "SS"), None, lambda: engine)
+    seq_pssm = struct_pssm = None
+    if args.pfm_seq:
+        bg = fasta.load_background(args.bg_seq, args.uniform_background, args.fastafiles[0], fasta.RNA, True)
+        seq_pssm = cli.load_motif(args.pfm_seq, args.pseudocount, fasta.RNA, bg)
+    if args.pfm_struct:
+        bg = fasta.load_background(args.bg_struct, args.uniform_background, args.fastafiles[-1], fasta.STRUCT, True)
+        struct_pssm = cli.load_motif(args.pfm_struct, args.pseudocount, fasta.STRUCT, bg)
+    results = gather_letters(engine, args, seq_pssm, struct_pssm, rank, world, dist)
+    return write_letters(args, results, has_seq=bool(args.pfm_seq), has_struct=two or not args.pfm_seq, rank=rank)
+
+
 def main(argv=None, engine=None):
     from . import background, cli, scanner
     args = getoptions(argv)
@@ -693,6 +1058,11 @@ def main(argv=None, engine=None):
     try:
         seq_pssm = struct_pssm = None
         source = args.fastafiles[-1]
+        if os.path.isfile(source):                 # FASTA inputs: letter strings (a directory takes the route below)
+            rc = main_letters(engine, args, rank, world, dist)
+            if dist is not None:
+                dist.barrier()
+            return rc
         if not os.path.isdir(source):
             raise InputError("%s is neither a directory of structure.<id>.txt files nor a packed profile store" % source)
         if args.pfm_seq:

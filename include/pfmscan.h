@@ -59,7 +59,7 @@
 extern "C" {
 #endif
 
-#define PFMSCAN_ABI_VERSION 19
+#define PFMSCAN_ABI_VERSION 20
 #define PFMSCAN_NCODE   8      /* columns of a letter table */
 #define PFMSCAN_SEP     7      /* separator / foreign-letter code */
 #define PFMSCAN_NSTRUCT 7      /* columns of a structure profile / structure PSSM */
@@ -1079,6 +1079,55 @@ int pfmscan_place_alloc(pfmscan_ctx *ctx, int n_arrays, const int64_t *bytes, vo
 int pfmscan_place_free(pfmscan_ctx *ctx, void *first_array);
 int pfmscan_place_trim(pfmscan_ctx *ctx);
 const char *pfmscan_place_note(const pfmscan_ctx *ctx);
+
+/* ---- in-silico mutagenesis: every single-letter change scored in one pass -------------------------------------
+ * No counterpart in the reference: it would write a mutated FASTA and scan again (pssm.search, rnascan.py:263), once per
+ * variant.  Over a packed RNA stream (codes 0..3 = A, C, G, U; anything >= 4 is foreign here, whatever the table holds in
+ * columns 4..7) and the letters part T [m][8] of a motif, m <= PFMSCAN_MAX_M:
+ *   score(s | p->a)  the value pfmscan_scan_dev would write at window s if codes[p] were a: 0.0 (double), += T[k][code(s+k)]
+ *                    for k ascending, every addition rounded, then (float) (_pwm.c:34-68); NaN when the window holds a
+ *                    foreign code or a separator, or runs past n_pos
+ *   cover(p)         the starts s with max(0, p-m+1) <= s <= min(p, n_pos-m)
+ *   best[p][a]       the greatest non-NaN score(s | p->a) over cover(p), compared as float32, reported bit for bit; ties go
+ *                    to the LOWEST start; where[p][a] = p - s of that window; no non-NaN window: NaN and -1.  Column
+ *                    a = codes[p] is the unmutated best ("ref").  A position whose code is >= 4 has NaN / -1 in all four
+ *                    columns: a foreign letter cannot be substituted, a separator is never bridged.
+ * pfmscan_mutmap_dev writes d_best float [n_pos][4] and, unless NULL, d_where int8 [n_pos][4] (16-byte aligned device
+ * pointers); asynchronous on `stream` (NULL = the ctx's), never synchronises.  pfmscan_mutmap_staged: the same over the
+ * stream staged by pfmscan_stage, HOST outputs, synchronises.
+ * A motif without a letters part, or wider than PFMSCAN_MAX_M, is PFMSCAN_E_BADSHAPE; a NULL that is not allowed
+ * PFMSCAN_E_BADARG. */
+int pfmscan_mutmap_dev(pfmscan_ctx *ctx, const pfmscan_motif *motif, const uint8_t *d_codes, int64_t n_pos,
+                       float *d_best, int8_t *d_where, void *stream);
+int pfmscan_mutmap_staged(pfmscan_ctx *ctx, const pfmscan_motif *motif, float *best, int8_t *where);
+/* Only the changes that create or destroy a site at threshold thr leave the device: for a != codes[p]
+ *   gain <=> best[p][a] > thr and not best[p][ref] > thr;   loss <=> the reverse        (strict compares of the float32 with
+ *   the double thr, as score > minscore everywhere in this header: NaN and -inf never pass; a NaN thr is PFMSCAN_E_BADARG)
+ * An event is key = 4 p + a, the ref best and the alt best (its kind follows from the two).  _dev appends in no particular
+ * order: d_ev_key int64 [capacity], d_ev_ref / d_ev_alt float [capacity], d_ev_count one uint64 the caller zeroes, afterwards
+ * the TOTAL number of events (only the first `capacity` are stored), as pfmscan_hits_dev; asynchronous, never synchronises.
+ * _staged returns them sorted by key; PFMSCAN_E_CAPACITY: *n_events holds the capacity that suffices, nothing was written
+ * to the event arrays (as pfmscan_hits_host). */
+int pfmscan_mutmap_events_dev(pfmscan_ctx *ctx, const pfmscan_motif *motif, const uint8_t *d_codes, int64_t n_pos,
+                              double thr, int64_t capacity, int64_t *d_ev_key, float *d_ev_ref, float *d_ev_alt,
+                              uint64_t *d_ev_count, void *stream);
+int pfmscan_mutmap_events_staged(pfmscan_ctx *ctx, const pfmscan_motif *motif, double thr, int64_t capacity,
+                                 int64_t *ev_key, float *ev_ref, float *ev_alt, int64_t *n_events);
+/* A list of n_var variants (position, alt letter) x n_motifs letter tables of one width m (HOST double [n_motifs][m][8] as in
+ * pfmscan_library_create; the call uploads them onto `stream` into scratch of the ctx).  For variant v and motif q:
+ *   ref[v][q] = best[pos][codes[pos]], alt[v][q] = best[pos][alt] of motif q's map above, ref_where / alt_where their `where`
+ *   (either may be NULL).  alt == codes[pos] is allowed (the ref columns twice).  A variant whose position holds a code >= 4,
+ *   lies outside [0, n_pos) or has alt > 3 gets NaN / -1 for every motif and reads nothing out of bounds.
+ * d_var_pos int64 [n_var], d_var_alt uint8 [n_var], d_ref / d_alt float [n_var][n_motifs], the where arrays int8 of the same
+ * shape: device pointers for _dev (asynchronous, never synchronises; libraries that do not fit the LDS at once run as motif
+ * chunks of one launch), host pointers and the staged stream for _staged.  NULL letter_tables or m outside
+ * 1 .. PFMSCAN_MAX_M: PFMSCAN_E_BADSHAPE. */
+int pfmscan_variants_dev(pfmscan_ctx *ctx, const double *letter_tables, int n_motifs, int m, const uint8_t *d_codes,
+                         int64_t n_pos, const int64_t *d_var_pos, const uint8_t *d_var_alt, int64_t n_var,
+                         float *d_ref, float *d_alt, int8_t *d_ref_where, int8_t *d_alt_where, void *stream);
+int pfmscan_variants_staged(pfmscan_ctx *ctx, const double *letter_tables, int n_motifs, int m,
+                            const int64_t *var_pos, const uint8_t *var_alt, int64_t n_var, float *ref, float *alt,
+                            int8_t *ref_where, int8_t *alt_where);
 
 #ifdef __cplusplus
 }

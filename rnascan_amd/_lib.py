@@ -22,7 +22,7 @@ NCODE = 8
 NSTRUCT = 7
 MAX_M = 64            # widest PFM of the tuned kernels and of PFM libraries
 MAX_WIDTH = 4096      # widest PFM accepted (wider than MAX_M: the plain rolled-loop kernel)
-ABI_VERSION = 19
+ABI_VERSION = 20
 
 # every symbol include/pfmscan.h declares (checked by tests/test_abi.py)
 SYMBOLS = [
@@ -54,6 +54,8 @@ SYMBOLS = [
     "pfmscan_library_hits_letters_sum_dev", "pfmscan_library_hits_letters_sum_host", "pfmscan_library_letters_sum_thresholds",
     "pfmscan_library_last_launches",
     "pfmscan_site_joint_dev", "pfmscan_site_joint_staged",
+    "pfmscan_mutmap_dev", "pfmscan_mutmap_staged", "pfmscan_mutmap_events_dev", "pfmscan_mutmap_events_staged",
+    "pfmscan_variants_dev", "pfmscan_variants_staged",
 ]
 PAIR_ROUTE_NONE, PAIR_ROUTE_FUSED, PAIR_ROUTE_TWO_PHASE, PAIR_ROUTE_DENSE, PAIR_ROUTE_CREDITS = range(5)   # Context.pair_sum_route()
 SITE_GROUP = 4096     # most hits of one group of the site profiles
@@ -227,6 +229,12 @@ def load():
     L.pfmscan_library_letters_sum_thresholds.argtypes = [vp, vp, i32, i32, vp, vp, vp]
     L.pfmscan_debug_pair_credits.argtypes = [vp, vp, i32, dbl, vp, vp] + [ctypes.POINTER(dbl)] * 4 + [ctypes.POINTER(i32)]
     L.pfmscan_debug_pair_sum_test.argtypes = [vp, vp, i64, dbl, vp, vp, ctypes.POINTER(dbl)]
+    L.pfmscan_mutmap_dev.argtypes = [vp, vp, vp, i64, vp, vp, vp]
+    L.pfmscan_mutmap_staged.argtypes = [vp, vp, vp, vp]
+    L.pfmscan_mutmap_events_dev.argtypes = [vp, vp, vp, i64, dbl, i64, vp, vp, vp, vp, vp]
+    L.pfmscan_mutmap_events_staged.argtypes = [vp, vp, dbl, i64, vp, vp, vp, ctypes.POINTER(i64)]
+    L.pfmscan_variants_dev.argtypes = [vp, vp, i32, i32, vp, i64, vp, vp, i64, vp, vp, vp, vp, vp]
+    L.pfmscan_variants_staged.argtypes = [vp, vp, i32, i32, vp, vp, i64, vp, vp, vp, vp]
     L.pfmscan_tsv_format.argtypes = [ctypes.POINTER(TsvColumn), i32, i64, i64, vp, i64, ctypes.POINTER(i64), vp, ctypes.POINTER(i32), i32]
     for name in SYMBOLS:          # every other entry point returns a status
         if name not in ("pfmscan_ctx_destroy", "pfmscan_motif_destroy", "pfmscan_last_error", "pfmscan_library_destroy",
@@ -1580,6 +1588,74 @@ class Context(object):
                                                       int(profile_dtype), int(n_pos), float(thr_seq), float(thr_struct),
                                                       int(capacity), _ptr(d_hit_pos), _ptr(d_hit_seq), _ptr(d_hit_struct),
                                                       _ptr(d_hit_count), _ptr(stream)))
+
+    # -- in-silico mutagenesis (include/pfmscan.h: pfmscan_mutmap_*, pfmscan_variants_*) --------------------
+    def mutmap_dev(self, motif, d_codes, n_pos, d_best, d_where=None, stream=None):
+        self._check(self._L.pfmscan_mutmap_dev(self._h, motif._h, _ptr(d_codes), int(n_pos), _ptr(d_best), _ptr(d_where), _ptr(stream)))
+
+    def mutmap_staged(self, motif, where=True):
+        """best float32 [n_pos][4] (and where int8 [n_pos][4], or None) of the staged codes"""
+        n = int(self._L.pfmscan_staged_positions(self._h))
+        if n < 0:
+            raise ValueError("no stream staged (call stage first)")
+        best = np.empty((n, 4), dtype=np.float32)
+        wh = np.empty((n, 4), dtype=np.int8) if where else None
+        self._check(self._L.pfmscan_mutmap_staged(self._h, motif._h, _ptr(best), _ptr(wh)))
+        return best, wh
+
+    def mutmap_events_dev(self, motif, d_codes, n_pos, thr, capacity, d_ev_key, d_ev_ref, d_ev_alt, d_ev_count, stream=None):
+        self._check(self._L.pfmscan_mutmap_events_dev(self._h, motif._h, _ptr(d_codes), int(n_pos), float(thr), int(capacity),
+                                                      _ptr(d_ev_key), _ptr(d_ev_ref), _ptr(d_ev_alt), _ptr(d_ev_count), _ptr(stream)))
+
+    def mutmap_events_staged(self, motif, thr, capacity=None):
+        """gain / loss events of the staged codes at thr -> (key int64[k] = 4 p + a sorted, ref float32[k], alt float32[k])"""
+        n = int(self._L.pfmscan_staged_positions(self._h))
+        if n < 0:
+            raise ValueError("no stream staged (call stage first)")
+        cap = int(capacity) if capacity is not None else max(1024, n // 16)
+        while True:
+            key = np.empty(cap, dtype=np.int64)
+            ref = np.empty(cap, dtype=np.float32)
+            alt = np.empty(cap, dtype=np.float32)
+            k = ctypes.c_int64(0)
+            rc = self._L.pfmscan_mutmap_events_staged(self._h, motif._h, float(thr), cap, _ptr(key), _ptr(ref), _ptr(alt), ctypes.byref(k))
+            if rc == E_CAPACITY and capacity is None:
+                cap = int(k.value)
+                continue
+            self._check(rc, k.value)
+            k = int(k.value)
+            return key[:k].copy(), ref[:k].copy(), alt[:k].copy()
+
+    @staticmethod
+    def _variant_tables(letter_tables):
+        lt = np.ascontiguousarray(letter_tables, dtype=np.float64)
+        if lt.ndim == 2:
+            lt = lt[None]
+        if lt.ndim != 3 or lt.shape[2] != NCODE:
+            raise ValueError("letter_tables must be [n_motifs][m][8]")
+        return lt
+
+    def variants_dev(self, letter_tables, d_codes, n_pos, d_var_pos, d_var_alt, n_var, d_ref, d_alt, d_ref_where=None,
+                     d_alt_where=None, stream=None):
+        lt = self._variant_tables(letter_tables)
+        self._check(self._L.pfmscan_variants_dev(self._h, _ptr(lt), lt.shape[0], lt.shape[1], _ptr(d_codes), int(n_pos), _ptr(d_var_pos),
+                                                 _ptr(d_var_alt), int(n_var), _ptr(d_ref), _ptr(d_alt), _ptr(d_ref_where),
+                                                 _ptr(d_alt_where), _ptr(stream)))
+
+    def variants_staged(self, letter_tables, pos, alt, where=True):
+        """-> ref, alt float32 [n_var][n_motifs], ref_where, alt_where int8 (or None) over the staged codes"""
+        lt = self._variant_tables(letter_tables)
+        pos = np.ascontiguousarray(pos, dtype=np.int64)
+        alt = np.ascontiguousarray(alt, dtype=np.uint8)
+        if pos.ndim != 1 or pos.shape != alt.shape:
+            raise ValueError("pos and alt must be lists of one length")
+        shape = (pos.size, lt.shape[0])
+        ref_s, alt_s = np.empty(shape, dtype=np.float32), np.empty(shape, dtype=np.float32)
+        ref_w = np.empty(shape, dtype=np.int8) if where else None
+        alt_w = np.empty(shape, dtype=np.int8) if where else None
+        self._check(self._L.pfmscan_variants_staged(self._h, _ptr(lt), lt.shape[0], lt.shape[1], _ptr(pos), _ptr(alt), pos.size,
+                                                    _ptr(ref_s), _ptr(alt_s), _ptr(ref_w), _ptr(alt_w)))
+        return ref_s, alt_s, ref_w, alt_w
 
     def time_scan_dev(self, motif, d_codes, d_profile, profile_dtype, n_pos, d_out_seq, d_out_struct,
                       stream=None, warmup=1, iters=5):

@@ -120,7 +120,8 @@ void pfmscan_ctx_destroy(pfmscan_ctx *ctx)
                       &ctx->pipe_profile[0], &ctx->pipe_profile[1], &ctx->codes2, &ctx->db_in, &ctx->db_out,
                       &ctx->db_tree, &ctx->db_part, &ctx->db_marks, &ctx->db_tiles, &ctx->db_flags,
                       &ctx->avg_tab, &ctx->avg_blk, &ctx->avg_out, &ctx->bg_tab, &ctx->bg_part, &ctx->bg_blk, &ctx->bg_sums, &ctx->rb_part,
-                      &ctx->site_tab, &ctx->site_blk, &ctx->site_sums, &ctx->site_counts})
+                      &ctx->site_tab, &ctx->site_blk, &ctx->site_sums, &ctx->site_counts,
+                      &ctx->mut_tab, &ctx->mut_best, &ctx->mut_alt, &ctx->mut_where, &ctx->mut_key, &ctx->mut_valt})
         release(*b);
     upload_release(ctx);
     place_release_all(ctx);

@@ -53,6 +53,7 @@ struct pfmscan_ctx {
     DevBuf bg_tab, bg_part, bg_blk, bg_sums;    // profile column sums (pfmscan_background.hip): record tables, piece sums, verdicts, record sums
     DevBuf site_tab, site_blk, site_sums, site_counts;   // site profiles (pfmscan_sites.hip): hit / group / record tables, verdict keys, group sums, group counts
     DevBuf rb_part;                             // profile row bound (pfmscan_rowbound.hip): workgroup partials + the result
+    DevBuf mut_tab, mut_best, mut_alt, mut_where, mut_key, mut_valt;   // mutagenesis (pfmscan_mutation.hip): a call's tables, staged outputs, event / variant lists
     DevBuf pipe_codes[2], pipe_profile[2];      // chunked host pipeline: double-buffered chunk of the stream
     hipEvent_t pipe_copied[2] = {nullptr, nullptr}, pipe_scanned[2] = {nullptr, nullptr};
     // host ranges known to be read-only mappings of files (pfmscan_upload_source_file): the staged uploader preads them

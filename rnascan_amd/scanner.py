@@ -131,6 +131,27 @@ class HipEngine(object):
         self._stage(stream)
         return self.ctx.hits_staged(motif, thr_seq, thr_struct)
 
+    def mutmap(self, stream, letter_table, where=True):
+        """in-silico mutagenesis of the stream's codes: best float32 [n_pos][4] = for every position and
+        letter the greatest score over the windows that cover the position if it held that letter (column codes[p]: the
+        unmutated best), and where int8 [n_pos][4] = position minus that window's start (None when not asked for)"""
+        motif = self._motif(letter_table, None)
+        self._stage(stream)
+        return self.ctx.mutmap_staged(motif, where)
+
+    def mutmap_events(self, stream, letter_table, thr):
+        """the single-letter changes that create or destroy a site at thr, decided on the device ->
+        (key int64 = 4 * position + alt letter, sorted; ref best float32; alt best float32)"""
+        motif = self._motif(letter_table, None)
+        self._stage(stream)
+        return self.ctx.mutmap_events_staged(motif, thr)
+
+    def variants(self, stream, letter_tables, pos, alt):
+        """a list of variants (stream position, alt letter 0..3) x letter tables [n_motifs][m][8] of one width ->
+        (ref float32 [n_var][n_motifs], alt, ref_where int8, alt_where)"""
+        self._stage(stream)
+        return self.ctx.variants_staged(letter_tables, pos, alt)
+
     def hits_sum(self, stream, letter_table, struct_pssm, thr_seq, thr_struct, thr_sum, one_shot=True):
         """``hits`` of a motif with both parts, with the joint threshold decided on the device: a window is kept iff
         seq > thr_seq AND struct > thr_struct AND float64(round(float32 seq, 3)) + struct > thr_sum -- the printed

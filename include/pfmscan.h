@@ -59,7 +59,7 @@
 extern "C" {
 #endif
 
-#define PFMSCAN_ABI_VERSION 20
+#define PFMSCAN_ABI_VERSION 21
 #define PFMSCAN_NCODE   8      /* columns of a letter table */
 #define PFMSCAN_SEP     7      /* separator / foreign-letter code */
 #define PFMSCAN_NSTRUCT 7      /* columns of a structure profile / structure PSSM */
@@ -1128,6 +1128,39 @@ int pfmscan_variants_dev(pfmscan_ctx *ctx, const double *letter_tables, int n_mo
 int pfmscan_variants_staged(pfmscan_ctx *ctx, const double *letter_tables, int n_motifs, int m,
                             const int64_t *var_pos, const uint8_t *var_alt, int64_t n_var, float *ref, float *alt,
                             int8_t *ref_where, int8_t *alt_where);
+
+/* ---- occupancy: the summed likelihood ratio of every record under every motif ------------------------------------
+ * No counterpart in the reference.  Threshold-free: a records x motifs matrix instead of a table of hits.
+ *   R [m][8]      ratio table of a motif of width m <= PFMSCAN_MAX_M over n_letters letters (4: RNA codes 0..3, 7:
+ *                 structure-letter codes 0..6).  For a letter with normalised background b > 0 and normalised, pseudocounted
+ *                 probability p: R = p / b if that quotient is > 0, else +0.0 (the cell whose log-odds is -inf); for b == 0:
+ *                 +inf if p > 0, else NaN -- the operands of the log-odds cell before its log.  Columns >= n_letters are NaN
+ *                 and never read.  Every cell is +0.0, positive, +inf or NaN; never negative, never -0.0.
+ *   term(s)       t = R[0][c_0], then t = t * R[k][c_k] for k = 1 .. m-1, every product rounded to double, never fused with
+ *                 the addition that follows; c_k = codes[s + k] & 7 (a lower-case structure letter carries bit 3 and counts
+ *                 as its letter).  A window that holds a code >= n_letters has NO term: it adds +0.0 and is not counted.
+ *                 Otherwise IEEE as it falls: subnormals stay, 0 x inf is NaN, NaN and +inf poison / saturate the sum.
+ *   occ[r][q]     the terms of record r's n_win = max(L - m + 1, 0) windows in order (skipped ones as +0.0), summed in a
+ *                 left-aligned tree of fan-in PFMSCAN_OCC_FANIN: element j of level l+1 is a[32 j], then + a[32 j + 1], ...
+ *                 over the children that exist, sequential, ascending, each rounded; until one value is left; n_win = 0
+ *                 gives +0.0.  The tree is anchored at the record's first window: the bits do not depend on where the
+ *                 record lies in the stream, on the batch or on the launch geometry.
+ *   windows[r]    the number of windows of record r that have a term (width and codes only, not the motif).
+ * ratio_tables: HOST double [n_motifs][m][8], uploaded into scratch of the ctx by the call.  Records: rec_off / rec_len
+ * int64 [n_rec], ascending and disjoint inside [0, n_pos) (else PFMSCAN_E_BADARG); occ double [n_rec][n_motifs]; windows
+ * int64 [n_rec] or NULL.  pfmscan_occupancy_dev: device pointers (d_codes 16-byte aligned), on the ctx's stream; it reads
+ * the record table back and checks it before anything is launched (one synchronisation), then returns without waiting for
+ * the kernels (pfmscan_synchronize).  pfmscan_occupancy_staged: the stream left by pfmscan_stage (which = 0) or
+ * pfmscan_stage_codes2 (which = 1), HOST record table and outputs, synchronises.  Device scratch for the partial sums is
+ * bounded (256 MB of block sums, or one motif's block sums of the longest record if that is more): records, then motifs,
+ * run in passes.  m outside 1 .. PFMSCAN_MAX_M: PFMSCAN_E_BADSHAPE; n_letters not 4 or 7, a NULL that is needed:
+ * PFMSCAN_E_BADARG; n_rec == 0 or n_motifs == 0: PFMSCAN_OK, nothing written. */
+#define PFMSCAN_OCC_FANIN 32
+int pfmscan_occupancy_dev(pfmscan_ctx *ctx, const double *ratio_tables, int n_motifs, int m, int n_letters,
+                          const uint8_t *d_codes, int64_t n_pos, const int64_t *d_rec_off, const int64_t *d_rec_len,
+                          int64_t n_rec, double *d_occ, int64_t *d_windows);
+int pfmscan_occupancy_staged(pfmscan_ctx *ctx, int which, const double *ratio_tables, int n_motifs, int m, int n_letters,
+                             const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec, double *occ, int64_t *windows);
 
 #ifdef __cplusplus
 }

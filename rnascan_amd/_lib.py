@@ -22,7 +22,7 @@ NCODE = 8
 NSTRUCT = 7
 MAX_M = 64            # widest PFM of the tuned kernels and of PFM libraries
 MAX_WIDTH = 4096      # widest PFM accepted (wider than MAX_M: the plain rolled-loop kernel)
-ABI_VERSION = 20
+ABI_VERSION = 21
 
 # every symbol include/pfmscan.h declares (checked by tests/test_abi.py)
 SYMBOLS = [
@@ -56,11 +56,13 @@ SYMBOLS = [
     "pfmscan_site_joint_dev", "pfmscan_site_joint_staged",
     "pfmscan_mutmap_dev", "pfmscan_mutmap_staged", "pfmscan_mutmap_events_dev", "pfmscan_mutmap_events_staged",
     "pfmscan_variants_dev", "pfmscan_variants_staged",
+    "pfmscan_occupancy_dev", "pfmscan_occupancy_staged",
 ]
 PAIR_ROUTE_NONE, PAIR_ROUTE_FUSED, PAIR_ROUTE_TWO_PHASE, PAIR_ROUTE_DENSE, PAIR_ROUTE_CREDITS = range(5)   # Context.pair_sum_route()
 SITE_GROUP = 4096     # most hits of one group of the site profiles
 SITE_LIMBS = 66       # 64-bit limbs of one cell of a long accumulator (site profiles of a library)
 SITE_JOINT_COLS = 64  # columns of one LDS tile of the letter-pair counts (PFMSCAN_SITE_JOINT_COLS)
+OCC_FANIN = 32        # fan-in of the occupancy's summation tree (PFMSCAN_OCC_FANIN)
 MAX_COVER = 1024      # largest coverage of a row the averaging accepts
 AVG_OK, AVG_DOTBRACKET, AVG_UNCOVERED, AVG_COVER, AVG_BAD_TABLE = range(5)   # what a rejected averaging names
 TSV_CONST, TSV_I64, TSV_F32, TSV_F64, TSV_INDEXED, TSV_FIXED, TSV_WINDOW, TSV_SPAN = range(8)
@@ -235,6 +237,8 @@ def load():
     L.pfmscan_mutmap_events_staged.argtypes = [vp, vp, dbl, i64, vp, vp, vp, ctypes.POINTER(i64)]
     L.pfmscan_variants_dev.argtypes = [vp, vp, i32, i32, vp, i64, vp, vp, i64, vp, vp, vp, vp, vp]
     L.pfmscan_variants_staged.argtypes = [vp, vp, i32, i32, vp, vp, i64, vp, vp, vp, vp]
+    L.pfmscan_occupancy_dev.argtypes = [vp, vp, i32, i32, i32, vp, i64, vp, vp, i64, vp, vp]
+    L.pfmscan_occupancy_staged.argtypes = [vp, i32, vp, i32, i32, i32, vp, vp, i64, vp, vp]
     L.pfmscan_tsv_format.argtypes = [ctypes.POINTER(TsvColumn), i32, i64, i64, vp, i64, ctypes.POINTER(i64), vp, ctypes.POINTER(i32), i32]
     for name in SYMBOLS:          # every other entry point returns a status
         if name not in ("pfmscan_ctx_destroy", "pfmscan_motif_destroy", "pfmscan_last_error", "pfmscan_library_destroy",
@@ -1656,6 +1660,34 @@ class Context(object):
         self._check(self._L.pfmscan_variants_staged(self._h, _ptr(lt), lt.shape[0], lt.shape[1], _ptr(pos), _ptr(alt), pos.size,
                                                     _ptr(ref_s), _ptr(alt_s), _ptr(ref_w), _ptr(alt_w)))
         return ref_s, alt_s, ref_w, alt_w
+
+    # -- occupancy (include/pfmscan.h: pfmscan_occupancy_*) ------------------------------------------------
+    @staticmethod
+    def _ratio_tables(ratio_tables):
+        rt = np.ascontiguousarray(ratio_tables, dtype=np.float64)
+        if rt.ndim == 2:
+            rt = rt[None]
+        if rt.ndim != 3 or rt.shape[2] != NCODE:
+            raise ValueError("ratio_tables must be [n_motifs][m][8]")
+        return rt
+
+    def occupancy_dev(self, ratio_tables, n_letters, d_codes, n_pos, d_rec_off, d_rec_len, n_rec, d_occ, d_windows=None):
+        rt = self._ratio_tables(ratio_tables)
+        self._check(self._L.pfmscan_occupancy_dev(self._h, _ptr(rt), rt.shape[0], rt.shape[1], int(n_letters), _ptr(d_codes), int(n_pos),
+                                                  _ptr(d_rec_off), _ptr(d_rec_len), int(n_rec), _ptr(d_occ), _ptr(d_windows)))
+
+    def occupancy_staged(self, ratio_tables, n_letters, rec_off, rec_len, which=0):
+        """-> occ float64 [n_rec][n_motifs], windows int64 [n_rec] over the staged codes (which = 0) or codes2 (1)"""
+        rt = self._ratio_tables(ratio_tables)
+        rec_off = np.ascontiguousarray(rec_off, dtype=np.int64)
+        rec_len = np.ascontiguousarray(rec_len, dtype=np.int64)
+        if rec_off.ndim != 1 or rec_off.shape != rec_len.shape:
+            raise ValueError("rec_off and rec_len must be lists of one length")
+        occ = np.zeros((rec_off.size, rt.shape[0]), dtype=np.float64)
+        windows = np.zeros(rec_off.size, dtype=np.int64)
+        self._check(self._L.pfmscan_occupancy_staged(self._h, int(which), _ptr(rt), rt.shape[0], rt.shape[1], int(n_letters), _ptr(rec_off),
+                                                     _ptr(rec_len), rec_off.size, _ptr(occ), _ptr(windows)))
+        return occ, windows
 
     def time_scan_dev(self, motif, d_codes, d_profile, profile_dtype, n_pos, d_out_seq, d_out_struct,
                       stream=None, warmup=1, iters=5):

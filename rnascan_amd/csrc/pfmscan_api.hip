@@ -121,7 +121,8 @@ void pfmscan_ctx_destroy(pfmscan_ctx *ctx)
                       &ctx->db_tree, &ctx->db_part, &ctx->db_marks, &ctx->db_tiles, &ctx->db_flags,
                       &ctx->avg_tab, &ctx->avg_blk, &ctx->avg_out, &ctx->bg_tab, &ctx->bg_part, &ctx->bg_blk, &ctx->bg_sums, &ctx->rb_part,
                       &ctx->site_tab, &ctx->site_blk, &ctx->site_sums, &ctx->site_counts,
-                      &ctx->mut_tab, &ctx->mut_best, &ctx->mut_alt, &ctx->mut_where, &ctx->mut_key, &ctx->mut_valt})
+                      &ctx->mut_tab, &ctx->mut_best, &ctx->mut_alt, &ctx->mut_where, &ctx->mut_key, &ctx->mut_valt,
+                      &ctx->occ_tab, &ctx->occ_idx, &ctx->occ_rec, &ctx->occ_bs, &ctx->occ_gs, &ctx->occ_cnt, &ctx->occ_out})
         release(*b);
     upload_release(ctx);
     place_release_all(ctx);

@@ -54,6 +54,7 @@ struct pfmscan_ctx {
     DevBuf site_tab, site_blk, site_sums, site_counts;   // site profiles (pfmscan_sites.hip): hit / group / record tables, verdict keys, group sums, group counts
     DevBuf rb_part;                             // profile row bound (pfmscan_rowbound.hip): workgroup partials + the result
     DevBuf mut_tab, mut_best, mut_alt, mut_where, mut_key, mut_valt;   // mutagenesis (pfmscan_mutation.hip): a call's tables, staged outputs, event / variant lists
+    DevBuf occ_tab, occ_idx, occ_rec, occ_bs, occ_gs, occ_cnt, occ_out;   // occupancy (pfmscan_occupancy.hip): ratio tables, block / group prefixes, record table, block and level-1 sums, window counts, staged outputs
     DevBuf pipe_codes[2], pipe_profile[2];      // chunked host pipeline: double-buffered chunk of the stream
     hipEvent_t pipe_copied[2] = {nullptr, nullptr}, pipe_scanned[2] = {nullptr, nullptr};
     // host ranges known to be read-only mappings of files (pfmscan_upload_source_file): the staged uploader preads them

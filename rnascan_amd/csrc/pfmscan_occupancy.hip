@@ -1,0 +1,448 @@
+// pfmscan_occupancy.hip -- occupancy: the summed likelihood ratio of every record under every motif.
+//
+// R [m][8] holds the motif's odds ratios p / b (pssm.odds): +0.0, positive, +inf or NaN, never negative.  The term of window s
+// is t = R[0][c_0], then t = t * R[k][c_k] for k ascending, every product rounded to double (c_k = codes[s + k] & 7); a window
+// that holds a code >= n_letters has no term.  The occupancy of a record is the sum of its n_win = max(L - m + 1, 0) terms
+// (skipped windows as +0.0) in a left-aligned tree of fan-in PFMSCAN_OCC_FANIN = 32 anchored at the record's first window:
+// element j of the next level is a[32 j], + a[32 j + 1], ... over the children that exist, sequential and each rounded.  No
+// transcendental, no atomics, no tolerance: tests/occupancy_rules.py restates it in numpy and the bits are compared.
+//
+//   k_occ_blocks<QN>   level 0.  A lane owns one (record, block of 32 consecutive windows) and walks the windows serially for
+//                      QN = 8, 4, 2 or 1 motifs at a time: 0.0 + t_0 + t_1 ... is the definition's sum (x + +0.0 == x for
+//                      every value a term can take, so a skipped window adds nothing).  The block's 32 + m - 1 codes sit in
+//                      a lane-private strip of LDS an odd number of dwords wide (aligned dwords as loaded, foreign codes
+//                      zeroed and kept as a 128-bit mask in registers: no register array is indexed at run time); the
+//                      ratio tables of a chunk of motifs sit in LDS transposed [row][letter][motif], so one letter serves
+//                      QN adjacent motifs with 16-byte reads.
+//   k_occ_level1       level 1: a thread adds the <= 32 block sums of one (group of 32 blocks, motif), in order.
+//   k_occ_finish       levels 2 and up: a thread per (record, motif) folds the record's level-1 sums in place, in order, and
+//                      writes the cell.  One writer per cell.
+// The block sums go through scratch that is bounded (OCC_SCRATCH_DOUBLES) by running the records, and if one record alone is
+// too long the motifs, in passes.
+#include <algorithm>
+#include <cstdlib>
+#include <string>
+#include <vector>
+
+#include "pfmscan_ctx.hpp"
+#include "pfmscan_device.hpp"
+
+#pragma clang fp contract(off)   // the product chain and the sums are rounded one operation at a time: never an FMA
+
+namespace pfmscan {
+
+constexpr int OCC_FANIN = PFMSCAN_OCC_FANIN;
+// table cells of one chunk of motifs, padding included (occ_chunk).  Measured: 256 motifs of w = 12 at C2 size take 70.4 ms
+// with 2048, 74.8 with 4096, 72.1 with 1024 (profiles/occupancy/NOTES.md)
+constexpr int OCC_LDS_DOUBLES = 2048;
+static_assert(OCC_LDS_DOUBLES >= PFMSCAN_MAX_M * PFMSCAN_NSTRUCT, "one motif of the widest kind fits");
+constexpr int OCC_CODE_DWORDS = 25;                   // aligned dwords that cover 3 + 32 + PFMSCAN_MAX_M - 1 bytes
+constexpr int64_t OCC_SCRATCH_DOUBLES = int64_t(1) << 25;   // block sums of one pass (256 MB); PFMSCAN_OCC_SCRATCH_DOUBLES overrides
+static_assert(OCC_FANIN == 32, "a block is the 32 windows one lane walks; the masks below are 32 bits wide");
+static_assert(OCC_CODE_DWORDS * 4 >= 3 + OCC_FANIN + PFMSCAN_MAX_M - 1, "strip");
+
+struct OccArgs {
+    const uint8_t *codes;        // [n_pos]
+    int64_t n_pos;
+    const int64_t *rec_off, *rec_len;   // [n_rec]
+    const int64_t *blk_start;    // [n_rec + 1] prefix of ceil(n_win / 32)
+    const int64_t *grp_start;    // [n_rec + 1] prefix of ceil(blocks / 32)
+    int64_t r0, r1;              // records of this pass
+    int64_t blk_base, n_blk;     // blk_start[r0], blocks of the pass
+    int64_t grp_base, n_grp;
+    const double *tables;        // [n_motifs][m][8] device
+    int m, n_letters;
+    int q_first, n_q;            // motifs of this pass (n_q = row stride of the scratch)
+    int chunk;                   // motifs per LDS chunk (gridDim.y chunks)
+    int n_motifs;
+    double *bs;                  // [n_blk][n_q] block sums
+    double *gs;                  // [n_grp][n_q] level-1 sums, folded in place by k_occ_finish
+    int *bcnt;                   // [n_blk] windows with a term, or null
+    int *gcnt;                   // [n_grp]
+    double *occ;                 // [n_rec][n_motifs]
+    int64_t *windows;            // [n_rec] or null
+};
+
+// dwords of a lane's strip of codes: the aligned dwords that cover 3 + 32 + m - 1 bytes, made odd so that the byte reads of
+// the 32 lanes of a group fall on 32 banks
+__host__ __device__ inline int occ_strip(int m) { return ((3 + OCC_FANIN + m - 1 + 3) / 4) | 1; }
+
+__host__ __device__ inline int occ_ls(int nq, int qn)
+{
+    int ls = (nq + qn - 1) / qn * qn;
+    return ls % 16 == 0 ? ls + 2 : ls;                // the letters of a row must not all start on one bank
+}
+
+// the record of element e of a prefix table: the last r in [r0, r1) with start[r] <= e (start[r1] > e)
+__device__ __forceinline__ int64_t occ_record(const int64_t *__restrict__ start, int64_t r0, int64_t r1, int64_t e)
+{
+    int64_t lo = r0 + 1, hi = r1;
+    while (lo < hi) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        if (start[mid] > e) hi = mid;
+        else lo = mid + 1;
+    }
+    return lo - 1;
+}
+
+// QN adjacent motifs' cells of one (row, letter): 16-byte reads (ls is even and q a multiple of QN)
+template <int QN>
+__device__ __forceinline__ void occ_cells(const double *p, double (&v)[QN])
+{
+    if constexpr (QN == 1) {
+        v[0] = p[0];
+    } else {
+#pragma unroll
+        for (int i = 0; i < QN; i += 2) {
+            const double2 x = *reinterpret_cast<const double2 *>(p + i);
+            v[i] = x.x;
+            v[i + 1] = x.y;
+        }
+    }
+}
+
+template <int QN>
+__global__ __launch_bounds__(BLOCK) void k_occ_blocks(const OccArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char occ_lds[];
+    const int m = a.m, nl = a.n_letters;
+    const int cs = occ_strip(m);                                   // dwords per lane strip
+    uint32_t *cw = reinterpret_cast<uint32_t *>(occ_lds);          // [BLOCK][cs]
+    double *lt = reinterpret_cast<double *>(occ_lds + (size_t)BLOCK * cs * 4);   // [m][n_letters][ls]; BLOCK * 4 is a multiple of 16
+    const int qc = (int)blockIdx.y * a.chunk;                      // first motif of the chunk, within the pass
+    const int nq = min(a.chunk, a.n_q - qc);
+    const int ls = occ_ls(a.chunk, QN);
+    for (int i = threadIdx.x; i < m * nl * ls; i += BLOCK) {
+        const int r = i / ls, q = i - r * ls;                      // r = row * n_letters + letter
+        const int row = r / nl, c = r - row * nl;
+        lt[i] = q < nq ? a.tables[((int64_t)(a.q_first + qc + q) * m + row) * 8 + c] : 0.0;
+    }
+    // this lane's block: its codes as aligned dwords into the lane's strip, foreign codes zeroed and remembered
+    const int64_t gb = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    uint32_t valid = 0;                                            // bit w: window w of the block has a term
+    int sh = 0;
+    if (gb < a.n_blk) {
+        const int64_t b = a.blk_base + gb;
+        const int64_t r = occ_record(a.blk_start, a.r0, a.r1, b);
+        const int64_t w0 = (b - a.blk_start[r]) * OCC_FANIN;
+        const int64_t left = a.rec_len[r] - m + 1 - w0;            // >= 1: the block exists
+        const int nw = (int)min((int64_t)OCC_FANIN, left);
+        const int need = nw + m - 1;                               // codes of the block, all inside the record
+        const int64_t s0 = a.rec_off[r] + w0;
+        sh = (int)(s0 & 3);
+        const int64_t base = s0 - sh;
+        unsigned long long f0 = 0, f1 = 0;                         // bit i: code i of the block is foreign or not the block's
+        uint32_t *mine = cw + threadIdx.x * cs;
+#pragma unroll
+        for (int i = 0; i < OCC_CODE_DWORDS; ++i) {
+            const int64_t p = base + 4 * i;
+            uint32_t dw = 0;
+            if (4 * i - sh < need) {
+                if (p + 4 <= a.n_pos) dw = *reinterpret_cast<const uint32_t *>(a.codes + p);   // the base pointer is 16-byte aligned
+                else
+                    for (int j = 0; j < 4; ++j)
+                        if (p + j < a.n_pos) dw |= (uint32_t)a.codes[p + j] << (8 * j);
+            }
+            uint32_t out = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int idx = 4 * i + j - sh;                    // -3 .. 99
+                const uint32_t c = (dw >> (8 * j)) & 7u;
+                const bool bad = idx >= need || (int)c >= nl;
+                if (idx >= 0) {
+                    if (idx < 64) f0 |= (unsigned long long)bad << idx;
+                    else f1 |= (unsigned long long)bad << (idx - 64);
+                }
+                out |= (bad ? 0u : c) << (8 * j);
+            }
+            if (i < cs) mine[i] = out;                             // beyond: no code of a block of this width (4 i - sh >= need)
+        }
+        const unsigned long long wmask = m == 64 ? ~0ull : (1ull << m) - 1;
+        for (int w = 0; w < OCC_FANIN; ++w) {
+            const unsigned long long win = w ? (f0 >> w) | (f1 << (64 - w)) : f0;
+            valid |= (uint32_t)((win & wmask) == 0) << w;          // w >= nw: code w + m - 1 >= need is marked
+        }
+        if (a.bcnt && blockIdx.y == 0) a.bcnt[gb] = __popc(valid);
+    }
+    __syncthreads();                                               // the last barrier
+    if (gb >= a.n_blk) return;
+    const uint8_t *cb = reinterpret_cast<const uint8_t *>(cw + threadIdx.x * cs) + sh;
+    const int rs = nl * ls;                                        // doubles per table row
+    double *out = a.bs + gb * a.n_q + qc;
+    if (valid == 0) {                                              // no window with a term: +0.0 without walking the block
+        for (int q = 0; q < nq; ++q) out[q] = 0.0;
+        return;
+    }
+    for (int q = 0; q < nq; q += QN) {
+        double sum[QN];
+#pragma unroll
+        for (int i = 0; i < QN; ++i) sum[i] = 0.0;
+#pragma unroll 1
+        for (int w = 0; w < OCC_FANIN; ++w) {
+            const uint8_t *cp = cb + w;
+            const double *row = lt + q;
+            double t[QN];
+            occ_cells<QN>(row + (int)cp[0] * ls, t);
+#pragma unroll 4
+            for (int k = 1; k < m; ++k) {
+                row += rs;
+                double c[QN];
+                occ_cells<QN>(row + (int)cp[k] * ls, c);
+#pragma unroll
+                for (int i = 0; i < QN; ++i) t[i] = t[i] * c[i];
+            }
+            const bool has = (valid >> w) & 1u;
+#pragma unroll
+            for (int i = 0; i < QN; ++i) sum[i] = sum[i] + (has ? t[i] : 0.0);
+        }
+#pragma unroll
+        for (int i = 0; i < QN; ++i)
+            if (q + i < nq) out[q + i] = sum[i];
+    }
+}
+
+__global__ __launch_bounds__(BLOCK) void k_occ_level1(const OccArgs a)
+{
+    const int64_t t = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (t >= a.n_grp * a.n_q) return;
+    const int64_t gg = t / a.n_q;
+    const int q = (int)(t - gg * a.n_q);
+    const int64_t g = a.grp_base + gg;
+    const int64_t r = occ_record(a.grp_start, a.r0, a.r1, g);
+    const int64_t first = (g - a.grp_start[r]) * OCC_FANIN;        // first block of the group, within the record
+    const int n = (int)min((int64_t)OCC_FANIN, a.blk_start[r + 1] - a.blk_start[r] - first);
+    const int64_t b0 = a.blk_start[r] - a.blk_base + first;
+    const double *in = a.bs + b0 * a.n_q + q;
+    double s = in[0];
+    for (int i = 1; i < n; ++i) s = s + in[(int64_t)i * a.n_q];
+    a.gs[gg * a.n_q + q] = s;
+    if (a.bcnt && q == 0) {
+        int c = 0;
+        for (int i = 0; i < n; ++i) c += a.bcnt[b0 + i];
+        a.gcnt[gg] = c;
+    }
+}
+
+__global__ __launch_bounds__(BLOCK) void k_occ_finish(const OccArgs a)
+{
+    const int64_t t = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (t >= (a.r1 - a.r0) * a.n_q) return;
+    const int64_t rr = t / a.n_q;
+    const int q = (int)(t - rr * a.n_q);
+    const int64_t r = a.r0 + rr;
+    const int64_t g0 = a.grp_start[r] - a.grp_base;
+    int64_t n = a.grp_start[r + 1] - a.grp_start[r];
+    double res = 0.0;                                              // n_win == 0
+    if (n > 0) {
+        double *x = a.gs + g0 * a.n_q + q;                         // element i at x[i * n_q]; level l + 1 overwrites the front of level l
+        while (n > 1) {
+            const int64_t no = (n + OCC_FANIN - 1) / OCC_FANIN;
+            for (int64_t j = 0; j < no; ++j) {
+                const int64_t c0 = j * OCC_FANIN, c1 = min(n, c0 + OCC_FANIN);
+                double s = x[c0 * a.n_q];
+                for (int64_t i = c0 + 1; i < c1; ++i) s = s + x[i * a.n_q];
+                x[j * a.n_q] = s;                                  // j <= c0: read before it is overwritten, by this thread alone
+            }
+            n = no;
+        }
+        res = x[0];
+    }
+    a.occ[r * a.n_motifs + a.q_first + q] = res;
+    if (a.windows && a.bcnt && q == 0) {
+        int64_t c = 0;
+        const int64_t ng = a.grp_start[r + 1] - a.grp_start[r];
+        for (int64_t i = 0; i < ng; ++i) c += a.gcnt[g0 + i];
+        a.windows[r] = c;
+    }
+}
+
+static int occ_qn(int nq) { return nq >= 8 ? 8 : nq >= 4 ? 4 : nq >= 2 ? 2 : 1; }
+
+
+// motifs per LDS chunk: the most (up to n_q) whose padded tables fit OCC_LDS_DOUBLES; one motif always fits
+static int occ_chunk(int m, int n_letters, int n_q)
+{
+    int c = std::max(1, std::min(n_q, OCC_LDS_DOUBLES / (m * n_letters)));
+    while (c > 1 && m * n_letters * occ_ls(c, occ_qn(c)) > OCC_LDS_DOUBLES) --c;
+    return c;
+}
+
+static hipError_t occ_launch_blocks(const OccArgs &a, hipStream_t st)
+{
+    const int qn = occ_qn(a.chunk);
+    const size_t lds = (size_t)BLOCK * occ_strip(a.m) * 4 + (size_t)a.m * a.n_letters * occ_ls(a.chunk, qn) * sizeof(double);
+    const dim3 grid((unsigned)((a.n_blk + BLOCK - 1) / BLOCK), (unsigned)((a.n_q + a.chunk - 1) / a.chunk));
+    if (qn == 8) hipLaunchKernelGGL(k_occ_blocks<8>, grid, dim3(BLOCK), lds, st, a);
+    else if (qn == 4) hipLaunchKernelGGL(k_occ_blocks<4>, grid, dim3(BLOCK), lds, st, a);
+    else if (qn == 2) hipLaunchKernelGGL(k_occ_blocks<2>, grid, dim3(BLOCK), lds, st, a);
+    else hipLaunchKernelGGL(k_occ_blocks<1>, grid, dim3(BLOCK), lds, st, a);
+    return hipGetLastError();
+}
+
+// rec_off / rec_len: HOST copies, already checked; d_rec_off / d_rec_len: the same on the device.  Launches on st, does not wait.
+static int occ_run(pfmscan_ctx *ctx, const char *who, const double *ratio_tables, int n_motifs, int m, int n_letters, const uint8_t *d_codes,
+                   int64_t n_pos, const int64_t *rec_off, const int64_t *rec_len, const int64_t *d_rec_off, const int64_t *d_rec_len,
+                   int64_t n_rec, double *d_occ, int64_t *d_windows, hipStream_t st)
+{
+    std::vector<int64_t> start(2 * (size_t)(n_rec + 1));
+    int64_t *blk = start.data(), *grp = blk + n_rec + 1;
+    int64_t max_blk = 0;
+    blk[0] = grp[0] = 0;
+    for (int64_t r = 0; r < n_rec; ++r) {
+        const int64_t nw = std::max<int64_t>(rec_len[r] - m + 1, 0), nb = (nw + OCC_FANIN - 1) / OCC_FANIN;
+        blk[r + 1] = blk[r] + nb;
+        grp[r + 1] = grp[r] + (nb + OCC_FANIN - 1) / OCC_FANIN;
+        max_blk = std::max(max_blk, nb);
+    }
+    int64_t cap = OCC_SCRATCH_DOUBLES;
+    if (const char *e = std::getenv("PFMSCAN_OCC_SCRATCH_DOUBLES")) cap = std::max<int64_t>(1, std::atoll(e));
+    // motifs per pass: all of them unless the longest record's block sums alone pass the cap; then records per pass
+    const int n_q_max = (int)std::min<int64_t>(n_motifs, std::max<int64_t>(1, cap / std::max<int64_t>(max_blk, 1)));
+    const int64_t blk_cap = std::max<int64_t>(cap / n_q_max, 1), rec_cap = std::max<int64_t>((int64_t(1) << 30) / n_q_max, 1);
+    std::vector<int64_t> cuts(1, 0);
+    int64_t need_blk = 0, need_grp = 0;
+    for (int64_t r0 = 0; r0 < n_rec;) {
+        int64_t r1 = r0 + 1;
+        while (r1 < n_rec && r1 - r0 < rec_cap && blk[r1 + 1] - blk[r0] <= blk_cap) ++r1;
+        cuts.push_back(r1);
+        need_blk = std::max(need_blk, blk[r1] - blk[r0]);
+        need_grp = std::max(need_grp, grp[r1] - grp[r0]);
+        r0 = r1;
+    }
+    if ((need_blk + BLOCK - 1) / BLOCK > 0x7FFFFFFF) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": a record is too long for one call");
+    int rc;
+    const size_t tab_bytes = (size_t)n_motifs * m * 8 * sizeof(double);
+    if ((rc = ensure(ctx, ctx->occ_tab, tab_bytes))) return rc;
+    if ((rc = ensure(ctx, ctx->occ_idx, start.size() * 8))) return rc;
+    if ((rc = ensure(ctx, ctx->occ_bs, std::max<size_t>((size_t)need_blk * n_q_max * 8, 16)))) return rc;
+    if ((rc = ensure(ctx, ctx->occ_gs, std::max<size_t>((size_t)need_grp * n_q_max * 8, 16)))) return rc;
+    if ((rc = ensure(ctx, ctx->occ_cnt, std::max<size_t>((size_t)(need_blk + need_grp) * 4, 16)))) return rc;
+    if ((rc = upload(ctx, ctx->occ_tab.p, ratio_tables, tab_bytes, st))) return rc;
+    if ((rc = upload(ctx, ctx->occ_idx.p, start.data(), start.size() * 8, st))) return rc;
+    OccArgs a{};
+    a.codes = d_codes;
+    a.n_pos = n_pos;
+    a.rec_off = d_rec_off;
+    a.rec_len = d_rec_len;
+    a.blk_start = (const int64_t *)ctx->occ_idx.p;
+    a.grp_start = a.blk_start + n_rec + 1;
+    a.tables = (const double *)ctx->occ_tab.p;
+    a.m = m;
+    a.n_letters = n_letters;
+    a.n_motifs = n_motifs;
+    a.bs = (double *)ctx->occ_bs.p;
+    a.gs = (double *)ctx->occ_gs.p;
+    a.occ = d_occ;
+    a.windows = d_windows;
+    for (int q0 = 0; q0 < n_motifs; q0 += n_q_max) {
+        a.q_first = q0;
+        a.n_q = std::min(n_q_max, n_motifs - q0);
+        a.chunk = occ_chunk(m, n_letters, a.n_q);
+        if ((a.n_q + a.chunk - 1) / a.chunk > 65535) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": too many motifs for one call");
+        const bool count = d_windows && q0 == 0;                   // Windows does not depend on the motif: counted in the first pass
+        for (size_t i = 0; i + 1 < cuts.size(); ++i) {
+            a.r0 = cuts[i];
+            a.r1 = cuts[i + 1];
+            a.blk_base = blk[a.r0];
+            a.n_blk = blk[a.r1] - a.blk_base;
+            a.grp_base = grp[a.r0];
+            a.n_grp = grp[a.r1] - a.grp_base;
+            a.bcnt = count ? (int *)ctx->occ_cnt.p : nullptr;
+            a.gcnt = count ? a.bcnt + need_blk : nullptr;
+            hipError_t e = hipSuccess;
+            if (a.n_blk > 0) {
+                e = occ_launch_blocks(a, st);
+                if (e != hipSuccess) return fail_hip(ctx, e, "k_occ_blocks");
+                hipLaunchKernelGGL(k_occ_level1, dim3((unsigned)((a.n_grp * a.n_q + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, a);
+                if ((e = hipGetLastError()) != hipSuccess) return fail_hip(ctx, e, "k_occ_level1");
+            }
+            hipLaunchKernelGGL(k_occ_finish, dim3((unsigned)(((a.r1 - a.r0) * a.n_q + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, a);
+            if ((e = hipGetLastError()) != hipSuccess) return fail_hip(ctx, e, "k_occ_finish");
+        }
+    }
+    return PFMSCAN_OK;
+}
+
+static int occ_check(pfmscan_ctx *ctx, const char *who, const double *ratio_tables, int n_motifs, int m, int n_letters, int64_t n_pos, int64_t n_rec)
+{
+    if (!ctx) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": NULL ctx");
+    if (m < 1 || m > PFMSCAN_MAX_M)
+        return fail(ctx, PFMSCAN_E_BADSHAPE, std::string(who) + ": width " + std::to_string(m) + " outside 1 .. PFMSCAN_MAX_M (" + std::to_string(PFMSCAN_MAX_M) + ")");
+    if (n_letters != 4 && n_letters != PFMSCAN_NSTRUCT) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": n_letters must be 4 or 7");
+    if (n_motifs < 0 || n_rec < 0 || n_pos < 0) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": negative size");
+    if (n_motifs > 0 && !ratio_tables) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": ratio_tables is NULL");
+    return PFMSCAN_OK;
+}
+
+// ascending, disjoint, inside [0, n_pos)
+static int occ_check_records(pfmscan_ctx *ctx, const char *who, const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec, int64_t n_pos)
+{
+    int64_t end = 0;
+    for (int64_t r = 0; r < n_rec; ++r) {
+        if (rec_len[r] < 0 || rec_off[r] < end || rec_len[r] > n_pos - rec_off[r])
+            return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": record " + std::to_string(r) + " does not ascend or leaves the stream");
+        end = rec_off[r] + rec_len[r];
+    }
+    return PFMSCAN_OK;
+}
+
+}  // namespace pfmscan
+
+using namespace pfmscan;
+
+extern "C" {
+
+int pfmscan_occupancy_dev(pfmscan_ctx *ctx, const double *ratio_tables, int n_motifs, int m, int n_letters, const uint8_t *d_codes,
+                          int64_t n_pos, const int64_t *d_rec_off, const int64_t *d_rec_len, int64_t n_rec, double *d_occ,
+                          int64_t *d_windows)
+{
+    const char *who = "pfmscan_occupancy_dev";
+    if (int rc = occ_check(ctx, who, ratio_tables, n_motifs, m, n_letters, n_pos, n_rec)) return rc;
+    if (n_rec == 0 || n_motifs == 0) return PFMSCAN_OK;
+    if (!d_rec_off || !d_rec_len || !d_occ || (n_pos > 0 && !d_codes)) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": NULL record table, codes or output");
+    if (misaligned(d_codes)) return fail(ctx, PFMSCAN_E_BADSHAPE, std::string(who) + ": stream base pointers must be 16-byte aligned");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // the record table decides every address the kernels form: it is read back and checked before anything is launched
+    std::vector<int64_t> rec(2 * (size_t)n_rec);
+    HIP_TRY(ctx, hipMemcpyAsync(rec.data(), d_rec_off, (size_t)n_rec * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(rec.data() + n_rec, d_rec_len, (size_t)n_rec * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (int rc = occ_check_records(ctx, who, rec.data(), rec.data() + n_rec, n_rec, n_pos)) return rc;
+    return occ_run(ctx, who, ratio_tables, n_motifs, m, n_letters, d_codes, n_pos, rec.data(), rec.data() + n_rec, d_rec_off, d_rec_len, n_rec,
+                   d_occ, d_windows, ctx->stream);
+}
+
+int pfmscan_occupancy_staged(pfmscan_ctx *ctx, int which, const double *ratio_tables, int n_motifs, int m, int n_letters,
+                             const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec, double *occ, int64_t *windows)
+{
+    const char *who = "pfmscan_occupancy_staged";
+    if (!ctx) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": NULL ctx");
+    if (which != 0 && which != 1) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": which must be 0 (codes) or 1 (codes2)");
+    if (ctx->staged_n < 0) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": no stream staged (call pfmscan_stage first)");
+    if (ctx->staged_n > 0 && !(which ? ctx->staged_codes2 : ctx->staged_codes))
+        return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + (which ? ": no codes2 are staged (pfmscan_stage_codes2)" : ": no codes are staged"));
+    const int64_t n_pos = ctx->staged_n;
+    if (int rc = occ_check(ctx, who, ratio_tables, n_motifs, m, n_letters, n_pos, n_rec)) return rc;
+    if (n_rec == 0 || n_motifs == 0) return PFMSCAN_OK;
+    if (!rec_off || !rec_len || !occ) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": NULL record table or output");
+    if (int rc = occ_check_records(ctx, who, rec_off, rec_len, n_rec, n_pos)) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc;
+    const size_t cells = (size_t)n_rec * n_motifs;
+    if ((rc = ensure(ctx, ctx->occ_rec, (size_t)n_rec * 16))) return rc;
+    if ((rc = ensure(ctx, ctx->occ_out, cells * 8 + (size_t)n_rec * 8))) return rc;
+    int64_t *d_off = (int64_t *)ctx->occ_rec.p, *d_len = d_off + n_rec;
+    if ((rc = upload(ctx, d_off, rec_off, (size_t)n_rec * 8, ctx->stream))) return rc;
+    if ((rc = upload(ctx, d_len, rec_len, (size_t)n_rec * 8, ctx->stream))) return rc;
+    double *d_occ = (double *)ctx->occ_out.p;
+    int64_t *d_win = windows ? (int64_t *)(d_occ + cells) : nullptr;
+    const uint8_t *d_codes = (const uint8_t *)(which ? ctx->codes2.p : ctx->codes.p);
+    if ((rc = occ_run(ctx, who, ratio_tables, n_motifs, m, n_letters, d_codes, n_pos, rec_off, rec_len, d_off, d_len, n_rec, d_occ, d_win, ctx->stream)))
+        return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(occ, d_occ, cells * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (windows) HIP_TRY(ctx, hipMemcpyAsync(windows, d_win, (size_t)n_rec * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return PFMSCAN_OK;
+}
+
+}  // extern "C"

@@ -78,6 +78,32 @@ def log_odds(pwm, background=None):
     return out
 
 
+def odds(pwm, background=None):
+    """The odds ratios whose log ``log_odds`` takes: the same operands in the same order, the same loop, no log.
+    R = p / b where that quotient is > 0, +0.0 otherwise (the cell whose log-odds is -inf, a NaN quotient included);
+    b = 0 < p -> +inf, both 0 -> NaN.  Never negative, never -0.0 (occupancy)."""
+    letters = list(pwm.keys())
+    if background is None:
+        bg = {l: 1.0 / len(letters) for l in letters}
+    else:
+        total = 0.0
+        for l in letters:
+            total += float(background[l])
+        bg = {l: float(background[l]) / total for l in letters}
+    out = OrderedDict()
+    for l in letters:
+        b = bg[l]
+        col = []
+        for p in np.asarray(pwm[l], dtype=np.float64).tolist():
+            if b > 0:
+                q = p / b
+                col.append(q if q > 0 else 0.0)
+            else:
+                col.append(math.inf if p > 0 else math.nan)
+        out[l] = np.array(col, dtype=np.float64)
+    return out
+
+
 class PSSM(OrderedDict):
     """letter -> float64[m] log-odds, plus the bits of Biopython's
     PositionSpecificScoringMatrix the scan path touches (``length``, ``alphabet``
@@ -159,6 +185,14 @@ class PSSM(OrderedDict):
                 yield p, float(full[p])
 
 
+class Odds(PSSM):
+    """letter -> float64[m] odds ratios (``odds``): what the occupancy kernels multiply"""
+
+    def ratio_table(self, letters):
+        """[m][8] ratio table for the kernels: column c = letters[c], the rest NaN (never read)."""
+        return self.letter_table(letters)
+
+
 def pfm2pssm(pfm_file, pseudocount, letters, background=None):
     """rnascan.py:238-252.  ``letters`` = alphabet.letters (the order Biopython
     fills the matrix in); a PFM lacking one of them raises KeyError like the
@@ -215,6 +249,20 @@ def load_pssms(pfm_file, pseudocount, letters, background=None):
             out[motif_id] = PSSM(letters, log_odds(normalize(counts, pseudocount), background))
     else:
         out[motif_id_of(pfm_file)] = pfm2pssm(pfm_file, pseudocount, letters, background)
+    return out
+
+
+def load_odds(pfm_file, pseudocount, letters, background=None):
+    """``load_pssms`` with ``odds`` in the place of ``log_odds``: OrderedDict motif id -> Odds, the file's motif order."""
+    out = OrderedDict()
+    if is_multi_pfm(pfm_file):
+        for motif_id, counts in read_multi_pfm(pfm_file):
+            counts = OrderedDict((l, counts[l]) for l in letters)
+            out[motif_id] = Odds(letters, odds(normalize(counts, pseudocount), background))
+    else:
+        counts = read_pfm(pfm_file)
+        counts = OrderedDict((l, counts[l]) for l in letters)
+        out[motif_id_of(pfm_file)] = Odds(letters, odds(normalize(counts, pseudocount), background))
     return out
 
 

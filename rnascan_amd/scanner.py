@@ -152,6 +152,16 @@ class HipEngine(object):
         self._stage(stream)
         return self.ctx.variants_staged(letter_tables, pos, alt)
 
+    def occupancy(self, stream, ratio_tables, n_letters, which=0):
+        """summed likelihood ratios: ratio tables [n_motifs][m][8] of one width (pssm.Odds.ratio_table) over
+        the stream's codes (which = 0) or codes2 (1), n_letters 4 (RNA) or 7 (structure letters) ->
+        (occ float64 [n_rec][n_motifs], windows int64 [n_rec])"""
+        self._stage(stream)
+        if which == 1 and self._staged2 is not stream:
+            self.ctx.stage_codes2(stream.codes2)
+            self._staged2 = stream
+        return self.ctx.occupancy_staged(ratio_tables, n_letters, stream.offsets, stream.lengths, which)
+
     def hits_sum(self, stream, letter_table, struct_pssm, thr_seq, thr_struct, thr_sum, one_shot=True):
         """``hits`` of a motif with both parts, with the joint threshold decided on the device: a window is kept iff
         seq > thr_seq AND struct > thr_struct AND float64(round(float32 seq, 3)) + struct > thr_sum -- the printed

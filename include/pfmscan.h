@@ -59,7 +59,7 @@
 extern "C" {
 #endif
 
-#define PFMSCAN_ABI_VERSION 21
+#define PFMSCAN_ABI_VERSION 22
 #define PFMSCAN_NCODE   8      /* columns of a letter table */
 #define PFMSCAN_SEP     7      /* separator / foreign-letter code */
 #define PFMSCAN_NSTRUCT 7      /* columns of a structure profile / structure PSSM */
@@ -1161,6 +1161,44 @@ int pfmscan_occupancy_dev(pfmscan_ctx *ctx, const double *ratio_tables, int n_mo
                           int64_t n_rec, double *d_occ, int64_t *d_windows);
 int pfmscan_occupancy_staged(pfmscan_ctx *ctx, int which, const double *ratio_tables, int n_motifs, int m, int n_letters,
                              const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec, double *occ, int64_t *windows);
+
+/* ---- occupancy on averaged-structure profiles: marginal ratios -------------------------------------------------------
+ * The occupancy above for a stream whose structure is a profile r [n_pos][7] (float or double rows) instead of letters:
+ * the expected odds of a window, not 2 ** (expected log-odds), which is what a structure scan's score gives.
+ * No transcendental, no tolerance; tests/occupancy_profile_rules.py restates it in numpy and the bits are compared.
+ *   S [m][7]      structure table of a motif of width m <= PFMSCAN_MAX_M: odds ratios as pssm.odds makes them (+0.0,
+ *                 positive, +inf or NaN), the columns arranged on the host in the profile's STORED column order, exactly as
+ *                 scanner.struct_matrix arranges a PSSM for --pairing aligned or positional.
+ *   d(x, k)       the marginal of row x under motif row k: d = r[x][0] * S[k][0], then d = d + r[x][c] * S[k][c] for
+ *                 c = 1 .. 6, ascending in stored column order.  Every product and every addition is rounded to double;
+ *                 nothing is fused.  float rows are widened first (exact).  No nan_to_num, no validity check: IEEE as it
+ *                 falls -- 0 x inf is NaN, a NaN or negative profile cell goes where arithmetic takes it.
+ *   term(s)       structure only (seq_tables NULL): t = d(s, 0), then t = t * d(s + k, k) for k = 1 .. m-1, each product
+ *                 rounded; the codes are not read and every window inside the record has a term.
+ *                 joint (seq_tables R [m][8] over the 4 RNA letters): first the letter chain of the occupancy above,
+ *                 t = R[0][c_0], then t = t * R[k][c_k]; then t = t * d(s + k, k) for k = 0 .. m-1.  A window that holds a
+ *                 code >= 4 has no term.  This is the ratio behind LogOdds.SeqStruct.
+ *   occ, windows  as above, unchanged: n_win = max(L - m + 1, 0) windows in order, skipped ones as +0.0, the left-aligned
+ *                 tree of fan-in PFMSCAN_OCC_FANIN anchored at the record's first window; windows[r] = the windows with a term, n_win in structure-only mode.  The separator row behind
+ *                 a record is never read as data.
+ * Every term and partial sum is +0.0, positive, +inf or NaN whenever the rows are non-negative; where they are not, the
+ * rules still define the result operation by operation.  The bits depend on the row dtype and on the stored column order
+ * and on nothing else: not on the batch, the position in the stream, the launch geometry, the scratch cap or the staged /
+ * _dev form.
+ * struct_tables: HOST double [n_motifs][m][7]; seq_tables: HOST double [n_motifs][m][8] or NULL; both are uploaded into
+ * scratch of the ctx by the call.  pfmscan_occupancy_profile_dev: d_profile (and d_codes in joint mode; otherwise it may be
+ * NULL and is not read) are device pointers, 16-byte aligned (else PFMSCAN_E_BADSHAPE), profile_dtype PFMSCAN_PROFILE_F32 or
+ * _F64; record table, the one synchronisation, outputs and the bounded scratch as for pfmscan_occupancy_dev.
+ * pfmscan_occupancy_profile_staged: the profile (and codes) left by pfmscan_stage, HOST record table and outputs,
+ * synchronises.  seq_tables without codes, no staged profile, a bad profile_dtype, a NULL that is needed: PFMSCAN_E_BADARG;
+ * m outside 1 .. PFMSCAN_MAX_M: PFMSCAN_E_BADSHAPE; n_rec == 0 or n_motifs == 0: PFMSCAN_OK, nothing written. */
+int pfmscan_occupancy_profile_dev(pfmscan_ctx *ctx, const double *struct_tables, const double *seq_tables, int n_motifs, int m,
+                                  const uint8_t *d_codes, const void *d_profile, int profile_dtype, int64_t n_pos,
+                                  const int64_t *d_rec_off, const int64_t *d_rec_len, int64_t n_rec, double *d_occ,
+                                  int64_t *d_windows);
+int pfmscan_occupancy_profile_staged(pfmscan_ctx *ctx, const double *struct_tables, const double *seq_tables, int n_motifs,
+                                     int m, const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec, double *occ,
+                                     int64_t *windows);
 
 #ifdef __cplusplus
 }

@@ -22,7 +22,7 @@ NCODE = 8
 NSTRUCT = 7
 MAX_M = 64            # widest PFM of the tuned kernels and of PFM libraries
 MAX_WIDTH = 4096      # widest PFM accepted (wider than MAX_M: the plain rolled-loop kernel)
-ABI_VERSION = 21
+ABI_VERSION = 22
 
 # every symbol include/pfmscan.h declares (checked by tests/test_abi.py)
 SYMBOLS = [
@@ -57,6 +57,7 @@ SYMBOLS = [
     "pfmscan_mutmap_dev", "pfmscan_mutmap_staged", "pfmscan_mutmap_events_dev", "pfmscan_mutmap_events_staged",
     "pfmscan_variants_dev", "pfmscan_variants_staged",
     "pfmscan_occupancy_dev", "pfmscan_occupancy_staged",
+    "pfmscan_occupancy_profile_dev", "pfmscan_occupancy_profile_staged",
 ]
 PAIR_ROUTE_NONE, PAIR_ROUTE_FUSED, PAIR_ROUTE_TWO_PHASE, PAIR_ROUTE_DENSE, PAIR_ROUTE_CREDITS = range(5)   # Context.pair_sum_route()
 SITE_GROUP = 4096     # most hits of one group of the site profiles
@@ -239,6 +240,8 @@ def load():
     L.pfmscan_variants_staged.argtypes = [vp, vp, i32, i32, vp, vp, i64, vp, vp, vp, vp]
     L.pfmscan_occupancy_dev.argtypes = [vp, vp, i32, i32, i32, vp, i64, vp, vp, i64, vp, vp]
     L.pfmscan_occupancy_staged.argtypes = [vp, i32, vp, i32, i32, i32, vp, vp, i64, vp, vp]
+    L.pfmscan_occupancy_profile_dev.argtypes = [vp, vp, vp, i32, i32, vp, vp, i32, i64, vp, vp, i64, vp, vp]
+    L.pfmscan_occupancy_profile_staged.argtypes = [vp, vp, vp, i32, i32, vp, vp, i64, vp, vp]
     L.pfmscan_tsv_format.argtypes = [ctypes.POINTER(TsvColumn), i32, i64, i64, vp, i64, ctypes.POINTER(i64), vp, ctypes.POINTER(i32), i32]
     for name in SYMBOLS:          # every other entry point returns a status
         if name not in ("pfmscan_ctx_destroy", "pfmscan_motif_destroy", "pfmscan_last_error", "pfmscan_library_destroy",
@@ -1687,6 +1690,42 @@ class Context(object):
         windows = np.zeros(rec_off.size, dtype=np.int64)
         self._check(self._L.pfmscan_occupancy_staged(self._h, int(which), _ptr(rt), rt.shape[0], rt.shape[1], int(n_letters), _ptr(rec_off),
                                                      _ptr(rec_len), rec_off.size, _ptr(occ), _ptr(windows)))
+        return occ, windows
+
+    # -- occupancy on averaged-structure profiles (include/pfmscan.h: pfmscan_occupancy_profile_*) --------
+    @staticmethod
+    def _profile_tables(struct_tables, seq_tables):
+        st = np.ascontiguousarray(struct_tables, dtype=np.float64)
+        if st.ndim == 2:
+            st = st[None]
+        if st.ndim != 3 or st.shape[2] != NSTRUCT:
+            raise ValueError("struct_tables must be [n_motifs][m][7]")
+        sq = None
+        if seq_tables is not None:
+            sq = Context._ratio_tables(seq_tables)
+            if sq.shape[:2] != st.shape[:2]:
+                raise ValueError("seq_tables must hold as many motifs of the same width as struct_tables")
+        return st, sq
+
+    def occupancy_profile_dev(self, struct_tables, seq_tables, d_codes, d_profile, profile_dtype, n_pos, d_rec_off, d_rec_len, n_rec,
+                              d_occ, d_windows=None):
+        st, sq = self._profile_tables(struct_tables, seq_tables)
+        self._check(self._L.pfmscan_occupancy_profile_dev(self._h, _ptr(st), _ptr(sq), st.shape[0], st.shape[1], _ptr(d_codes), _ptr(d_profile),
+                                                          int(profile_dtype), int(n_pos), _ptr(d_rec_off), _ptr(d_rec_len), int(n_rec),
+                                                          _ptr(d_occ), _ptr(d_windows)))
+
+    def occupancy_profile_staged(self, struct_tables, seq_tables, rec_off, rec_len):
+        """-> occ float64 [n_rec][n_motifs], windows int64 [n_rec] over the staged profile (structure only) or the staged
+        codes and profile (joint: seq_tables [n_motifs][m][8])"""
+        st, sq = self._profile_tables(struct_tables, seq_tables)
+        rec_off = np.ascontiguousarray(rec_off, dtype=np.int64)
+        rec_len = np.ascontiguousarray(rec_len, dtype=np.int64)
+        if rec_off.ndim != 1 or rec_off.shape != rec_len.shape:
+            raise ValueError("rec_off and rec_len must be lists of one length")
+        occ = np.zeros((rec_off.size, st.shape[0]), dtype=np.float64)
+        windows = np.zeros(rec_off.size, dtype=np.int64)
+        self._check(self._L.pfmscan_occupancy_profile_staged(self._h, _ptr(st), _ptr(sq), st.shape[0], st.shape[1], _ptr(rec_off),
+                                                             _ptr(rec_len), rec_off.size, _ptr(occ), _ptr(windows)))
         return occ, windows
 
     def time_scan_dev(self, motif, d_codes, d_profile, profile_dtype, n_pos, d_out_seq, d_out_struct,

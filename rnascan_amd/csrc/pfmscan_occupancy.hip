@@ -19,6 +19,19 @@
 //                      writes the cell.  One writer per cell.
 // The block sums go through scratch that is bounded (OCC_SCRATCH_DOUBLES) by running the records, and if one record alone is
 // too long the motifs, in passes.
+//
+// Averaged-structure profiles (include/pfmscan.h "occupancy on averaged-structure profiles"): the term of a
+// window is the product over k of the marginal d(s + k, k) = sum_c r[s + k][c] * S[k][c] (7 rounded products, 6 rounded
+// additions, ascending c), in joint mode continued from the letter chain above.  Only level 0 differs:
+//   k_occ_profile_blocks<T, SEQ, QN>   a workgroup owns a run of 8 consecutive blocks of one record (256 windows, a lane per
+//                      window).  The run's 256 + m - 1 rows are fetched as the aligned 16-byte vectors that cover them and
+//                      parked in LDS as doubles; for every k a lane holds its row's 7 doubles in registers and advances the
+//                      product chains of QN motifs, whose table rows are workgroup-uniform (scalar loads).  The QN x 256
+//                      terms go to LDS (a block's 32 terms one double apart from the next block's: the serial readers fall
+//                      on different banks) and one lane per (block, motif) adds the 32 in order.  A workgroup walks up to
+//                      OCCP_CHUNK motifs over the rows it staged; gridDim.y covers the rest.
+//   k_occ_run_records  before it, per pass: a thread per record writes the record of each of its runs (a third prefix table,
+//                      ceil(blocks / 8) per record, numbers the runs), so that a workgroup does not bisect that table.
 #include <algorithm>
 #include <cstdlib>
 #include <string>
@@ -61,6 +74,11 @@ struct OccArgs {
     int *gcnt;                   // [n_grp]
     double *occ;                 // [n_rec][n_motifs]
     int64_t *windows;            // [n_rec] or null
+    // averaged-structure profiles (k_occ_profile_blocks)
+    const unsigned char *profile;   // [n_pos][7] float or double, 16-byte aligned
+    const int64_t *run_start;    // [n_rec + 1] prefix of ceil(blocks / OCCP_RUN)
+    int64_t run_base;            // run_start[r0]
+    int64_t *run_rec;            // [runs of the pass] the record of every run (k_occ_run_records)
 };
 
 // dwords of a lane's strip of codes: the aligned dwords that cover 3 + 32 + m - 1 bytes, made odd so that the byte reads of
@@ -256,6 +274,167 @@ __global__ __launch_bounds__(BLOCK) void k_occ_finish(const OccArgs a)
     }
 }
 
+// ---- level 0 on averaged-structure profiles ----------------------------------------------------------------------------
+constexpr int OCCP_RUN = 8;                                        // blocks of a workgroup's run
+constexpr int OCCP_WIN = OCCP_RUN * OCC_FANIN;                     // its windows: a lane each
+constexpr int OCCP_ROWS = OCCP_WIN + PFMSCAN_MAX_M - 1;            // rows it stages at most
+constexpr int OCCP_TS = OCCP_RUN * (OCC_FANIN + 1);                // doubles of one motif's terms in LDS: window w at w + w / 32
+constexpr int OCCP_CHUNK = 32;                                     // motifs a workgroup walks over the rows it staged
+static_assert(OCCP_WIN == BLOCK, "a lane per window of the run");
+
+// the aligned 16 bytes at byte_off; the stream's last vector may be cut short (rows are a multiple of 4 bytes)
+__device__ __forceinline__ uint4 occp_load(const unsigned char *__restrict__ base, int64_t byte_off, int64_t total_bytes)
+{
+    uint4 v = make_uint4(0u, 0u, 0u, 0u);
+    if (byte_off + 16 <= total_bytes) {
+        v = *reinterpret_cast<const uint4 *>(base + byte_off);
+    } else {
+        const uint32_t *p = reinterpret_cast<const uint32_t *>(base + byte_off);
+        const int64_t n = (total_bytes - byte_off) / 4;
+        if (n > 0) v.x = p[0];
+        if (n > 1) v.y = p[1];
+        if (n > 2) v.z = p[2];
+    }
+    return v;
+}
+
+// the cells of one 16-byte vector, widened (exact)
+__device__ __forceinline__ void occp_cells(const uint4 v, double (&d)[4], float)
+{
+    d[0] = (double)__uint_as_float(v.x);
+    d[1] = (double)__uint_as_float(v.y);
+    d[2] = (double)__uint_as_float(v.z);
+    d[3] = (double)__uint_as_float(v.w);
+}
+__device__ __forceinline__ void occp_cells(const uint4 v, double (&d)[2], double)
+{
+    d[0] = __hiloint2double((int)v.y, (int)v.x);
+    d[1] = __hiloint2double((int)v.w, (int)v.z);
+}
+
+// the marginal of row x under table row s: 7 rounded products, 6 rounded additions, ascending
+__device__ __forceinline__ double occp_marginal(const double (&x)[7], const double *__restrict__ s)
+{
+    double d = x[0] * s[0];
+#pragma unroll
+    for (int c = 1; c < 7; ++c) d = d + x[c] * s[c];
+    return d;
+}
+
+// the record of every run of the pass, so that a workgroup of k_occ_profile_blocks finds its run with two round trips to memory
+// instead of a bisection of ~17 dependent loads (which, at 8 workgroups per CU, was most of a single-motif call's time)
+__global__ __launch_bounds__(BLOCK) void k_occ_run_records(const OccArgs a)
+{
+    const int64_t r = a.r0 + (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (r >= a.r1) return;
+    const int64_t u1 = a.run_start[r + 1] - a.run_base;
+    for (int64_t u = a.run_start[r] - a.run_base; u < u1; ++u) a.run_rec[u] = r;
+}
+
+template <typename T, bool SEQ, int QN>
+__global__ __launch_bounds__(BLOCK) void k_occ_profile_blocks(const OccArgs a, const double *__restrict__ stab, const double *__restrict__ ltab,
+                                                              double *__restrict__ bs)
+{
+    constexpr int RB = 7 * (int)sizeof(T);                         // bytes of a row
+    constexpr int PER = 16 / (int)sizeof(T);                       // cells of a vector
+    __shared__ double rows[OCCP_ROWS * 7];
+    __shared__ double tl[QN * OCCP_TS];
+    __shared__ uint8_t cl[SEQ ? (OCCP_ROWS + 7) / 8 * 8 : 8];
+    const int t = threadIdx.x, m = a.m;
+    const int64_t u = a.run_base + blockIdx.x;                     // this workgroup's run
+    const int64_t r = a.run_rec[blockIdx.x];
+    const int64_t b0 = (u - a.run_start[r]) * OCCP_RUN;            // its first block, within the record
+    const int64_t w0 = b0 * OCC_FANIN;
+    const int64_t n_win = a.rec_len[r] - m + 1;                    // > w0: the run exists
+    const int nw = (int)min((int64_t)OCCP_WIN, n_win - w0);
+    const int nb = (nw + OCC_FANIN - 1) / OCC_FANIN;
+    const int nrows = nw + m - 1;                                  // all inside the record: the separator is not among them
+    const int64_t row0 = a.rec_off[r] + w0;
+    {
+        const int64_t first = row0 * RB, end = first + (int64_t)nrows * RB, base = first & ~(int64_t)15, total = a.n_pos * RB;
+        const int shift = (int)(first - base) / (int)sizeof(T);
+        const int ncell = nrows * 7, nvec = (int)((end - base + 15) / 16);
+        for (int v = t; v < nvec; v += BLOCK) {
+            double d[PER];
+            occp_cells(occp_load(a.profile, base + (int64_t)v * 16, total), d, T());
+#pragma unroll
+            for (int j = 0; j < PER; ++j) {
+                const int idx = v * PER + j - shift;
+                if (idx >= 0 && idx < ncell) rows[idx] = d[j];
+            }
+        }
+        if constexpr (SEQ)
+            for (int i = t; i < nrows; i += BLOCK) cl[i] = a.codes[row0 + i];
+    }
+    __syncthreads();
+    const bool mine = t < nw;
+    bool has = mine;                                               // this lane's window has a term
+    if constexpr (SEQ) {
+        if (mine)
+            for (int k = 0; k < m; ++k) has = has && (cl[t + k] & 7u) < 4u;
+    }
+    const int64_t gb = a.blk_start[r] - a.blk_base + b0;           // the run's first block, within the pass
+    if (a.bcnt && blockIdx.y == 0) {
+        const unsigned long long bal = __ballot(has);
+        const int lane = t & 63, b = 2 * (t >> 6) + (lane >> 5);
+        if ((lane & 31) == 0 && b < nb) a.bcnt[gb + b] = __popcll(lane ? bal >> 32 : bal & 0xFFFFFFFFull);
+    }
+    const int qc = (int)blockIdx.y * OCCP_CHUNK;                   // first motif of this workgroup, within the pass
+    const int nq = min(OCCP_CHUNK, a.n_q - qc);
+    const int64_t ms = (int64_t)m * 7, ml = (int64_t)m * 8;
+    for (int q = 0; q < nq; q += QN) {
+        double tt[QN];
+#pragma unroll
+        for (int i = 0; i < QN; ++i) tt[i] = 0.0;
+        if (mine) {
+            const int64_t qg = (int64_t)a.q_first + qc + q;
+            const double *rw = rows + t * 7;
+            double x[7];
+            if constexpr (SEQ) {
+                int c = cl[t] & 7;
+#pragma unroll
+                for (int i = 0; i < QN; ++i) tt[i] = ltab[(qg + min(i, nq - 1 - q)) * ml + c];
+                for (int k = 1; k < m; ++k) {
+                    c = cl[t + k] & 7;
+#pragma unroll
+                    for (int i = 0; i < QN; ++i) tt[i] = tt[i] * ltab[(qg + min(i, nq - 1 - q)) * ml + k * 8 + c];
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < 7; ++c) x[c] = rw[c];
+#pragma unroll
+            for (int i = 0; i < QN; ++i) {
+                const double d = occp_marginal(x, stab + (qg + min(i, nq - 1 - q)) * ms);
+                tt[i] = SEQ ? tt[i] * d : d;
+            }
+            for (int k = 1; k < m; ++k) {
+                rw += 7;
+#pragma unroll
+                for (int c = 0; c < 7; ++c) x[c] = rw[c];
+#pragma unroll
+                for (int i = 0; i < QN; ++i) tt[i] = tt[i] * occp_marginal(x, stab + (qg + min(i, nq - 1 - q)) * ms + k * 7);
+            }
+        }
+        if (q) __syncthreads();                                    // the adders of the last round are done with tl
+#pragma unroll
+        for (int i = 0; i < QN; ++i) tl[i * OCCP_TS + t + (t >> 5)] = has ? tt[i] : 0.0;
+        __syncthreads();
+        if (t < OCCP_RUN * QN) {
+            const int i = t >> 3, b = t & 7;
+            if (b < nb && q + i < nq) {
+                const double *p = tl + i * OCCP_TS + b * (OCC_FANIN + 1);
+                double v[OCC_FANIN];                               // all 32 reads in flight before the dependent additions
+#pragma unroll
+                for (int j = 0; j < OCC_FANIN; ++j) v[j] = p[j];
+                double s = v[0];
+#pragma unroll
+                for (int j = 1; j < OCC_FANIN; ++j) s = s + v[j];  // the block padded with +0.0 to 32 (skipped windows are +0.0 too)
+                bs[(gb + b) * a.n_q + qc + q + i] = n_win == 1 ? v[0] : s;   // a lone window is the record's sum as it is
+            }
+        }
+    }
+}
+
 static int occ_qn(int nq) { return nq >= 8 ? 8 : nq >= 4 ? 4 : nq >= 2 ? 2 : 1; }
 
 
@@ -279,19 +458,53 @@ static hipError_t occ_launch_blocks(const OccArgs &a, hipStream_t st)
     return hipGetLastError();
 }
 
+// what level 0 reads when the stream is an averaged-structure profile: its rows and the structure tables (HOST double
+// [n_motifs][m][7]); the letter tables and the codes are then those of joint mode, or null
+struct OccProfile {
+    const double *struct_tables;
+    const void *d_profile;
+    int dtype;
+};
+
+template <typename T, bool SEQ>
+static void occ_launch_profile_qn(const OccArgs &a, int qn, const dim3 grid, const double *stab, hipStream_t st)
+{
+    if (qn == 8) hipLaunchKernelGGL((k_occ_profile_blocks<T, SEQ, 8>), grid, dim3(BLOCK), 0, st, a, stab, a.tables, a.bs);
+    else if (qn == 4) hipLaunchKernelGGL((k_occ_profile_blocks<T, SEQ, 4>), grid, dim3(BLOCK), 0, st, a, stab, a.tables, a.bs);
+    else if (qn == 2) hipLaunchKernelGGL((k_occ_profile_blocks<T, SEQ, 2>), grid, dim3(BLOCK), 0, st, a, stab, a.tables, a.bs);
+    else hipLaunchKernelGGL((k_occ_profile_blocks<T, SEQ, 1>), grid, dim3(BLOCK), 0, st, a, stab, a.tables, a.bs);
+}
+
+static hipError_t occ_launch_profile(const OccArgs &a, int dtype, bool seq, int64_t n_run, const double *stab, hipStream_t st)
+{
+    const int qn = occ_qn(std::min(a.n_q, OCCP_CHUNK));
+    const dim3 grid((unsigned)n_run, (unsigned)((a.n_q + OCCP_CHUNK - 1) / OCCP_CHUNK));
+    if (dtype == PFMSCAN_PROFILE_F64) {
+        if (seq) occ_launch_profile_qn<double, true>(a, qn, grid, stab, st);
+        else occ_launch_profile_qn<double, false>(a, qn, grid, stab, st);
+    } else {
+        if (seq) occ_launch_profile_qn<float, true>(a, qn, grid, stab, st);
+        else occ_launch_profile_qn<float, false>(a, qn, grid, stab, st);
+    }
+    return hipGetLastError();
+}
+
 // rec_off / rec_len: HOST copies, already checked; d_rec_off / d_rec_len: the same on the device.  Launches on st, does not wait.
+// pf == null: letter strings (ratio_tables over d_codes); otherwise an averaged-structure profile, and ratio_tables / d_codes
+// are the letter part of joint mode or null.  Only the level-0 launch differs.
 static int occ_run(pfmscan_ctx *ctx, const char *who, const double *ratio_tables, int n_motifs, int m, int n_letters, const uint8_t *d_codes,
                    int64_t n_pos, const int64_t *rec_off, const int64_t *rec_len, const int64_t *d_rec_off, const int64_t *d_rec_len,
-                   int64_t n_rec, double *d_occ, int64_t *d_windows, hipStream_t st)
+                   int64_t n_rec, double *d_occ, int64_t *d_windows, hipStream_t st, const OccProfile *pf = nullptr)
 {
-    std::vector<int64_t> start(2 * (size_t)(n_rec + 1));
-    int64_t *blk = start.data(), *grp = blk + n_rec + 1;
+    std::vector<int64_t> start(3 * (size_t)(n_rec + 1));
+    int64_t *blk = start.data(), *grp = blk + n_rec + 1, *run = grp + n_rec + 1;
     int64_t max_blk = 0;
-    blk[0] = grp[0] = 0;
+    blk[0] = grp[0] = run[0] = 0;
     for (int64_t r = 0; r < n_rec; ++r) {
         const int64_t nw = std::max<int64_t>(rec_len[r] - m + 1, 0), nb = (nw + OCC_FANIN - 1) / OCC_FANIN;
         blk[r + 1] = blk[r] + nb;
         grp[r + 1] = grp[r] + (nb + OCC_FANIN - 1) / OCC_FANIN;
+        run[r + 1] = run[r] + (nb + OCCP_RUN - 1) / OCCP_RUN;
         max_blk = std::max(max_blk, nb);
     }
     int64_t cap = OCC_SCRATCH_DOUBLES;
@@ -300,24 +513,29 @@ static int occ_run(pfmscan_ctx *ctx, const char *who, const double *ratio_tables
     const int n_q_max = (int)std::min<int64_t>(n_motifs, std::max<int64_t>(1, cap / std::max<int64_t>(max_blk, 1)));
     const int64_t blk_cap = std::max<int64_t>(cap / n_q_max, 1), rec_cap = std::max<int64_t>((int64_t(1) << 30) / n_q_max, 1);
     std::vector<int64_t> cuts(1, 0);
-    int64_t need_blk = 0, need_grp = 0;
+    int64_t need_blk = 0, need_grp = 0, need_run = 0;
     for (int64_t r0 = 0; r0 < n_rec;) {
         int64_t r1 = r0 + 1;
         while (r1 < n_rec && r1 - r0 < rec_cap && blk[r1 + 1] - blk[r0] <= blk_cap) ++r1;
         cuts.push_back(r1);
         need_blk = std::max(need_blk, blk[r1] - blk[r0]);
         need_grp = std::max(need_grp, grp[r1] - grp[r0]);
+        need_run = std::max(need_run, run[r1] - run[r0]);
         r0 = r1;
     }
-    if ((need_blk + BLOCK - 1) / BLOCK > 0x7FFFFFFF) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": a record is too long for one call");
+    // a profile pass launches a workgroup per run, and has no more runs than blocks
+    if ((need_blk + BLOCK - 1) / BLOCK > 0x7FFFFFFF || (pf && need_blk > 0x7FFFFFFF)) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": a record is too long for one call");
     int rc;
-    const size_t tab_bytes = (size_t)n_motifs * m * 8 * sizeof(double);
-    if ((rc = ensure(ctx, ctx->occ_tab, tab_bytes))) return rc;
-    if ((rc = ensure(ctx, ctx->occ_idx, start.size() * 8))) return rc;
+    const size_t tab_bytes = ratio_tables ? (size_t)n_motifs * m * 8 * sizeof(double) : 0;
+    const size_t stab_bytes = pf ? (size_t)n_motifs * m * 7 * sizeof(double) : 0;   // behind the letter tables
+    if ((rc = ensure(ctx, ctx->occ_tab, tab_bytes + stab_bytes))) return rc;
+    if ((rc = ensure(ctx, ctx->occ_idx, (start.size() + (pf ? (size_t)need_run : 0)) * 8))) return rc;   // the prefix tables, then a pass's run -> record
     if ((rc = ensure(ctx, ctx->occ_bs, std::max<size_t>((size_t)need_blk * n_q_max * 8, 16)))) return rc;
     if ((rc = ensure(ctx, ctx->occ_gs, std::max<size_t>((size_t)need_grp * n_q_max * 8, 16)))) return rc;
     if ((rc = ensure(ctx, ctx->occ_cnt, std::max<size_t>((size_t)(need_blk + need_grp) * 4, 16)))) return rc;
-    if ((rc = upload(ctx, ctx->occ_tab.p, ratio_tables, tab_bytes, st))) return rc;
+    if (tab_bytes && (rc = upload(ctx, ctx->occ_tab.p, ratio_tables, tab_bytes, st))) return rc;
+    const double *d_stab = (const double *)((const unsigned char *)ctx->occ_tab.p + tab_bytes);
+    if (pf && (rc = upload(ctx, (void *)d_stab, pf->struct_tables, stab_bytes, st))) return rc;
     if ((rc = upload(ctx, ctx->occ_idx.p, start.data(), start.size() * 8, st))) return rc;
     OccArgs a{};
     a.codes = d_codes;
@@ -326,7 +544,10 @@ static int occ_run(pfmscan_ctx *ctx, const char *who, const double *ratio_tables
     a.rec_len = d_rec_len;
     a.blk_start = (const int64_t *)ctx->occ_idx.p;
     a.grp_start = a.blk_start + n_rec + 1;
-    a.tables = (const double *)ctx->occ_tab.p;
+    a.tables = tab_bytes ? (const double *)ctx->occ_tab.p : nullptr;
+    a.run_start = a.grp_start + n_rec + 1;
+    a.run_rec = (int64_t *)ctx->occ_idx.p + start.size();
+    a.profile = pf ? (const unsigned char *)pf->d_profile : nullptr;
     a.m = m;
     a.n_letters = n_letters;
     a.n_motifs = n_motifs;
@@ -337,7 +558,7 @@ static int occ_run(pfmscan_ctx *ctx, const char *who, const double *ratio_tables
     for (int q0 = 0; q0 < n_motifs; q0 += n_q_max) {
         a.q_first = q0;
         a.n_q = std::min(n_q_max, n_motifs - q0);
-        a.chunk = occ_chunk(m, n_letters, a.n_q);
+        a.chunk = pf ? OCCP_CHUNK : occ_chunk(m, n_letters, a.n_q);
         if ((a.n_q + a.chunk - 1) / a.chunk > 65535) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": too many motifs for one call");
         const bool count = d_windows && q0 == 0;                   // Windows does not depend on the motif: counted in the first pass
         for (size_t i = 0; i + 1 < cuts.size(); ++i) {
@@ -351,8 +572,10 @@ static int occ_run(pfmscan_ctx *ctx, const char *who, const double *ratio_tables
             a.gcnt = count ? a.bcnt + need_blk : nullptr;
             hipError_t e = hipSuccess;
             if (a.n_blk > 0) {
-                e = occ_launch_blocks(a, st);
-                if (e != hipSuccess) return fail_hip(ctx, e, "k_occ_blocks");
+                a.run_base = run[a.r0];
+                if (pf) hipLaunchKernelGGL(k_occ_run_records, dim3((unsigned)((a.r1 - a.r0 + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, a);
+                e = pf ? occ_launch_profile(a, pf->dtype, ratio_tables != nullptr, run[a.r1] - a.run_base, d_stab, st) : occ_launch_blocks(a, st);
+                if (e != hipSuccess) return fail_hip(ctx, e, pf ? "k_occ_profile_blocks" : "k_occ_blocks");
                 hipLaunchKernelGGL(k_occ_level1, dim3((unsigned)((a.n_grp * a.n_q + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, a);
                 if ((e = hipGetLastError()) != hipSuccess) return fail_hip(ctx, e, "k_occ_level1");
             }
@@ -438,6 +661,84 @@ int pfmscan_occupancy_staged(pfmscan_ctx *ctx, int which, const double *ratio_ta
     int64_t *d_win = windows ? (int64_t *)(d_occ + cells) : nullptr;
     const uint8_t *d_codes = (const uint8_t *)(which ? ctx->codes2.p : ctx->codes.p);
     if ((rc = occ_run(ctx, who, ratio_tables, n_motifs, m, n_letters, d_codes, n_pos, rec_off, rec_len, d_off, d_len, n_rec, d_occ, d_win, ctx->stream)))
+        return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(occ, d_occ, cells * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (windows) HIP_TRY(ctx, hipMemcpyAsync(windows, d_win, (size_t)n_rec * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return PFMSCAN_OK;
+}
+
+}  // extern "C"
+
+namespace pfmscan {
+
+// the checks both profile entry points share, before the rule "n_rec == 0 or n_motifs == 0: nothing to do"
+static int occp_check(pfmscan_ctx *ctx, const char *who, const double *struct_tables, int n_motifs, int m, int profile_dtype, int64_t n_pos,
+                      int64_t n_rec)
+{
+    if (m < 1 || m > PFMSCAN_MAX_M)
+        return fail(ctx, PFMSCAN_E_BADSHAPE, std::string(who) + ": width " + std::to_string(m) + " outside 1 .. PFMSCAN_MAX_M (" + std::to_string(PFMSCAN_MAX_M) + ")");
+    if (profile_dtype != PFMSCAN_PROFILE_F32 && profile_dtype != PFMSCAN_PROFILE_F64)
+        return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": profile_dtype must be PFMSCAN_PROFILE_F32 or F64");
+    if (n_motifs < 0 || n_rec < 0 || n_pos < 0) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": negative size");
+    if (n_motifs > 0 && !struct_tables) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": struct_tables is NULL");
+    return PFMSCAN_OK;
+}
+
+}  // namespace pfmscan
+
+extern "C" {
+
+int pfmscan_occupancy_profile_dev(pfmscan_ctx *ctx, const double *struct_tables, const double *seq_tables, int n_motifs, int m,
+                                  const uint8_t *d_codes, const void *d_profile, int profile_dtype, int64_t n_pos,
+                                  const int64_t *d_rec_off, const int64_t *d_rec_len, int64_t n_rec, double *d_occ, int64_t *d_windows)
+{
+    const char *who = "pfmscan_occupancy_profile_dev";
+    if (!ctx) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": NULL ctx");
+    if (int rc = occp_check(ctx, who, struct_tables, n_motifs, m, profile_dtype, n_pos, n_rec)) return rc;
+    if (seq_tables && !d_codes) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": seq_tables (joint mode) needs the codes");
+    if (n_rec == 0 || n_motifs == 0) return PFMSCAN_OK;
+    if (!d_rec_off || !d_rec_len || !d_occ || (n_pos > 0 && !d_profile)) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": NULL record table, profile or output");
+    if (misaligned(d_profile) || (seq_tables && misaligned(d_codes)))
+        return fail(ctx, PFMSCAN_E_BADSHAPE, std::string(who) + ": stream base pointers must be 16-byte aligned");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // the record table decides every address the kernels form: it is read back and checked before anything is launched
+    std::vector<int64_t> rec(2 * (size_t)n_rec);
+    HIP_TRY(ctx, hipMemcpyAsync(rec.data(), d_rec_off, (size_t)n_rec * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(rec.data() + n_rec, d_rec_len, (size_t)n_rec * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (int rc = occ_check_records(ctx, who, rec.data(), rec.data() + n_rec, n_rec, n_pos)) return rc;
+    const OccProfile pf{struct_tables, d_profile, profile_dtype};
+    return occ_run(ctx, who, seq_tables, n_motifs, m, 4, seq_tables ? d_codes : nullptr, n_pos, rec.data(), rec.data() + n_rec, d_rec_off,
+                   d_rec_len, n_rec, d_occ, d_windows, ctx->stream, &pf);
+}
+
+int pfmscan_occupancy_profile_staged(pfmscan_ctx *ctx, const double *struct_tables, const double *seq_tables, int n_motifs, int m,
+                                     const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec, double *occ, int64_t *windows)
+{
+    const char *who = "pfmscan_occupancy_profile_staged";
+    if (!ctx) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": NULL ctx");
+    if (ctx->staged_n < 0) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": no stream staged (call pfmscan_stage first)");
+    if (!ctx->staged_profile) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": no profile is staged");
+    if (seq_tables && !ctx->staged_codes) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": seq_tables (joint mode) needs staged codes");
+    const int64_t n_pos = ctx->staged_n;
+    if (int rc = occp_check(ctx, who, struct_tables, n_motifs, m, ctx->staged_dtype, n_pos, n_rec)) return rc;
+    if (n_rec == 0 || n_motifs == 0) return PFMSCAN_OK;
+    if (!rec_off || !rec_len || !occ) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": NULL record table or output");
+    if (int rc = occ_check_records(ctx, who, rec_off, rec_len, n_rec, n_pos)) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc;
+    const size_t cells = (size_t)n_rec * n_motifs;
+    if ((rc = ensure(ctx, ctx->occ_rec, (size_t)n_rec * 16))) return rc;
+    if ((rc = ensure(ctx, ctx->occ_out, cells * 8 + (size_t)n_rec * 8))) return rc;
+    int64_t *d_off = (int64_t *)ctx->occ_rec.p, *d_len = d_off + n_rec;
+    if ((rc = upload(ctx, d_off, rec_off, (size_t)n_rec * 8, ctx->stream))) return rc;
+    if ((rc = upload(ctx, d_len, rec_len, (size_t)n_rec * 8, ctx->stream))) return rc;
+    double *d_occ = (double *)ctx->occ_out.p;
+    int64_t *d_win = windows ? (int64_t *)(d_occ + cells) : nullptr;
+    const OccProfile pf{struct_tables, ctx->profile.p, ctx->staged_dtype};
+    if ((rc = occ_run(ctx, who, seq_tables, n_motifs, m, 4, seq_tables ? (const uint8_t *)ctx->codes.p : nullptr, n_pos, rec_off, rec_len, d_off,
+                      d_len, n_rec, d_occ, d_win, ctx->stream, &pf)))
         return rc;
     HIP_TRY(ctx, hipMemcpyAsync(occ, d_occ, cells * 8, hipMemcpyDeviceToHost, ctx->stream));
     if (windows) HIP_TRY(ctx, hipMemcpyAsync(windows, d_win, (size_t)n_rec * 8, hipMemcpyDeviceToHost, ctx->stream));

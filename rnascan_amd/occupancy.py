@@ -2,6 +2,8 @@
 
     python -m rnascan_amd.occupancy (-p seq.pfm | -q struct.pfm) [-C c] [-u | -b bg | -B bg] [--all-motifs]
                                     [--struct-format auto|letters|dotbracket] [--device N] in.fa > table.tsv
+    python -m rnascan_amd.occupancy -q struct.pfm [...] avgdir_or_store/ > table.tsv
+    python -m rnascan_amd.occupancy -p seq.pfm -q struct.pfm [...] seqs.fa avgdir_or_store/ > table.tsv
 
 The occupancy (summed affinity) of a record under a motif is the sum over its windows of the window's likelihood ratio
 prod_k p_k(x) / b(x) = 2 ** score, taken from the PFM's own odds ratios (``pssm.odds``: what ``rnascan`` takes the log of)
@@ -16,9 +18,20 @@ One row per record x motif, in record order and then the file's motif order (the
 motif with ``--all-motifs``).  Columns: Motif_ID Seq_ID Windows Occupancy Log2.Occupancy -- ``Occupancy`` as ``repr`` prints
 the double (the shortest string that reads back to the same bits), ``Log2.Occupancy = round(log2(occ), 3)``, ``-inf`` for 0.
 A record shorter than the motif gets its row with ``Windows`` 0 and ``Occupancy`` 0.0.
+
+Averaged-structure profiles (a directory of ``structure.<id>.txt`` files or a packed store as the last input):
+the structure part of a window's ratio is the product over its rows of the marginal ratio sum_c r[c] * R[c] -- the expected
+odds of the row, not 2 ** (expected log-odds), which is what a structure scan's score would give.  ``-q`` alone: structure
+only, every window inside a record has a term.  ``-p`` with ``-q``: the sequence ratio of the FASTA's record times the
+structure marginals of its profile, the ratio behind ``LogOdds.SeqStruct``; records and profiles are matched by id, the
+motifs of two libraries are paired as ``rnascan`` pairs them (``Motif_ID`` as the site profiles name a pair).  The
+structure background is ``-u``, ``-B file``, or else computed from the profiles as ``rnascan`` computes it; ``--pairing``
+pairs the profile's columns with the PFM's as ``rnascan`` does, ``--profile-dtype`` is the rows' storage on the device (the
+store's own, or float64 for text files, unless given).  Two-FASTA pairs (``-p -q seqs.fa structs.fa``) are not supported.
 """
 import argparse
 import math
+from collections import OrderedDict
 import os
 import sys
 
@@ -76,11 +89,58 @@ def run(engine, out, recs, odds, motif_ids, letters, code_letters, batch_records
     return total
 
 
+def _by_width(widths):
+    groups = {}
+    for k, m in enumerate(widths):
+        groups.setdefault(m, []).append(k)
+    return groups
+
+
+def run_profiles(engine, out, recs, profiles, seq_odds, struct_odds, pairs, pairing="aligned", batch_records=BATCH_RECORDS):
+    """the rows of an averaged-structure input (``sites._Profiles``), batch by batch of records; within a batch one device
+    call per run of equal column order and per width.  ``recs``: the FASTA's records in the profiles' order for joint mode
+    (``pairs`` = [(sequence id, structure id)]), None for structure only ([(None, structure id)])"""
+    from . import scanner, sites
+    motif_ids = [sites.pair_id(a, b) for a, b in pairs]
+    groups = _by_width([struct_odds[b].length for _, b in pairs])
+    seq_tables = None
+    if recs is not None:
+        seq_tables = dict((m, np.stack([seq_odds[pairs[k][0]].ratio_table(pack.RNA_LETTERS) for k in ks])) for m, ks in groups.items())
+    total = 0
+    for a in range(0, len(profiles.ids), batch_records):
+        b = min(len(profiles.ids), a + batch_records)
+        at = a
+        for ids, cols, pst in profiles.runs(a, b):
+            n = len(ids)
+            stream = pst
+            if recs is not None:
+                batch = scanner._RnaBatch(recs[at:at + n])
+                if not np.array_equal(batch.lengths, pst.lengths):
+                    r = int(np.flatnonzero(batch.lengths != pst.lengths)[0])
+                    raise sites.InputError("record %s is %d letters long but its averaged-structure profile has %d rows" %
+                                           (ids[r], int(batch.lengths[r]), int(pst.lengths[r])))
+                stream = pack.Stream(batch.codes, pst.profile, batch.offsets, batch.lengths)
+            occ = np.zeros((n, len(pairs)), dtype=np.float64)
+            win = np.zeros((n, len(pairs)), dtype=np.int64)
+            for m, ks in groups.items():
+                # the structure tables in THIS run's stored column order
+                st = np.stack([scanner.struct_matrix(struct_odds[pairs[k][1]], cols, pairing) for k in ks])
+                o, w = engine.occupancy_profile(stream, st, None if recs is None else seq_tables[m])
+                occ[:, ks] = o
+                win[:, ks] = w[:, None]
+            out.write("".join(format_rows(motif_ids, list(ids), win, occ)))
+            total += n * len(pairs)
+            at += n
+    return total
+
+
 def getoptions(argv=None):
     parser = argparse.ArgumentParser(prog="python -m rnascan_amd.occupancy",
                                      description=("Occupancy: the summed likelihood ratio of every record under every motif, "
                                                   "a threshold-free records x motifs table."))
-    parser.add_argument("fasta", metavar="in.fa", help="the sequence FASTA (-p) or structure FASTA (-q)")
+    parser.add_argument("inputs", metavar="input", nargs="+",
+                        help=("the sequence FASTA (-p) or structure FASTA (-q); or an averaged-structure directory or packed store (-q); "
+                              "or the sequence FASTA and the averaged-structure directory or store (-p with -q)"))
     parser.add_argument("-p", "--pfm_seq", dest="pfm_seq", type=str, default=None, help="Sequence PFM")
     parser.add_argument("-q", "--pfm_struct", dest="pfm_struct", type=str, default=None, help="Structure PFM")
     parser.add_argument("-C", "--pseudocount", type=float, dest="pseudocount", default=0, help="Pseudocount for normalizing PFM. [%(default)s]")
@@ -93,13 +153,124 @@ def getoptions(argv=None):
                         help="-q: what the structure FASTA holds; dot-bracket strings are annotated on the GPU first [%(default)s]")
     parser.add_argument("--batch-records", type=int, default=BATCH_RECORDS, dest="batch_records",
                         help="records per device call; the table does not depend on it [%(default)s]")
+    parser.add_argument("--pairing", choices=["aligned", "positional"], default="aligned",
+                        help="averaged-structure columns vs structure PFM, as rnascan's [%(default)s]")
+    parser.add_argument("--profile-dtype", choices=["float32", "float64"], default=None, dest="profile_dtype",
+                        help="device storage of averaged-structure rows [the store's own dtype; float64 for text files]")
     parser.add_argument("--device", type=int, default=int(os.environ.get("RNASCAN_DEVICE", "0")), help="HIP device index [%(default)s]")
-    args = parser.parse_args(argv)
+    args = parser.parse_intermixed_args(argv)                      # `seqs.fa --batch-records 64 avgdir/` is fine
     if args.uniform_background and (args.bg_seq or args.bg_struct):
         parser.error("You cannot set uniform and custom background options at the same time\n")
     if args.batch_records < 1:
         parser.error("--batch-records: must be positive")
+    if len(args.inputs) > 2:
+        parser.error("one input, or the sequence FASTA and the averaged-structure directory or store")
+    args.fasta = args.inputs[0]
     return args
+
+
+def _is_profiles(path):
+    from . import store
+    return os.path.isdir(path) or store.is_store(path)
+
+
+def _widths_ok(shapes, motif_ids, option, pfm_file):
+    from ._lib import MAX_M
+    for mid in motif_ids:
+        if shapes[mid].length > MAX_M:
+            fasta.eprint("%s: motif %s of %s is %d positions wide, more than %d (PFMSCAN_MAX_M)" %
+                         (option, mid, pfm_file, shapes[mid].length, MAX_M))
+            return False
+    return True
+
+
+def _load_shapes(pfm_file, option, pseudocount, letters):
+    """widths only, before any device work -> {id: Odds} or None (said on stderr)"""
+    from . import pssm
+    try:
+        shapes = pssm.load_odds(pfm_file, pseudocount, letters, None)
+    except KeyError:
+        fasta.eprint("Failed to load motif %s (%s): check that the PFM has the letters %s" % (pfm_file, option, letters))
+        return None
+    if not shapes:
+        fasta.eprint("No motif could be read from %s (%s)" % (pfm_file, option))
+        return None
+    return shapes
+
+
+def main_profiles(args, engine, out):
+    """the averaged-structure modes: ``-q st.pfm avgdir_or_store`` and ``-p seq.pfm -q st.pfm seqs.fa avgdir_or_store``"""
+    from . import background, pssm, scanner, sites, store
+    joint = bool(args.pfm_seq)
+    source = args.inputs[-1]
+    own = engine is None
+    try:
+        st_shapes = _load_shapes(args.pfm_struct, "-q", args.pseudocount, fasta.STRUCT)
+        seq_shapes = _load_shapes(args.pfm_seq, "-p", args.pseudocount, fasta.RNA) if joint and st_shapes else None
+        if st_shapes is None or (joint and seq_shapes is None):
+            return 1
+        if not args.all_motifs:
+            st_shapes = OrderedDict([scanner._first_motif(st_shapes)])
+            seq_shapes = OrderedDict([scanner._first_motif(seq_shapes)]) if joint else None
+        if joint:
+            try:
+                pairs = sites.motif_pairs(seq_shapes, st_shapes)
+            except sites.InputError as e:
+                fasta.eprint(str(e))
+                return 1
+            # scanner.pair_motifs leaves out the pairs of unequal width (they share no window): here that is an error
+            sk, tk = list(seq_shapes.keys()), list(st_shapes.keys())
+            if len(sk) == 1 or len(tk) == 1:
+                meant = [(a, b) for a in sk for b in tk]
+            else:
+                meant = [(a, a) for a in sk if a in st_shapes] or list(zip(sk, tk))
+            for a, b in meant:
+                if seq_shapes[a].length != st_shapes[b].length:
+                    fasta.eprint("-p motif %s is %d positions wide and -q motif %s %d: they share no window" %
+                                 (a, seq_shapes[a].length, b, st_shapes[b].length))
+                    return 1
+        else:
+            pairs = [(None, b) for b in st_shapes]                 # the file's motif order, as for a structure FASTA
+        if not _widths_ok(st_shapes, [b for _, b in pairs], "-q", args.pfm_struct):
+            return 1
+        if joint and not _widths_ok(seq_shapes, [a for a, _ in pairs], "-p", args.pfm_seq):
+            return 1
+        if engine is None:
+            engine = scanner.HipEngine(args.device)
+        stored = store.ProfileStore(source).dtype if store.is_store(source) else None
+        dtype = np.dtype(args.profile_dtype).type if args.profile_dtype else (np.dtype(stored).type if stored is not None else np.float64)
+        recs = None
+        if joint:
+            recs = fasta.open_lazy(args.inputs[0])
+            if len(set(recs.ids)) != len(recs):
+                seen = set()
+                dup = next(i for i in recs.ids if i in seen or seen.add(i))
+                raise sites.InputError("record %s occurs more than once in the FASTA" % dup)
+            profiles = sites._Profiles(source, dtype, order=list(recs.ids))
+        else:
+            profiles = sites._Profiles(source, dtype)
+        if args.uniform_background:
+            bg_struct = None
+        elif args.bg_struct:
+            bg_struct = fasta.load_background(args.bg_struct, False, source, fasta.STRUCT, True)
+        else:
+            bg_struct = background.profile_background(engine, source)
+        struct_odds = pssm.load_odds(args.pfm_struct, args.pseudocount, fasta.STRUCT, bg_struct)
+        seq_odds = None
+        if joint:
+            bg_seq = fasta.load_background(args.bg_seq, args.uniform_background, args.inputs[0], fasta.RNA, True)
+            seq_odds = pssm.load_odds(args.pfm_seq, args.pseudocount, fasta.RNA, bg_seq)
+        out.write("\t".join(COLUMNS) + "\n")
+        n = run_profiles(engine, out, recs, profiles, seq_odds, struct_odds, pairs, args.pairing, args.batch_records)
+        out.flush()
+        fasta.eprint("Wrote %d rows" % n)
+        return 0
+    except (IOError, sites.InputError, background.BackgroundError, background.InputError) as e:
+        fasta.eprint(str(e))
+        return 1
+    finally:
+        if own and engine is not None:
+            engine.close()
 
 
 def main(argv=None, engine=None, out=None):
@@ -107,12 +278,25 @@ def main(argv=None, engine=None, out=None):
     from ._lib import MAX_M
     args = getoptions(argv)
     out = sys.stdout if out is None else out
-    if args.pfm_seq and args.pfm_struct:
-        fasta.eprint("-p and -q cannot be given together: the occupancy of two-FASTA pairs is not supported, run one at a time")
-        return 1
     if not args.pfm_seq and not args.pfm_struct:
         fasta.eprint("one of -p (sequence PFM) or -q (structure PFM) is required")
         return 1
+    profiles = _is_profiles(args.inputs[-1])
+    if args.pfm_seq and args.pfm_struct:
+        if len(args.inputs) != 2 or not profiles or _is_profiles(args.inputs[0]):
+            fasta.eprint("-p with -q needs the sequence FASTA and an averaged-structure directory or packed store (seqs.fa avgdir/): "
+                         "the occupancy of two-FASTA pairs is not supported, run -p and -q one at a time")
+            return 1
+        return main_profiles(args, engine, out)
+    if len(args.inputs) == 2:
+        fasta.eprint("%s alone takes one input: give -p and -q with the sequence FASTA and the averaged-structure directory or store" %
+                     ("-p" if args.pfm_seq else "-q"))
+        return 1
+    if profiles:
+        if args.pfm_seq:
+            fasta.eprint("-p alone needs a sequence FASTA, %s is an averaged-structure directory or store: give -q, or -p with -q and both inputs" % args.inputs[0])
+            return 1
+        return main_profiles(args, engine, out)
     seq = bool(args.pfm_seq)
     option, pfm_file = ("-p", args.pfm_seq) if seq else ("-q", args.pfm_struct)
     letters, code_letters = (fasta.RNA, pack.RNA_LETTERS) if seq else (fasta.STRUCT, pack.STRUCT_LETTERS)

@@ -162,6 +162,14 @@ class HipEngine(object):
             self._staged2 = stream
         return self.ctx.occupancy_staged(ratio_tables, n_letters, stream.offsets, stream.lengths, which)
 
+    def occupancy_profile(self, stream, struct_tables, seq_tables=None):
+        """summed marginal likelihood ratios of an averaged-structure profile: structure tables
+        [n_motifs][m][7] of one width (pssm.Odds.struct_table, columns in the profile's stored order) over ``stream.profile``;
+        with ``seq_tables`` [n_motifs][m][8] joint mode, the letter chain over ``stream.codes`` times the marginals ->
+        (occ float64 [n_rec][n_motifs], windows int64 [n_rec])"""
+        self._stage(stream)
+        return self.ctx.occupancy_profile_staged(struct_tables, seq_tables, stream.offsets, stream.lengths)
+
     def hits_sum(self, stream, letter_table, struct_pssm, thr_seq, thr_struct, thr_sum, one_shot=True):
         """``hits`` of a motif with both parts, with the joint threshold decided on the device: a window is kept iff
         seq > thr_seq AND struct > thr_struct AND float64(round(float32 seq, 3)) + struct > thr_sum -- the printed

@@ -59,7 +59,7 @@
 extern "C" {
 #endif
 
-#define PFMSCAN_ABI_VERSION 22
+#define PFMSCAN_ABI_VERSION 23
 #define PFMSCAN_NCODE   8      /* columns of a letter table */
 #define PFMSCAN_SEP     7      /* separator / foreign-letter code */
 #define PFMSCAN_NSTRUCT 7      /* columns of a structure profile / structure PSSM */
@@ -1199,6 +1199,38 @@ int pfmscan_occupancy_profile_dev(pfmscan_ctx *ctx, const double *struct_tables,
 int pfmscan_occupancy_profile_staged(pfmscan_ctx *ctx, const double *struct_tables, const double *seq_tables, int n_motifs,
                                      int m, const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec, double *occ,
                                      int64_t *windows);
+
+/* ---- expected counts: the letters under every window, weighted by the window's likelihood ratio --------------------
+ * No counterpart in the reference.  The E-step of motif refinement: per record and motif a matrix [m][8] of
+ * expected letter counts per motif column, with no threshold.  No transcendental, no tolerance; tests/expect_rules.py
+ * restates it in numpy and the bits are compared.  Everything not said here is the occupancy above, unchanged: the ratio
+ * table R [m][8], n_letters 4 or 7, c_k = codes[s + k] & 7, and "a window that holds a foreign code has no term".
+ *   t_s, has_s    the term of window s of record r and whether it has one, exactly as for the occupancy.
+ *   occ_r         the record's occupancy under the motif: the bits pfmscan_occupancy_dev gives.
+ *   w_s           the weight of window s.  PFMSCAN_EXPECT_RATIO: w_s = t_s.  PFMSCAN_EXPECT_POSTERIOR: v = 1.0 / occ_r, one
+ *                 rounded division per record and motif, and w_s = t_s * v, one rounded product per window, never
+ *                 contracted (a division per window would give other bits); if occ_r is +0.0 (no window with a term, or
+ *                 every term zero) every w_s of the record is +0.0.  That rule and the skipped windows are the only special
+ *                 cases: subnormals stay, inf and NaN propagate into the record's cells.
+ *   E_r[k][c]     for k < m, c < n_letters: the values x_s = (has_s && (codes[s + k] & 7) == c) ? w_s : +0.0 over the
+ *                 record's n_win = max(L - m + 1, 0) windows in order, summed in the occupancy's left-aligned tree of fan-in
+ *                 PFMSCAN_OCC_FANIN anchored at the record's first window.  Columns c >= n_letters are +0.0; n_win = 0 gives
+ *                 +0.0 everywhere.  The bits do not depend on the batch, on where the record lies in the stream, on the
+ *                 launch geometry or on the scratch cap.
+ * exp double [n_rec][n_motifs][m][8]; occ double [n_rec][n_motifs] or NULL: the occupancy, the same bits as
+ * pfmscan_occupancy_*; windows int64 [n_rec] or NULL, as there.  ratio_tables, the record table and its check (a table that
+ * is not ascending, disjoint and inside the stream: PFMSCAN_E_BADARG before any kernel forms an address from it, nothing
+ * written), the one synchronisation of the _dev form, `which` of the _staged form and the error codes are those of
+ * pfmscan_occupancy_dev / _staged; a mode other than the two: PFMSCAN_E_BADARG.  Device scratch is bounded as there: block
+ * sums of blocks x (motifs x m x n_letters) doubles under the same cap, records, then cells and motifs, run in passes. */
+#define PFMSCAN_EXPECT_RATIO 0
+#define PFMSCAN_EXPECT_POSTERIOR 1
+int pfmscan_expect_dev(pfmscan_ctx *ctx, const double *ratio_tables, int n_motifs, int m, int n_letters, int mode,
+                       const uint8_t *d_codes, int64_t n_pos, const int64_t *d_rec_off, const int64_t *d_rec_len,
+                       int64_t n_rec, double *d_exp, double *d_occ, int64_t *d_windows);
+int pfmscan_expect_staged(pfmscan_ctx *ctx, int which, const double *ratio_tables, int n_motifs, int m, int n_letters,
+                          int mode, const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec, double *exp, double *occ,
+                          int64_t *windows);
 
 #ifdef __cplusplus
 }

@@ -22,7 +22,7 @@ NCODE = 8
 NSTRUCT = 7
 MAX_M = 64            # widest PFM of the tuned kernels and of PFM libraries
 MAX_WIDTH = 4096      # widest PFM accepted (wider than MAX_M: the plain rolled-loop kernel)
-ABI_VERSION = 22
+ABI_VERSION = 23
 
 # every symbol include/pfmscan.h declares (checked by tests/test_abi.py)
 SYMBOLS = [
@@ -58,11 +58,13 @@ SYMBOLS = [
     "pfmscan_variants_dev", "pfmscan_variants_staged",
     "pfmscan_occupancy_dev", "pfmscan_occupancy_staged",
     "pfmscan_occupancy_profile_dev", "pfmscan_occupancy_profile_staged",
+    "pfmscan_expect_dev", "pfmscan_expect_staged",
 ]
 PAIR_ROUTE_NONE, PAIR_ROUTE_FUSED, PAIR_ROUTE_TWO_PHASE, PAIR_ROUTE_DENSE, PAIR_ROUTE_CREDITS = range(5)   # Context.pair_sum_route()
 SITE_GROUP = 4096     # most hits of one group of the site profiles
 SITE_LIMBS = 66       # 64-bit limbs of one cell of a long accumulator (site profiles of a library)
 SITE_JOINT_COLS = 64  # columns of one LDS tile of the letter-pair counts (PFMSCAN_SITE_JOINT_COLS)
+EXPECT_RATIO, EXPECT_POSTERIOR = 0, 1   # weight of a window in the expected counts (PFMSCAN_EXPECT_*)
 OCC_FANIN = 32        # fan-in of the occupancy's summation tree (PFMSCAN_OCC_FANIN)
 MAX_COVER = 1024      # largest coverage of a row the averaging accepts
 AVG_OK, AVG_DOTBRACKET, AVG_UNCOVERED, AVG_COVER, AVG_BAD_TABLE = range(5)   # what a rejected averaging names
@@ -242,6 +244,8 @@ def load():
     L.pfmscan_occupancy_staged.argtypes = [vp, i32, vp, i32, i32, i32, vp, vp, i64, vp, vp]
     L.pfmscan_occupancy_profile_dev.argtypes = [vp, vp, vp, i32, i32, vp, vp, i32, i64, vp, vp, i64, vp, vp]
     L.pfmscan_occupancy_profile_staged.argtypes = [vp, vp, vp, i32, i32, vp, vp, i64, vp, vp]
+    L.pfmscan_expect_dev.argtypes = [vp, vp, i32, i32, i32, i32, vp, i64, vp, vp, i64, vp, vp, vp]
+    L.pfmscan_expect_staged.argtypes = [vp, i32, vp, i32, i32, i32, i32, vp, vp, i64, vp, vp, vp]
     L.pfmscan_tsv_format.argtypes = [ctypes.POINTER(TsvColumn), i32, i64, i64, vp, i64, ctypes.POINTER(i64), vp, ctypes.POINTER(i32), i32]
     for name in SYMBOLS:          # every other entry point returns a status
         if name not in ("pfmscan_ctx_destroy", "pfmscan_motif_destroy", "pfmscan_last_error", "pfmscan_library_destroy",
@@ -1727,6 +1731,27 @@ class Context(object):
         self._check(self._L.pfmscan_occupancy_profile_staged(self._h, _ptr(st), _ptr(sq), st.shape[0], st.shape[1], _ptr(rec_off),
                                                              _ptr(rec_len), rec_off.size, _ptr(occ), _ptr(windows)))
         return occ, windows
+
+    # -- expected counts (include/pfmscan.h: pfmscan_expect_*) ---------------------------------------------
+    def expect_dev(self, ratio_tables, n_letters, mode, d_codes, n_pos, d_rec_off, d_rec_len, n_rec, d_exp, d_occ=None, d_windows=None):
+        rt = self._ratio_tables(ratio_tables)
+        self._check(self._L.pfmscan_expect_dev(self._h, _ptr(rt), rt.shape[0], rt.shape[1], int(n_letters), int(mode), _ptr(d_codes), int(n_pos),
+                                               _ptr(d_rec_off), _ptr(d_rec_len), int(n_rec), _ptr(d_exp), _ptr(d_occ), _ptr(d_windows)))
+
+    def expect_staged(self, ratio_tables, n_letters, mode, rec_off, rec_len, which=0):
+        """-> exp float64 [n_rec][n_motifs][m][8], occ float64 [n_rec][n_motifs], windows int64 [n_rec] over the staged codes
+        (which = 0) or codes2 (1); mode EXPECT_RATIO or EXPECT_POSTERIOR"""
+        rt = self._ratio_tables(ratio_tables)
+        rec_off = np.ascontiguousarray(rec_off, dtype=np.int64)
+        rec_len = np.ascontiguousarray(rec_len, dtype=np.int64)
+        if rec_off.ndim != 1 or rec_off.shape != rec_len.shape:
+            raise ValueError("rec_off and rec_len must be lists of one length")
+        exp = np.zeros((rec_off.size, rt.shape[0], rt.shape[1], NCODE), dtype=np.float64)
+        occ = np.zeros((rec_off.size, rt.shape[0]), dtype=np.float64)
+        windows = np.zeros(rec_off.size, dtype=np.int64)
+        self._check(self._L.pfmscan_expect_staged(self._h, int(which), _ptr(rt), rt.shape[0], rt.shape[1], int(n_letters), int(mode),
+                                                  _ptr(rec_off), _ptr(rec_len), rec_off.size, _ptr(exp), _ptr(occ), _ptr(windows)))
+        return exp, occ, windows
 
     def time_scan_dev(self, motif, d_codes, d_profile, profile_dtype, n_pos, d_out_seq, d_out_struct,
                       stream=None, warmup=1, iters=5):

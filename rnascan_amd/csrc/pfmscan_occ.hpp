@@ -1,0 +1,69 @@
+// pfmscan_occ.hpp -- what the occupancy (pfmscan_occupancy.hip) and the expected counts (pfmscan_expect.hip) share: the
+// arguments of a pass, the bisection of a prefix table, and the host side of levels 1 and up of the summation tree.
+#pragma once
+#include <cstdint>
+
+#include "pfmscan_ctx.hpp"
+
+namespace pfmscan {
+
+constexpr int OCC_FANIN = PFMSCAN_OCC_FANIN;
+constexpr int64_t OCC_SCRATCH_DOUBLES = int64_t(1) << 25;   // block sums of one pass (256 MB); PFMSCAN_OCC_SCRATCH_DOUBLES overrides
+static_assert(OCC_FANIN == 32, "a block is the 32 windows one lane walks; the masks are 32 bits wide");
+
+struct OccArgs {
+    const uint8_t *codes;        // [n_pos]
+    int64_t n_pos;
+    const int64_t *rec_off, *rec_len;   // [n_rec]
+    const int64_t *blk_start;    // [n_rec + 1] prefix of ceil(n_win / 32)
+    const int64_t *grp_start;    // [n_rec + 1] prefix of ceil(blocks / 32)
+    int64_t r0, r1;              // records of this pass
+    int64_t blk_base, n_blk;     // blk_start[r0], blocks of the pass
+    int64_t grp_base, n_grp;
+    const double *tables;        // [n_motifs][m][8] device
+    int m, n_letters;
+    int q_first, n_q;            // columns of this pass (n_q = row stride of the scratch): motifs, or cells of motifs (cell_nl)
+    int chunk;                   // motifs per LDS chunk (gridDim.y chunks)
+    int n_motifs;
+    double *bs;                  // [n_blk][n_q] block sums
+    double *gs;                  // [n_grp][n_q] level-1 sums, folded in place by k_occ_finish
+    int *bcnt;                   // [n_blk] windows with a term, or null
+    int *gcnt;                   // [n_grp]
+    double *occ;                 // [n_rec][out_stride]: column q_first + q of record r, see cell_nl
+    int64_t out_stride;          // doubles per record of occ
+    int cell_nl;                 // 0: column x is stored at x.  n_letters: column x = row * n_letters + c is stored at row * 8 + c
+    int64_t *windows;            // [n_rec] or null
+    // averaged-structure profiles (k_occ_profile_blocks)
+    const unsigned char *profile;   // [n_pos][7] float or double, 16-byte aligned
+    const int64_t *run_start;    // [n_rec + 1] prefix of ceil(blocks / OCCP_RUN)
+    int64_t run_base;            // run_start[r0]
+    int64_t *run_rec;            // [runs of the pass] the record of every run (k_occ_run_records)
+};
+
+// the record of element e of a prefix table: the last r in [r0, r1) with start[r] <= e (start[r1] > e)
+__device__ __forceinline__ int64_t occ_record(const int64_t *__restrict__ start, int64_t r0, int64_t r1, int64_t e)
+{
+    int64_t lo = r0 + 1, hi = r1;
+    while (lo < hi) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        if (start[mid] > e) hi = mid;
+        else lo = mid + 1;
+    }
+    return lo - 1;
+}
+
+// pfmscan_occupancy.hip.  Levels 1 and up of a pass whose block sums lie in a.bs: k_occ_level1 (when the pass has blocks)
+// and k_occ_finish on st; n_q independent columns per record, one writer per cell of a.occ.
+int occ_launch_upper(pfmscan_ctx *ctx, const OccArgs &a, hipStream_t st);
+// the scratch cap in doubles: OCC_SCRATCH_DOUBLES unless the environment says otherwise
+int64_t occ_scratch_cap();
+int occ_check(pfmscan_ctx *ctx, const char *who, const double *ratio_tables, int n_motifs, int m, int n_letters, int64_t n_pos, int64_t n_rec);
+// ascending, disjoint, inside [0, n_pos)
+int occ_check_records(pfmscan_ctx *ctx, const char *who, const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec, int64_t n_pos);
+// the occupancy of letter strings on st, without waiting: rec_off / rec_len are HOST copies, already checked, d_rec_off /
+// d_rec_len the same on the device
+int occ_run_letters(pfmscan_ctx *ctx, const char *who, const double *ratio_tables, int n_motifs, int m, int n_letters, const uint8_t *d_codes,
+                    int64_t n_pos, const int64_t *rec_off, const int64_t *rec_len, const int64_t *d_rec_off, const int64_t *d_rec_len,
+                    int64_t n_rec, double *d_occ, int64_t *d_windows, hipStream_t st);
+
+}  // namespace pfmscan

@@ -18,7 +18,8 @@
 //   k_occ_finish       levels 2 and up: a thread per (record, motif) folds the record's level-1 sums in place, in order, and
 //                      writes the cell.  One writer per cell.
 // The block sums go through scratch that is bounded (OCC_SCRATCH_DOUBLES) by running the records, and if one record alone is
-// too long the motifs, in passes.
+// too long the motifs, in passes.  What the expected counts (pfmscan_expect.hip) share -- the arguments of a pass, the bisection
+// and levels 1 and up, whose n_q columns are then the cells of motifs -- is declared in pfmscan_occ.hpp.
 //
 // Averaged-structure profiles (include/pfmscan.h "occupancy on averaged-structure profiles"): the term of a
 // window is the product over k of the marginal d(s + k, k) = sum_c r[s + k][c] * S[k][c] (7 rounded products, 6 rounded
@@ -39,47 +40,18 @@
 
 #include "pfmscan_ctx.hpp"
 #include "pfmscan_device.hpp"
+#include "pfmscan_occ.hpp"
 
 #pragma clang fp contract(off)   // the product chain and the sums are rounded one operation at a time: never an FMA
 
 namespace pfmscan {
 
-constexpr int OCC_FANIN = PFMSCAN_OCC_FANIN;
 // table cells of one chunk of motifs, padding included (occ_chunk).  Measured: 256 motifs of w = 12 at C2 size take 70.4 ms
 // with 2048, 74.8 with 4096, 72.1 with 1024 (profiles/occupancy/NOTES.md)
 constexpr int OCC_LDS_DOUBLES = 2048;
 static_assert(OCC_LDS_DOUBLES >= PFMSCAN_MAX_M * PFMSCAN_NSTRUCT, "one motif of the widest kind fits");
 constexpr int OCC_CODE_DWORDS = 25;                   // aligned dwords that cover 3 + 32 + PFMSCAN_MAX_M - 1 bytes
-constexpr int64_t OCC_SCRATCH_DOUBLES = int64_t(1) << 25;   // block sums of one pass (256 MB); PFMSCAN_OCC_SCRATCH_DOUBLES overrides
-static_assert(OCC_FANIN == 32, "a block is the 32 windows one lane walks; the masks below are 32 bits wide");
 static_assert(OCC_CODE_DWORDS * 4 >= 3 + OCC_FANIN + PFMSCAN_MAX_M - 1, "strip");
-
-struct OccArgs {
-    const uint8_t *codes;        // [n_pos]
-    int64_t n_pos;
-    const int64_t *rec_off, *rec_len;   // [n_rec]
-    const int64_t *blk_start;    // [n_rec + 1] prefix of ceil(n_win / 32)
-    const int64_t *grp_start;    // [n_rec + 1] prefix of ceil(blocks / 32)
-    int64_t r0, r1;              // records of this pass
-    int64_t blk_base, n_blk;     // blk_start[r0], blocks of the pass
-    int64_t grp_base, n_grp;
-    const double *tables;        // [n_motifs][m][8] device
-    int m, n_letters;
-    int q_first, n_q;            // motifs of this pass (n_q = row stride of the scratch)
-    int chunk;                   // motifs per LDS chunk (gridDim.y chunks)
-    int n_motifs;
-    double *bs;                  // [n_blk][n_q] block sums
-    double *gs;                  // [n_grp][n_q] level-1 sums, folded in place by k_occ_finish
-    int *bcnt;                   // [n_blk] windows with a term, or null
-    int *gcnt;                   // [n_grp]
-    double *occ;                 // [n_rec][n_motifs]
-    int64_t *windows;            // [n_rec] or null
-    // averaged-structure profiles (k_occ_profile_blocks)
-    const unsigned char *profile;   // [n_pos][7] float or double, 16-byte aligned
-    const int64_t *run_start;    // [n_rec + 1] prefix of ceil(blocks / OCCP_RUN)
-    int64_t run_base;            // run_start[r0]
-    int64_t *run_rec;            // [runs of the pass] the record of every run (k_occ_run_records)
-};
 
 // dwords of a lane's strip of codes: the aligned dwords that cover 3 + 32 + m - 1 bytes, made odd so that the byte reads of
 // the 32 lanes of a group fall on 32 banks
@@ -89,18 +61,6 @@ __host__ __device__ inline int occ_ls(int nq, int qn)
 {
     int ls = (nq + qn - 1) / qn * qn;
     return ls % 16 == 0 ? ls + 2 : ls;                // the letters of a row must not all start on one bank
-}
-
-// the record of element e of a prefix table: the last r in [r0, r1) with start[r] <= e (start[r1] > e)
-__device__ __forceinline__ int64_t occ_record(const int64_t *__restrict__ start, int64_t r0, int64_t r1, int64_t e)
-{
-    int64_t lo = r0 + 1, hi = r1;
-    while (lo < hi) {
-        const int64_t mid = lo + ((hi - lo) >> 1);
-        if (start[mid] > e) hi = mid;
-        else lo = mid + 1;
-    }
-    return lo - 1;
 }
 
 // QN adjacent motifs' cells of one (row, letter): 16-byte reads (ls is even and q a multiple of QN)
@@ -265,7 +225,8 @@ __global__ __launch_bounds__(BLOCK) void k_occ_finish(const OccArgs a)
         }
         res = x[0];
     }
-    a.occ[r * a.n_motifs + a.q_first + q] = res;
+    const int x = a.q_first + q;                                   // the column; a cell of a motif is stored under a letter stride of 8
+    a.occ[r * a.out_stride + (a.cell_nl ? x / a.cell_nl * 8 + x % a.cell_nl : x)] = res;
     if (a.windows && a.bcnt && q == 0) {
         int64_t c = 0;
         const int64_t ng = a.grp_start[r + 1] - a.grp_start[r];
@@ -435,6 +396,24 @@ __global__ __launch_bounds__(BLOCK) void k_occ_profile_blocks(const OccArgs a, c
     }
 }
 
+int occ_launch_upper(pfmscan_ctx *ctx, const OccArgs &a, hipStream_t st)
+{
+    hipError_t e;
+    if (a.n_blk > 0) {
+        hipLaunchKernelGGL(k_occ_level1, dim3((unsigned)((a.n_grp * a.n_q + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, a);
+        if ((e = hipGetLastError()) != hipSuccess) return fail_hip(ctx, e, "k_occ_level1");
+    }
+    hipLaunchKernelGGL(k_occ_finish, dim3((unsigned)(((a.r1 - a.r0) * a.n_q + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, a);
+    if ((e = hipGetLastError()) != hipSuccess) return fail_hip(ctx, e, "k_occ_finish");
+    return PFMSCAN_OK;
+}
+
+int64_t occ_scratch_cap()
+{
+    if (const char *e = std::getenv("PFMSCAN_OCC_SCRATCH_DOUBLES")) return std::max<int64_t>(1, std::atoll(e));
+    return OCC_SCRATCH_DOUBLES;
+}
+
 static int occ_qn(int nq) { return nq >= 8 ? 8 : nq >= 4 ? 4 : nq >= 2 ? 2 : 1; }
 
 
@@ -507,8 +486,7 @@ static int occ_run(pfmscan_ctx *ctx, const char *who, const double *ratio_tables
         run[r + 1] = run[r] + (nb + OCCP_RUN - 1) / OCCP_RUN;
         max_blk = std::max(max_blk, nb);
     }
-    int64_t cap = OCC_SCRATCH_DOUBLES;
-    if (const char *e = std::getenv("PFMSCAN_OCC_SCRATCH_DOUBLES")) cap = std::max<int64_t>(1, std::atoll(e));
+    const int64_t cap = occ_scratch_cap();
     // motifs per pass: all of them unless the longest record's block sums alone pass the cap; then records per pass
     const int n_q_max = (int)std::min<int64_t>(n_motifs, std::max<int64_t>(1, cap / std::max<int64_t>(max_blk, 1)));
     const int64_t blk_cap = std::max<int64_t>(cap / n_q_max, 1), rec_cap = std::max<int64_t>((int64_t(1) << 30) / n_q_max, 1);
@@ -554,6 +532,7 @@ static int occ_run(pfmscan_ctx *ctx, const char *who, const double *ratio_tables
     a.bs = (double *)ctx->occ_bs.p;
     a.gs = (double *)ctx->occ_gs.p;
     a.occ = d_occ;
+    a.out_stride = n_motifs;
     a.windows = d_windows;
     for (int q0 = 0; q0 < n_motifs; q0 += n_q_max) {
         a.q_first = q0;
@@ -576,17 +555,14 @@ static int occ_run(pfmscan_ctx *ctx, const char *who, const double *ratio_tables
                 if (pf) hipLaunchKernelGGL(k_occ_run_records, dim3((unsigned)((a.r1 - a.r0 + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, a);
                 e = pf ? occ_launch_profile(a, pf->dtype, ratio_tables != nullptr, run[a.r1] - a.run_base, d_stab, st) : occ_launch_blocks(a, st);
                 if (e != hipSuccess) return fail_hip(ctx, e, pf ? "k_occ_profile_blocks" : "k_occ_blocks");
-                hipLaunchKernelGGL(k_occ_level1, dim3((unsigned)((a.n_grp * a.n_q + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, a);
-                if ((e = hipGetLastError()) != hipSuccess) return fail_hip(ctx, e, "k_occ_level1");
             }
-            hipLaunchKernelGGL(k_occ_finish, dim3((unsigned)(((a.r1 - a.r0) * a.n_q + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, a);
-            if ((e = hipGetLastError()) != hipSuccess) return fail_hip(ctx, e, "k_occ_finish");
+            if ((rc = occ_launch_upper(ctx, a, st))) return rc;
         }
     }
     return PFMSCAN_OK;
 }
 
-static int occ_check(pfmscan_ctx *ctx, const char *who, const double *ratio_tables, int n_motifs, int m, int n_letters, int64_t n_pos, int64_t n_rec)
+int occ_check(pfmscan_ctx *ctx, const char *who, const double *ratio_tables, int n_motifs, int m, int n_letters, int64_t n_pos, int64_t n_rec)
 {
     if (!ctx) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": NULL ctx");
     if (m < 1 || m > PFMSCAN_MAX_M)
@@ -598,7 +574,7 @@ static int occ_check(pfmscan_ctx *ctx, const char *who, const double *ratio_tabl
 }
 
 // ascending, disjoint, inside [0, n_pos)
-static int occ_check_records(pfmscan_ctx *ctx, const char *who, const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec, int64_t n_pos)
+int occ_check_records(pfmscan_ctx *ctx, const char *who, const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec, int64_t n_pos)
 {
     int64_t end = 0;
     for (int64_t r = 0; r < n_rec; ++r) {
@@ -607,6 +583,13 @@ static int occ_check_records(pfmscan_ctx *ctx, const char *who, const int64_t *r
         end = rec_off[r] + rec_len[r];
     }
     return PFMSCAN_OK;
+}
+
+int occ_run_letters(pfmscan_ctx *ctx, const char *who, const double *ratio_tables, int n_motifs, int m, int n_letters, const uint8_t *d_codes,
+                    int64_t n_pos, const int64_t *rec_off, const int64_t *rec_len, const int64_t *d_rec_off, const int64_t *d_rec_len,
+                    int64_t n_rec, double *d_occ, int64_t *d_windows, hipStream_t st)
+{
+    return occ_run(ctx, who, ratio_tables, n_motifs, m, n_letters, d_codes, n_pos, rec_off, rec_len, d_rec_off, d_rec_len, n_rec, d_occ, d_windows, st);
 }
 
 }  // namespace pfmscan

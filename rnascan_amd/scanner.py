@@ -162,6 +162,17 @@ class HipEngine(object):
             self._staged2 = stream
         return self.ctx.occupancy_staged(ratio_tables, n_letters, stream.offsets, stream.lengths, which)
 
+    def expect(self, stream, ratio_tables, n_letters, mode, which=0):
+        """expected letter counts per motif column: ratio tables [n_motifs][m][8] of one width over the stream's
+        codes (which = 0) or codes2 (1), every window weighted by its likelihood ratio (mode _lib.EXPECT_RATIO) or by that
+        ratio over the record's occupancy (_lib.EXPECT_POSTERIOR) ->
+        (exp float64 [n_rec][n_motifs][m][8], occ float64 [n_rec][n_motifs], windows int64 [n_rec])"""
+        self._stage(stream)
+        if which == 1 and self._staged2 is not stream:
+            self.ctx.stage_codes2(stream.codes2)
+            self._staged2 = stream
+        return self.ctx.expect_staged(ratio_tables, n_letters, mode, stream.offsets, stream.lengths, which)
+
     def occupancy_profile(self, stream, struct_tables, seq_tables=None):
         """summed marginal likelihood ratios of an averaged-structure profile: structure tables
         [n_motifs][m][7] of one width (pssm.Odds.struct_table, columns in the profile's stored order) over ``stream.profile``;

@@ -59,7 +59,7 @@
 extern "C" {
 #endif
 
-#define PFMSCAN_ABI_VERSION 23
+#define PFMSCAN_ABI_VERSION 24
 #define PFMSCAN_NCODE   8      /* columns of a letter table */
 #define PFMSCAN_SEP     7      /* separator / foreign-letter code */
 #define PFMSCAN_NSTRUCT 7      /* columns of a structure profile / structure PSSM */
@@ -1231,6 +1231,48 @@ int pfmscan_expect_dev(pfmscan_ctx *ctx, const double *ratio_tables, int n_motif
 int pfmscan_expect_staged(pfmscan_ctx *ctx, int which, const double *ratio_tables, int n_motifs, int m, int n_letters,
                           int mode, const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec, double *exp, double *occ,
                           int64_t *windows);
+
+/* ---- expected counts on averaged-structure profiles: weighted row sums ---------------------------------------------
+ * No counterpart in the reference.  The expected counts above for a stream whose structure is a profile r [n_pos][7]: per
+ * record and motif the weighted sum of the profile's ROWS under every motif column -- the threshold-free form
+ * of what the site profiles sum under hits; on one-hot rows it is the letters' expected count.  (The posterior of the letter
+ * given the motif, r * S / d, is a different quantity and is not computed.)  No transcendental, no tolerance;
+ * tests/expect_profile_rules.py restates it in numpy and the bits are compared.  Everything not said here is the occupancy
+ * on averaged-structure profiles and the expected counts above, unchanged: S [m][7] in the profile's STORED column order,
+ * R [m][8] over the 4 RNA letters, the marginal d(x, k) of 7 rounded products and 6 rounded additions (float rows widened
+ * first), the tree of fan-in PFMSCAN_OCC_FANIN anchored at the record's first window (the first value of a block is copied,
+ * not added to zero; a lone window is the record's sum as it is; every level is padded with +0.0 as the rules pad it), the
+ * two modes, v = 1.0 / occ_r (one rounded division per record and motif), w_s = t_s * v (one rounded product per window), and
+ * "occ_r == 0.0 makes every weight of the record +0.0".
+ *   t_s, has_s    by the tables that are given (both NULL: PFMSCAN_E_BADARG):
+ *                 struct_tables only: the structure-only chain of marginals; every window inside the record has a term, the
+ *                   codes are not read; occ, windows are the bits of pfmscan_occupancy_profile_* (structure only).
+ *                 both: the joint chain -- the letters, then m marginals; a window with a code >= 4 has no term; occ, windows
+ *                   are the bits of pfmscan_occupancy_profile_* (joint).
+ *                 seq_tables only: the letter chain over the 4 RNA letters; occ, windows are the bits of
+ *                   pfmscan_occupancy_* / pfmscan_expect_*.
+ *   exp_struct    double [n_rec][n_motifs][m][8], always.  For k < m, c < 7 (stored column order): the values
+ *                 x_s = has_s ? w_s * r[s + k][c] : +0.0, one rounded product each, over the record's n_win = max(L - m + 1, 0)
+ *                 windows in order, summed in the tree.  Column 7 is +0.0; n_win = 0 gives +0.0 everywhere.
+ *   exp_seq       double [n_rec][n_motifs][m][8] or NULL; only where seq_tables is given (else PFMSCAN_E_BADARG).  The cell of
+ *                 the expected counts above, x_s = (has_s && (codes[s + k] & 7) == c) ? w_s : +0.0 for c < 4, with this call's
+ *                 weights; with seq_tables alone, bit for bit what pfmscan_expect_dev returns.
+ * No nan_to_num, no validity check: IEEE as it falls.  A negative or NaN profile cell goes where arithmetic takes it, and
+ * w * (-0.0) keeps its sign into the tree.  The separator row behind a record is never read as data.  The bits depend on the
+ * row dtype and the stored column order and on nothing else: not on the batch, the position in the stream, the launch
+ * geometry, the scratch cap or the _dev / _staged form.
+ * Pointers, alignment, the record table and its check (PFMSCAN_E_BADARG before any kernel forms an address from it, nothing
+ * written), the one synchronisation of the _dev form and the error codes are those of pfmscan_occupancy_profile_* and
+ * pfmscan_expect_*; d_profile is needed in every mode, d_codes where seq_tables is given.  A bad mode or profile_dtype:
+ * PFMSCAN_E_BADARG, outputs untouched.  Device scratch is bounded as there: records, then matrix rows (the 7 + 4 cells of a
+ * row (motif, k) stay together) and with them motifs, run in passes. */
+int pfmscan_expect_profile_dev(pfmscan_ctx *ctx, const double *struct_tables, const double *seq_tables, int n_motifs, int m,
+                               int mode, const uint8_t *d_codes, const void *d_profile, int profile_dtype, int64_t n_pos,
+                               const int64_t *d_rec_off, const int64_t *d_rec_len, int64_t n_rec, double *d_exp_struct,
+                               double *d_exp_seq, double *d_occ, int64_t *d_windows);
+int pfmscan_expect_profile_staged(pfmscan_ctx *ctx, const double *struct_tables, const double *seq_tables, int n_motifs, int m,
+                                  int mode, const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec, double *exp_struct,
+                                  double *exp_seq, double *occ, int64_t *windows);
 
 #ifdef __cplusplus
 }

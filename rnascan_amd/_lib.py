@@ -22,7 +22,7 @@ NCODE = 8
 NSTRUCT = 7
 MAX_M = 64            # widest PFM of the tuned kernels and of PFM libraries
 MAX_WIDTH = 4096      # widest PFM accepted (wider than MAX_M: the plain rolled-loop kernel)
-ABI_VERSION = 23
+ABI_VERSION = 24
 
 # every symbol include/pfmscan.h declares (checked by tests/test_abi.py)
 SYMBOLS = [
@@ -59,6 +59,7 @@ SYMBOLS = [
     "pfmscan_occupancy_dev", "pfmscan_occupancy_staged",
     "pfmscan_occupancy_profile_dev", "pfmscan_occupancy_profile_staged",
     "pfmscan_expect_dev", "pfmscan_expect_staged",
+    "pfmscan_expect_profile_dev", "pfmscan_expect_profile_staged",
 ]
 PAIR_ROUTE_NONE, PAIR_ROUTE_FUSED, PAIR_ROUTE_TWO_PHASE, PAIR_ROUTE_DENSE, PAIR_ROUTE_CREDITS = range(5)   # Context.pair_sum_route()
 SITE_GROUP = 4096     # most hits of one group of the site profiles
@@ -246,6 +247,8 @@ def load():
     L.pfmscan_occupancy_profile_staged.argtypes = [vp, vp, vp, i32, i32, vp, vp, i64, vp, vp]
     L.pfmscan_expect_dev.argtypes = [vp, vp, i32, i32, i32, i32, vp, i64, vp, vp, i64, vp, vp, vp]
     L.pfmscan_expect_staged.argtypes = [vp, i32, vp, i32, i32, i32, i32, vp, vp, i64, vp, vp, vp]
+    L.pfmscan_expect_profile_dev.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, i32, i64, vp, vp, i64, vp, vp, vp, vp]
+    L.pfmscan_expect_profile_staged.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, i64, vp, vp, vp, vp]
     L.pfmscan_tsv_format.argtypes = [ctypes.POINTER(TsvColumn), i32, i64, i64, vp, i64, ctypes.POINTER(i64), vp, ctypes.POINTER(i32), i32]
     for name in SYMBOLS:          # every other entry point returns a status
         if name not in ("pfmscan_ctx_destroy", "pfmscan_motif_destroy", "pfmscan_last_error", "pfmscan_library_destroy",
@@ -1752,6 +1755,41 @@ class Context(object):
         self._check(self._L.pfmscan_expect_staged(self._h, int(which), _ptr(rt), rt.shape[0], rt.shape[1], int(n_letters), int(mode),
                                                   _ptr(rec_off), _ptr(rec_len), rec_off.size, _ptr(exp), _ptr(occ), _ptr(windows)))
         return exp, occ, windows
+
+    # -- expected counts on averaged-structure profiles (include/pfmscan.h: pfmscan_expect_profile_*) ------
+    @staticmethod
+    def _expect_profile_tables(struct_tables, seq_tables):
+        if struct_tables is None and seq_tables is None:
+            raise ValueError("struct_tables and seq_tables are both None")
+        if struct_tables is None:
+            return None, Context._ratio_tables(seq_tables)
+        return Context._profile_tables(struct_tables, seq_tables)
+
+    def expect_profile_dev(self, struct_tables, seq_tables, mode, d_codes, d_profile, profile_dtype, n_pos, d_rec_off, d_rec_len, n_rec,
+                           d_exp_struct, d_exp_seq=None, d_occ=None, d_windows=None):
+        st, sq = self._expect_profile_tables(struct_tables, seq_tables)
+        n_motifs, m = (st if st is not None else sq).shape[:2]
+        self._check(self._L.pfmscan_expect_profile_dev(self._h, _ptr(st), _ptr(sq), n_motifs, m, int(mode), _ptr(d_codes), _ptr(d_profile),
+                                                       int(profile_dtype), int(n_pos), _ptr(d_rec_off), _ptr(d_rec_len), int(n_rec),
+                                                       _ptr(d_exp_struct), _ptr(d_exp_seq), _ptr(d_occ), _ptr(d_windows)))
+
+    def expect_profile_staged(self, struct_tables, seq_tables, mode, rec_off, rec_len):
+        """-> exp_struct float64 [n_rec][n_motifs][m][8], exp_seq the same or None (no seq_tables), occ float64
+        [n_rec][n_motifs], windows int64 [n_rec] over the staged profile (and codes where seq_tables is given); the weights
+        come from struct_tables [n_motifs][m][7], seq_tables [n_motifs][m][8] or both; mode EXPECT_RATIO or EXPECT_POSTERIOR"""
+        st, sq = self._expect_profile_tables(struct_tables, seq_tables)
+        n_motifs, m = (st if st is not None else sq).shape[:2]
+        rec_off = np.ascontiguousarray(rec_off, dtype=np.int64)
+        rec_len = np.ascontiguousarray(rec_len, dtype=np.int64)
+        if rec_off.ndim != 1 or rec_off.shape != rec_len.shape:
+            raise ValueError("rec_off and rec_len must be lists of one length")
+        exp_struct = np.zeros((rec_off.size, n_motifs, m, NCODE), dtype=np.float64)
+        exp_seq = None if sq is None else np.zeros((rec_off.size, n_motifs, m, NCODE), dtype=np.float64)
+        occ = np.zeros((rec_off.size, n_motifs), dtype=np.float64)
+        windows = np.zeros(rec_off.size, dtype=np.int64)
+        self._check(self._L.pfmscan_expect_profile_staged(self._h, _ptr(st), _ptr(sq), n_motifs, m, int(mode), _ptr(rec_off), _ptr(rec_len),
+                                                          rec_off.size, _ptr(exp_struct), _ptr(exp_seq), _ptr(occ), _ptr(windows)))
+        return exp_struct, exp_seq, occ, windows
 
     def time_scan_dev(self, motif, d_codes, d_profile, profile_dtype, n_pos, d_out_seq, d_out_struct,
                       stream=None, warmup=1, iters=5):

@@ -47,6 +47,13 @@ __global__ __launch_bounds__(BLOCK) void k_exp_inverse(const double *__restrict_
     inv[i] = o == 0.0 ? -1.0 : 1.0 / o;
 }
 
+int exp_launch_inverse(pfmscan_ctx *ctx, const double *d_occ, double *d_inv, int64_t n, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_exp_inverse, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, d_occ, d_inv, n);
+    const hipError_t e = hipGetLastError();
+    return e != hipSuccess ? fail_hip(ctx, e, "k_exp_inverse") : PFMSCAN_OK;
+}
+
 // the record of the first block of every workgroup of k_exp_blocks, so that a workgroup finds its records with two round trips
 // to memory and a short walk instead of a bisection of ~17 dependent loads (as k_occ_run_records does for the profile kernel)
 __global__ __launch_bounds__(BLOCK) void k_exp_group_records(const OccArgs a, int64_t *__restrict__ wg_rec)
@@ -147,9 +154,7 @@ static int exp_run(pfmscan_ctx *ctx, const char *who, const double *ratio_tables
     const double *d_inv = nullptr;
     if (posterior) {
         if ((rc = ensure(ctx, ctx->exp_inv, (size_t)pairs * 8))) return rc;
-        hipLaunchKernelGGL(k_exp_inverse, dim3((unsigned)((pairs + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, d_occ, (double *)ctx->exp_inv.p, pairs);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail_hip(ctx, e, "k_exp_inverse");
+        if ((rc = exp_launch_inverse(ctx, d_occ, (double *)ctx->exp_inv.p, pairs, st))) return rc;
         d_inv = (const double *)ctx->exp_inv.p;
     }
     // the columns >= n_letters of every matrix row are +0.0; every other cell is written by k_occ_finish

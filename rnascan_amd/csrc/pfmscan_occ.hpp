@@ -1,5 +1,7 @@
-// pfmscan_occ.hpp -- what the occupancy (pfmscan_occupancy.hip) and the expected counts (pfmscan_expect.hip) share: the
-// arguments of a pass, the bisection of a prefix table, and the host side of levels 1 and up of the summation tree.
+// pfmscan_occ.hpp -- what the occupancy (pfmscan_occupancy.hip) and the expected counts (pfmscan_expect.hip,
+// pfmscan_expect_profile.hip) share: the arguments of a pass, the bisection of a prefix table, the host side of levels 1 and
+// up of the summation tree, and for averaged-structure profiles the geometry of a run, the loads of its rows and the
+// marginal of a row (one definition: k_occ_profile_blocks and k_expp_blocks make the same bits of it).
 #pragma once
 #include <cstdint>
 
@@ -52,7 +54,67 @@ __device__ __forceinline__ int64_t occ_record(const int64_t *__restrict__ start,
     return lo - 1;
 }
 
-// pfmscan_occupancy.hip.  Levels 1 and up of a pass whose block sums lie in a.bs: k_occ_level1 (when the pass has blocks)
+// ---- averaged-structure profiles: what the level-0 kernels of both files share -----------------------------------------
+constexpr int OCCP_RUN = 8;                                        // blocks of a workgroup's run
+constexpr int OCCP_WIN = OCCP_RUN * OCC_FANIN;                     // its windows: a lane each
+constexpr int OCCP_ROWS = OCCP_WIN + PFMSCAN_MAX_M - 1;            // rows it stages at most
+constexpr int OCCP_TS = OCCP_RUN * (OCC_FANIN + 1);                // doubles of one motif's terms in LDS: window w at w + w / 32
+constexpr int OCCP_CHUNK = 32;                                     // motifs a workgroup walks over the rows it staged
+static_assert(OCCP_WIN == BLOCK, "a lane per window of the run");
+
+// the aligned 16 bytes at byte_off; the stream's last vector may be cut short (rows are a multiple of 4 bytes)
+__device__ __forceinline__ uint4 occp_load(const unsigned char *__restrict__ base, int64_t byte_off, int64_t total_bytes)
+{
+    uint4 v = make_uint4(0u, 0u, 0u, 0u);
+    if (byte_off + 16 <= total_bytes) {
+        v = *reinterpret_cast<const uint4 *>(base + byte_off);
+    } else {
+        const uint32_t *p = reinterpret_cast<const uint32_t *>(base + byte_off);
+        const int64_t n = (total_bytes - byte_off) / 4;
+        if (n > 0) v.x = p[0];
+        if (n > 1) v.y = p[1];
+        if (n > 2) v.z = p[2];
+    }
+    return v;
+}
+
+// the cells of one 16-byte vector, widened (exact)
+__device__ __forceinline__ void occp_cells(const uint4 v, double (&d)[4], float)
+{
+    d[0] = (double)__uint_as_float(v.x);
+    d[1] = (double)__uint_as_float(v.y);
+    d[2] = (double)__uint_as_float(v.z);
+    d[3] = (double)__uint_as_float(v.w);
+}
+__device__ __forceinline__ void occp_cells(const uint4 v, double (&d)[2], double)
+{
+    d[0] = __hiloint2double((int)v.y, (int)v.x);
+    d[1] = __hiloint2double((int)v.w, (int)v.z);
+}
+
+// the marginal of row x under table row s: 7 rounded products, 6 rounded additions, ascending.  Every file that includes
+// this header compiles under `#pragma clang fp contract(off)`: nothing here is fused.
+__device__ __forceinline__ double occp_marginal(const double (&x)[7], const double *__restrict__ s)
+{
+#pragma clang fp contract(off)
+    double d = x[0] * s[0];
+#pragma unroll
+    for (int c = 1; c < 7; ++c) d = d + x[c] * s[c];
+    return d;
+}
+
+// what level 0 reads when the stream is an averaged-structure profile: its rows and the structure tables (HOST double
+// [n_motifs][m][7]); the letter tables and the codes are then those of joint mode, or null
+struct OccProfile {
+    const double *struct_tables;
+    const void *d_profile;
+    int dtype;
+};
+
+// pfmscan_occupancy.hip.  k_occ_run_records on st: the record of every run of the pass a describes (a.run_rec, from
+// a.run_start / a.run_base over records a.r0 .. a.r1)
+void occ_launch_run_records(const OccArgs &a, hipStream_t st);
+// Levels 1 and up of a pass whose block sums lie in a.bs: k_occ_level1 (when the pass has blocks)
 // and k_occ_finish on st; n_q independent columns per record, one writer per cell of a.occ.
 int occ_launch_upper(pfmscan_ctx *ctx, const OccArgs &a, hipStream_t st);
 // the scratch cap in doubles: OCC_SCRATCH_DOUBLES unless the environment says otherwise
@@ -65,5 +127,11 @@ int occ_check_records(pfmscan_ctx *ctx, const char *who, const int64_t *rec_off,
 int occ_run_letters(pfmscan_ctx *ctx, const char *who, const double *ratio_tables, int n_motifs, int m, int n_letters, const uint8_t *d_codes,
                     int64_t n_pos, const int64_t *rec_off, const int64_t *rec_len, const int64_t *d_rec_off, const int64_t *d_rec_len,
                     int64_t n_rec, double *d_occ, int64_t *d_windows, hipStream_t st);
+// the same on an averaged-structure profile: structure only (seq_tables null: d_codes is not read) or joint
+int occ_run_profile(pfmscan_ctx *ctx, const char *who, const OccProfile &pf, const double *seq_tables, int n_motifs, int m, const uint8_t *d_codes,
+                    int64_t n_pos, const int64_t *rec_off, const int64_t *rec_len, const int64_t *d_rec_off, const int64_t *d_rec_len,
+                    int64_t n_rec, double *d_occ, int64_t *d_windows, hipStream_t st);
+// pfmscan_expect.hip.  k_exp_inverse on st: inv[i] = 1.0 / occ[i], one rounded division each; -1.0 where occ[i] == 0.0
+int exp_launch_inverse(pfmscan_ctx *ctx, const double *d_occ, double *d_inv, int64_t n, hipStream_t st);
 
 }  // namespace pfmscan

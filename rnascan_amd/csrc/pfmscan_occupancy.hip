@@ -235,53 +235,7 @@ __global__ __launch_bounds__(BLOCK) void k_occ_finish(const OccArgs a)
     }
 }
 
-// ---- level 0 on averaged-structure profiles ----------------------------------------------------------------------------
-constexpr int OCCP_RUN = 8;                                        // blocks of a workgroup's run
-constexpr int OCCP_WIN = OCCP_RUN * OCC_FANIN;                     // its windows: a lane each
-constexpr int OCCP_ROWS = OCCP_WIN + PFMSCAN_MAX_M - 1;            // rows it stages at most
-constexpr int OCCP_TS = OCCP_RUN * (OCC_FANIN + 1);                // doubles of one motif's terms in LDS: window w at w + w / 32
-constexpr int OCCP_CHUNK = 32;                                     // motifs a workgroup walks over the rows it staged
-static_assert(OCCP_WIN == BLOCK, "a lane per window of the run");
-
-// the aligned 16 bytes at byte_off; the stream's last vector may be cut short (rows are a multiple of 4 bytes)
-__device__ __forceinline__ uint4 occp_load(const unsigned char *__restrict__ base, int64_t byte_off, int64_t total_bytes)
-{
-    uint4 v = make_uint4(0u, 0u, 0u, 0u);
-    if (byte_off + 16 <= total_bytes) {
-        v = *reinterpret_cast<const uint4 *>(base + byte_off);
-    } else {
-        const uint32_t *p = reinterpret_cast<const uint32_t *>(base + byte_off);
-        const int64_t n = (total_bytes - byte_off) / 4;
-        if (n > 0) v.x = p[0];
-        if (n > 1) v.y = p[1];
-        if (n > 2) v.z = p[2];
-    }
-    return v;
-}
-
-// the cells of one 16-byte vector, widened (exact)
-__device__ __forceinline__ void occp_cells(const uint4 v, double (&d)[4], float)
-{
-    d[0] = (double)__uint_as_float(v.x);
-    d[1] = (double)__uint_as_float(v.y);
-    d[2] = (double)__uint_as_float(v.z);
-    d[3] = (double)__uint_as_float(v.w);
-}
-__device__ __forceinline__ void occp_cells(const uint4 v, double (&d)[2], double)
-{
-    d[0] = __hiloint2double((int)v.y, (int)v.x);
-    d[1] = __hiloint2double((int)v.w, (int)v.z);
-}
-
-// the marginal of row x under table row s: 7 rounded products, 6 rounded additions, ascending
-__device__ __forceinline__ double occp_marginal(const double (&x)[7], const double *__restrict__ s)
-{
-    double d = x[0] * s[0];
-#pragma unroll
-    for (int c = 1; c < 7; ++c) d = d + x[c] * s[c];
-    return d;
-}
-
+// ---- level 0 on averaged-structure profiles (OCCP_*, occp_load, occp_cells, occp_marginal: pfmscan_occ.hpp) -----------------
 // the record of every run of the pass, so that a workgroup of k_occ_profile_blocks finds its run with two round trips to memory
 // instead of a bisection of ~17 dependent loads (which, at 8 workgroups per CU, was most of a single-motif call's time)
 __global__ __launch_bounds__(BLOCK) void k_occ_run_records(const OccArgs a)
@@ -396,6 +350,11 @@ __global__ __launch_bounds__(BLOCK) void k_occ_profile_blocks(const OccArgs a, c
     }
 }
 
+void occ_launch_run_records(const OccArgs &a, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_occ_run_records, dim3((unsigned)((a.r1 - a.r0 + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, a);
+}
+
 int occ_launch_upper(pfmscan_ctx *ctx, const OccArgs &a, hipStream_t st)
 {
     hipError_t e;
@@ -436,14 +395,6 @@ static hipError_t occ_launch_blocks(const OccArgs &a, hipStream_t st)
     else hipLaunchKernelGGL(k_occ_blocks<1>, grid, dim3(BLOCK), lds, st, a);
     return hipGetLastError();
 }
-
-// what level 0 reads when the stream is an averaged-structure profile: its rows and the structure tables (HOST double
-// [n_motifs][m][7]); the letter tables and the codes are then those of joint mode, or null
-struct OccProfile {
-    const double *struct_tables;
-    const void *d_profile;
-    int dtype;
-};
 
 template <typename T, bool SEQ>
 static void occ_launch_profile_qn(const OccArgs &a, int qn, const dim3 grid, const double *stab, hipStream_t st)
@@ -552,7 +503,7 @@ static int occ_run(pfmscan_ctx *ctx, const char *who, const double *ratio_tables
             hipError_t e = hipSuccess;
             if (a.n_blk > 0) {
                 a.run_base = run[a.r0];
-                if (pf) hipLaunchKernelGGL(k_occ_run_records, dim3((unsigned)((a.r1 - a.r0 + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, a);
+                if (pf) occ_launch_run_records(a, st);
                 e = pf ? occ_launch_profile(a, pf->dtype, ratio_tables != nullptr, run[a.r1] - a.run_base, d_stab, st) : occ_launch_blocks(a, st);
                 if (e != hipSuccess) return fail_hip(ctx, e, pf ? "k_occ_profile_blocks" : "k_occ_blocks");
             }
@@ -590,6 +541,14 @@ int occ_run_letters(pfmscan_ctx *ctx, const char *who, const double *ratio_table
                     int64_t n_rec, double *d_occ, int64_t *d_windows, hipStream_t st)
 {
     return occ_run(ctx, who, ratio_tables, n_motifs, m, n_letters, d_codes, n_pos, rec_off, rec_len, d_rec_off, d_rec_len, n_rec, d_occ, d_windows, st);
+}
+
+int occ_run_profile(pfmscan_ctx *ctx, const char *who, const OccProfile &pf, const double *seq_tables, int n_motifs, int m, const uint8_t *d_codes,
+                    int64_t n_pos, const int64_t *rec_off, const int64_t *rec_len, const int64_t *d_rec_off, const int64_t *d_rec_len,
+                    int64_t n_rec, double *d_occ, int64_t *d_windows, hipStream_t st)
+{
+    return occ_run(ctx, who, seq_tables, n_motifs, m, 4, seq_tables ? d_codes : nullptr, n_pos, rec_off, rec_len, d_rec_off, d_rec_len, n_rec, d_occ,
+                   d_windows, st, &pf);
 }
 
 }  // namespace pfmscan

@@ -112,14 +112,7 @@ def run_profiles(engine, out, recs, profiles, seq_odds, struct_odds, pairs, pair
         at = a
         for ids, cols, pst in profiles.runs(a, b):
             n = len(ids)
-            stream = pst
-            if recs is not None:
-                batch = scanner._RnaBatch(recs[at:at + n])
-                if not np.array_equal(batch.lengths, pst.lengths):
-                    r = int(np.flatnonzero(batch.lengths != pst.lengths)[0])
-                    raise sites.InputError("record %s is %d letters long but its averaged-structure profile has %d rows" %
-                                           (ids[r], int(batch.lengths[r]), int(pst.lengths[r])))
-                stream = pack.Stream(batch.codes, pst.profile, batch.offsets, batch.lengths)
+            stream = paired_batch(recs, at, ids, pst)
             occ = np.zeros((n, len(pairs)), dtype=np.float64)
             win = np.zeros((n, len(pairs)), dtype=np.int64)
             for m, ks in groups.items():
@@ -198,57 +191,74 @@ def _load_shapes(pfm_file, option, pseudocount, letters):
     return shapes
 
 
-def main_profiles(args, engine, out):
-    """the averaged-structure modes: ``-q st.pfm avgdir_or_store`` and ``-p seq.pfm -q st.pfm seqs.fa avgdir_or_store``"""
-    from . import background, pssm, scanner, sites, store
-    joint = bool(args.pfm_seq)
-    source = args.inputs[-1]
-    own = engine is None
-    try:
+def profile_motifs(args):
+    """the motifs of an averaged-structure run, before any device work: -> (pairs, st_shapes, seq_shapes) or None (said on
+    stderr).  ``-q`` alone: pairs [(None, structure id)]; ``-p`` with ``-q``: [(sequence id, structure id)] as ``rnascan``
+    pairs two libraries, pairs of unequal width an error; ``-p`` alone (``expect_profile``): [(sequence id, None)].  Shared
+    with ``expect_profile``."""
+    from . import scanner, sites
+    joint = bool(args.pfm_seq) and bool(args.pfm_struct)
+    st_shapes = seq_shapes = None
+    if args.pfm_struct:
         st_shapes = _load_shapes(args.pfm_struct, "-q", args.pseudocount, fasta.STRUCT)
-        seq_shapes = _load_shapes(args.pfm_seq, "-p", args.pseudocount, fasta.RNA) if joint and st_shapes else None
-        if st_shapes is None or (joint and seq_shapes is None):
-            return 1
-        if not args.all_motifs:
-            st_shapes = OrderedDict([scanner._first_motif(st_shapes)])
-            seq_shapes = OrderedDict([scanner._first_motif(seq_shapes)]) if joint else None
-        if joint:
-            try:
-                pairs = sites.motif_pairs(seq_shapes, st_shapes)
-            except sites.InputError as e:
-                fasta.eprint(str(e))
-                return 1
-            # scanner.pair_motifs leaves out the pairs of unequal width (they share no window): here that is an error
-            sk, tk = list(seq_shapes.keys()), list(st_shapes.keys())
-            if len(sk) == 1 or len(tk) == 1:
-                meant = [(a, b) for a in sk for b in tk]
-            else:
-                meant = [(a, a) for a in sk if a in st_shapes] or list(zip(sk, tk))
-            for a, b in meant:
-                if seq_shapes[a].length != st_shapes[b].length:
-                    fasta.eprint("-p motif %s is %d positions wide and -q motif %s %d: they share no window" %
-                                 (a, seq_shapes[a].length, b, st_shapes[b].length))
-                    return 1
+        if st_shapes is None:
+            return None
+    if args.pfm_seq:
+        seq_shapes = _load_shapes(args.pfm_seq, "-p", args.pseudocount, fasta.RNA)
+        if seq_shapes is None:
+            return None
+    if not args.all_motifs:
+        st_shapes = OrderedDict([scanner._first_motif(st_shapes)]) if st_shapes is not None else None
+        seq_shapes = OrderedDict([scanner._first_motif(seq_shapes)]) if seq_shapes is not None else None
+    if joint:
+        try:
+            pairs = sites.motif_pairs(seq_shapes, st_shapes)
+        except sites.InputError as e:
+            fasta.eprint(str(e))
+            return None
+        # scanner.pair_motifs leaves out the pairs of unequal width (they share no window): here that is an error
+        sk, tk = list(seq_shapes.keys()), list(st_shapes.keys())
+        if len(sk) == 1 or len(tk) == 1:
+            meant = [(a, b) for a in sk for b in tk]
         else:
-            pairs = [(None, b) for b in st_shapes]                 # the file's motif order, as for a structure FASTA
-        if not _widths_ok(st_shapes, [b for _, b in pairs], "-q", args.pfm_struct):
-            return 1
-        if joint and not _widths_ok(seq_shapes, [a for a, _ in pairs], "-p", args.pfm_seq):
-            return 1
-        if engine is None:
-            engine = scanner.HipEngine(args.device)
-        stored = store.ProfileStore(source).dtype if store.is_store(source) else None
-        dtype = np.dtype(args.profile_dtype).type if args.profile_dtype else (np.dtype(stored).type if stored is not None else np.float64)
-        recs = None
-        if joint:
-            recs = fasta.open_lazy(args.inputs[0])
-            if len(set(recs.ids)) != len(recs):
-                seen = set()
-                dup = next(i for i in recs.ids if i in seen or seen.add(i))
-                raise sites.InputError("record %s occurs more than once in the FASTA" % dup)
-            profiles = sites._Profiles(source, dtype, order=list(recs.ids))
-        else:
-            profiles = sites._Profiles(source, dtype)
+            meant = [(a, a) for a in sk if a in st_shapes] or list(zip(sk, tk))
+        for a, b in meant:
+            if seq_shapes[a].length != st_shapes[b].length:
+                fasta.eprint("-p motif %s is %d positions wide and -q motif %s %d: they share no window" %
+                             (a, seq_shapes[a].length, b, st_shapes[b].length))
+                return None
+    elif st_shapes is not None:
+        pairs = [(None, b) for b in st_shapes]                     # the file's motif order, as for a structure FASTA
+    else:
+        pairs = [(a, None) for a in seq_shapes]
+    if st_shapes is not None and not _widths_ok(st_shapes, [b for _, b in pairs], "-q", args.pfm_struct):
+        return None
+    if seq_shapes is not None and not _widths_ok(seq_shapes, [a for a, _ in pairs], "-p", args.pfm_seq):
+        return None
+    return pairs, st_shapes, seq_shapes
+
+
+def profile_sources(args, engine):
+    """the inputs of an averaged-structure run once a device is open: -> (recs | None, profiles, seq_odds | None,
+    struct_odds | None, bg_seq, bg_struct).  With ``-p`` the FASTA's records (ids unique) and the profiles matched to them
+    by id in the FASTA's order; the row dtype is ``--profile-dtype``, else the store's own, else float64; the structure
+    background is ``-u``, ``-B`` or the profiles' own (background.profile_background).  Shared with ``expect_profile``."""
+    from . import background, pssm, sites, store
+    source = args.inputs[-1]
+    stored = store.ProfileStore(source).dtype if store.is_store(source) else None
+    dtype = np.dtype(args.profile_dtype).type if args.profile_dtype else (np.dtype(stored).type if stored is not None else np.float64)
+    recs = None
+    if args.pfm_seq:
+        recs = fasta.open_lazy(args.inputs[0])
+        if len(set(recs.ids)) != len(recs):
+            seen = set()
+            dup = next(i for i in recs.ids if i in seen or seen.add(i))
+            raise sites.InputError("record %s occurs more than once in the FASTA" % dup)
+        profiles = sites._Profiles(source, dtype, order=list(recs.ids))
+    else:
+        profiles = sites._Profiles(source, dtype)
+    bg_struct = struct_odds = None
+    if args.pfm_struct:
         if args.uniform_background:
             bg_struct = None
         elif args.bg_struct:
@@ -256,10 +266,39 @@ def main_profiles(args, engine, out):
         else:
             bg_struct = background.profile_background(engine, source)
         struct_odds = pssm.load_odds(args.pfm_struct, args.pseudocount, fasta.STRUCT, bg_struct)
-        seq_odds = None
-        if joint:
-            bg_seq = fasta.load_background(args.bg_seq, args.uniform_background, args.inputs[0], fasta.RNA, True)
-            seq_odds = pssm.load_odds(args.pfm_seq, args.pseudocount, fasta.RNA, bg_seq)
+    bg_seq = seq_odds = None
+    if args.pfm_seq:
+        bg_seq = fasta.load_background(args.bg_seq, args.uniform_background, args.inputs[0], fasta.RNA, True)
+        seq_odds = pssm.load_odds(args.pfm_seq, args.pseudocount, fasta.RNA, bg_seq)
+    return recs, profiles, seq_odds, struct_odds, bg_seq, bg_struct
+
+
+def paired_batch(recs, at, ids, pst):
+    """the stream of one run of ``profiles.runs``: the profile's own (structure only, ``recs`` None), or the codes of the
+    FASTA's records at..at+len(ids) beside the rows; a record whose length is not its profile's is an InputError"""
+    from . import scanner, sites
+    if recs is None:
+        return pst
+    batch = scanner._RnaBatch(recs[at:at + len(ids)])
+    if not np.array_equal(batch.lengths, pst.lengths):
+        r = int(np.flatnonzero(batch.lengths != pst.lengths)[0])
+        raise sites.InputError("record %s is %d letters long but its averaged-structure profile has %d rows" %
+                               (ids[r], int(batch.lengths[r]), int(pst.lengths[r])))
+    return pack.Stream(batch.codes, pst.profile, batch.offsets, batch.lengths)
+
+
+def main_profiles(args, engine, out):
+    """the averaged-structure modes: ``-q st.pfm avgdir_or_store`` and ``-p seq.pfm -q st.pfm seqs.fa avgdir_or_store``"""
+    from . import background, scanner, sites
+    own = engine is None
+    try:
+        motifs = profile_motifs(args)
+        if motifs is None:
+            return 1
+        pairs = motifs[0]
+        if engine is None:
+            engine = scanner.HipEngine(args.device)
+        recs, profiles, seq_odds, struct_odds, _, _ = profile_sources(args, engine)
         out.write("\t".join(COLUMNS) + "\n")
         n = run_profiles(engine, out, recs, profiles, seq_odds, struct_odds, pairs, args.pairing, args.batch_records)
         out.flush()

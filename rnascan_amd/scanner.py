@@ -181,6 +181,15 @@ class HipEngine(object):
         self._stage(stream)
         return self.ctx.occupancy_profile_staged(struct_tables, seq_tables, stream.offsets, stream.lengths)
 
+    def expect_profile(self, stream, struct_tables, seq_tables, mode):
+        """expected counts on an averaged-structure profile: every window weighted as ``expect`` weights it, by
+        the structure tables [n_motifs][m][7] (columns in the profile's stored order) over ``stream.profile``, the sequence
+        tables [n_motifs][m][8] over ``stream.codes``, or both (joint); the profile's rows under every motif column are
+        added up with these weights, and with sequence tables the letters too ->
+        (exp_struct float64 [n_rec][n_motifs][m][8], exp_seq the same | None, occ float64 [n_rec][n_motifs], windows int64 [n_rec])"""
+        self._stage(stream)
+        return self.ctx.expect_profile_staged(struct_tables, seq_tables, mode, stream.offsets, stream.lengths)
+
     def hits_sum(self, stream, letter_table, struct_pssm, thr_seq, thr_struct, thr_sum, one_shot=True):
         """``hits`` of a motif with both parts, with the joint threshold decided on the device: a window is kept iff
         seq > thr_seq AND struct > thr_struct AND float64(round(float32 seq, 3)) + struct > thr_sum -- the printed

@@ -59,7 +59,7 @@
 extern "C" {
 #endif
 
-#define PFMSCAN_ABI_VERSION 24
+#define PFMSCAN_ABI_VERSION 25
 #define PFMSCAN_NCODE   8      /* columns of a letter table */
 #define PFMSCAN_SEP     7      /* separator / foreign-letter code */
 #define PFMSCAN_NSTRUCT 7      /* columns of a structure profile / structure PSSM */
@@ -1273,6 +1273,53 @@ int pfmscan_expect_profile_dev(pfmscan_ctx *ctx, const double *struct_tables, co
 int pfmscan_expect_profile_staged(pfmscan_ctx *ctx, const double *struct_tables, const double *seq_tables, int n_motifs, int m,
                                   int mode, const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec, double *exp_struct,
                                   double *exp_seq, double *occ, int64_t *windows);
+
+/* ---- occupancy and expected counts of two code streams: sequence letters AND structure letters ------------------------
+ * No counterpart in the reference.  The occupancy and the expected counts above for the input mode `-p seq.pfm -q struct.pfm
+ * seqs.fa structs.fa`, where the structure of a record is a letter string.  No transcendental, no tolerance;
+ * tests/pair_rules.py restates it in numpy and the bits are compared.  Everything not said here is the occupancy and the
+ * expected counts above, unchanged: the cells of the tables, c = code & 7, the left-aligned tree of fan-in PFMSCAN_OCC_FANIN
+ * anchored at the record's first window, v = 1.0 / occ_r (one rounded division per record and pair), w_s = t_s * v (one
+ * rounded product per window), "occ_r == +0.0 makes every weight +0.0", IEEE as it falls, nothing contracted.
+ * Two streams of equal length n_pos share one record table: codes holds RNA codes (n_letters 4), codes2 structure-letter
+ * codes (n_letters 7; a lower-case structure letter carries bit 3 and counts as its letter).  seq_tables R and struct_tables
+ * S are HOST double [n_motifs][m][8], both made as the ratio table of the occupancy is made; pair q is (R_q, S_q), both of
+ * width m.
+ *   term(s)       t = R[0][a_0], then t = t * R[k][a_k] for k = 1 .. m-1, then t = t * S[k][b_k] for k = 0 .. m-1, where
+ *                 a_k = codes[s + k] & 7 and b_k = codes2[s + k] & 7: 2 m - 1 rounded products, the letters first, then the
+ *                 structure -- the order of the joint chain on averaged-structure profiles.  R[k][a] * S[k][b] is never
+ *                 made on its own: a pre-multiplied 28-entry row is another rounding and not this contract.
+ *   has(s)        every a_k < 4 and every b_k < 7.  Otherwise the window has no term: it adds +0.0 and is not counted.
+ *   occ[r][q], windows[r]   as for the occupancy, over these terms.
+ *   exp_seq[r][q][k][c], c < 4      the tree sum of (has_s && a_k == c) ? w_s : +0.0.
+ *   exp_struct[r][q][k][c], c < 7   the tree sum of (has_s && b_k == c) ? w_s : +0.0.
+ *                 Both matrices are double [n_rec][n_motifs][m][8], the other columns +0.0.  Either pointer may be NULL (that
+ *                 matrix is not computed); both NULL: PFMSCAN_E_BADARG.
+ * Exact multiplication by 1.0 gives two identities: with every cell of S equal to 1.0 and no foreign structure code, occ,
+ * windows and exp_seq are bit for bit those of pfmscan_occupancy_* / pfmscan_expect_* on codes; with every cell of R equal to
+ * 1.0 and no foreign sequence code, occ, windows and exp_struct are those of the single-stream calls on codes2 with
+ * n_letters 7.  The bits depend on the codes and the tables and on nothing else: not on the batch, the record's place in the
+ * stream, the launch geometry, the scratch cap or the _dev / _staged form.
+ * The _dev forms take device pointers, both code streams 16-byte aligned (else PFMSCAN_E_BADSHAPE), on the ctx's stream; they
+ * read the record table back and check it before any kernel forms an address from it (one synchronisation; a table that is
+ * not ascending, disjoint and inside the stream: PFMSCAN_E_BADARG, nothing written), then return without waiting.  The
+ * _staged forms read the streams left by pfmscan_stage and pfmscan_stage_codes2, take a HOST record table and outputs, and
+ * synchronise.  A missing staged stream, a NULL that is needed or a bad mode: PFMSCAN_E_BADARG, outputs untouched; m outside
+ * 1 .. PFMSCAN_MAX_M: PFMSCAN_E_BADSHAPE; n_rec == 0 or n_motifs == 0: PFMSCAN_OK, nothing written.  Device scratch is bounded
+ * as above: records, then pairs (occupancy) or matrix rows (expected counts; the 4 + 7 cells of a row (pair, k) stay
+ * together), run in passes. */
+int pfmscan_occupancy_pair_dev(pfmscan_ctx *ctx, const double *seq_tables, const double *struct_tables, int n_motifs, int m,
+                               const uint8_t *d_codes, const uint8_t *d_codes2, int64_t n_pos, const int64_t *d_rec_off,
+                               const int64_t *d_rec_len, int64_t n_rec, double *d_occ, int64_t *d_windows);
+int pfmscan_occupancy_pair_staged(pfmscan_ctx *ctx, const double *seq_tables, const double *struct_tables, int n_motifs, int m,
+                                  const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec, double *occ, int64_t *windows);
+int pfmscan_expect_pair_dev(pfmscan_ctx *ctx, const double *seq_tables, const double *struct_tables, int n_motifs, int m, int mode,
+                            const uint8_t *d_codes, const uint8_t *d_codes2, int64_t n_pos, const int64_t *d_rec_off,
+                            const int64_t *d_rec_len, int64_t n_rec, double *d_exp_seq, double *d_exp_struct, double *d_occ,
+                            int64_t *d_windows);
+int pfmscan_expect_pair_staged(pfmscan_ctx *ctx, const double *seq_tables, const double *struct_tables, int n_motifs, int m,
+                               int mode, const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec, double *exp_seq,
+                               double *exp_struct, double *occ, int64_t *windows);
 
 #ifdef __cplusplus
 }

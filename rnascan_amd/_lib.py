@@ -22,7 +22,7 @@ NCODE = 8
 NSTRUCT = 7
 MAX_M = 64            # widest PFM of the tuned kernels and of PFM libraries
 MAX_WIDTH = 4096      # widest PFM accepted (wider than MAX_M: the plain rolled-loop kernel)
-ABI_VERSION = 24
+ABI_VERSION = 25
 
 # every symbol include/pfmscan.h declares (checked by tests/test_abi.py)
 SYMBOLS = [
@@ -60,6 +60,7 @@ SYMBOLS = [
     "pfmscan_occupancy_profile_dev", "pfmscan_occupancy_profile_staged",
     "pfmscan_expect_dev", "pfmscan_expect_staged",
     "pfmscan_expect_profile_dev", "pfmscan_expect_profile_staged",
+    "pfmscan_occupancy_pair_dev", "pfmscan_occupancy_pair_staged", "pfmscan_expect_pair_dev", "pfmscan_expect_pair_staged",
 ]
 PAIR_ROUTE_NONE, PAIR_ROUTE_FUSED, PAIR_ROUTE_TWO_PHASE, PAIR_ROUTE_DENSE, PAIR_ROUTE_CREDITS = range(5)   # Context.pair_sum_route()
 SITE_GROUP = 4096     # most hits of one group of the site profiles
@@ -249,6 +250,10 @@ def load():
     L.pfmscan_expect_staged.argtypes = [vp, i32, vp, i32, i32, i32, i32, vp, vp, i64, vp, vp, vp]
     L.pfmscan_expect_profile_dev.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, i32, i64, vp, vp, i64, vp, vp, vp, vp]
     L.pfmscan_expect_profile_staged.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, i64, vp, vp, vp, vp]
+    L.pfmscan_occupancy_pair_dev.argtypes = [vp, vp, vp, i32, i32, vp, vp, i64, vp, vp, i64, vp, vp]
+    L.pfmscan_occupancy_pair_staged.argtypes = [vp, vp, vp, i32, i32, vp, vp, i64, vp, vp]
+    L.pfmscan_expect_pair_dev.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, i64, vp, vp, i64, vp, vp, vp, vp]
+    L.pfmscan_expect_pair_staged.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, i64, vp, vp, vp, vp]
     L.pfmscan_tsv_format.argtypes = [ctypes.POINTER(TsvColumn), i32, i64, i64, vp, i64, ctypes.POINTER(i64), vp, ctypes.POINTER(i32), i32]
     for name in SYMBOLS:          # every other entry point returns a status
         if name not in ("pfmscan_ctx_destroy", "pfmscan_motif_destroy", "pfmscan_last_error", "pfmscan_library_destroy",
@@ -1790,6 +1795,57 @@ class Context(object):
         self._check(self._L.pfmscan_expect_profile_staged(self._h, _ptr(st), _ptr(sq), n_motifs, m, int(mode), _ptr(rec_off), _ptr(rec_len),
                                                           rec_off.size, _ptr(exp_struct), _ptr(exp_seq), _ptr(occ), _ptr(windows)))
         return exp_struct, exp_seq, occ, windows
+
+    # -- two code streams (include/pfmscan.h: pfmscan_occupancy_pair_*, pfmscan_expect_pair_*) ---------------
+    @staticmethod
+    def _pair_tables(seq_tables, struct_tables):
+        sq, st = Context._ratio_tables(seq_tables), Context._ratio_tables(struct_tables)
+        if sq.shape != st.shape:
+            raise ValueError("seq_tables and struct_tables must hold as many motifs of the same width")
+        return sq, st
+
+    def occupancy_pair_dev(self, seq_tables, struct_tables, d_codes, d_codes2, n_pos, d_rec_off, d_rec_len, n_rec, d_occ, d_windows=None):
+        sq, st = self._pair_tables(seq_tables, struct_tables)
+        self._check(self._L.pfmscan_occupancy_pair_dev(self._h, _ptr(sq), _ptr(st), sq.shape[0], sq.shape[1], _ptr(d_codes), _ptr(d_codes2),
+                                                       int(n_pos), _ptr(d_rec_off), _ptr(d_rec_len), int(n_rec), _ptr(d_occ), _ptr(d_windows)))
+
+    def occupancy_pair_staged(self, seq_tables, struct_tables, rec_off, rec_len):
+        """-> occ float64 [n_rec][n_motifs], windows int64 [n_rec] over the staged codes and codes2; pair q is
+        (seq_tables[q], struct_tables[q]), [m][8] both"""
+        sq, st = self._pair_tables(seq_tables, struct_tables)
+        rec_off = np.ascontiguousarray(rec_off, dtype=np.int64)
+        rec_len = np.ascontiguousarray(rec_len, dtype=np.int64)
+        if rec_off.ndim != 1 or rec_off.shape != rec_len.shape:
+            raise ValueError("rec_off and rec_len must be lists of one length")
+        occ = np.zeros((rec_off.size, sq.shape[0]), dtype=np.float64)
+        windows = np.zeros(rec_off.size, dtype=np.int64)
+        self._check(self._L.pfmscan_occupancy_pair_staged(self._h, _ptr(sq), _ptr(st), sq.shape[0], sq.shape[1], _ptr(rec_off), _ptr(rec_len),
+                                                          rec_off.size, _ptr(occ), _ptr(windows)))
+        return occ, windows
+
+    def expect_pair_dev(self, seq_tables, struct_tables, mode, d_codes, d_codes2, n_pos, d_rec_off, d_rec_len, n_rec, d_exp_seq, d_exp_struct,
+                        d_occ=None, d_windows=None):
+        sq, st = self._pair_tables(seq_tables, struct_tables)
+        self._check(self._L.pfmscan_expect_pair_dev(self._h, _ptr(sq), _ptr(st), sq.shape[0], sq.shape[1], int(mode), _ptr(d_codes), _ptr(d_codes2),
+                                                    int(n_pos), _ptr(d_rec_off), _ptr(d_rec_len), int(n_rec), _ptr(d_exp_seq), _ptr(d_exp_struct),
+                                                    _ptr(d_occ), _ptr(d_windows)))
+
+    def expect_pair_staged(self, seq_tables, struct_tables, mode, rec_off, rec_len, want_seq=True, want_struct=True):
+        """-> exp_seq, exp_struct float64 [n_rec][n_motifs][m][8] (None where not wanted), occ float64 [n_rec][n_motifs], windows
+        int64 [n_rec] over the staged codes and codes2; mode EXPECT_RATIO or EXPECT_POSTERIOR"""
+        sq, st = self._pair_tables(seq_tables, struct_tables)
+        n_motifs, m = sq.shape[:2]
+        rec_off = np.ascontiguousarray(rec_off, dtype=np.int64)
+        rec_len = np.ascontiguousarray(rec_len, dtype=np.int64)
+        if rec_off.ndim != 1 or rec_off.shape != rec_len.shape:
+            raise ValueError("rec_off and rec_len must be lists of one length")
+        exp_seq = np.zeros((rec_off.size, n_motifs, m, NCODE), dtype=np.float64) if want_seq else None
+        exp_struct = np.zeros((rec_off.size, n_motifs, m, NCODE), dtype=np.float64) if want_struct else None
+        occ = np.zeros((rec_off.size, n_motifs), dtype=np.float64)
+        windows = np.zeros(rec_off.size, dtype=np.int64)
+        self._check(self._L.pfmscan_expect_pair_staged(self._h, _ptr(sq), _ptr(st), n_motifs, m, int(mode), _ptr(rec_off), _ptr(rec_len),
+                                                       rec_off.size, _ptr(exp_seq), _ptr(exp_struct), _ptr(occ), _ptr(windows)))
+        return exp_seq, exp_struct, occ, windows
 
     def time_scan_dev(self, motif, d_codes, d_profile, profile_dtype, n_pos, d_out_seq, d_out_struct,
                       stream=None, warmup=1, iters=5):

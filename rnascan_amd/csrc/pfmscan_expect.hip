@@ -18,6 +18,9 @@
 //                   term or beyond the record) in LDS; then a lane per (block, column k, letter c) walks the block's 32
 //                   weights in order and adds (code[w + k] == c ? weight : +0.0) from 0.0.  One writer per scratch cell.
 //                   Nothing is indexed at run time but LDS.
+//   k_exp_pair_blocks   level 0 on two code streams: the same plan with both strips of a block in LDS, the joint
+//                   weight made once per pair and the 4 + 7 columns of a matrix row (pair, k) summed together; described
+//                   above the kernel.
 // The m x n_letters cells of a motif are independent columns of block sums: levels 1 and up are the occupancy's own
 // k_occ_level1 and k_occ_finish (occ_launch_upper), which store column row * n_letters + c at [row][c] of the [m][8] matrix.
 // Scratch is blocks x columns doubles under the occupancy's cap: records run in passes, and when the longest record alone
@@ -129,6 +132,229 @@ __global__ __launch_bounds__(BLOCK) void k_exp_blocks(const OccArgs a, const dou
             }
         }
     }
+}
+
+// ---- two code streams (include/pfmscan.h "occupancy and expected counts of two code streams") -----------------
+// k_exp_blocks with a second stream.  Both strips of a block are parked in LDS (foreign codes as 0xFF, each in its own
+// stream); a window has a term when no position under it is foreign in either.  Per pair a lane makes its window's term by
+// the joint chain (the letters over R, then the structure letters over S: 2 m - 1 rounded products) and its weight ONCE and
+// parks it; then a lane per (block, k, letter) of the 4 + 7 columns of the matrix rows (pair, k) of the pass walks the
+// block's 32 weights in order and adds (code == letter ? weight : +0.0) from 0.0 -- letters 0..3 against the RNA strip into
+// bs_seq, 4..10 against the structure strip into bs_struct.  A region that is null is not computed.  One writer per cell.
+struct ExpPairArgs {
+    const double *inv;           // [n_rec][n_motifs] or null (ratio mode)
+    double *bs_seq;              // [n_blk][n_u * 4] or null
+    double *bs_struct;           // [n_blk][n_u * 7] or null
+    int u_first, n_u;            // matrix rows of the pass: u = pair * m + k
+};
+
+__global__ __launch_bounds__(BLOCK) void k_exp_pair_blocks(const OccArgs a, const ExpPairArgs e, const int64_t *__restrict__ wg_rec)
+{
+    __shared__ double tab[2][PFMSCAN_MAX_M * 8];
+    __shared__ double wl[EXP_WB][OCC_FANIN + 1];
+    __shared__ uint8_t cl[2][EXP_WB][EXP_CS];
+    constexpr int NS = PFMSCAN_NSTRUCT, NC = 4 + NS;
+    const int t = threadIdx.x, j = t >> 5, w = t & 31, m = a.m;
+    const int64_t gb = (int64_t)blockIdx.x * EXP_WB + j;           // this lane's block, within the pass
+    const bool live = gb < a.n_blk;
+    int64_t r = 0;
+    int nw = 0;
+    if (live) {
+        const int64_t b = a.blk_base + gb;
+        r = wg_rec[blockIdx.x];                                    // the record of the workgroup's first block
+        while (a.blk_start[r + 1] <= b) ++r;                       // ends inside the pass: blk_start[r1] > b
+        const int64_t w0 = (b - a.blk_start[r]) * OCC_FANIN;
+        nw = (int)min((int64_t)OCC_FANIN, a.rec_len[r] - m + 1 - w0);   // >= 1: the block exists
+        const int need = nw + m - 1;                               // positions of the block, all inside the record
+        const int64_t s0 = a.rec_off[r] + w0;
+        for (int i = w; i < EXP_CS; i += OCC_FANIN) {
+            uint8_t c1 = EXP_FOREIGN, c2 = EXP_FOREIGN;
+            if (i < need) {
+                const uint8_t x1 = a.codes[s0 + i] & 7u, x2 = a.codes2[s0 + i] & 7u;
+                if (x1 < 4u) c1 = x1;
+                if ((int)x2 < NS) c2 = x2;
+            }
+            cl[0][j][i] = c1;
+            cl[1][j][i] = c2;
+        }
+    }
+    __syncthreads();
+    bool has = live && w < nw;                                     // this lane's window has a term
+    if (has)
+        for (int k = 0; k < m; ++k) has = has && cl[0][j][w + k] != EXP_FOREIGN && cl[1][j][w + k] != EXP_FOREIGN;
+    const int u_lo = e.u_first, u_hi = e.u_first + e.n_u;
+    const int q_lo = u_lo / m;
+    const int64_t sq = (int64_t)e.n_u * 4, ss = (int64_t)e.n_u * NS;   // doubles per block of the two scratch regions
+    for (int q = q_lo; q * m < u_hi; ++q) {
+        if (q != q_lo) __syncthreads();                            // the adders of the last pair are done with wl
+        for (int i = t; i < m * 8; i += BLOCK) {
+            tab[0][i] = a.tables[(int64_t)q * m * 8 + i];
+            tab[1][i] = a.tables2[(int64_t)q * m * 8 + i];
+        }
+        __syncthreads();
+        double wt = 0.0;
+        if (has) {
+            const uint8_t *cp = &cl[0][j][w];
+            double x = tab[0][cp[0]];
+            for (int k = 1; k < m; ++k) x = x * tab[0][k * 8 + cp[k]];
+            cp = &cl[1][j][w];
+            for (int k = 0; k < m; ++k) x = x * tab[1][k * 8 + cp[k]];
+            if (e.inv) {
+                const double v = e.inv[r * a.n_motifs + q];
+                x = v < 0.0 ? 0.0 : x * v;
+            }
+            wt = x;
+        }
+        wl[j][w] = wt;
+        __syncthreads();
+        if (live) {
+            const int k_lo = max(u_lo - q * m, 0), k_hi = min(u_hi - q * m, m);   // the pair's matrix rows that are rows of the pass
+            const int items = (k_hi - k_lo) * NC;
+            for (int it = w; it < items; it += OCC_FANIN) {
+                const int kk = it / NC, c = it - kk * NC, k = k_lo + kk;
+                const bool st = c >= 4;
+                double *region = st ? e.bs_struct : e.bs_seq;
+                if (!region) continue;
+                const int letter = st ? c - 4 : c;
+                const uint8_t *cp = &cl[st ? 1 : 0][j][k];
+                double s = 0.0;
+#pragma unroll
+                for (int i = 0; i < OCC_FANIN; ++i) s = s + ((int)cp[i] == letter ? wl[j][i] : 0.0);
+                const int64_t u = (int64_t)q * m + k - u_lo;
+                if (st) region[gb * ss + u * NS + letter] = s;
+                else region[gb * sq + u * 4 + letter] = s;
+            }
+        }
+    }
+}
+
+// rec_off / rec_len: HOST copies, already checked; d_rec_off / d_rec_len: the same on the device.  Launches on st, does not wait.
+// d_exp_seq / d_exp_struct: one of them may be null.
+static int exp_pair_run(pfmscan_ctx *ctx, const char *who, const double *seq_tables, const double *struct_tables, int n_motifs, int m, int mode,
+                        const uint8_t *d_codes, const uint8_t *d_codes2, int64_t n_pos, const int64_t *rec_off, const int64_t *rec_len,
+                        const int64_t *d_rec_off, const int64_t *d_rec_len, int64_t n_rec, double *d_exp_seq, double *d_exp_struct, double *d_occ,
+                        int64_t *d_windows, hipStream_t st)
+{
+    int rc;
+    const bool posterior = mode == PFMSCAN_EXPECT_POSTERIOR;
+    const int64_t pairs = n_rec * n_motifs;
+    const int64_t n_unit = (int64_t)n_motifs * m;                  // matrix rows (pair, k)
+    if (n_unit * PFMSCAN_NSTRUCT > (int64_t(1) << 30)) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": too many motifs for one call");
+    // the occupancy of the same records first: v of posterior mode, and what the caller asked for
+    if (posterior || d_occ || d_windows) {
+        if (!d_occ) {
+            if ((rc = ensure(ctx, ctx->exp_occ, (size_t)pairs * 8))) return rc;
+            d_occ = (double *)ctx->exp_occ.p;
+        }
+        if ((rc = occ_run_pair(ctx, who, seq_tables, struct_tables, n_motifs, m, d_codes, d_codes2, n_pos, rec_off, rec_len, d_rec_off, d_rec_len, n_rec,
+                               d_occ, d_windows, st)))
+            return rc;
+    }
+    ExpPairArgs e{};
+    if (posterior) {
+        if ((rc = ensure(ctx, ctx->exp_inv, (size_t)pairs * 8))) return rc;
+        if ((rc = exp_launch_inverse(ctx, d_occ, (double *)ctx->exp_inv.p, pairs, st))) return rc;
+        e.inv = (const double *)ctx->exp_inv.p;
+    }
+    // the columns past the letters of every matrix row are +0.0; every other cell is written by k_occ_finish
+    if (d_exp_seq) HIP_TRY(ctx, hipMemsetAsync(d_exp_seq, 0, (size_t)pairs * m * 8 * sizeof(double), st));
+    if (d_exp_struct) HIP_TRY(ctx, hipMemsetAsync(d_exp_struct, 0, (size_t)pairs * m * 8 * sizeof(double), st));
+    std::vector<int64_t> start(2 * (size_t)(n_rec + 1));
+    int64_t *blk = start.data(), *grp = blk + n_rec + 1;
+    int64_t max_blk = 0;
+    blk[0] = grp[0] = 0;
+    for (int64_t r = 0; r < n_rec; ++r) {
+        const int64_t nw = std::max<int64_t>(rec_len[r] - m + 1, 0), nb = (nw + OCC_FANIN - 1) / OCC_FANIN;
+        blk[r + 1] = blk[r] + nb;
+        grp[r + 1] = grp[r] + (nb + OCC_FANIN - 1) / OCC_FANIN;
+        max_blk = std::max(max_blk, nb);
+    }
+    const int cells = (d_exp_seq ? 4 : 0) + (d_exp_struct ? PFMSCAN_NSTRUCT : 0);   // scratch doubles of a matrix row, both regions
+    const int64_t cap = occ_scratch_cap();
+    // matrix rows per pass: all of them unless the longest record's block sums alone pass the cap; then records per pass
+    const int n_u_max = (int)std::min<int64_t>(n_unit, std::max<int64_t>(1, cap / (std::max<int64_t>(max_blk, 1) * cells)));
+    const int64_t blk_cap = std::max<int64_t>(cap / ((int64_t)n_u_max * cells), 1);
+    const int64_t rec_cap = std::max<int64_t>((int64_t(1) << 30) / ((int64_t)n_u_max * PFMSCAN_NSTRUCT), 1);
+    std::vector<int64_t> cuts(1, 0);
+    int64_t need_blk = 0, need_grp = 0;
+    for (int64_t r0 = 0; r0 < n_rec;) {
+        int64_t r1 = r0 + 1;
+        while (r1 < n_rec && r1 - r0 < rec_cap && blk[r1 + 1] - blk[r0] <= blk_cap) ++r1;
+        cuts.push_back(r1);
+        need_blk = std::max(need_blk, blk[r1] - blk[r0]);
+        need_grp = std::max(need_grp, grp[r1] - grp[r0]);
+        r0 = r1;
+    }
+    if ((need_blk + EXP_WB - 1) / EXP_WB > 0x7FFFFFFF) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": a record is too long for one call");
+    const size_t tab_bytes = (size_t)n_motifs * m * 8 * sizeof(double);   // the sequence tables, the structure tables behind them
+    if ((rc = ensure(ctx, ctx->occ_tab, 2 * tab_bytes))) return rc;
+    if ((rc = ensure(ctx, ctx->occ_idx, start.size() * 8))) return rc;
+    if ((rc = ensure(ctx, ctx->occ_bs, std::max<size_t>((size_t)need_blk * n_u_max * cells * 8, 16)))) return rc;
+    if ((rc = ensure(ctx, ctx->occ_gs, std::max<size_t>((size_t)need_grp * n_u_max * cells * 8, 16)))) return rc;
+    if ((rc = ensure(ctx, ctx->occ_cnt, std::max<size_t>((size_t)((need_blk + EXP_WB - 1) / EXP_WB) * 8, 16)))) return rc;   // a pass's workgroup -> record
+    int64_t *wg_rec = (int64_t *)ctx->occ_cnt.p;
+    double *d_stab = (double *)((unsigned char *)ctx->occ_tab.p + tab_bytes);
+    if ((rc = upload(ctx, ctx->occ_tab.p, seq_tables, tab_bytes, st))) return rc;
+    if ((rc = upload(ctx, d_stab, struct_tables, tab_bytes, st))) return rc;
+    if ((rc = upload(ctx, ctx->occ_idx.p, start.data(), start.size() * 8, st))) return rc;
+    OccArgs a{};
+    a.codes = d_codes;
+    a.codes2 = d_codes2;
+    a.n_pos = n_pos;
+    a.rec_off = d_rec_off;
+    a.rec_len = d_rec_len;
+    a.blk_start = (const int64_t *)ctx->occ_idx.p;
+    a.grp_start = a.blk_start + n_rec + 1;
+    a.tables = (const double *)ctx->occ_tab.p;
+    a.tables2 = d_stab;
+    a.m = m;
+    a.n_letters = 4;
+    a.n_motifs = n_motifs;
+    a.out_stride = (int64_t)n_motifs * m * 8;
+    // the two scratch regions of a pass: the sequence matrix's block and level-1 sums, then the structure matrix's
+    const int nsq = d_exp_seq ? 4 : 0;
+    double *bs_seq = (double *)ctx->occ_bs.p, *bs_struct = bs_seq + need_blk * n_u_max * nsq;
+    double *gs_seq = (double *)ctx->occ_gs.p, *gs_struct = gs_seq + need_grp * n_u_max * nsq;
+    e.bs_seq = d_exp_seq ? bs_seq : nullptr;
+    e.bs_struct = d_exp_struct ? bs_struct : nullptr;
+    for (int64_t u0 = 0; u0 < n_unit; u0 += n_u_max) {
+        e.u_first = (int)u0;
+        e.n_u = (int)std::min<int64_t>(n_u_max, n_unit - u0);
+        for (size_t i = 0; i + 1 < cuts.size(); ++i) {
+            const bool make_table = cuts.size() > 2 || u0 == 0;    // one range of records: its table is made once, for all passes over the rows
+            a.r0 = cuts[i];
+            a.r1 = cuts[i + 1];
+            a.blk_base = blk[a.r0];
+            a.n_blk = blk[a.r1] - a.blk_base;
+            a.grp_base = grp[a.r0];
+            a.n_grp = grp[a.r1] - a.grp_base;
+            if (a.n_blk > 0) {
+                if (make_table) hipLaunchKernelGGL(k_exp_group_records, dim3((unsigned)((a.r1 - a.r0 + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, a, wg_rec);
+                hipLaunchKernelGGL(k_exp_pair_blocks, dim3((unsigned)((a.n_blk + EXP_WB - 1) / EXP_WB)), dim3(BLOCK), 0, st, a, e, wg_rec);
+                hipError_t err = hipGetLastError();
+                if (err != hipSuccess) return fail_hip(ctx, err, "k_exp_pair_blocks");
+            }
+            if (d_exp_seq) {
+                a.bs = bs_seq;
+                a.gs = gs_seq;
+                a.occ = d_exp_seq;
+                a.q_first = e.u_first * 4;
+                a.n_q = e.n_u * 4;
+                a.cell_nl = 4;
+                if ((rc = occ_launch_upper(ctx, a, st))) return rc;
+            }
+            if (d_exp_struct) {
+                a.bs = bs_struct;
+                a.gs = gs_struct;
+                a.occ = d_exp_struct;
+                a.q_first = e.u_first * PFMSCAN_NSTRUCT;
+                a.n_q = e.n_u * PFMSCAN_NSTRUCT;
+                a.cell_nl = PFMSCAN_NSTRUCT;
+                if ((rc = occ_launch_upper(ctx, a, st))) return rc;
+            }
+        }
+    }
+    return PFMSCAN_OK;
 }
 
 // rec_off / rec_len: HOST copies, already checked; d_rec_off / d_rec_len: the same on the device.  Launches on st, does not wait.
@@ -297,6 +523,70 @@ int pfmscan_expect_staged(pfmscan_ctx *ctx, int which, const double *ratio_table
                       d_win, ctx->stream)))
         return rc;
     HIP_TRY(ctx, hipMemcpyAsync(exp, d_exp, cells * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (occ) HIP_TRY(ctx, hipMemcpyAsync(occ, d_occ, pairs * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (windows) HIP_TRY(ctx, hipMemcpyAsync(windows, d_win, (size_t)n_rec * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return PFMSCAN_OK;
+}
+
+int pfmscan_expect_pair_dev(pfmscan_ctx *ctx, const double *seq_tables, const double *struct_tables, int n_motifs, int m, int mode,
+                            const uint8_t *d_codes, const uint8_t *d_codes2, int64_t n_pos, const int64_t *d_rec_off,
+                            const int64_t *d_rec_len, int64_t n_rec, double *d_exp_seq, double *d_exp_struct, double *d_occ,
+                            int64_t *d_windows)
+{
+    const char *who = "pfmscan_expect_pair_dev";
+    if (!ctx) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": NULL ctx");
+    if (int rc = occ_pair_check(ctx, who, seq_tables, struct_tables, n_motifs, m, n_pos, n_rec)) return rc;
+    if (int rc = exp_check_mode(ctx, who, mode)) return rc;
+    if (!d_exp_seq && !d_exp_struct) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": d_exp_seq and d_exp_struct are both NULL");
+    if (n_rec == 0 || n_motifs == 0) return PFMSCAN_OK;
+    if (!d_rec_off || !d_rec_len || (n_pos > 0 && (!d_codes || !d_codes2))) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": NULL record table or codes");
+    if (misaligned(d_codes) || misaligned(d_codes2)) return fail(ctx, PFMSCAN_E_BADSHAPE, std::string(who) + ": stream base pointers must be 16-byte aligned");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // the record table decides every address the kernels form: it is read back and checked before anything is launched
+    std::vector<int64_t> rec(2 * (size_t)n_rec);
+    HIP_TRY(ctx, hipMemcpyAsync(rec.data(), d_rec_off, (size_t)n_rec * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(rec.data() + n_rec, d_rec_len, (size_t)n_rec * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (int rc = occ_check_records(ctx, who, rec.data(), rec.data() + n_rec, n_rec, n_pos)) return rc;
+    return exp_pair_run(ctx, who, seq_tables, struct_tables, n_motifs, m, mode, d_codes, d_codes2, n_pos, rec.data(), rec.data() + n_rec, d_rec_off,
+                        d_rec_len, n_rec, d_exp_seq, d_exp_struct, d_occ, d_windows, ctx->stream);
+}
+
+int pfmscan_expect_pair_staged(pfmscan_ctx *ctx, const double *seq_tables, const double *struct_tables, int n_motifs, int m, int mode,
+                               const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec, double *exp_seq, double *exp_struct,
+                               double *occ, int64_t *windows)
+{
+    const char *who = "pfmscan_expect_pair_staged";
+    if (!ctx) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": NULL ctx");
+    if (ctx->staged_n < 0) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": no stream staged (call pfmscan_stage first)");
+    if (ctx->staged_n > 0 && !ctx->staged_codes) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": no codes are staged");
+    if (ctx->staged_n > 0 && !ctx->staged_codes2) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": no codes2 are staged (pfmscan_stage_codes2)");
+    const int64_t n_pos = ctx->staged_n;
+    if (int rc = occ_pair_check(ctx, who, seq_tables, struct_tables, n_motifs, m, n_pos, n_rec)) return rc;
+    if (int rc = exp_check_mode(ctx, who, mode)) return rc;
+    if (!exp_seq && !exp_struct) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": exp_seq and exp_struct are both NULL");
+    if (n_rec == 0 || n_motifs == 0) return PFMSCAN_OK;
+    if (!rec_off || !rec_len) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": NULL record table");
+    if (int rc = occ_check_records(ctx, who, rec_off, rec_len, n_rec, n_pos)) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc;
+    const size_t pairs = (size_t)n_rec * n_motifs, cells = pairs * m * 8;
+    if ((rc = ensure(ctx, ctx->occ_rec, (size_t)n_rec * 16))) return rc;
+    if ((rc = ensure(ctx, ctx->exp_out, (2 * cells + pairs + (size_t)n_rec) * 8))) return rc;
+    int64_t *d_off = (int64_t *)ctx->occ_rec.p, *d_len = d_off + n_rec;
+    if ((rc = upload(ctx, d_off, rec_off, (size_t)n_rec * 8, ctx->stream))) return rc;
+    if ((rc = upload(ctx, d_len, rec_len, (size_t)n_rec * 8, ctx->stream))) return rc;
+    double *d_base = (double *)ctx->exp_out.p;
+    double *d_sq = exp_seq ? d_base : nullptr;
+    double *d_st = exp_struct ? d_base + cells : nullptr;
+    double *d_occ = occ ? d_base + 2 * cells : nullptr;
+    int64_t *d_win = windows ? (int64_t *)(d_base + 2 * cells + pairs) : nullptr;
+    if ((rc = exp_pair_run(ctx, who, seq_tables, struct_tables, n_motifs, m, mode, (const uint8_t *)ctx->codes.p, (const uint8_t *)ctx->codes2.p, n_pos,
+                           rec_off, rec_len, d_off, d_len, n_rec, d_sq, d_st, d_occ, d_win, ctx->stream)))
+        return rc;
+    if (exp_seq) HIP_TRY(ctx, hipMemcpyAsync(exp_seq, d_sq, cells * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (exp_struct) HIP_TRY(ctx, hipMemcpyAsync(exp_struct, d_st, cells * 8, hipMemcpyDeviceToHost, ctx->stream));
     if (occ) HIP_TRY(ctx, hipMemcpyAsync(occ, d_occ, pairs * 8, hipMemcpyDeviceToHost, ctx->stream));
     if (windows) HIP_TRY(ctx, hipMemcpyAsync(windows, d_win, (size_t)n_rec * 8, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));

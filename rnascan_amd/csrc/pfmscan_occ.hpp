@@ -40,6 +40,9 @@ struct OccArgs {
     const int64_t *run_start;    // [n_rec + 1] prefix of ceil(blocks / OCCP_RUN)
     int64_t run_base;            // run_start[r0]
     int64_t *run_rec;            // [runs of the pass] the record of every run (k_occ_run_records)
+    // two code streams (k_occ_pair_blocks, k_exp_pair_blocks): codes are the RNA codes, tables the sequence tables
+    const uint8_t *codes2;       // [n_pos] structure-letter codes
+    const double *tables2;       // [n_motifs][m][8] device: the structure tables of the pairs
 };
 
 // the record of element e of a prefix table: the last r in [r0, r1) with start[r] <= e (start[r1] > e)
@@ -131,6 +134,13 @@ int occ_run_letters(pfmscan_ctx *ctx, const char *who, const double *ratio_table
 int occ_run_profile(pfmscan_ctx *ctx, const char *who, const OccProfile &pf, const double *seq_tables, int n_motifs, int m, const uint8_t *d_codes,
                     int64_t n_pos, const int64_t *rec_off, const int64_t *rec_len, const int64_t *d_rec_off, const int64_t *d_rec_len,
                     int64_t n_rec, double *d_occ, int64_t *d_windows, hipStream_t st);
+// the same on two code streams: pair q is (seq_tables[q], struct_tables[q]), HOST double [n_motifs][m][8] both
+int occ_run_pair(pfmscan_ctx *ctx, const char *who, const double *seq_tables, const double *struct_tables, int n_motifs, int m,
+                 const uint8_t *d_codes, const uint8_t *d_codes2, int64_t n_pos, const int64_t *rec_off, const int64_t *rec_len,
+                 const int64_t *d_rec_off, const int64_t *d_rec_len, int64_t n_rec, double *d_occ, int64_t *d_windows, hipStream_t st);
+// the checks the four two-stream entry points share, before the rule "n_rec == 0 or n_motifs == 0: nothing to do"
+int occ_pair_check(pfmscan_ctx *ctx, const char *who, const double *seq_tables, const double *struct_tables, int n_motifs, int m, int64_t n_pos,
+                   int64_t n_rec);
 // pfmscan_expect.hip.  k_exp_inverse on st: inv[i] = 1.0 / occ[i], one rounded division each; -1.0 where occ[i] == 0.0
 int exp_launch_inverse(pfmscan_ctx *ctx, const double *d_occ, double *d_inv, int64_t n, hipStream_t st);
 

@@ -14,6 +14,9 @@
 //                      zeroed and kept as a 128-bit mask in registers: no register array is indexed at run time); the
 //                      ratio tables of a chunk of motifs sit in LDS transposed [row][letter][motif], so one letter serves
 //                      QN adjacent motifs with 16-byte reads.
+//   k_occ_pair_blocks<QN>   level 0 on two code streams: k_occ_blocks with both codes of a position packed
+//                      into one byte of the strip and the letter chain continued over the structure letters; described
+//                      above the kernel, with the rule for the pairs of an LDS chunk.
 //   k_occ_level1       level 1: a thread adds the <= 32 block sums of one (group of 32 blocks, motif), in order.
 //   k_occ_finish       levels 2 and up: a thread per (record, motif) folds the record's level-1 sums in place, in order, and
 //                      writes the cell.  One writer per cell.
@@ -166,6 +169,138 @@ __global__ __launch_bounds__(BLOCK) void k_occ_blocks(const OccArgs a)
                 row += rs;
                 double c[QN];
                 occ_cells<QN>(row + (int)cp[k] * ls, c);
+#pragma unroll
+                for (int i = 0; i < QN; ++i) t[i] = t[i] * c[i];
+            }
+            const bool has = (valid >> w) & 1u;
+#pragma unroll
+            for (int i = 0; i < QN; ++i) sum[i] = sum[i] + (has ? t[i] : 0.0);
+        }
+#pragma unroll
+        for (int i = 0; i < QN; ++i)
+            if (q + i < nq) out[q + i] = sum[i];
+    }
+}
+
+// ---- level 0 on two code streams (include/pfmscan.h "occupancy and expected counts of two code streams") -------
+// k_occ_blocks with a second stream: the term of a window is the letter chain over codes (4 RNA letters) continued by the
+// letter chain over codes2 (7 structure letters), 2 m - 1 rounded products, letters first.  Both codes of a position share
+// ONE byte of the lane's strip -- bits 0..2 the RNA code, bits 3..5 the structure code, a position that is foreign in either
+// stream zeroed and remembered in the 128-bit mask -- so the byte traffic of the strip and its size are k_occ_blocks' own
+// (a second strip would double the reads of an LDS-bound kernel and pass 64 KB of dynamic LDS at m = 64).  The tables of a
+// chunk of pairs sit in LDS as [row][letter][pair] with OCC_PAIR_LETTERS = 4 + 7 letters per row: 0..3 the row of R, 4..10
+// the row of S.  The products R[k][a] * S[k][b] are never made: that would be another rounding.
+// Chunk rule (occ_chunk with 11 letters): the most pairs c <= n_q with m * 11 * occ_ls(c, occ_qn(c)) <= OCC_LDS_DOUBLES, at
+// least 1; occ_qn(c) = 8, 4, 2, 1 for c >= 8, 4, 2, 1 and occ_ls(c, qn) = c rounded up to a multiple of qn, plus 2 when that
+// is a multiple of 16.
+constexpr int OCC_PAIR_LETTERS = 4 + PFMSCAN_NSTRUCT;
+static_assert(OCC_LDS_DOUBLES >= PFMSCAN_MAX_M * OCC_PAIR_LETTERS, "one pair of the widest kind fits");
+
+// the aligned dword at p of a stream of n_pos codes (the base pointer is 16-byte aligned); the stream's last one may be cut short
+__device__ __forceinline__ uint32_t occ_dword(const uint8_t *__restrict__ codes, int64_t p, int64_t n_pos)
+{
+    if (p + 4 <= n_pos) return *reinterpret_cast<const uint32_t *>(codes + p);
+    uint32_t dw = 0;
+    for (int j = 0; j < 4; ++j)
+        if (p + j < n_pos) dw |= (uint32_t)codes[p + j] << (8 * j);
+    return dw;
+}
+
+template <int QN>
+__global__ __launch_bounds__(BLOCK) void k_occ_pair_blocks(const OccArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char occ_lds[];
+    constexpr int NL = OCC_PAIR_LETTERS;
+    const int m = a.m;
+    const int cs = occ_strip(m);                                   // dwords per lane strip
+    uint32_t *cw = reinterpret_cast<uint32_t *>(occ_lds);          // [BLOCK][cs]
+    double *lt = reinterpret_cast<double *>(occ_lds + (size_t)BLOCK * cs * 4);   // [m][11][ls]
+    const int qc = (int)blockIdx.y * a.chunk;                      // first pair of the chunk, within the pass
+    const int nq = min(a.chunk, a.n_q - qc);
+    const int ls = occ_ls(a.chunk, QN);
+    for (int i = threadIdx.x; i < m * NL * ls; i += BLOCK) {
+        const int r = i / ls, q = i - r * ls;                      // r = row * 11 + letter
+        const int row = r / NL, c = r - row * NL;
+        const double *src = c < 4 ? a.tables : a.tables2;
+        lt[i] = q < nq ? src[((int64_t)(a.q_first + qc + q) * m + row) * 8 + (c < 4 ? c : c - 4)] : 0.0;
+    }
+    const int64_t gb = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    uint32_t valid = 0;                                            // bit w: window w of the block has a term
+    int sh = 0;
+    if (gb < a.n_blk) {
+        const int64_t b = a.blk_base + gb;
+        const int64_t r = occ_record(a.blk_start, a.r0, a.r1, b);
+        const int64_t w0 = (b - a.blk_start[r]) * OCC_FANIN;
+        const int64_t left = a.rec_len[r] - m + 1 - w0;            // >= 1: the block exists
+        const int nw = (int)min((int64_t)OCC_FANIN, left);
+        const int need = nw + m - 1;                               // positions of the block, all inside the record
+        const int64_t s0 = a.rec_off[r] + w0;
+        sh = (int)(s0 & 3);
+        const int64_t base = s0 - sh;
+        unsigned long long f0 = 0, f1 = 0;                         // bit i: position i of the block is foreign (in either stream) or not the block's
+        uint32_t *mine = cw + threadIdx.x * cs;
+#pragma unroll
+        for (int i = 0; i < OCC_CODE_DWORDS; ++i) {
+            const int64_t p = base + 4 * i;
+            uint32_t d1 = 0, d2 = 0;
+            if (4 * i - sh < need) {
+                d1 = occ_dword(a.codes, p, a.n_pos);
+                d2 = occ_dword(a.codes2, p, a.n_pos);
+            }
+            uint32_t out = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int idx = 4 * i + j - sh;                    // -3 .. 99
+                const uint32_t c1 = (d1 >> (8 * j)) & 7u, c2 = (d2 >> (8 * j)) & 7u;
+                const bool bad = idx >= need || c1 >= 4u || c2 >= (uint32_t)PFMSCAN_NSTRUCT;
+                if (idx >= 0) {
+                    if (idx < 64) f0 |= (unsigned long long)bad << idx;
+                    else f1 |= (unsigned long long)bad << (idx - 64);
+                }
+                out |= (bad ? 0u : (c1 | (c2 << 3))) << (8 * j);
+            }
+            if (i < cs) mine[i] = out;                             // beyond: no position of a block of this width
+        }
+        const unsigned long long wmask = m == 64 ? ~0ull : (1ull << m) - 1;
+        for (int w = 0; w < OCC_FANIN; ++w) {
+            const unsigned long long win = w ? (f0 >> w) | (f1 << (64 - w)) : f0;
+            valid |= (uint32_t)((win & wmask) == 0) << w;          // w >= nw: position w + m - 1 >= need is marked
+        }
+        if (a.bcnt && blockIdx.y == 0) a.bcnt[gb] = __popc(valid);
+    }
+    __syncthreads();                                               // the last barrier
+    if (gb >= a.n_blk) return;
+    const uint8_t *cb = reinterpret_cast<const uint8_t *>(cw + threadIdx.x * cs) + sh;
+    const int rs = NL * ls;                                        // doubles per table row
+    double *out = a.bs + gb * a.n_q + qc;
+    if (valid == 0) {                                              // no window with a term: +0.0 without walking the block
+        for (int q = 0; q < nq; ++q) out[q] = 0.0;
+        return;
+    }
+    for (int q = 0; q < nq; q += QN) {
+        double sum[QN];
+#pragma unroll
+        for (int i = 0; i < QN; ++i) sum[i] = 0.0;
+#pragma unroll 1
+        for (int w = 0; w < OCC_FANIN; ++w) {
+            const uint8_t *cp = cb + w;
+            const double *row = lt + q;
+            double t[QN];
+            occ_cells<QN>(row + (int)(cp[0] & 7u) * ls, t);
+#pragma unroll 4
+            for (int k = 1; k < m; ++k) {                          // the letters ...
+                row += rs;
+                double c[QN];
+                occ_cells<QN>(row + (int)(cp[k] & 7u) * ls, c);
+#pragma unroll
+                for (int i = 0; i < QN; ++i) t[i] = t[i] * c[i];
+            }
+            row = lt + q + 4 * ls;
+#pragma unroll 4
+            for (int k = 0; k < m; ++k) {                          // ... then the structure, continuing the same chain
+                double c[QN];
+                occ_cells<QN>(row + (int)(cp[k] >> 3) * ls, c);
+                row += rs;
 #pragma unroll
                 for (int i = 0; i < QN; ++i) t[i] = t[i] * c[i];
             }
@@ -396,6 +531,18 @@ static hipError_t occ_launch_blocks(const OccArgs &a, hipStream_t st)
     return hipGetLastError();
 }
 
+static hipError_t occ_launch_pair_blocks(const OccArgs &a, hipStream_t st)
+{
+    const int qn = occ_qn(a.chunk);
+    const size_t lds = (size_t)BLOCK * occ_strip(a.m) * 4 + (size_t)a.m * OCC_PAIR_LETTERS * occ_ls(a.chunk, qn) * sizeof(double);
+    const dim3 grid((unsigned)((a.n_blk + BLOCK - 1) / BLOCK), (unsigned)((a.n_q + a.chunk - 1) / a.chunk));
+    if (qn == 8) hipLaunchKernelGGL(k_occ_pair_blocks<8>, grid, dim3(BLOCK), lds, st, a);
+    else if (qn == 4) hipLaunchKernelGGL(k_occ_pair_blocks<4>, grid, dim3(BLOCK), lds, st, a);
+    else if (qn == 2) hipLaunchKernelGGL(k_occ_pair_blocks<2>, grid, dim3(BLOCK), lds, st, a);
+    else hipLaunchKernelGGL(k_occ_pair_blocks<1>, grid, dim3(BLOCK), lds, st, a);
+    return hipGetLastError();
+}
+
 template <typename T, bool SEQ>
 static void occ_launch_profile_qn(const OccArgs &a, int qn, const dim3 grid, const double *stab, hipStream_t st)
 {
@@ -421,10 +568,16 @@ static hipError_t occ_launch_profile(const OccArgs &a, int dtype, bool seq, int6
 
 // rec_off / rec_len: HOST copies, already checked; d_rec_off / d_rec_len: the same on the device.  Launches on st, does not wait.
 // pf == null: letter strings (ratio_tables over d_codes); otherwise an averaged-structure profile, and ratio_tables / d_codes
-// are the letter part of joint mode or null.  Only the level-0 launch differs.
+// are the letter part of joint mode or null.  pr != null (pf null): two code streams, ratio_tables / d_codes the sequence side.
+// Only the level-0 launch differs.
+struct OccPair {
+    const double *struct_tables;   // HOST double [n_motifs][m][8]
+    const uint8_t *d_codes2;
+};
+
 static int occ_run(pfmscan_ctx *ctx, const char *who, const double *ratio_tables, int n_motifs, int m, int n_letters, const uint8_t *d_codes,
                    int64_t n_pos, const int64_t *rec_off, const int64_t *rec_len, const int64_t *d_rec_off, const int64_t *d_rec_len,
-                   int64_t n_rec, double *d_occ, int64_t *d_windows, hipStream_t st, const OccProfile *pf = nullptr)
+                   int64_t n_rec, double *d_occ, int64_t *d_windows, hipStream_t st, const OccProfile *pf = nullptr, const OccPair *pr = nullptr)
 {
     std::vector<int64_t> start(3 * (size_t)(n_rec + 1));
     int64_t *blk = start.data(), *grp = blk + n_rec + 1, *run = grp + n_rec + 1;
@@ -456,7 +609,7 @@ static int occ_run(pfmscan_ctx *ctx, const char *who, const double *ratio_tables
     if ((need_blk + BLOCK - 1) / BLOCK > 0x7FFFFFFF || (pf && need_blk > 0x7FFFFFFF)) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": a record is too long for one call");
     int rc;
     const size_t tab_bytes = ratio_tables ? (size_t)n_motifs * m * 8 * sizeof(double) : 0;
-    const size_t stab_bytes = pf ? (size_t)n_motifs * m * 7 * sizeof(double) : 0;   // behind the letter tables
+    const size_t stab_bytes = pf ? (size_t)n_motifs * m * 7 * sizeof(double) : pr ? tab_bytes : 0;   // behind the letter tables
     if ((rc = ensure(ctx, ctx->occ_tab, tab_bytes + stab_bytes))) return rc;
     if ((rc = ensure(ctx, ctx->occ_idx, (start.size() + (pf ? (size_t)need_run : 0)) * 8))) return rc;   // the prefix tables, then a pass's run -> record
     if ((rc = ensure(ctx, ctx->occ_bs, std::max<size_t>((size_t)need_blk * n_q_max * 8, 16)))) return rc;
@@ -465,6 +618,7 @@ static int occ_run(pfmscan_ctx *ctx, const char *who, const double *ratio_tables
     if (tab_bytes && (rc = upload(ctx, ctx->occ_tab.p, ratio_tables, tab_bytes, st))) return rc;
     const double *d_stab = (const double *)((const unsigned char *)ctx->occ_tab.p + tab_bytes);
     if (pf && (rc = upload(ctx, (void *)d_stab, pf->struct_tables, stab_bytes, st))) return rc;
+    if (pr && (rc = upload(ctx, (void *)d_stab, pr->struct_tables, stab_bytes, st))) return rc;
     if ((rc = upload(ctx, ctx->occ_idx.p, start.data(), start.size() * 8, st))) return rc;
     OccArgs a{};
     a.codes = d_codes;
@@ -477,6 +631,8 @@ static int occ_run(pfmscan_ctx *ctx, const char *who, const double *ratio_tables
     a.run_start = a.grp_start + n_rec + 1;
     a.run_rec = (int64_t *)ctx->occ_idx.p + start.size();
     a.profile = pf ? (const unsigned char *)pf->d_profile : nullptr;
+    a.codes2 = pr ? pr->d_codes2 : nullptr;
+    a.tables2 = pr ? d_stab : nullptr;
     a.m = m;
     a.n_letters = n_letters;
     a.n_motifs = n_motifs;
@@ -488,7 +644,7 @@ static int occ_run(pfmscan_ctx *ctx, const char *who, const double *ratio_tables
     for (int q0 = 0; q0 < n_motifs; q0 += n_q_max) {
         a.q_first = q0;
         a.n_q = std::min(n_q_max, n_motifs - q0);
-        a.chunk = pf ? OCCP_CHUNK : occ_chunk(m, n_letters, a.n_q);
+        a.chunk = pf ? OCCP_CHUNK : occ_chunk(m, pr ? OCC_PAIR_LETTERS : n_letters, a.n_q);
         if ((a.n_q + a.chunk - 1) / a.chunk > 65535) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": too many motifs for one call");
         const bool count = d_windows && q0 == 0;                   // Windows does not depend on the motif: counted in the first pass
         for (size_t i = 0; i + 1 < cuts.size(); ++i) {
@@ -504,8 +660,9 @@ static int occ_run(pfmscan_ctx *ctx, const char *who, const double *ratio_tables
             if (a.n_blk > 0) {
                 a.run_base = run[a.r0];
                 if (pf) occ_launch_run_records(a, st);
-                e = pf ? occ_launch_profile(a, pf->dtype, ratio_tables != nullptr, run[a.r1] - a.run_base, d_stab, st) : occ_launch_blocks(a, st);
-                if (e != hipSuccess) return fail_hip(ctx, e, pf ? "k_occ_profile_blocks" : "k_occ_blocks");
+                e = pf ? occ_launch_profile(a, pf->dtype, ratio_tables != nullptr, run[a.r1] - a.run_base, d_stab, st)
+                       : pr ? occ_launch_pair_blocks(a, st) : occ_launch_blocks(a, st);
+                if (e != hipSuccess) return fail_hip(ctx, e, pf ? "k_occ_profile_blocks" : pr ? "k_occ_pair_blocks" : "k_occ_blocks");
             }
             if ((rc = occ_launch_upper(ctx, a, st))) return rc;
         }
@@ -549,6 +706,24 @@ int occ_run_profile(pfmscan_ctx *ctx, const char *who, const OccProfile &pf, con
 {
     return occ_run(ctx, who, seq_tables, n_motifs, m, 4, seq_tables ? d_codes : nullptr, n_pos, rec_off, rec_len, d_rec_off, d_rec_len, n_rec, d_occ,
                    d_windows, st, &pf);
+}
+
+int occ_run_pair(pfmscan_ctx *ctx, const char *who, const double *seq_tables, const double *struct_tables, int n_motifs, int m,
+                 const uint8_t *d_codes, const uint8_t *d_codes2, int64_t n_pos, const int64_t *rec_off, const int64_t *rec_len,
+                 const int64_t *d_rec_off, const int64_t *d_rec_len, int64_t n_rec, double *d_occ, int64_t *d_windows, hipStream_t st)
+{
+    const OccPair pr{struct_tables, d_codes2};
+    return occ_run(ctx, who, seq_tables, n_motifs, m, 4, d_codes, n_pos, rec_off, rec_len, d_rec_off, d_rec_len, n_rec, d_occ, d_windows, st, nullptr, &pr);
+}
+
+int occ_pair_check(pfmscan_ctx *ctx, const char *who, const double *seq_tables, const double *struct_tables, int n_motifs, int m, int64_t n_pos,
+                   int64_t n_rec)
+{
+    if (m < 1 || m > PFMSCAN_MAX_M)
+        return fail(ctx, PFMSCAN_E_BADSHAPE, std::string(who) + ": width " + std::to_string(m) + " outside 1 .. PFMSCAN_MAX_M (" + std::to_string(PFMSCAN_MAX_M) + ")");
+    if (n_motifs < 0 || n_rec < 0 || n_pos < 0) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": negative size");
+    if (n_motifs > 0 && (!seq_tables || !struct_tables)) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": seq_tables or struct_tables is NULL");
+    return PFMSCAN_OK;
 }
 
 }  // namespace pfmscan
@@ -681,6 +856,60 @@ int pfmscan_occupancy_profile_staged(pfmscan_ctx *ctx, const double *struct_tabl
     const OccProfile pf{struct_tables, ctx->profile.p, ctx->staged_dtype};
     if ((rc = occ_run(ctx, who, seq_tables, n_motifs, m, 4, seq_tables ? (const uint8_t *)ctx->codes.p : nullptr, n_pos, rec_off, rec_len, d_off,
                       d_len, n_rec, d_occ, d_win, ctx->stream, &pf)))
+        return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(occ, d_occ, cells * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (windows) HIP_TRY(ctx, hipMemcpyAsync(windows, d_win, (size_t)n_rec * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return PFMSCAN_OK;
+}
+
+int pfmscan_occupancy_pair_dev(pfmscan_ctx *ctx, const double *seq_tables, const double *struct_tables, int n_motifs, int m,
+                               const uint8_t *d_codes, const uint8_t *d_codes2, int64_t n_pos, const int64_t *d_rec_off,
+                               const int64_t *d_rec_len, int64_t n_rec, double *d_occ, int64_t *d_windows)
+{
+    const char *who = "pfmscan_occupancy_pair_dev";
+    if (!ctx) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": NULL ctx");
+    if (int rc = occ_pair_check(ctx, who, seq_tables, struct_tables, n_motifs, m, n_pos, n_rec)) return rc;
+    if (n_rec == 0 || n_motifs == 0) return PFMSCAN_OK;
+    if (!d_rec_off || !d_rec_len || !d_occ || (n_pos > 0 && (!d_codes || !d_codes2)))
+        return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": NULL record table, codes or output");
+    if (misaligned(d_codes) || misaligned(d_codes2)) return fail(ctx, PFMSCAN_E_BADSHAPE, std::string(who) + ": stream base pointers must be 16-byte aligned");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // the record table decides every address the kernels form: it is read back and checked before anything is launched
+    std::vector<int64_t> rec(2 * (size_t)n_rec);
+    HIP_TRY(ctx, hipMemcpyAsync(rec.data(), d_rec_off, (size_t)n_rec * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(rec.data() + n_rec, d_rec_len, (size_t)n_rec * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (int rc = occ_check_records(ctx, who, rec.data(), rec.data() + n_rec, n_rec, n_pos)) return rc;
+    return occ_run_pair(ctx, who, seq_tables, struct_tables, n_motifs, m, d_codes, d_codes2, n_pos, rec.data(), rec.data() + n_rec, d_rec_off,
+                        d_rec_len, n_rec, d_occ, d_windows, ctx->stream);
+}
+
+int pfmscan_occupancy_pair_staged(pfmscan_ctx *ctx, const double *seq_tables, const double *struct_tables, int n_motifs, int m,
+                                  const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec, double *occ, int64_t *windows)
+{
+    const char *who = "pfmscan_occupancy_pair_staged";
+    if (!ctx) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": NULL ctx");
+    if (ctx->staged_n < 0) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": no stream staged (call pfmscan_stage first)");
+    if (ctx->staged_n > 0 && !ctx->staged_codes) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": no codes are staged");
+    if (ctx->staged_n > 0 && !ctx->staged_codes2) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": no codes2 are staged (pfmscan_stage_codes2)");
+    const int64_t n_pos = ctx->staged_n;
+    if (int rc = occ_pair_check(ctx, who, seq_tables, struct_tables, n_motifs, m, n_pos, n_rec)) return rc;
+    if (n_rec == 0 || n_motifs == 0) return PFMSCAN_OK;
+    if (!rec_off || !rec_len || !occ) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": NULL record table or output");
+    if (int rc = occ_check_records(ctx, who, rec_off, rec_len, n_rec, n_pos)) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc;
+    const size_t cells = (size_t)n_rec * n_motifs;
+    if ((rc = ensure(ctx, ctx->occ_rec, (size_t)n_rec * 16))) return rc;
+    if ((rc = ensure(ctx, ctx->occ_out, cells * 8 + (size_t)n_rec * 8))) return rc;
+    int64_t *d_off = (int64_t *)ctx->occ_rec.p, *d_len = d_off + n_rec;
+    if ((rc = upload(ctx, d_off, rec_off, (size_t)n_rec * 8, ctx->stream))) return rc;
+    if ((rc = upload(ctx, d_len, rec_len, (size_t)n_rec * 8, ctx->stream))) return rc;
+    double *d_occ = (double *)ctx->occ_out.p;
+    int64_t *d_win = windows ? (int64_t *)(d_occ + cells) : nullptr;
+    if ((rc = occ_run_pair(ctx, who, seq_tables, struct_tables, n_motifs, m, (const uint8_t *)ctx->codes.p, (const uint8_t *)ctx->codes2.p, n_pos,
+                           rec_off, rec_len, d_off, d_len, n_rec, d_occ, d_win, ctx->stream)))
         return rc;
     HIP_TRY(ctx, hipMemcpyAsync(occ, d_occ, cells * 8, hipMemcpyDeviceToHost, ctx->stream));
     if (windows) HIP_TRY(ctx, hipMemcpyAsync(windows, d_win, (size_t)n_rec * 8, hipMemcpyDeviceToHost, ctx->stream));

@@ -24,8 +24,9 @@ against the same background -- what reading iteration i's file would give, so ``
 on the output of a run.
 
 ``-p`` takes a sequence FASTA, ``-q`` a structure-letter FASTA; dot-bracket structures are annotated on the GPU first, as
-``occupancy -q`` does.  Not supported: averaged-structure profiles, two-FASTA pairs, ``--gpus``, priors other than one
-site per record, convergence criteria, a change of the motif's width.
+``occupancy -q`` does.  Averaged-structure profiles are ``python -m rnascan_amd.expect_profile``, two-FASTA pairs
+``python -m rnascan_amd.expect_pair``.  Not supported: ``--gpus``, priors other than one site per record, convergence criteria, a
+change of the motif's width.
 """
 import argparse
 import io

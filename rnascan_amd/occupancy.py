@@ -27,7 +27,8 @@ structure marginals of its profile, the ratio behind ``LogOdds.SeqStruct``; reco
 motifs of two libraries are paired as ``rnascan`` pairs them (``Motif_ID`` as the site profiles name a pair).  The
 structure background is ``-u``, ``-B file``, or else computed from the profiles as ``rnascan`` computes it; ``--pairing``
 pairs the profile's columns with the PFM's as ``rnascan`` does, ``--profile-dtype`` is the rows' storage on the device (the
-store's own, or float64 for text files, unless given).  Two-FASTA pairs (``-p -q seqs.fa structs.fa``) are not supported.
+store's own, or float64 for text files, unless given).  Two-FASTA pairs (``-p -q seqs.fa structs.fa``) are refused here: they are
+``python -m rnascan_amd.occupancy_pair``.
 """
 import argparse
 import math

@@ -190,6 +190,28 @@ class HipEngine(object):
         self._stage(stream)
         return self.ctx.expect_profile_staged(struct_tables, seq_tables, mode, stream.offsets, stream.lengths)
 
+    def _stage_pair(self, stream):
+        if stream.codes2 is None:
+            raise ValueError("the stream holds no second code stream (codes2)")
+        self._stage(stream)
+        if self._staged2 is not stream:
+            self.ctx.stage_codes2(stream.codes2)
+            self._staged2 = stream
+
+    def occupancy_pair(self, stream, seq_tables, struct_tables):
+        """summed likelihood ratios of two code streams: pair q is (seq_tables[q], struct_tables[q]), both
+        [m][8] of one width, the letter chain over ``stream.codes`` continued over ``stream.codes2`` ->
+        (occ float64 [n_rec][n_motifs], windows int64 [n_rec])"""
+        self._stage_pair(stream)
+        return self.ctx.occupancy_pair_staged(seq_tables, struct_tables, stream.offsets, stream.lengths)
+
+    def expect_pair(self, stream, seq_tables, struct_tables, mode):
+        """expected counts of two code streams: every window weighted by its joint ratio (or that over the
+        record's joint occupancy), the letters of both streams added up with these weights ->
+        (exp_seq, exp_struct float64 [n_rec][n_motifs][m][8], occ float64 [n_rec][n_motifs], windows int64 [n_rec])"""
+        self._stage_pair(stream)
+        return self.ctx.expect_pair_staged(seq_tables, struct_tables, mode, stream.offsets, stream.lengths)
+
     def hits_sum(self, stream, letter_table, struct_pssm, thr_seq, thr_struct, thr_sum, one_shot=True):
         """``hits`` of a motif with both parts, with the joint threshold decided on the device: a window is kept iff
         seq > thr_seq AND struct > thr_struct AND float64(round(float32 seq, 3)) + struct > thr_sum -- the printed

@@ -59,7 +59,7 @@
 extern "C" {
 #endif
 
-#define PFMSCAN_ABI_VERSION 25
+#define PFMSCAN_ABI_VERSION 26
 #define PFMSCAN_NCODE   8      /* columns of a letter table */
 #define PFMSCAN_SEP     7      /* separator / foreign-letter code */
 #define PFMSCAN_NSTRUCT 7      /* columns of a structure profile / structure PSSM */
@@ -1320,6 +1320,53 @@ int pfmscan_expect_pair_dev(pfmscan_ctx *ctx, const double *seq_tables, const do
 int pfmscan_expect_pair_staged(pfmscan_ctx *ctx, const double *seq_tables, const double *struct_tables, int n_motifs, int m,
                                int mode, const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec, double *exp_seq,
                                double *exp_struct, double *occ, int64_t *windows);
+
+/* ---- expected counts: the records added up on the device -------------------------------------------------------------------
+ * No counterpart in the reference.  The three families of expected counts above leave one matrix [m][8] per record and motif;
+ * a refinement step wants their sum over the records, which the commands used to make on the host with math.fsum.  These
+ * entry points make the same sum on the device, exactly, in the LONG ACCUMULATOR of "site profiles of a library" above: its
+ * layout (limbs the slow index inside a motif), its decomposition of a double into three 32-bit pieces
+ * (rnascan_amd/csrc/pfmscan_superacc.hpp), its headroom rule, RAW and NORMALISED, and the host helpers pfmscan_site_acc_add /
+ * _round / _from_doubles are used as they stand, with m * 8 cells per motif where a site profile has W * 7.  A sum of finite
+ * doubles >= 0 held exactly and rounded once IS math.fsum of them: pfmscan_site_acc_round of these accumulators is bit for bit
+ * what math.fsum gives cell by cell over the records; tests/expect_merge_rules.py restates it in Python ints.
+ * Integer additions do not depend on their order: 64-bit integer atomics, no float atomics, no tolerance.
+ *   d_exp   DEVICE double [n_rec][n_motifs][m][8]: what pfmscan_expect_dev, pfmscan_expect_profile_dev or
+ *           pfmscan_expect_pair_dev wrote, either of their matrices.
+ *   d_acc   DEVICE uint64 [n_motifs][PFMSCAN_SITE_LIMBS][m * 8]; cell e = 8 k + c of motif q is sum_i d_acc[q][i][e] * 2^(32 i).
+ *   d_bad   DEVICE int64 [n_motifs][2]: [q][0] the smallest record index of this call with a NaN or +-inf cell of motif q,
+ *           [q][1] the smallest with a cell < 0 (-inf is both); -1: none.
+ *   zero_first != 0: d_acc is zeroed and d_bad set to -1 first.  zero_first == 0: the call adds to what is there, so the batches
+ *           of a pass accumulate on the device and nothing goes home in between; an entry of d_bad that is >= 0 already stays
+ *           if it is the smaller one.  The caller keeps the records of one accumulator below 2^31; the sums are left RAW.
+ *   Cells   a NaN, +-inf or negative cell is never decomposed: it adds nothing and only sets d_bad.  +0.0 and -0.0 add nothing,
+ *           and -0.0 is not negative (math.fsum([-0.0]) is 0.0).  Every other cell is added exactly.
+ * pfmscan_expect_merge_dev is asynchronous on the ctx's stream and does not synchronise.  A NULL that is needed (d_acc, d_bad
+ * with n_motifs > 0; d_exp with records too), a negative size or n_rec >= 2^31: PFMSCAN_E_BADARG; m outside 1 .. PFMSCAN_MAX_M:
+ * PFMSCAN_E_BADSHAPE; n_rec == 0 or n_motifs == 0: PFMSCAN_OK, after zeroing if asked.
+ *
+ * _merged_staged: the _staged form of the same name with its matrices replaced by accumulators.  The pass runs into the ctx's
+ * scratch as before, the merge runs over that scratch, and only the accumulators, bad, occ and windows come home.
+ *   acc*    HOST uint64 [n_motifs][PFMSCAN_SITE_LIMBS][m * 8], NORMALISED in and out: this call's sums are ADDED with the
+ *           arithmetic of pfmscan_site_acc_add (a top limb that overflows: PFMSCAN_E_BADSHAPE).  Zero them once, call per batch.
+ *   bad*    HOST int64 [n_motifs][2] of THIS call: indices into this call's record table.
+ *   occ, windows   as in the form each one mirrors, bit for bit; either may be NULL.
+ * Which pointers are needed, the error codes and the order of the checks are those of the mirrored form, an accumulator where
+ * it takes a matrix; an accumulator that is given needs its bad (PFMSCAN_E_BADARG).  pfmscan_expect_profile_merged_staged
+ * takes acc_seq only with seq_tables; pfmscan_expect_pair_merged_staged takes either accumulator or both.  n_rec == 0 or
+ * n_motifs == 0: PFMSCAN_OK, nothing written. */
+int pfmscan_expect_merge_dev(pfmscan_ctx *ctx, const double *d_exp, int64_t n_rec, int n_motifs, int m, int zero_first,
+                             uint64_t *d_acc, int64_t *d_bad);
+int pfmscan_expect_merged_staged(pfmscan_ctx *ctx, int which, const double *ratio_tables, int n_motifs, int m, int n_letters,
+                                 int mode, const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec, uint64_t *acc,
+                                 int64_t *bad, double *occ, int64_t *windows);
+int pfmscan_expect_profile_merged_staged(pfmscan_ctx *ctx, const double *struct_tables, const double *seq_tables, int n_motifs,
+                                         int m, int mode, const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec,
+                                         uint64_t *acc_struct, uint64_t *acc_seq, int64_t *bad_struct, int64_t *bad_seq,
+                                         double *occ, int64_t *windows);
+int pfmscan_expect_pair_merged_staged(pfmscan_ctx *ctx, const double *seq_tables, const double *struct_tables, int n_motifs, int m,
+                                      int mode, const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec, uint64_t *acc_seq,
+                                      uint64_t *acc_struct, int64_t *bad_seq, int64_t *bad_struct, double *occ, int64_t *windows);
 
 #ifdef __cplusplus
 }

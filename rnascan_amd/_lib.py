@@ -22,7 +22,7 @@ NCODE = 8
 NSTRUCT = 7
 MAX_M = 64            # widest PFM of the tuned kernels and of PFM libraries
 MAX_WIDTH = 4096      # widest PFM accepted (wider than MAX_M: the plain rolled-loop kernel)
-ABI_VERSION = 25
+ABI_VERSION = 26
 
 # every symbol include/pfmscan.h declares (checked by tests/test_abi.py)
 SYMBOLS = [
@@ -61,6 +61,7 @@ SYMBOLS = [
     "pfmscan_expect_dev", "pfmscan_expect_staged",
     "pfmscan_expect_profile_dev", "pfmscan_expect_profile_staged",
     "pfmscan_occupancy_pair_dev", "pfmscan_occupancy_pair_staged", "pfmscan_expect_pair_dev", "pfmscan_expect_pair_staged",
+    "pfmscan_expect_merge_dev", "pfmscan_expect_merged_staged", "pfmscan_expect_profile_merged_staged", "pfmscan_expect_pair_merged_staged",
 ]
 PAIR_ROUTE_NONE, PAIR_ROUTE_FUSED, PAIR_ROUTE_TWO_PHASE, PAIR_ROUTE_DENSE, PAIR_ROUTE_CREDITS = range(5)   # Context.pair_sum_route()
 SITE_GROUP = 4096     # most hits of one group of the site profiles
@@ -254,6 +255,10 @@ def load():
     L.pfmscan_occupancy_pair_staged.argtypes = [vp, vp, vp, i32, i32, vp, vp, i64, vp, vp]
     L.pfmscan_expect_pair_dev.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, i64, vp, vp, i64, vp, vp, vp, vp]
     L.pfmscan_expect_pair_staged.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, i64, vp, vp, vp, vp]
+    L.pfmscan_expect_merge_dev.argtypes = [vp, vp, i64, i32, i32, i32, vp, vp]
+    L.pfmscan_expect_merged_staged.argtypes = [vp, i32, vp, i32, i32, i32, i32, vp, vp, i64, vp, vp, vp, vp]
+    L.pfmscan_expect_profile_merged_staged.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, i64, vp, vp, vp, vp, vp, vp]
+    L.pfmscan_expect_pair_merged_staged.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, i64, vp, vp, vp, vp, vp, vp]
     L.pfmscan_tsv_format.argtypes = [ctypes.POINTER(TsvColumn), i32, i64, i64, vp, i64, ctypes.POINTER(i64), vp, ctypes.POINTER(i32), i32]
     for name in SYMBOLS:          # every other entry point returns a status
         if name not in ("pfmscan_ctx_destroy", "pfmscan_motif_destroy", "pfmscan_last_error", "pfmscan_library_destroy",
@@ -1846,6 +1851,80 @@ class Context(object):
         self._check(self._L.pfmscan_expect_pair_staged(self._h, _ptr(sq), _ptr(st), n_motifs, m, int(mode), _ptr(rec_off), _ptr(rec_len),
                                                        rec_off.size, _ptr(exp_seq), _ptr(exp_struct), _ptr(occ), _ptr(windows)))
         return exp_seq, exp_struct, occ, windows
+
+    # -- expected counts, the records added up on the device (include/pfmscan.h: pfmscan_expect_merge_dev, *_merged_staged) --
+    def expect_merge_dev(self, d_exp, n_rec, n_motifs, m, zero_first, d_acc, d_bad):
+        """d_exp [n_rec][n_motifs][m][8] -> d_acc uint64 [n_motifs][SITE_LIMBS][m * 8] (RAW sums, added unless zero_first),
+        d_bad int64 [n_motifs][2]; device buffers, asynchronous on the ctx's stream"""
+        self._check(self._L.pfmscan_expect_merge_dev(self._h, _ptr(d_exp), int(n_rec), int(n_motifs), int(m), int(bool(zero_first)), _ptr(d_acc),
+                                                     _ptr(d_bad)))
+
+    @staticmethod
+    def _merge_acc(acc, n_motifs, m, name):
+        if not (isinstance(acc, np.ndarray) and acc.dtype == np.uint64 and acc.flags.c_contiguous and acc.flags.writeable) or \
+                acc.shape != (n_motifs, SITE_LIMBS, m * NCODE):
+            raise ValueError("%s must be a writable C-contiguous uint64 [%d][%d][%d]" % (name, n_motifs, SITE_LIMBS, m * NCODE))
+        return acc
+
+    @staticmethod
+    def _merge_records(rec_off, rec_len):
+        rec_off = np.ascontiguousarray(rec_off, dtype=np.int64)
+        rec_len = np.ascontiguousarray(rec_len, dtype=np.int64)
+        if rec_off.ndim != 1 or rec_off.shape != rec_len.shape:
+            raise ValueError("rec_off and rec_len must be lists of one length")
+        return rec_off, rec_len
+
+    def expect_merged_staged(self, ratio_tables, n_letters, mode, rec_off, rec_len, acc, which=0):
+        """``expect_staged`` with the matrices added up over the records on the device: acc uint64 [n_motifs][SITE_LIMBS][m * 8]
+        (normalised, changed in place: this call's sums are added) -> bad int64 [n_motifs][2] of this call (first record with a
+        non-finite cell, first with a negative one; -1: none), occ float64 [n_rec][n_motifs], windows int64 [n_rec]"""
+        rt = self._ratio_tables(ratio_tables)
+        rec_off, rec_len = self._merge_records(rec_off, rec_len)
+        self._merge_acc(acc, rt.shape[0], rt.shape[1], "acc")
+        bad = np.full((rt.shape[0], 2), -1, dtype=np.int64)
+        occ = np.zeros((rec_off.size, rt.shape[0]), dtype=np.float64)
+        windows = np.zeros(rec_off.size, dtype=np.int64)
+        self._check(self._L.pfmscan_expect_merged_staged(self._h, int(which), _ptr(rt), rt.shape[0], rt.shape[1], int(n_letters), int(mode),
+                                                         _ptr(rec_off), _ptr(rec_len), rec_off.size, _ptr(acc), _ptr(bad), _ptr(occ), _ptr(windows)))
+        return bad, occ, windows
+
+    def expect_profile_merged_staged(self, struct_tables, seq_tables, mode, rec_off, rec_len, acc_struct, acc_seq=None):
+        """``expect_profile_staged`` with both matrices added up over the records on the device into acc_struct and (with
+        seq_tables) acc_seq, uint64 [n_motifs][SITE_LIMBS][m * 8] normalised, changed in place ->
+        bad_struct int64 [n_motifs][2], bad_seq the same | None, occ float64 [n_rec][n_motifs], windows int64 [n_rec]"""
+        st, sq = self._expect_profile_tables(struct_tables, seq_tables)
+        n_motifs, m = (st if st is not None else sq).shape[:2]
+        rec_off, rec_len = self._merge_records(rec_off, rec_len)
+        self._merge_acc(acc_struct, n_motifs, m, "acc_struct")
+        if acc_seq is not None:
+            self._merge_acc(acc_seq, n_motifs, m, "acc_seq")
+        bad_struct = np.full((n_motifs, 2), -1, dtype=np.int64)
+        bad_seq = None if acc_seq is None else np.full((n_motifs, 2), -1, dtype=np.int64)
+        occ = np.zeros((rec_off.size, n_motifs), dtype=np.float64)
+        windows = np.zeros(rec_off.size, dtype=np.int64)
+        self._check(self._L.pfmscan_expect_profile_merged_staged(self._h, _ptr(st), _ptr(sq), n_motifs, m, int(mode), _ptr(rec_off), _ptr(rec_len),
+                                                                 rec_off.size, _ptr(acc_struct), _ptr(acc_seq), _ptr(bad_struct), _ptr(bad_seq),
+                                                                 _ptr(occ), _ptr(windows)))
+        return bad_struct, bad_seq, occ, windows
+
+    def expect_pair_merged_staged(self, seq_tables, struct_tables, mode, rec_off, rec_len, acc_seq, acc_struct):
+        """``expect_pair_staged`` with the matrices added up over the records on the device into acc_seq and acc_struct (either
+        may be None), uint64 [n_motifs][SITE_LIMBS][m * 8] normalised, changed in place ->
+        bad_seq, bad_struct int64 [n_motifs][2] (None where no accumulator), occ float64 [n_rec][n_motifs], windows int64 [n_rec]"""
+        sq, st = self._pair_tables(seq_tables, struct_tables)
+        n_motifs, m = sq.shape[:2]
+        rec_off, rec_len = self._merge_records(rec_off, rec_len)
+        for acc, name in ((acc_seq, "acc_seq"), (acc_struct, "acc_struct")):
+            if acc is not None:
+                self._merge_acc(acc, n_motifs, m, name)
+        bad_seq = None if acc_seq is None else np.full((n_motifs, 2), -1, dtype=np.int64)
+        bad_struct = None if acc_struct is None else np.full((n_motifs, 2), -1, dtype=np.int64)
+        occ = np.zeros((rec_off.size, n_motifs), dtype=np.float64)
+        windows = np.zeros(rec_off.size, dtype=np.int64)
+        self._check(self._L.pfmscan_expect_pair_merged_staged(self._h, _ptr(sq), _ptr(st), n_motifs, m, int(mode), _ptr(rec_off), _ptr(rec_len),
+                                                              rec_off.size, _ptr(acc_seq), _ptr(acc_struct), _ptr(bad_seq), _ptr(bad_struct), _ptr(occ),
+                                                              _ptr(windows)))
+        return bad_seq, bad_struct, occ, windows
 
     def time_scan_dev(self, motif, d_codes, d_profile, profile_dtype, n_pos, d_out_seq, d_out_struct,
                       stream=None, warmup=1, iters=5):

@@ -492,10 +492,11 @@ int pfmscan_expect_dev(pfmscan_ctx *ctx, const double *ratio_tables, int n_motif
                    n_rec, d_exp, d_occ, d_windows, ctx->stream);
 }
 
-int pfmscan_expect_staged(pfmscan_ctx *ctx, int which, const double *ratio_tables, int n_motifs, int m, int n_letters, int mode,
-                          const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec, double *exp, double *occ, int64_t *windows)
+// both _staged forms: the matrices come home (exp), or their exact sums over the records do (acc, bad: the merged form)
+static int expect_staged_any(pfmscan_ctx *ctx, const char *who, int which, const double *ratio_tables, int n_motifs, int m, int n_letters, int mode,
+                             const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec, double *exp, uint64_t *acc, int64_t *bad, bool merged,
+                             double *occ, int64_t *windows)
 {
-    const char *who = "pfmscan_expect_staged";
     if (!ctx) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": NULL ctx");
     if (which != 0 && which != 1) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": which must be 0 (codes) or 1 (codes2)");
     if (ctx->staged_n < 0) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": no stream staged (call pfmscan_stage first)");
@@ -505,7 +506,7 @@ int pfmscan_expect_staged(pfmscan_ctx *ctx, int which, const double *ratio_table
     if (int rc = occ_check(ctx, who, ratio_tables, n_motifs, m, n_letters, n_pos, n_rec)) return rc;
     if (int rc = exp_check_mode(ctx, who, mode)) return rc;
     if (n_rec == 0 || n_motifs == 0) return PFMSCAN_OK;
-    if (!rec_off || !rec_len || !exp) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": NULL record table or output");
+    if (!rec_off || !rec_len || (merged ? !acc || !bad : !exp)) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": NULL record table or output");
     if (int rc = occ_check_records(ctx, who, rec_off, rec_len, n_rec, n_pos)) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     int rc;
@@ -522,11 +523,30 @@ int pfmscan_expect_staged(pfmscan_ctx *ctx, int which, const double *ratio_table
     if ((rc = exp_run(ctx, who, ratio_tables, n_motifs, m, n_letters, mode, d_codes, n_pos, rec_off, rec_len, d_off, d_len, n_rec, d_exp, d_occ,
                       d_win, ctx->stream)))
         return rc;
+    if (merged) {
+        const ExpMergeOut out{d_exp, acc, bad};
+        return exp_merge_home(ctx, who, &out, 1, n_rec, n_motifs, m, d_occ, occ, d_win, windows);
+    }
     HIP_TRY(ctx, hipMemcpyAsync(exp, d_exp, cells * 8, hipMemcpyDeviceToHost, ctx->stream));
     if (occ) HIP_TRY(ctx, hipMemcpyAsync(occ, d_occ, pairs * 8, hipMemcpyDeviceToHost, ctx->stream));
     if (windows) HIP_TRY(ctx, hipMemcpyAsync(windows, d_win, (size_t)n_rec * 8, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return PFMSCAN_OK;
+}
+
+int pfmscan_expect_staged(pfmscan_ctx *ctx, int which, const double *ratio_tables, int n_motifs, int m, int n_letters, int mode,
+                          const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec, double *exp, double *occ, int64_t *windows)
+{
+    return expect_staged_any(ctx, "pfmscan_expect_staged", which, ratio_tables, n_motifs, m, n_letters, mode, rec_off, rec_len, n_rec, exp, nullptr,
+                             nullptr, false, occ, windows);
+}
+
+int pfmscan_expect_merged_staged(pfmscan_ctx *ctx, int which, const double *ratio_tables, int n_motifs, int m, int n_letters, int mode,
+                                 const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec, uint64_t *acc, int64_t *bad, double *occ,
+                                 int64_t *windows)
+{
+    return expect_staged_any(ctx, "pfmscan_expect_merged_staged", which, ratio_tables, n_motifs, m, n_letters, mode, rec_off, rec_len, n_rec, nullptr,
+                             acc, bad, true, occ, windows);
 }
 
 int pfmscan_expect_pair_dev(pfmscan_ctx *ctx, const double *seq_tables, const double *struct_tables, int n_motifs, int m, int mode,
@@ -553,11 +573,12 @@ int pfmscan_expect_pair_dev(pfmscan_ctx *ctx, const double *seq_tables, const do
                         d_rec_len, n_rec, d_exp_seq, d_exp_struct, d_occ, d_windows, ctx->stream);
 }
 
-int pfmscan_expect_pair_staged(pfmscan_ctx *ctx, const double *seq_tables, const double *struct_tables, int n_motifs, int m, int mode,
-                               const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec, double *exp_seq, double *exp_struct,
-                               double *occ, int64_t *windows)
+// both _staged forms of two code streams.  merged: exp_seq / exp_struct only say which matrices are asked for (acc_seq / acc_struct)
+static int expect_pair_staged_any(pfmscan_ctx *ctx, const char *who, const double *seq_tables, const double *struct_tables, int n_motifs, int m, int mode,
+                                  const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec, double *exp_seq, double *exp_struct,
+                                  uint64_t *acc_seq, uint64_t *acc_struct, int64_t *bad_seq, int64_t *bad_struct, bool merged, double *occ,
+                                  int64_t *windows)
 {
-    const char *who = "pfmscan_expect_pair_staged";
     if (!ctx) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": NULL ctx");
     if (ctx->staged_n < 0) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": no stream staged (call pfmscan_stage first)");
     if (ctx->staged_n > 0 && !ctx->staged_codes) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": no codes are staged");
@@ -565,7 +586,10 @@ int pfmscan_expect_pair_staged(pfmscan_ctx *ctx, const double *seq_tables, const
     const int64_t n_pos = ctx->staged_n;
     if (int rc = occ_pair_check(ctx, who, seq_tables, struct_tables, n_motifs, m, n_pos, n_rec)) return rc;
     if (int rc = exp_check_mode(ctx, who, mode)) return rc;
-    if (!exp_seq && !exp_struct) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": exp_seq and exp_struct are both NULL");
+    const bool want_seq = merged ? acc_seq != nullptr : exp_seq != nullptr, want_struct = merged ? acc_struct != nullptr : exp_struct != nullptr;
+    if (!want_seq && !want_struct)
+        return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + (merged ? ": acc_seq and acc_struct are both NULL" : ": exp_seq and exp_struct are both NULL"));
+    if (merged && ((want_seq && !bad_seq) || (want_struct && !bad_struct))) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": an accumulator without its bad");
     if (n_rec == 0 || n_motifs == 0) return PFMSCAN_OK;
     if (!rec_off || !rec_len) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": NULL record table");
     if (int rc = occ_check_records(ctx, who, rec_off, rec_len, n_rec, n_pos)) return rc;
@@ -578,19 +602,39 @@ int pfmscan_expect_pair_staged(pfmscan_ctx *ctx, const double *seq_tables, const
     if ((rc = upload(ctx, d_off, rec_off, (size_t)n_rec * 8, ctx->stream))) return rc;
     if ((rc = upload(ctx, d_len, rec_len, (size_t)n_rec * 8, ctx->stream))) return rc;
     double *d_base = (double *)ctx->exp_out.p;
-    double *d_sq = exp_seq ? d_base : nullptr;
-    double *d_st = exp_struct ? d_base + cells : nullptr;
+    double *d_sq = want_seq ? d_base : nullptr;
+    double *d_st = want_struct ? d_base + cells : nullptr;
     double *d_occ = occ ? d_base + 2 * cells : nullptr;
     int64_t *d_win = windows ? (int64_t *)(d_base + 2 * cells + pairs) : nullptr;
     if ((rc = exp_pair_run(ctx, who, seq_tables, struct_tables, n_motifs, m, mode, (const uint8_t *)ctx->codes.p, (const uint8_t *)ctx->codes2.p, n_pos,
                            rec_off, rec_len, d_off, d_len, n_rec, d_sq, d_st, d_occ, d_win, ctx->stream)))
         return rc;
+    if (merged) {
+        const ExpMergeOut out[2] = {{d_sq, acc_seq, bad_seq}, {d_st, acc_struct, bad_struct}};
+        return exp_merge_home(ctx, who, out, 2, n_rec, n_motifs, m, d_occ, occ, d_win, windows);
+    }
     if (exp_seq) HIP_TRY(ctx, hipMemcpyAsync(exp_seq, d_sq, cells * 8, hipMemcpyDeviceToHost, ctx->stream));
     if (exp_struct) HIP_TRY(ctx, hipMemcpyAsync(exp_struct, d_st, cells * 8, hipMemcpyDeviceToHost, ctx->stream));
     if (occ) HIP_TRY(ctx, hipMemcpyAsync(occ, d_occ, pairs * 8, hipMemcpyDeviceToHost, ctx->stream));
     if (windows) HIP_TRY(ctx, hipMemcpyAsync(windows, d_win, (size_t)n_rec * 8, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return PFMSCAN_OK;
+}
+
+int pfmscan_expect_pair_staged(pfmscan_ctx *ctx, const double *seq_tables, const double *struct_tables, int n_motifs, int m, int mode,
+                               const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec, double *exp_seq, double *exp_struct,
+                               double *occ, int64_t *windows)
+{
+    return expect_pair_staged_any(ctx, "pfmscan_expect_pair_staged", seq_tables, struct_tables, n_motifs, m, mode, rec_off, rec_len, n_rec, exp_seq,
+                                  exp_struct, nullptr, nullptr, nullptr, nullptr, false, occ, windows);
+}
+
+int pfmscan_expect_pair_merged_staged(pfmscan_ctx *ctx, const double *seq_tables, const double *struct_tables, int n_motifs, int m, int mode,
+                                      const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec, uint64_t *acc_seq, uint64_t *acc_struct,
+                                      int64_t *bad_seq, int64_t *bad_struct, double *occ, int64_t *windows)
+{
+    return expect_pair_staged_any(ctx, "pfmscan_expect_pair_merged_staged", seq_tables, struct_tables, n_motifs, m, mode, rec_off, rec_len, n_rec,
+                                  nullptr, nullptr, acc_seq, acc_struct, bad_seq, bad_struct, true, occ, windows);
 }
 
 }  // extern "C"

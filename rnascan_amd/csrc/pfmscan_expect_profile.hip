@@ -406,7 +406,7 @@ static int expp_run(pfmscan_ctx *ctx, const char *who, const double *struct_tabl
 
 // the checks both entry points share, before the rule "n_rec == 0 or n_motifs == 0: nothing to do"
 static int expp_check(pfmscan_ctx *ctx, const char *who, const double *struct_tables, const double *seq_tables, int n_motifs, int m, int mode,
-                      int profile_dtype, int64_t n_pos, int64_t n_rec, const void *exp_seq)
+                      int profile_dtype, int64_t n_pos, int64_t n_rec, bool with_exp_seq)
 {
     if (m < 1 || m > PFMSCAN_MAX_M)
         return fail(ctx, PFMSCAN_E_BADSHAPE, std::string(who) + ": width " + std::to_string(m) + " outside 1 .. PFMSCAN_MAX_M (" + std::to_string(PFMSCAN_MAX_M) + ")");
@@ -416,7 +416,7 @@ static int expp_check(pfmscan_ctx *ctx, const char *who, const double *struct_ta
         return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": mode must be PFMSCAN_EXPECT_RATIO or PFMSCAN_EXPECT_POSTERIOR");
     if (n_motifs < 0 || n_rec < 0 || n_pos < 0) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": negative size");
     if (!struct_tables && !seq_tables) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": struct_tables and seq_tables are both NULL");
-    if (exp_seq && !seq_tables) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": exp_seq needs seq_tables");
+    if (with_exp_seq && !seq_tables) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": exp_seq needs seq_tables");
     return PFMSCAN_OK;
 }
 
@@ -433,7 +433,7 @@ int pfmscan_expect_profile_dev(pfmscan_ctx *ctx, const double *struct_tables, co
 {
     const char *who = "pfmscan_expect_profile_dev";
     if (!ctx) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": NULL ctx");
-    if (int rc = expp_check(ctx, who, struct_tables, seq_tables, n_motifs, m, mode, profile_dtype, n_pos, n_rec, d_exp_seq)) return rc;
+    if (int rc = expp_check(ctx, who, struct_tables, seq_tables, n_motifs, m, mode, profile_dtype, n_pos, n_rec, d_exp_seq != nullptr)) return rc;
     if (seq_tables && !d_codes) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": seq_tables needs the codes");
     if (n_rec == 0 || n_motifs == 0) return PFMSCAN_OK;
     if (!d_rec_off || !d_rec_len || !d_exp_struct || (n_pos > 0 && !d_profile))
@@ -451,19 +451,21 @@ int pfmscan_expect_profile_dev(pfmscan_ctx *ctx, const double *struct_tables, co
                     d_rec_off, d_rec_len, n_rec, d_exp_struct, d_exp_seq, d_occ, d_windows, ctx->stream);
 }
 
-int pfmscan_expect_profile_staged(pfmscan_ctx *ctx, const double *struct_tables, const double *seq_tables, int n_motifs, int m, int mode,
-                                  const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec, double *exp_struct, double *exp_seq,
-                                  double *occ, int64_t *windows)
+// both _staged forms.  merged: the sums of the matrices over the records come home (acc_*, bad_*) instead of the matrices
+static int expect_profile_staged_any(pfmscan_ctx *ctx, const char *who, const double *struct_tables, const double *seq_tables, int n_motifs, int m,
+                                     int mode, const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec, double *exp_struct, double *exp_seq,
+                                     uint64_t *acc_struct, uint64_t *acc_seq, int64_t *bad_struct, int64_t *bad_seq, bool merged, double *occ,
+                                     int64_t *windows)
 {
-    const char *who = "pfmscan_expect_profile_staged";
     if (!ctx) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": NULL ctx");
     if (ctx->staged_n < 0) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": no stream staged (call pfmscan_stage first)");
     if (!ctx->staged_profile) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": no profile is staged");
     if (seq_tables && !ctx->staged_codes) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": seq_tables needs staged codes");
     const int64_t n_pos = ctx->staged_n;
-    if (int rc = expp_check(ctx, who, struct_tables, seq_tables, n_motifs, m, mode, ctx->staged_dtype, n_pos, n_rec, exp_seq)) return rc;
+    const bool want_seq = merged ? acc_seq != nullptr : exp_seq != nullptr;
+    if (int rc = expp_check(ctx, who, struct_tables, seq_tables, n_motifs, m, mode, ctx->staged_dtype, n_pos, n_rec, want_seq)) return rc;
     if (n_rec == 0 || n_motifs == 0) return PFMSCAN_OK;
-    if (!rec_off || !rec_len || !exp_struct) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": NULL record table or output");
+    if (!rec_off || !rec_len || (merged ? !acc_struct || !bad_struct || (want_seq && !bad_seq) : !exp_struct)) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": NULL record table or output");
     if (int rc = occ_check_records(ctx, who, rec_off, rec_len, n_rec, n_pos)) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     int rc;
@@ -474,18 +476,38 @@ int pfmscan_expect_profile_staged(pfmscan_ctx *ctx, const double *struct_tables,
     if ((rc = upload(ctx, d_off, rec_off, (size_t)n_rec * 8, ctx->stream))) return rc;
     if ((rc = upload(ctx, d_len, rec_len, (size_t)n_rec * 8, ctx->stream))) return rc;
     double *d_st = (double *)ctx->exp_out.p;
-    double *d_sq = exp_seq ? d_st + cells : nullptr;
+    double *d_sq = want_seq ? d_st + cells : nullptr;
     double *d_occ = occ ? d_st + 2 * cells : nullptr;
     int64_t *d_win = windows ? (int64_t *)(d_st + 2 * cells + pairs) : nullptr;
     if ((rc = expp_run(ctx, who, struct_tables, seq_tables, n_motifs, m, mode, (const uint8_t *)ctx->codes.p, ctx->profile.p, ctx->staged_dtype, n_pos,
                        rec_off, rec_len, d_off, d_len, n_rec, d_st, d_sq, d_occ, d_win, ctx->stream)))
         return rc;
+    if (merged) {
+        const ExpMergeOut out[2] = {{d_st, acc_struct, bad_struct}, {d_sq, acc_seq, bad_seq}};
+        return exp_merge_home(ctx, who, out, 2, n_rec, n_motifs, m, d_occ, occ, d_win, windows);
+    }
     HIP_TRY(ctx, hipMemcpyAsync(exp_struct, d_st, cells * 8, hipMemcpyDeviceToHost, ctx->stream));
     if (exp_seq) HIP_TRY(ctx, hipMemcpyAsync(exp_seq, d_sq, cells * 8, hipMemcpyDeviceToHost, ctx->stream));
     if (occ) HIP_TRY(ctx, hipMemcpyAsync(occ, d_occ, pairs * 8, hipMemcpyDeviceToHost, ctx->stream));
     if (windows) HIP_TRY(ctx, hipMemcpyAsync(windows, d_win, (size_t)n_rec * 8, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return PFMSCAN_OK;
+}
+
+int pfmscan_expect_profile_staged(pfmscan_ctx *ctx, const double *struct_tables, const double *seq_tables, int n_motifs, int m, int mode,
+                                  const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec, double *exp_struct, double *exp_seq,
+                                  double *occ, int64_t *windows)
+{
+    return expect_profile_staged_any(ctx, "pfmscan_expect_profile_staged", struct_tables, seq_tables, n_motifs, m, mode, rec_off, rec_len, n_rec,
+                                     exp_struct, exp_seq, nullptr, nullptr, nullptr, nullptr, false, occ, windows);
+}
+
+int pfmscan_expect_profile_merged_staged(pfmscan_ctx *ctx, const double *struct_tables, const double *seq_tables, int n_motifs, int m, int mode,
+                                         const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec, uint64_t *acc_struct, uint64_t *acc_seq,
+                                         int64_t *bad_struct, int64_t *bad_seq, double *occ, int64_t *windows)
+{
+    return expect_profile_staged_any(ctx, "pfmscan_expect_profile_merged_staged", struct_tables, seq_tables, n_motifs, m, mode, rec_off, rec_len,
+                                     n_rec, nullptr, nullptr, acc_struct, acc_seq, bad_struct, bad_seq, true, occ, windows);
 }
 
 }  // extern "C"

@@ -2,15 +2,16 @@
 
     python -m rnascan_amd.expect (-p seq.pfm | -q struct.pfm) [-C c] [-u | -b bg | -B bg] [--weight posterior|ratio]
                                  [--iterations N] [--all-motifs] [--struct-format auto|letters|dotbracket]
-                                 [--batch-records n] [--device d] -o PREFIX in.fa
+                                 [--batch-records n] [--merge auto|device|host] [--device d] -o PREFIX in.fa
 
 Every window of every record is weighted by its likelihood ratio prod_k p_k(x) / b(x) under the motif (``--weight ratio``)
 or by that ratio over the record's occupancy, the sum of the ratios of all its windows (``--weight posterior``, the default:
 every record carries one site in expectation, the OOPS model's E-step).  The letters under the windows are added up with
 these weights: ``E[k][c]`` is the expected number of times letter ``c`` lies under motif column ``k``.  The weights and the
 per-record sums are made on the GPU with the occupancy's arithmetic -- a sequential fp64 product per window, one rounded
-division per record, a fixed summation tree per record -- and the records are added up exactly
-(``math.fsum``), so the bytes written do not depend on ``--batch-records`` or on the order of the records.
+division per record, a fixed summation tree per record -- and the records are added up exactly, on the device
+in long integer accumulators or on the host with ``math.fsum`` (``--merge``, DESIGN.md 5k: the same bytes either way), so
+the bytes written do not depend on ``--batch-records`` or on the order of the records.
 
 ``PREFIX.expected.txt`` holds ``E`` as a PFM that ``-p`` / ``-q`` of ``rnascan``, ``sites``, ``occupancy`` and this command
 read (a multi-PFM library in the file's motif order with ``--all-motifs``; the file's first motif otherwise), every number in
@@ -58,9 +59,119 @@ def fsum_records(parts):
     return out
 
 
-def run(engine, recs, tables, motif_ids, letters, code_letters, mode, batch_records=BATCH_RECORDS):
+MERGES = ("auto", "device", "host")                  # --merge: where the records are added up
+NOT_FINITE = ("Motif %s, record %s: the occupancy or an expected count is infinite or not a number "
+              "(a ratio of the motif is; check the background and the pseudocount)")
+
+
+class NegativeCell(ExpectError):
+    """the device route met a cell < 0, which the long accumulator cannot hold"""
+
+
+def add_merge_option(parser):
+    parser.add_argument("--merge", choices=MERGES, default="auto",
+                        help="where the records are added up: exactly on the device (long accumulators), or on the host with "
+                             "math.fsum; the files do not depend on it [%(default)s: device where the engine offers it]")
+
+
+def merge_route(engine, merge, method):
+    """--merge and what the engine offers -> "device" or "host" """
+    if merge == "host" or (merge == "auto" and not hasattr(engine, method)):
+        return "host"
+    if not hasattr(engine, method):
+        raise ExpectError("--merge device: the engine has no %s" % method)
+    return "device"
+
+
+def with_merge(merge, route, device_pass, host_pass):
+    """the pass on its route; under ``auto`` a negative cell on the device sends the pass to the host, with a line on stderr"""
+    if route == "host":
+        return host_pass()
+    try:
+        return device_pass()
+    except NegativeCell as e:
+        if merge != "auto":
+            raise
+        fasta.eprint("%s; the pass is run again with the records added up on the host (--merge host)" % e)
+        return host_pass()
+
+
+def new_acc(n_motifs, m):
+    from ._lib import NCODE, SITE_LIMBS
+    return np.zeros((n_motifs, SITE_LIMBS, m * NCODE), dtype=np.uint64)
+
+
+def note_bad(first, bad, base):
+    """first int64 [n_motifs][2] (indices into the pass, -1: none) takes a batch's verdicts, whose records start at base"""
+    new = (first < 0) & (bad >= 0)
+    first[new] = bad[new] + base
+
+
+def merged_result(mid, occ, firsts, sums, ids, windows, not_finite=NOT_FINITE):
+    """what the host route makes of a motif's per-record matrices, from what the device route brings home: the checks in the
+    host route's order and with its messages.  ``firsts``: per written matrix, in the host route's order, int64 [2] = the
+    pass's first record with a non-finite cell and with a negative one; ``sums``: the rounded accumulators"""
+    bad = np.flatnonzero(~np.isfinite(occ))
+    who = int(bad[0]) if bad.size else next((int(f[0]) for f in firsts if f[0] >= 0), -1)
+    if who >= 0:
+        raise ExpectError(not_finite % (mid, ids[who]))
+    neg = next((int(f[1]) for f in firsts if f[1] >= 0), -1)
+    if neg >= 0:
+        raise NegativeCell("Motif %s, record %s: an expected count is negative (a cell of the profile is), which the device's "
+                           "accumulators cannot hold" % (mid, ids[neg]))
+    counted = occ > 0
+    if not counted.any():
+        raise ExpectError("Motif %s: no record contributes (every occupancy is 0)" % mid)
+    if not all(np.isfinite(s).all() for s in sums):
+        raise ExpectError("Motif %s: the sum of an expected count over the records is beyond the largest double" % mid)
+    ll = math.fsum(math.log2(x) for x in occ[counted].tolist())
+    return tuple(sums) + (int(counted.sum()), int((~counted).sum()), int(windows), round(ll, 3))
+
+
+def run_merged(engine, recs, tables, motif_ids, letters, code_letters, mode, batch_records=BATCH_RECORDS):
+    """``run`` with the records added up on the device: per width one long accumulator per motif, batch after batch added into
+    it (engine.expect_merged); only the occupancy and the window counts come home per record"""
+    from . import _lib, scanner
+    n_letters = len(code_letters)
+    groups = OrderedDict()
+    for mid in motif_ids:
+        groups.setdefault(tables[mid].shape[0], []).append(mid)
+    out = {}
+    for m, mids in groups.items():
+        stack = np.stack([tables[mid] for mid in mids])
+        acc = new_acc(len(mids), m)
+        first = np.full((len(mids), 2), -1, dtype=np.int64)
+        occs, wins, ids = [], [], []
+        for a in range(0, len(recs), batch_records):
+            b = min(len(recs), a + batch_records)
+            batch = scanner._RnaBatch(recs[a:b], None if letters == fasta.RNA else letters)
+            if len(batch) == 0:
+                continue
+            stream = pack.Stream(batch.codes, None, batch.offsets, batch.lengths)
+            bad, o, w = engine.expect_merged(stream, stack, n_letters, mode, acc)
+            note_bad(first, np.asarray(bad), len(ids))
+            occs.append(np.asarray(o))
+            wins.append(np.asarray(w))
+            ids += list(batch.ids)
+        E = _lib.site_acc_round(acc).reshape(len(mids), m, -1)[:, :, :n_letters]
+        for k, mid in enumerate(mids):
+            if not occs:
+                raise ExpectError("Motif %s: no record contributes (every occupancy is 0)" % mid)
+            out[mid] = merged_result(mid, np.concatenate([o[:, k] for o in occs]), [first[k]], [np.ascontiguousarray(E[k])], ids,
+                                     np.concatenate(wins).sum())
+    return out
+
+
+def run(engine, recs, tables, motif_ids, letters, code_letters, mode, batch_records=BATCH_RECORDS, merge="host"):
     """one pass over the records -> {motif id: (E float64 [m][n_letters] in code order, records, skipped, windows, log2
-    likelihood)}; tables {motif id: [m][8]}.  One motif group (width) at a time, batch by batch of records."""
+    likelihood)}; tables {motif id: [m][8]}.  One motif group (width) at a time, batch by batch of records.  ``merge``: where
+    the records are added up (MERGES); the result does not depend on it."""
+    args = (engine, recs, tables, motif_ids, letters, code_letters, mode, batch_records)
+    return with_merge(merge, merge_route(engine, merge, "expect_merged"), lambda: run_merged(*args), lambda: run_host(*args))
+
+
+def run_host(engine, recs, tables, motif_ids, letters, code_letters, mode, batch_records=BATCH_RECORDS):
+    """``run`` with every per-record matrix brought home and added up with math.fsum"""
     from . import scanner
     n_letters = len(code_letters)
     groups = OrderedDict()
@@ -141,6 +252,7 @@ def getoptions(argv=None):
                         help="-q: what the structure FASTA holds; dot-bracket strings are annotated on the GPU first [%(default)s]")
     parser.add_argument("--batch-records", type=int, default=BATCH_RECORDS, dest="batch_records",
                         help="records per device call; the files do not depend on it [%(default)s]")
+    add_merge_option(parser)
     parser.add_argument("--device", type=int, default=int(os.environ.get("RNASCAN_DEVICE", "0")), help="HIP device index [%(default)s]")
     args = parser.parse_args(argv)
     if args.uniform_background and (args.bg_seq or args.bg_struct):
@@ -199,7 +311,7 @@ def main(argv=None, engine=None):
         results = None
         for it in range(1, args.iterations + 1):
             tables = dict((mid, odds[mid].ratio_table(code_letters)) for mid in motif_ids)
-            got = run(engine, recs, tables, motif_ids, letters, code_letters, MODES[args.weight], args.batch_records)
+            got = run(engine, recs, tables, motif_ids, letters, code_letters, MODES[args.weight], args.batch_records, args.merge)
             for mid in motif_ids:
                 E, n, skipped, windows, ll = got[mid]
                 summary.append("%s\t%d\t%d\t%d\t%d\t%s\n" % (mid, it, n, skipped, windows, repr(ll)))

@@ -2,15 +2,16 @@
 
     python -m rnascan_amd.expect_pair -p seq.pfm -q struct.pfm [-C c] [-u | -b bg -B bg] [--weight posterior|ratio]
                                       [--iterations N] [--all-motifs] [--struct-format auto|letters|dotbracket]
-                                      [--batch-records n] [--device d] -o PREFIX seqs.fa structs.fa
+                                      [--batch-records n] [--merge auto|device|host] [--device d] -o PREFIX seqs.fa structs.fa
 
 Every window of every record is weighted by its JOINT likelihood ratio -- the sequence ratio times the structure ratio, the
 ratio behind ``LogOdds.SeqStruct`` (``--weight ratio``) -- or by that over the record's joint occupancy (``--weight
 posterior``, the default: one site per record in expectation).  Under these weights the letters of BOTH files are added up:
 ``E_seq[k][c]`` is the expected number of times nucleotide ``c`` lies under motif column ``k``, ``E_struct[k][c]`` the same
 for structure letter ``c``.  The joint weight of a window cannot be recovered from ``expect -p`` and ``expect -q``.  Weights
-and per-record sums are made on the GPU by the rules of DESIGN.md 5j; the records are added up exactly (``math.fsum``), so the
-bytes written do not depend on ``--batch-records`` or on the order of the records.
+and per-record sums are made on the GPU by the rules of DESIGN.md 5j; the records are added up exactly, on the device or with
+``math.fsum`` on the host (``--merge``, DESIGN.md 5k: the same bytes), so the bytes written do not depend on
+``--batch-records`` or on the order of the records.
 
 ``PREFIX.expected.seq.txt`` is a raw-sum PFM that ``-p`` reads, ``PREFIX.expected.struct.txt`` one that ``-q`` reads -- the
 names and formats of ``expect_profile``: multi-PFM libraries in pair order with ``--all-motifs`` (pairs named as the site
@@ -20,7 +21,7 @@ profiles name them), the first pair otherwise.  ``PREFIX.summary.txt`` has ``exp
 against the same backgrounds, and the pass is run again; ``--iterations 2`` writes the bytes of a run on the outputs of a run.
 
 Inputs, pairing, backgrounds and dot-bracket structures are handled exactly as ``occupancy_pair`` handles them (the same
-code).  Not supported: the per-column 4 x 7 joint expected table, ``--gpus``, other priors, merging records on the device.
+code).  Not supported: the per-column 4 x 7 joint expected table, ``--gpus``, other priors.
 """
 import argparse
 import math
@@ -34,9 +35,54 @@ from . import expect, fasta, occupancy, occupancy_pair, pack
 BATCH_RECORDS = expect.BATCH_RECORDS
 
 
-def run(engine, recs, srecs, seq_odds, struct_odds, pairs, mode, batch_records=BATCH_RECORDS):
+NOT_FINITE = ("Motif %s, record %s: the occupancy or an expected count is infinite or not a number "
+              "(a ratio of one of the motifs is; check the backgrounds and the pseudocount)")
+
+
+def run(engine, recs, srecs, seq_odds, struct_odds, pairs, mode, batch_records=BATCH_RECORDS, merge="host"):
     """one pass -> {pair id: (E_seq float64 [m][4] in code order, E_struct float64 [m][7] in code order
-    (pack.STRUCT_LETTERS), records, skipped, windows, log2 likelihood)}"""
+    (pack.STRUCT_LETTERS), records, skipped, windows, log2 likelihood)}.  ``merge``: where the records are added up
+    (expect.MERGES); the result does not depend on it."""
+    args = (engine, recs, srecs, seq_odds, struct_odds, pairs, mode, batch_records)
+    return expect.with_merge(merge, expect.merge_route(engine, merge, "expect_pair_merged"), lambda: run_merged(*args), lambda: run_host(*args))
+
+
+def run_merged(engine, recs, srecs, seq_odds, struct_odds, pairs, mode, batch_records=BATCH_RECORDS):
+    """``run`` with the records added up on the device (engine.expect_pair_merged): two long accumulators per pair"""
+    from . import _lib, sites
+    motif_ids = [sites.pair_id(a, b) for a, b in pairs]
+    groups = occupancy._by_width([seq_odds[a].length for a, _ in pairs])
+    tables = dict((m, occupancy_pair.pair_tables(seq_odds, struct_odds, pairs, ks)) for m, ks in groups.items())
+    acc = dict((m, (expect.new_acc(len(ks), m), expect.new_acc(len(ks), m))) for m, ks in groups.items())
+    first = dict((m, (np.full((len(ks), 2), -1, dtype=np.int64), np.full((len(ks), 2), -1, dtype=np.int64))) for m, ks in groups.items())
+    occs = dict((k, []) for k in range(len(pairs)))
+    wins = dict((m, 0) for m in groups)                            # Windows depends on the width
+    seen = []
+    for ids, stream in occupancy_pair.batches(recs, srecs, batch_records):
+        for m, ks in groups.items():
+            bq, bs, o, w = engine.expect_pair_merged(stream, tables[m][0], tables[m][1], mode, acc[m][0], acc[m][1])
+            expect.note_bad(first[m][0], np.asarray(bq), len(seen))
+            expect.note_bad(first[m][1], np.asarray(bs), len(seen))
+            o = np.asarray(o)
+            for j, k in enumerate(ks):
+                occs[k].append(o[:, j])
+            wins[m] += int(np.asarray(w).sum())
+        seen += ids
+    out = {}
+    place = dict((k, (m, j)) for m, ks in groups.items() for j, k in enumerate(ks))
+    sums = dict((m, (_lib.site_acc_round(acc[m][0]).reshape(len(ks), m, -1)[:, :, :4], _lib.site_acc_round(acc[m][1]).reshape(len(ks), m, -1)[:, :, :7]))
+                for m, ks in groups.items())
+    for k, mid in enumerate(motif_ids):
+        if not occs[k]:
+            raise expect.ExpectError("Motif %s: no record contributes (every occupancy is 0)" % mid)
+        m, j = place[k]
+        out[mid] = expect.merged_result(mid, np.concatenate(occs[k]), [first[m][0][j], first[m][1][j]],
+                                        [np.ascontiguousarray(sums[m][0][j]), np.ascontiguousarray(sums[m][1][j])], seen, wins[m], NOT_FINITE)
+    return out
+
+
+def run_host(engine, recs, srecs, seq_odds, struct_odds, pairs, mode, batch_records=BATCH_RECORDS):
+    """``run`` with every per-record matrix brought home and added up with math.fsum"""
     from . import sites
     motif_ids = [sites.pair_id(a, b) for a, b in pairs]
     groups = occupancy._by_width([seq_odds[a].length for a, _ in pairs])
@@ -87,6 +133,7 @@ def getoptions(argv=None):
     parser.add_argument("--weight", choices=sorted(expect.MODES), default="posterior",
                         help="weight of a window: its joint likelihood ratio, or that over the record's joint occupancy [%(default)s]")
     parser.add_argument("--iterations", type=int, default=1, help="EM steps: each takes the last one's expected matrices as its PFMs [%(default)s]")
+    expect.add_merge_option(parser)
     args = parser.parse_intermixed_args(argv)
     occupancy_pair.check_options(parser, args)
     args.single, args.profiles = "expect", "expect_profile"
@@ -113,7 +160,7 @@ def main(argv=None, engine=None):
         summary = ["\t".join(expect.COLUMNS) + "\n"]
         got = None
         for it in range(1, args.iterations + 1):
-            got = run(engine, recs, srecs, seq_odds, struct_odds, pairs, expect.MODES[args.weight], args.batch_records)
+            got = run(engine, recs, srecs, seq_odds, struct_odds, pairs, expect.MODES[args.weight], args.batch_records, args.merge)
             for mid in motif_ids:
                 _, _, n, skipped, windows, ll = got[mid]
                 summary.append("%s\t%d\t%d\t%d\t%d\t%s\n" % (mid, it, n, skipped, windows, repr(ll)))

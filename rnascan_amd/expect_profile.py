@@ -4,7 +4,8 @@
     python -m rnascan_amd.expect_profile -p seq.pfm -q struct.pfm [...] seqs.fa avgdir_or_store/ -o PREFIX
     python -m rnascan_amd.expect_profile -p seq.pfm [...] seqs.fa avgdir_or_store/ -o PREFIX
         [-C c] [-u | -b bg | -B bg] [--weight posterior|ratio] [--iterations N] [--all-motifs]
-        [--pairing aligned|positional] [--profile-dtype float32|float64] [--batch-records n] [--device d]
+        [--pairing aligned|positional] [--profile-dtype float32|float64] [--batch-records n]
+        [--merge auto|device|host] [--device d]
 
 Every window of every record is weighted as ``expect`` weights it (``--weight``), by the structure motif's marginal ratios
 over the averaged-structure profile (``-q`` alone), by the sequence motif's ratios over the FASTA's letters (``-p`` alone), or
@@ -14,8 +15,10 @@ amount of structural context ``c`` under motif column ``k``.  It 
 sums under hits; on profiles with a single 1 per row it is ``expect``'s count of structure letters.  It is NOT the posterior
 of the letter given the motif (``r * S / d``), which this does not compute.  With ``-p`` the letters are counted too, as
 ``expect`` counts them, under the same weights.  The weights and per-record sums are made on the GPU, bit for bit by the
-rules of DESIGN.md 5g / 5h / 5i; the records are added up exactly (``math.fsum``), so the bytes written do not depend on
-``--batch-records`` or on the order of the records.
+rules of DESIGN.md 5g / 5h / 5i; the records are added up exactly, on the device or with ``math.fsum`` on the host
+(``--merge``, DESIGN.md 5k: the same bytes; a negative profile cell, which the device's accumulators cannot hold, sends
+``auto`` to the host and ends ``device`` with exit 1), so the bytes written do not depend on ``--batch-records`` or on the
+order of the records.
 
 ``PREFIX.expected.struct.txt``: the structure matrix as a raw-sum PFM that ``-q`` reads; ``PREFIX.expected.seq.txt`` (with
 ``-p``): the sequence matrix as a raw-sum PFM that ``-p`` reads.  Both are multi-PFM libraries in pair order with
@@ -32,7 +35,7 @@ same background, and the pass is run again; with ``-p`` alone the sequence matri
 the last pass's.  ``--iterations 2`` writes the bytes of a run on the outputs of a run.  Refused with ``--pairing
 positional``, under which the written columns are not the ones the PFM's letters were paired with.
 
-Not supported: ``--flank``, two-FASTA pairs, ``--gpus``, other priors, merging records on the device.
+Not supported: ``--flank``, two-FASTA pairs, ``--gpus``, other priors.
 """
 import argparse
 import os
@@ -46,10 +49,98 @@ from . import expect, fasta, pack
 BATCH_RECORDS = expect.BATCH_RECORDS
 
 
-def run(engine, recs, profiles, seq_odds, struct_odds, pairs, mode, pairing="aligned", batch_records=BATCH_RECORDS):
+NOT_FINITE = ("Motif %s, record %s: the occupancy or an expected count is infinite or not a number "
+              "(a ratio of the motif or a cell of the profile is; check the background and the pseudocount)")
+
+
+def run(engine, recs, profiles, seq_odds, struct_odds, pairs, mode, pairing="aligned", batch_records=BATCH_RECORDS, merge="host"):
     """one pass -> {pair id: (E_struct float64 [m][7] in sites.STRUCT_ORDER, E_seq float64 [m][4] in code order | None,
     records, skipped, windows, log2 likelihood)}.  ``pairs``: [(sequence id | None, structure id | None)]; ``recs``: the
-    FASTA's records in the profiles' order, or None (structure only)"""
+    FASTA's records in the profiles' order, or None (structure only).  ``merge``: where the records are added up
+    (expect.MERGES); the result does not depend on it."""
+    args = (engine, recs, profiles, seq_odds, struct_odds, pairs, mode, pairing, batch_records)
+    return expect.with_merge(merge, expect.merge_route(engine, merge, "expect_profile_merged"), lambda: run_merged(*args), lambda: run_host(*args))
+
+
+class _Folded(object):
+    """the structure accumulators of one width, cell axis in the WRITTEN letters' order (sites.STRUCT_ORDER).  The device adds
+    in the run's stored column order: the runs of one order share an accumulator, which is folded in -- its columns mapped to
+    the letters -- when the order changes and at the end"""
+
+    def __init__(self, n_motifs, m):
+        self.total = expect.new_acc(n_motifs, m)
+        self.n_motifs, self.m = n_motifs, m
+        self.order, self.acc = None, None
+
+    def current(self, to_letters):
+        if self.order != to_letters:
+            self.fold()
+            self.order, self.acc = list(to_letters), expect.new_acc(self.n_motifs, self.m)
+        return self.acc
+
+    def fold(self):
+        from . import _lib
+        if self.acc is not None:
+            cells = self.acc.reshape(self.n_motifs, _lib.SITE_LIMBS, self.m, _lib.NCODE)
+            _lib.site_acc_add(self.total, np.ascontiguousarray(cells[:, :, :, self.order + [7]]).reshape(self.total.shape))
+        self.order, self.acc = None, None
+        return self.total
+
+
+def run_merged(engine, recs, profiles, seq_odds, struct_odds, pairs, mode, pairing="aligned", batch_records=BATCH_RECORDS):
+    """``run`` with the records added up on the device (engine.expect_profile_merged)"""
+    from . import _lib, occupancy, scanner, sites
+    motif_ids = [sites.pair_id(a, b) for a, b in pairs]
+    width = lambda a, b: (struct_odds[b] if b is not None else seq_odds[a]).length
+    groups = occupancy._by_width([width(a, b) for a, b in pairs])
+    with_seq, with_struct = pairs[0][0] is not None, pairs[0][1] is not None
+    seq_tables = None
+    if with_seq:
+        seq_tables = dict((m, np.stack([seq_odds[pairs[k][0]].ratio_table(pack.RNA_LETTERS) for k in ks])) for m, ks in groups.items())
+    folded = dict((m, _Folded(len(ks), m)) for m, ks in groups.items())
+    acc_seq = dict((m, expect.new_acc(len(ks), m) if with_seq else None) for m, ks in groups.items())
+    first = dict((m, (np.full((len(ks), 2), -1, dtype=np.int64), np.full((len(ks), 2), -1, dtype=np.int64))) for m, ks in groups.items())
+    occs = dict((k, []) for k in range(len(pairs)))
+    wins = dict((m, 0) for m in groups)                            # Windows depends on the width (and, with -p, on the codes)
+    seen = []
+    for a in range(0, len(profiles.ids), batch_records):
+        b = min(len(profiles.ids), a + batch_records)
+        at = a
+        for ids, cols, pst in profiles.runs(a, b):
+            stream = occupancy.paired_batch(recs, at, ids, pst)
+            to_letters = [list(cols).index(l) for l in sites.STRUCT_ORDER]   # stored column of every letter of the written PFM
+            for m, ks in groups.items():
+                st = np.stack([scanner.struct_matrix(struct_odds[pairs[k][1]], cols, pairing) for k in ks]) if with_struct else None
+                bs, bq, o, w = engine.expect_profile_merged(stream, st, seq_tables[m] if with_seq else None, mode,
+                                                            folded[m].current(to_letters), acc_seq[m])
+                expect.note_bad(first[m][0], np.asarray(bs), len(seen))
+                if with_seq:
+                    expect.note_bad(first[m][1], np.asarray(bq), len(seen))
+                o = np.asarray(o)
+                for j, k in enumerate(ks):
+                    occs[k].append(o[:, j])
+                wins[m] += int(np.asarray(w).sum())
+            seen += list(ids)
+            at += len(ids)
+    place = dict((k, (m, j)) for m, ks in groups.items() for j, k in enumerate(ks))
+    est = dict((m, _lib.site_acc_round(folded[m].fold()).reshape(len(ks), m, -1)[:, :, :7]) for m, ks in groups.items())
+    esq = dict((m, _lib.site_acc_round(acc_seq[m]).reshape(len(ks), m, -1)[:, :, :4] if with_seq else None) for m, ks in groups.items())
+    out = {}
+    for k, mid in enumerate(motif_ids):
+        if not occs[k]:
+            raise expect.ExpectError("Motif %s: no record contributes (every occupancy is 0)" % mid)
+        m, j = place[k]
+        firsts, sums = [first[m][0][j]], [np.ascontiguousarray(est[m][j])]
+        if with_seq:
+            firsts.append(first[m][1][j])
+            sums.append(np.ascontiguousarray(esq[m][j]))
+        got = expect.merged_result(mid, np.concatenate(occs[k]), firsts, sums, seen, wins[m], NOT_FINITE)
+        out[mid] = got if with_seq else (got[0], None) + got[1:]
+    return out
+
+
+def run_host(engine, recs, profiles, seq_odds, struct_odds, pairs, mode, pairing="aligned", batch_records=BATCH_RECORDS):
+    """``run`` with every per-record matrix brought home and added up with math.fsum"""
     import math
     from . import occupancy, scanner, sites
     motif_ids = [sites.pair_id(a, b) for a, b in pairs]
@@ -130,6 +221,7 @@ def getoptions(argv=None):
                         help="device storage of averaged-structure rows [the store's own dtype; float64 for text files]")
     parser.add_argument("--batch-records", type=int, default=BATCH_RECORDS, dest="batch_records",
                         help="records per device call; the files do not depend on it [%(default)s]")
+    expect.add_merge_option(parser)
     parser.add_argument("--device", type=int, default=int(os.environ.get("RNASCAN_DEVICE", "0")), help="HIP device index [%(default)s]")
     args = parser.parse_intermixed_args(argv)
     if args.uniform_background and (args.bg_seq or args.bg_struct):
@@ -181,7 +273,7 @@ def main(argv=None, engine=None):
         summary = ["\t".join(expect.COLUMNS) + "\n"]
         got = None
         for it in range(1, args.iterations + 1):
-            got = run(engine, recs, profiles, seq_odds, struct_odds, pairs, expect.MODES[args.weight], args.pairing, args.batch_records)
+            got = run(engine, recs, profiles, seq_odds, struct_odds, pairs, expect.MODES[args.weight], args.pairing, args.batch_records, args.merge)
             for mid in motif_ids:
                 _, _, n, skipped, windows, ll = got[mid]
                 summary.append("%s\t%d\t%d\t%d\t%d\t%s\n" % (mid, it, n, skipped, windows, repr(ll)))

@@ -212,6 +212,28 @@ class HipEngine(object):
         self._stage_pair(stream)
         return self.ctx.expect_pair_staged(seq_tables, struct_tables, mode, stream.offsets, stream.lengths)
 
+    # the three passes above with their matrices added up over the records on the device: the accumulators
+    # (uint64 [n_motifs][_lib.SITE_LIMBS][m * 8], normalised) are changed in place, one call per batch adds that batch's records
+    def expect_merged(self, stream, ratio_tables, n_letters, mode, acc, which=0):
+        """``expect`` -> (bad int64 [n_motifs][2]: this call's first record with a non-finite cell, first with a negative one, -1
+        for none; occ float64 [n_rec][n_motifs]; windows int64 [n_rec]); acc += the exact sum of the call's matrices"""
+        self._stage(stream)
+        if which == 1 and self._staged2 is not stream:
+            self.ctx.stage_codes2(stream.codes2)
+            self._staged2 = stream
+        return self.ctx.expect_merged_staged(ratio_tables, n_letters, mode, stream.offsets, stream.lengths, acc, which)
+
+    def expect_profile_merged(self, stream, struct_tables, seq_tables, mode, acc_struct, acc_seq=None):
+        """``expect_profile`` -> (bad_struct, bad_seq | None, occ, windows); the cell axis of acc_struct is in the profile's
+        STORED column order, as the matrices are"""
+        self._stage(stream)
+        return self.ctx.expect_profile_merged_staged(struct_tables, seq_tables, mode, stream.offsets, stream.lengths, acc_struct, acc_seq)
+
+    def expect_pair_merged(self, stream, seq_tables, struct_tables, mode, acc_seq, acc_struct):
+        """``expect_pair`` -> (bad_seq, bad_struct, occ, windows)"""
+        self._stage_pair(stream)
+        return self.ctx.expect_pair_merged_staged(seq_tables, struct_tables, mode, stream.offsets, stream.lengths, acc_seq, acc_struct)
+
     def hits_sum(self, stream, letter_table, struct_pssm, thr_seq, thr_struct, thr_sum, one_shot=True):
         """``hits`` of a motif with both parts, with the joint threshold decided on the device: a window is kept iff
         seq > thr_seq AND struct > thr_struct AND float64(round(float32 seq, 3)) + struct > thr_sum -- the printed

@@ -10,7 +10,7 @@
 // restates it in numpy and the bits are compared.
 //
 //   k_exp_inverse   v of every (record, motif) from the occupancy, which the call computes first over the same records
-//                   (occ_run_letters); -1.0 stands for "occ_r is +0.0" (no other v is negative).
+//                   (occ_run); -1.0 stands for "occ_r is +0.0" (no other v is negative).
 //   k_exp_group_records  before it, per range of records: the record of every workgroup's first block.
 //   k_exp_blocks    level 0.  A workgroup owns 8 consecutive blocks of the pass, 32 lanes each: a lane per window.  The
 //                   block's 32 + m - 1 codes are parked in LDS (foreign ones as 0xFF); for every motif of the pass a lane
@@ -24,7 +24,8 @@
 // The m x n_letters cells of a motif are independent columns of block sums: levels 1 and up are the occupancy's own
 // k_occ_level1 and k_occ_finish (occ_launch_upper), which store column row * n_letters + c at [row][c] of the [m][8] matrix.
 // Scratch is blocks x columns doubles under the occupancy's cap: records run in passes, and when the longest record alone
-// passes the cap, so do the columns (cells, then motifs).
+// passes the cap, so do the columns (cells, then motifs): occ_plan (pfmscan_occ_plan.hpp) over columns, or over the matrix rows
+// of pairs.  The two level-0 kernels share how a lane finds its block and what it parks in a strip (exp_block, exp_code).
 #include <algorithm>
 #include <string>
 #include <vector>
@@ -67,6 +68,34 @@ __global__ __launch_bounds__(BLOCK) void k_exp_group_records(const OccArgs a, in
     for (int64_t u = (b0 + EXP_WB - 1) / EXP_WB; u * EXP_WB < b1; ++u) wg_rec[u] = r;
 }
 
+// ---- what the two level-0 kernels share: a workgroup owns EXP_WB consecutive blocks of the pass, 32 lanes each ---------------
+struct ExpBlock {
+    int64_t r;                   // the block's record
+    int64_t s0;                  // its first position in the stream
+    int nw;                      // its windows, >= 1
+    int need;                    // its codes, nw + m - 1: all inside the record
+};
+
+// block gb < a.n_blk of the pass: its record by a short walk from the record of the workgroup's first block (wg_rec, written by
+// k_exp_group_records), and its geometry
+__device__ __forceinline__ ExpBlock exp_block(const OccArgs &a, const int64_t *__restrict__ wg_rec, int64_t gb)
+{
+    const int64_t b = a.blk_base + gb;
+    int64_t r = wg_rec[blockIdx.x];
+    while (a.blk_start[r + 1] <= b) ++r;                           // ends inside the pass: blk_start[r1] > b
+    const int64_t w0 = (b - a.blk_start[r]) * OCC_FANIN;
+    const int nw = (int)min((int64_t)OCC_FANIN, a.rec_len[r] - a.m + 1 - w0);   // >= 1: the block exists
+    return ExpBlock{r, a.rec_off[r] + w0, nw, nw + a.m - 1};
+}
+
+// the strip's byte for code i of the block: codes >= nl and what lies beyond the block as EXP_FOREIGN
+__device__ __forceinline__ uint8_t exp_code(const uint8_t *codes, const ExpBlock &blk, int i, int nl)
+{
+    if (i >= blk.need) return EXP_FOREIGN;
+    const uint8_t x = codes[blk.s0 + i] & 7u;
+    return (int)x < nl ? x : EXP_FOREIGN;
+}
+
 // a.q_first / a.n_q: the columns of the pass, column = (motif * m + k) * n_letters + c; inv [n_rec][n_motifs] or null (ratio mode)
 __global__ __launch_bounds__(BLOCK) void k_exp_blocks(const OccArgs a, const double *__restrict__ inv, const int64_t *__restrict__ wg_rec)
 {
@@ -76,29 +105,16 @@ __global__ __launch_bounds__(BLOCK) void k_exp_blocks(const OccArgs a, const dou
     const int t = threadIdx.x, j = t >> 5, w = t & 31, m = a.m, nl = a.n_letters;
     const int64_t gb = (int64_t)blockIdx.x * EXP_WB + j;           // this lane's block, within the pass
     const bool live = gb < a.n_blk;
-    int64_t r = 0;
-    int nw = 0;
+    ExpBlock blk{};
     if (live) {
-        const int64_t b = a.blk_base + gb;
-        r = wg_rec[blockIdx.x];                                    // the record of the workgroup's first block
-        while (a.blk_start[r + 1] <= b) ++r;                       // ends inside the pass: blk_start[r1] > b
-        const int64_t w0 = (b - a.blk_start[r]) * OCC_FANIN;
-        nw = (int)min((int64_t)OCC_FANIN, a.rec_len[r] - m + 1 - w0);   // >= 1: the block exists
-        const int need = nw + m - 1;                               // codes of the block, all inside the record
-        const int64_t s0 = a.rec_off[r] + w0;
-        for (int i = w; i < EXP_CS; i += OCC_FANIN) {
-            uint8_t c = EXP_FOREIGN;
-            if (i < need) {
-                const uint8_t x = a.codes[s0 + i] & 7u;
-                if ((int)x < nl) c = x;
-            }
-            cl[j][i] = c;
-        }
+        blk = exp_block(a, wg_rec, gb);
+        for (int i = w; i < EXP_CS; i += OCC_FANIN) cl[j][i] = exp_code(a.codes, blk, i, nl);
     }
     __syncthreads();
-    bool has = live && w < nw;                                     // this lane's window has a term
+    bool has = live && w < blk.nw;                                 // this lane's window has a term
     if (has)
         for (int k = 0; k < m; ++k) has = has && cl[j][w + k] != EXP_FOREIGN;
+    const int64_t r = blk.r;
     const int mc = m * nl;                                         // cells of a motif
     const int c_lo = a.q_first, c_hi = a.q_first + a.n_q;
     const int q_lo = c_lo / mc;
@@ -157,31 +173,19 @@ __global__ __launch_bounds__(BLOCK) void k_exp_pair_blocks(const OccArgs a, cons
     const int t = threadIdx.x, j = t >> 5, w = t & 31, m = a.m;
     const int64_t gb = (int64_t)blockIdx.x * EXP_WB + j;           // this lane's block, within the pass
     const bool live = gb < a.n_blk;
-    int64_t r = 0;
-    int nw = 0;
+    ExpBlock blk{};
     if (live) {
-        const int64_t b = a.blk_base + gb;
-        r = wg_rec[blockIdx.x];                                    // the record of the workgroup's first block
-        while (a.blk_start[r + 1] <= b) ++r;                       // ends inside the pass: blk_start[r1] > b
-        const int64_t w0 = (b - a.blk_start[r]) * OCC_FANIN;
-        nw = (int)min((int64_t)OCC_FANIN, a.rec_len[r] - m + 1 - w0);   // >= 1: the block exists
-        const int need = nw + m - 1;                               // positions of the block, all inside the record
-        const int64_t s0 = a.rec_off[r] + w0;
-        for (int i = w; i < EXP_CS; i += OCC_FANIN) {
-            uint8_t c1 = EXP_FOREIGN, c2 = EXP_FOREIGN;
-            if (i < need) {
-                const uint8_t x1 = a.codes[s0 + i] & 7u, x2 = a.codes2[s0 + i] & 7u;
-                if (x1 < 4u) c1 = x1;
-                if ((int)x2 < NS) c2 = x2;
-            }
-            cl[0][j][i] = c1;
-            cl[1][j][i] = c2;
+        blk = exp_block(a, wg_rec, gb);
+        for (int i = w; i < EXP_CS; i += OCC_FANIN) {              // both strips in one walk (a walk per strip measured 3 % slower)
+            cl[0][j][i] = exp_code(a.codes, blk, i, 4);
+            cl[1][j][i] = exp_code(a.codes2, blk, i, NS);
         }
     }
     __syncthreads();
-    bool has = live && w < nw;                                     // this lane's window has a term
+    bool has = live && w < blk.nw;                                 // this lane's window has a term
     if (has)
         for (int k = 0; k < m; ++k) has = has && cl[0][j][w + k] != EXP_FOREIGN && cl[1][j][w + k] != EXP_FOREIGN;
+    const int64_t r = blk.r;
     const int u_lo = e.u_first, u_hi = e.u_first + e.n_u;
     const int q_lo = u_lo / m;
     const int64_t sq = (int64_t)e.n_u * 4, ss = (int64_t)e.n_u * NS;   // doubles per block of the two scratch regions
@@ -228,16 +232,22 @@ __global__ __launch_bounds__(BLOCK) void k_exp_pair_blocks(const OccArgs a, cons
     }
 }
 
-// rec_off / rec_len: HOST copies, already checked; d_rec_off / d_rec_len: the same on the device.  Launches on st, does not wait.
-// d_exp_seq / d_exp_struct: one of them may be null.
+// room for a pass's workgroup -> record table, in ctx->occ_cnt
+static int exp_wg_rec(pfmscan_ctx *ctx, const OccPlan &p, int64_t *&wg_rec)
+{
+    const int rc = ensure(ctx, ctx->occ_cnt, std::max<size_t>((size_t)((p.need_blk + EXP_WB - 1) / EXP_WB) * 8, 16));
+    wg_rec = (int64_t *)ctx->occ_cnt.p;
+    return rc;
+}
+
+// Launches on st, does not wait.  d_exp_seq / d_exp_struct: one of them may be null.
 static int exp_pair_run(pfmscan_ctx *ctx, const char *who, const double *seq_tables, const double *struct_tables, int n_motifs, int m, int mode,
-                        const uint8_t *d_codes, const uint8_t *d_codes2, int64_t n_pos, const int64_t *rec_off, const int64_t *rec_len,
-                        const int64_t *d_rec_off, const int64_t *d_rec_len, int64_t n_rec, double *d_exp_seq, double *d_exp_struct, double *d_occ,
+                        const uint8_t *d_codes, const uint8_t *d_codes2, const OccRecords &rec, double *d_exp_seq, double *d_exp_struct, double *d_occ,
                         int64_t *d_windows, hipStream_t st)
 {
     int rc;
     const bool posterior = mode == PFMSCAN_EXPECT_POSTERIOR;
-    const int64_t pairs = n_rec * n_motifs;
+    const int64_t pairs = rec.n_rec * n_motifs;
     const int64_t n_unit = (int64_t)n_motifs * m;                  // matrix rows (pair, k)
     if (n_unit * PFMSCAN_NSTRUCT > (int64_t(1) << 30)) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": too many motifs for one call");
     // the occupancy of the same records first: v of posterior mode, and what the caller asked for
@@ -246,9 +256,8 @@ static int exp_pair_run(pfmscan_ctx *ctx, const char *who, const double *seq_tab
             if ((rc = ensure(ctx, ctx->exp_occ, (size_t)pairs * 8))) return rc;
             d_occ = (double *)ctx->exp_occ.p;
         }
-        if ((rc = occ_run_pair(ctx, who, seq_tables, struct_tables, n_motifs, m, d_codes, d_codes2, n_pos, rec_off, rec_len, d_rec_off, d_rec_len, n_rec,
-                               d_occ, d_windows, st)))
-            return rc;
+        const OccPair pr{struct_tables, d_codes2};
+        if ((rc = occ_run(ctx, who, seq_tables, n_motifs, m, 4, d_codes, rec, d_occ, d_windows, st, nullptr, &pr))) return rc;
     }
     ExpPairArgs e{};
     if (posterior) {
@@ -259,112 +268,60 @@ static int exp_pair_run(pfmscan_ctx *ctx, const char *who, const double *seq_tab
     // the columns past the letters of every matrix row are +0.0; every other cell is written by k_occ_finish
     if (d_exp_seq) HIP_TRY(ctx, hipMemsetAsync(d_exp_seq, 0, (size_t)pairs * m * 8 * sizeof(double), st));
     if (d_exp_struct) HIP_TRY(ctx, hipMemsetAsync(d_exp_struct, 0, (size_t)pairs * m * 8 * sizeof(double), st));
-    std::vector<int64_t> start(2 * (size_t)(n_rec + 1));
-    int64_t *blk = start.data(), *grp = blk + n_rec + 1;
-    int64_t max_blk = 0;
-    blk[0] = grp[0] = 0;
-    for (int64_t r = 0; r < n_rec; ++r) {
-        const int64_t nw = std::max<int64_t>(rec_len[r] - m + 1, 0), nb = (nw + OCC_FANIN - 1) / OCC_FANIN;
-        blk[r + 1] = blk[r] + nb;
-        grp[r + 1] = grp[r] + (nb + OCC_FANIN - 1) / OCC_FANIN;
-        max_blk = std::max(max_blk, nb);
-    }
-    const int cells = (d_exp_seq ? 4 : 0) + (d_exp_struct ? PFMSCAN_NSTRUCT : 0);   // scratch doubles of a matrix row, both regions
-    const int64_t cap = occ_scratch_cap();
     // matrix rows per pass: all of them unless the longest record's block sums alone pass the cap; then records per pass
-    const int n_u_max = (int)std::min<int64_t>(n_unit, std::max<int64_t>(1, cap / (std::max<int64_t>(max_blk, 1) * cells)));
-    const int64_t blk_cap = std::max<int64_t>(cap / ((int64_t)n_u_max * cells), 1);
-    const int64_t rec_cap = std::max<int64_t>((int64_t(1) << 30) / ((int64_t)n_u_max * PFMSCAN_NSTRUCT), 1);
-    std::vector<int64_t> cuts(1, 0);
-    int64_t need_blk = 0, need_grp = 0;
-    for (int64_t r0 = 0; r0 < n_rec;) {
-        int64_t r1 = r0 + 1;
-        while (r1 < n_rec && r1 - r0 < rec_cap && blk[r1 + 1] - blk[r0] <= blk_cap) ++r1;
-        cuts.push_back(r1);
-        need_blk = std::max(need_blk, blk[r1] - blk[r0]);
-        need_grp = std::max(need_grp, grp[r1] - grp[r0]);
-        r0 = r1;
-    }
-    if ((need_blk + EXP_WB - 1) / EXP_WB > 0x7FFFFFFF) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": a record is too long for one call");
-    const size_t tab_bytes = (size_t)n_motifs * m * 8 * sizeof(double);   // the sequence tables, the structure tables behind them
-    if ((rc = ensure(ctx, ctx->occ_tab, 2 * tab_bytes))) return rc;
-    if ((rc = ensure(ctx, ctx->occ_idx, start.size() * 8))) return rc;
-    if ((rc = ensure(ctx, ctx->occ_bs, std::max<size_t>((size_t)need_blk * n_u_max * cells * 8, 16)))) return rc;
-    if ((rc = ensure(ctx, ctx->occ_gs, std::max<size_t>((size_t)need_grp * n_u_max * cells * 8, 16)))) return rc;
-    if ((rc = ensure(ctx, ctx->occ_cnt, std::max<size_t>((size_t)((need_blk + EXP_WB - 1) / EXP_WB) * 8, 16)))) return rc;   // a pass's workgroup -> record
-    int64_t *wg_rec = (int64_t *)ctx->occ_cnt.p;
-    double *d_stab = (double *)((unsigned char *)ctx->occ_tab.p + tab_bytes);
-    if ((rc = upload(ctx, ctx->occ_tab.p, seq_tables, tab_bytes, st))) return rc;
-    if ((rc = upload(ctx, d_stab, struct_tables, tab_bytes, st))) return rc;
-    if ((rc = upload(ctx, ctx->occ_idx.p, start.data(), start.size() * 8, st))) return rc;
+    const int nsq = d_exp_seq ? 4 : 0, cells = nsq + (d_exp_struct ? PFMSCAN_NSTRUCT : 0);   // scratch doubles of a matrix row, both regions
+    const OccPlan p = occ_plan(rec.len, rec.n_rec, m, n_unit, cells, PFMSCAN_NSTRUCT, occ_scratch_cap(), false);
+    if ((p.need_blk + EXP_WB - 1) / EXP_WB > 0x7FFFFFFF) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": a record is too long for one call");
     OccArgs a{};
+    if ((rc = occ_upload_tables(ctx, seq_tables, struct_tables, (size_t)n_motifs * m * 8 * sizeof(double), n_motifs, m, st, a.tables, a.tables2))) return rc;
+    if ((rc = occ_frame(ctx, p, cells, rec, n_motifs, m, 4, st, a))) return rc;
+    int64_t *wg_rec;
+    if ((rc = exp_wg_rec(ctx, p, wg_rec))) return rc;
     a.codes = d_codes;
     a.codes2 = d_codes2;
-    a.n_pos = n_pos;
-    a.rec_off = d_rec_off;
-    a.rec_len = d_rec_len;
-    a.blk_start = (const int64_t *)ctx->occ_idx.p;
-    a.grp_start = a.blk_start + n_rec + 1;
-    a.tables = (const double *)ctx->occ_tab.p;
-    a.tables2 = d_stab;
-    a.m = m;
-    a.n_letters = 4;
-    a.n_motifs = n_motifs;
     a.out_stride = (int64_t)n_motifs * m * 8;
     // the two scratch regions of a pass: the sequence matrix's block and level-1 sums, then the structure matrix's
-    const int nsq = d_exp_seq ? 4 : 0;
-    double *bs_seq = (double *)ctx->occ_bs.p, *bs_struct = bs_seq + need_blk * n_u_max * nsq;
-    double *gs_seq = (double *)ctx->occ_gs.p, *gs_struct = gs_seq + need_grp * n_u_max * nsq;
-    e.bs_seq = d_exp_seq ? bs_seq : nullptr;
+    double *bs_struct = a.bs + p.need_blk * p.n_u_max * nsq, *gs_struct = a.gs + p.need_grp * p.n_u_max * nsq;
+    e.bs_seq = d_exp_seq ? a.bs : nullptr;
     e.bs_struct = d_exp_struct ? bs_struct : nullptr;
-    for (int64_t u0 = 0; u0 < n_unit; u0 += n_u_max) {
+    OccArgs as = a;                                                // levels 1 and up of the structure matrix
+    a.occ = d_exp_seq;
+    a.cell_nl = 4;
+    as.bs = bs_struct;
+    as.gs = gs_struct;
+    as.occ = d_exp_struct;
+    as.cell_nl = PFMSCAN_NSTRUCT;
+    for (int64_t u0 = 0; u0 < n_unit; u0 += p.n_u_max) {
         e.u_first = (int)u0;
-        e.n_u = (int)std::min<int64_t>(n_u_max, n_unit - u0);
-        for (size_t i = 0; i + 1 < cuts.size(); ++i) {
-            const bool make_table = cuts.size() > 2 || u0 == 0;    // one range of records: its table is made once, for all passes over the rows
-            a.r0 = cuts[i];
-            a.r1 = cuts[i + 1];
-            a.blk_base = blk[a.r0];
-            a.n_blk = blk[a.r1] - a.blk_base;
-            a.grp_base = grp[a.r0];
-            a.n_grp = grp[a.r1] - a.grp_base;
+        e.n_u = (int)std::min<int64_t>(p.n_u_max, n_unit - u0);
+        a.q_first = e.u_first * 4;
+        a.n_q = e.n_u * 4;
+        as.q_first = e.u_first * PFMSCAN_NSTRUCT;
+        as.n_q = e.n_u * PFMSCAN_NSTRUCT;
+        for (size_t i = 0; i < p.n_pass(); ++i) {
+            const bool make_table = p.n_pass() > 1 || u0 == 0;     // one range of records: its table is made once, for all passes over the rows
+            occ_set_pass(a, p, i);
+            occ_set_pass(as, p, i);
             if (a.n_blk > 0) {
                 if (make_table) hipLaunchKernelGGL(k_exp_group_records, dim3((unsigned)((a.r1 - a.r0 + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, a, wg_rec);
                 hipLaunchKernelGGL(k_exp_pair_blocks, dim3((unsigned)((a.n_blk + EXP_WB - 1) / EXP_WB)), dim3(BLOCK), 0, st, a, e, wg_rec);
                 hipError_t err = hipGetLastError();
                 if (err != hipSuccess) return fail_hip(ctx, err, "k_exp_pair_blocks");
             }
-            if (d_exp_seq) {
-                a.bs = bs_seq;
-                a.gs = gs_seq;
-                a.occ = d_exp_seq;
-                a.q_first = e.u_first * 4;
-                a.n_q = e.n_u * 4;
-                a.cell_nl = 4;
-                if ((rc = occ_launch_upper(ctx, a, st))) return rc;
-            }
-            if (d_exp_struct) {
-                a.bs = bs_struct;
-                a.gs = gs_struct;
-                a.occ = d_exp_struct;
-                a.q_first = e.u_first * PFMSCAN_NSTRUCT;
-                a.n_q = e.n_u * PFMSCAN_NSTRUCT;
-                a.cell_nl = PFMSCAN_NSTRUCT;
-                if ((rc = occ_launch_upper(ctx, a, st))) return rc;
-            }
+            if (d_exp_seq && (rc = occ_launch_upper(ctx, a, st))) return rc;
+            if (d_exp_struct && (rc = occ_launch_upper(ctx, as, st))) return rc;
         }
     }
     return PFMSCAN_OK;
 }
 
-// rec_off / rec_len: HOST copies, already checked; d_rec_off / d_rec_len: the same on the device.  Launches on st, does not wait.
+// Launches on st, does not wait.
 static int exp_run(pfmscan_ctx *ctx, const char *who, const double *ratio_tables, int n_motifs, int m, int n_letters, int mode,
-                   const uint8_t *d_codes, int64_t n_pos, const int64_t *rec_off, const int64_t *rec_len, const int64_t *d_rec_off,
-                   const int64_t *d_rec_len, int64_t n_rec, double *d_exp, double *d_occ, int64_t *d_windows, hipStream_t st)
+                   const uint8_t *d_codes, const OccRecords &rec, double *d_exp, double *d_occ, int64_t *d_windows, hipStream_t st)
 {
     int rc;
     const bool posterior = mode == PFMSCAN_EXPECT_POSTERIOR;
-    const int64_t pairs = n_rec * n_motifs;
+    const int64_t pairs = rec.n_rec * n_motifs;
     const int64_t n_col = (int64_t)n_motifs * m * n_letters;
     if (n_col > (int64_t(1) << 30)) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": too many motifs for one call");
     // the occupancy of the same records first: v of posterior mode, and what the caller asked for
@@ -373,9 +330,7 @@ static int exp_run(pfmscan_ctx *ctx, const char *who, const double *ratio_tables
             if ((rc = ensure(ctx, ctx->exp_occ, (size_t)pairs * 8))) return rc;
             d_occ = (double *)ctx->exp_occ.p;
         }
-        if ((rc = occ_run_letters(ctx, who, ratio_tables, n_motifs, m, n_letters, d_codes, n_pos, rec_off, rec_len, d_rec_off, d_rec_len, n_rec,
-                                  d_occ, d_windows, st)))
-            return rc;
+        if ((rc = occ_run(ctx, who, ratio_tables, n_motifs, m, n_letters, d_codes, rec, d_occ, d_windows, st))) return rc;
     }
     const double *d_inv = nullptr;
     if (posterior) {
@@ -385,67 +340,25 @@ static int exp_run(pfmscan_ctx *ctx, const char *who, const double *ratio_tables
     }
     // the columns >= n_letters of every matrix row are +0.0; every other cell is written by k_occ_finish
     HIP_TRY(ctx, hipMemsetAsync(d_exp, 0, (size_t)pairs * m * 8 * sizeof(double), st));
-    std::vector<int64_t> start(2 * (size_t)(n_rec + 1));
-    int64_t *blk = start.data(), *grp = blk + n_rec + 1;
-    int64_t max_blk = 0;
-    blk[0] = grp[0] = 0;
-    for (int64_t r = 0; r < n_rec; ++r) {
-        const int64_t nw = std::max<int64_t>(rec_len[r] - m + 1, 0), nb = (nw + OCC_FANIN - 1) / OCC_FANIN;
-        blk[r + 1] = blk[r] + nb;
-        grp[r + 1] = grp[r] + (nb + OCC_FANIN - 1) / OCC_FANIN;
-        max_blk = std::max(max_blk, nb);
-    }
-    const int64_t cap = occ_scratch_cap();
     // columns per pass: all of them unless the longest record's block sums alone pass the cap; then records per pass
-    const int n_c_max = (int)std::min<int64_t>(n_col, std::max<int64_t>(1, cap / std::max<int64_t>(max_blk, 1)));
-    const int64_t blk_cap = std::max<int64_t>(cap / n_c_max, 1), rec_cap = std::max<int64_t>((int64_t(1) << 30) / n_c_max, 1);
-    std::vector<int64_t> cuts(1, 0);
-    int64_t need_blk = 0, need_grp = 0;
-    for (int64_t r0 = 0; r0 < n_rec;) {
-        int64_t r1 = r0 + 1;
-        while (r1 < n_rec && r1 - r0 < rec_cap && blk[r1 + 1] - blk[r0] <= blk_cap) ++r1;
-        cuts.push_back(r1);
-        need_blk = std::max(need_blk, blk[r1] - blk[r0]);
-        need_grp = std::max(need_grp, grp[r1] - grp[r0]);
-        r0 = r1;
-    }
-    if ((need_blk + EXP_WB - 1) / EXP_WB > 0x7FFFFFFF) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": a record is too long for one call");
-    const size_t tab_bytes = (size_t)n_motifs * m * 8 * sizeof(double);
-    if ((rc = ensure(ctx, ctx->occ_tab, tab_bytes))) return rc;
-    if ((rc = ensure(ctx, ctx->occ_idx, start.size() * 8))) return rc;
-    if ((rc = ensure(ctx, ctx->occ_bs, std::max<size_t>((size_t)need_blk * n_c_max * 8, 16)))) return rc;
-    if ((rc = ensure(ctx, ctx->occ_gs, std::max<size_t>((size_t)need_grp * n_c_max * 8, 16)))) return rc;
-    if ((rc = ensure(ctx, ctx->occ_cnt, std::max<size_t>((size_t)((need_blk + EXP_WB - 1) / EXP_WB) * 8, 16)))) return rc;   // a pass's workgroup -> record
-    int64_t *wg_rec = (int64_t *)ctx->occ_cnt.p;
-    if ((rc = upload(ctx, ctx->occ_tab.p, ratio_tables, tab_bytes, st))) return rc;
-    if ((rc = upload(ctx, ctx->occ_idx.p, start.data(), start.size() * 8, st))) return rc;
+    const OccPlan p = occ_plan(rec.len, rec.n_rec, m, n_col, 1, 1, occ_scratch_cap(), false);
+    if ((p.need_blk + EXP_WB - 1) / EXP_WB > 0x7FFFFFFF) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": a record is too long for one call");
     OccArgs a{};
+    const double *none;
+    if ((rc = occ_upload_tables(ctx, ratio_tables, nullptr, 0, n_motifs, m, st, a.tables, none))) return rc;
+    if ((rc = occ_frame(ctx, p, 1, rec, n_motifs, m, n_letters, st, a))) return rc;
+    int64_t *wg_rec;
+    if ((rc = exp_wg_rec(ctx, p, wg_rec))) return rc;
     a.codes = d_codes;
-    a.n_pos = n_pos;
-    a.rec_off = d_rec_off;
-    a.rec_len = d_rec_len;
-    a.blk_start = (const int64_t *)ctx->occ_idx.p;
-    a.grp_start = a.blk_start + n_rec + 1;
-    a.tables = (const double *)ctx->occ_tab.p;
-    a.m = m;
-    a.n_letters = n_letters;
-    a.n_motifs = n_motifs;
-    a.bs = (double *)ctx->occ_bs.p;
-    a.gs = (double *)ctx->occ_gs.p;
     a.occ = d_exp;
     a.out_stride = (int64_t)n_motifs * m * 8;
     a.cell_nl = n_letters;
-    for (int64_t c0 = 0; c0 < n_col; c0 += n_c_max) {
+    for (int64_t c0 = 0; c0 < n_col; c0 += p.n_u_max) {
         a.q_first = (int)c0;
-        a.n_q = (int)std::min<int64_t>(n_c_max, n_col - c0);
-        for (size_t i = 0; i + 1 < cuts.size(); ++i) {
-            const bool make_table = cuts.size() > 2 || c0 == 0;    // one range of records: its table is made once, for all passes over the columns
-            a.r0 = cuts[i];
-            a.r1 = cuts[i + 1];
-            a.blk_base = blk[a.r0];
-            a.n_blk = blk[a.r1] - a.blk_base;
-            a.grp_base = grp[a.r0];
-            a.n_grp = grp[a.r1] - a.grp_base;
+        a.n_q = (int)std::min<int64_t>(p.n_u_max, n_col - c0);
+        for (size_t i = 0; i < p.n_pass(); ++i) {
+            const bool make_table = p.n_pass() > 1 || c0 == 0;     // one range of records: its table is made once, for all passes over the columns
+            occ_set_pass(a, p, i);
             if (a.n_blk > 0) {
                 if (make_table) hipLaunchKernelGGL(k_exp_group_records, dim3((unsigned)((a.r1 - a.r0 + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, a, wg_rec);
                 hipLaunchKernelGGL(k_exp_blocks, dim3((unsigned)((a.n_blk + EXP_WB - 1) / EXP_WB)), dim3(BLOCK), 0, st, a, d_inv, wg_rec);
@@ -481,15 +394,10 @@ int pfmscan_expect_dev(pfmscan_ctx *ctx, const double *ratio_tables, int n_motif
     if (n_rec == 0 || n_motifs == 0) return PFMSCAN_OK;
     if (!d_rec_off || !d_rec_len || !d_exp || (n_pos > 0 && !d_codes)) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": NULL record table, codes or output");
     if (misaligned(d_codes)) return fail(ctx, PFMSCAN_E_BADSHAPE, std::string(who) + ": stream base pointers must be 16-byte aligned");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    // the record table decides every address the kernels form: it is read back and checked before anything is launched
-    std::vector<int64_t> rec(2 * (size_t)n_rec);
-    HIP_TRY(ctx, hipMemcpyAsync(rec.data(), d_rec_off, (size_t)n_rec * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(rec.data() + n_rec, d_rec_len, (size_t)n_rec * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (int rc = occ_check_records(ctx, who, rec.data(), rec.data() + n_rec, n_rec, n_pos)) return rc;
-    return exp_run(ctx, who, ratio_tables, n_motifs, m, n_letters, mode, d_codes, n_pos, rec.data(), rec.data() + n_rec, d_rec_off, d_rec_len,
-                   n_rec, d_exp, d_occ, d_windows, ctx->stream);
+    std::vector<int64_t> host;
+    OccRecords rec;
+    if (int rc = occ_records_home(ctx, who, d_rec_off, d_rec_len, n_rec, n_pos, host, rec)) return rc;
+    return exp_run(ctx, who, ratio_tables, n_motifs, m, n_letters, mode, d_codes, rec, d_exp, d_occ, d_windows, ctx->stream);
 }
 
 // both _staged forms: the matrices come home (exp), or their exact sums over the records do (acc, bad: the merged form)
@@ -502,36 +410,25 @@ static int expect_staged_any(pfmscan_ctx *ctx, const char *who, int which, const
     if (ctx->staged_n < 0) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": no stream staged (call pfmscan_stage first)");
     if (ctx->staged_n > 0 && !(which ? ctx->staged_codes2 : ctx->staged_codes))
         return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + (which ? ": no codes2 are staged (pfmscan_stage_codes2)" : ": no codes are staged"));
-    const int64_t n_pos = ctx->staged_n;
-    if (int rc = occ_check(ctx, who, ratio_tables, n_motifs, m, n_letters, n_pos, n_rec)) return rc;
+    if (int rc = occ_check(ctx, who, ratio_tables, n_motifs, m, n_letters, ctx->staged_n, n_rec)) return rc;
     if (int rc = exp_check_mode(ctx, who, mode)) return rc;
     if (n_rec == 0 || n_motifs == 0) return PFMSCAN_OK;
     if (!rec_off || !rec_len || (merged ? !acc || !bad : !exp)) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": NULL record table or output");
-    if (int rc = occ_check_records(ctx, who, rec_off, rec_len, n_rec, n_pos)) return rc;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
     int rc;
+    OccRecords rec;
+    if ((rc = occ_records_up(ctx, who, rec_off, rec_len, n_rec, rec))) return rc;
     const size_t pairs = (size_t)n_rec * n_motifs, cells = pairs * m * 8;
-    if ((rc = ensure(ctx, ctx->occ_rec, (size_t)n_rec * 16))) return rc;
     if ((rc = ensure(ctx, ctx->exp_out, (cells + pairs + (size_t)n_rec) * 8))) return rc;
-    int64_t *d_off = (int64_t *)ctx->occ_rec.p, *d_len = d_off + n_rec;
-    if ((rc = upload(ctx, d_off, rec_off, (size_t)n_rec * 8, ctx->stream))) return rc;
-    if ((rc = upload(ctx, d_len, rec_len, (size_t)n_rec * 8, ctx->stream))) return rc;
     double *d_exp = (double *)ctx->exp_out.p;
     double *d_occ = occ ? d_exp + cells : nullptr;
     int64_t *d_win = windows ? (int64_t *)(d_exp + cells + pairs) : nullptr;
     const uint8_t *d_codes = (const uint8_t *)(which ? ctx->codes2.p : ctx->codes.p);
-    if ((rc = exp_run(ctx, who, ratio_tables, n_motifs, m, n_letters, mode, d_codes, n_pos, rec_off, rec_len, d_off, d_len, n_rec, d_exp, d_occ,
-                      d_win, ctx->stream)))
-        return rc;
+    if ((rc = exp_run(ctx, who, ratio_tables, n_motifs, m, n_letters, mode, d_codes, rec, d_exp, d_occ, d_win, ctx->stream))) return rc;
     if (merged) {
         const ExpMergeOut out{d_exp, acc, bad};
         return exp_merge_home(ctx, who, &out, 1, n_rec, n_motifs, m, d_occ, occ, d_win, windows);
     }
-    HIP_TRY(ctx, hipMemcpyAsync(exp, d_exp, cells * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (occ) HIP_TRY(ctx, hipMemcpyAsync(occ, d_occ, pairs * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (windows) HIP_TRY(ctx, hipMemcpyAsync(windows, d_win, (size_t)n_rec * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return PFMSCAN_OK;
+    return occ_copy_home(ctx, {{exp, d_exp, cells * 8}, {occ, d_occ, pairs * 8}, {windows, d_win, (size_t)n_rec * 8}});
 }
 
 int pfmscan_expect_staged(pfmscan_ctx *ctx, int which, const double *ratio_tables, int n_motifs, int m, int n_letters, int mode,
@@ -562,15 +459,11 @@ int pfmscan_expect_pair_dev(pfmscan_ctx *ctx, const double *seq_tables, const do
     if (n_rec == 0 || n_motifs == 0) return PFMSCAN_OK;
     if (!d_rec_off || !d_rec_len || (n_pos > 0 && (!d_codes || !d_codes2))) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": NULL record table or codes");
     if (misaligned(d_codes) || misaligned(d_codes2)) return fail(ctx, PFMSCAN_E_BADSHAPE, std::string(who) + ": stream base pointers must be 16-byte aligned");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    // the record table decides every address the kernels form: it is read back and checked before anything is launched
-    std::vector<int64_t> rec(2 * (size_t)n_rec);
-    HIP_TRY(ctx, hipMemcpyAsync(rec.data(), d_rec_off, (size_t)n_rec * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(rec.data() + n_rec, d_rec_len, (size_t)n_rec * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (int rc = occ_check_records(ctx, who, rec.data(), rec.data() + n_rec, n_rec, n_pos)) return rc;
-    return exp_pair_run(ctx, who, seq_tables, struct_tables, n_motifs, m, mode, d_codes, d_codes2, n_pos, rec.data(), rec.data() + n_rec, d_rec_off,
-                        d_rec_len, n_rec, d_exp_seq, d_exp_struct, d_occ, d_windows, ctx->stream);
+    std::vector<int64_t> host;
+    OccRecords rec;
+    if (int rc = occ_records_home(ctx, who, d_rec_off, d_rec_len, n_rec, n_pos, host, rec)) return rc;
+    return exp_pair_run(ctx, who, seq_tables, struct_tables, n_motifs, m, mode, d_codes, d_codes2, rec, d_exp_seq, d_exp_struct, d_occ, d_windows,
+                        ctx->stream);
 }
 
 // both _staged forms of two code streams.  merged: exp_seq / exp_struct only say which matrices are asked for (acc_seq / acc_struct)
@@ -583,8 +476,7 @@ static int expect_pair_staged_any(pfmscan_ctx *ctx, const char *who, const doubl
     if (ctx->staged_n < 0) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": no stream staged (call pfmscan_stage first)");
     if (ctx->staged_n > 0 && !ctx->staged_codes) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": no codes are staged");
     if (ctx->staged_n > 0 && !ctx->staged_codes2) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": no codes2 are staged (pfmscan_stage_codes2)");
-    const int64_t n_pos = ctx->staged_n;
-    if (int rc = occ_pair_check(ctx, who, seq_tables, struct_tables, n_motifs, m, n_pos, n_rec)) return rc;
+    if (int rc = occ_pair_check(ctx, who, seq_tables, struct_tables, n_motifs, m, ctx->staged_n, n_rec)) return rc;
     if (int rc = exp_check_mode(ctx, who, mode)) return rc;
     const bool want_seq = merged ? acc_seq != nullptr : exp_seq != nullptr, want_struct = merged ? acc_struct != nullptr : exp_struct != nullptr;
     if (!want_seq && !want_struct)
@@ -592,33 +484,24 @@ static int expect_pair_staged_any(pfmscan_ctx *ctx, const char *who, const doubl
     if (merged && ((want_seq && !bad_seq) || (want_struct && !bad_struct))) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": an accumulator without its bad");
     if (n_rec == 0 || n_motifs == 0) return PFMSCAN_OK;
     if (!rec_off || !rec_len) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": NULL record table");
-    if (int rc = occ_check_records(ctx, who, rec_off, rec_len, n_rec, n_pos)) return rc;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
     int rc;
+    OccRecords rec;
+    if ((rc = occ_records_up(ctx, who, rec_off, rec_len, n_rec, rec))) return rc;
     const size_t pairs = (size_t)n_rec * n_motifs, cells = pairs * m * 8;
-    if ((rc = ensure(ctx, ctx->occ_rec, (size_t)n_rec * 16))) return rc;
     if ((rc = ensure(ctx, ctx->exp_out, (2 * cells + pairs + (size_t)n_rec) * 8))) return rc;
-    int64_t *d_off = (int64_t *)ctx->occ_rec.p, *d_len = d_off + n_rec;
-    if ((rc = upload(ctx, d_off, rec_off, (size_t)n_rec * 8, ctx->stream))) return rc;
-    if ((rc = upload(ctx, d_len, rec_len, (size_t)n_rec * 8, ctx->stream))) return rc;
     double *d_base = (double *)ctx->exp_out.p;
     double *d_sq = want_seq ? d_base : nullptr;
     double *d_st = want_struct ? d_base + cells : nullptr;
     double *d_occ = occ ? d_base + 2 * cells : nullptr;
     int64_t *d_win = windows ? (int64_t *)(d_base + 2 * cells + pairs) : nullptr;
-    if ((rc = exp_pair_run(ctx, who, seq_tables, struct_tables, n_motifs, m, mode, (const uint8_t *)ctx->codes.p, (const uint8_t *)ctx->codes2.p, n_pos,
-                           rec_off, rec_len, d_off, d_len, n_rec, d_sq, d_st, d_occ, d_win, ctx->stream)))
+    if ((rc = exp_pair_run(ctx, who, seq_tables, struct_tables, n_motifs, m, mode, (const uint8_t *)ctx->codes.p, (const uint8_t *)ctx->codes2.p, rec,
+                           d_sq, d_st, d_occ, d_win, ctx->stream)))
         return rc;
     if (merged) {
         const ExpMergeOut out[2] = {{d_sq, acc_seq, bad_seq}, {d_st, acc_struct, bad_struct}};
         return exp_merge_home(ctx, who, out, 2, n_rec, n_motifs, m, d_occ, occ, d_win, windows);
     }
-    if (exp_seq) HIP_TRY(ctx, hipMemcpyAsync(exp_seq, d_sq, cells * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (exp_struct) HIP_TRY(ctx, hipMemcpyAsync(exp_struct, d_st, cells * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (occ) HIP_TRY(ctx, hipMemcpyAsync(occ, d_occ, pairs * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (windows) HIP_TRY(ctx, hipMemcpyAsync(windows, d_win, (size_t)n_rec * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return PFMSCAN_OK;
+    return occ_copy_home(ctx, {{exp_seq, d_sq, cells * 8}, {exp_struct, d_st, cells * 8}, {occ, d_occ, pairs * 8}, {windows, d_win, (size_t)n_rec * 8}});
 }
 
 int pfmscan_expect_pair_staged(pfmscan_ctx *ctx, const double *seq_tables, const double *struct_tables, int n_motifs, int m, int mode,

@@ -11,7 +11,7 @@
 //   seq_tables only      the letter chain of k_occ_blocks / k_exp_blocks over the 4 RNA letters
 // and the weight is the term (PFMSCAN_EXPECT_RATIO) or t_s * v, v = 1.0 / occ_r (PFMSCAN_EXPECT_POSTERIOR; occ_r == 0.0: every
 // weight +0.0).  occ_r is what pfmscan_occupancy_profile_* / pfmscan_occupancy_* give for the same tables: the call runs that
-// code first (occ_run_profile / occ_run_letters) and k_exp_inverse over its result.  The marginal has one definition
+// code first (occ_run, with the profile or without) and k_exp_inverse over its result.  The marginal has one definition
 // (occp_marginal, pfmscan_occ.hpp).  No transcendental, no atomics, no tolerance: tests/expect_profile_rules.py restates it
 // in numpy and the bits are compared.
 //
@@ -39,7 +39,7 @@
 // Levels 1 and up are occ_launch_upper, once over the structure matrix (cell_nl = 7) and once over the sequence matrix
 // (cell_nl = 4), each with its own scratch region.  Scratch is bounded by occ_scratch_cap(): records run in passes, and when
 // the longest record alone passes the cap, so do the matrix rows (motif, k) -- the 7 + 4 cells of a row stay together -- and
-// with them the motifs.
+// with them the motifs: occ_plan (pfmscan_occ_plan.hpp) over matrix rows, on the frame of pfmscan_occ.hpp.
 #include <algorithm>
 #include <string>
 #include <vector>
@@ -269,15 +269,14 @@ static void expp_launch_t(const OccArgs &a, const ExppArgs &e, bool st_given, bo
     else hipLaunchKernelGGL((k_expp_blocks<T, false, true>), grid, dim3(BLOCK), 0, st, a, e);
 }
 
-// rec_off / rec_len: HOST copies, already checked; d_rec_off / d_rec_len: the same on the device.  Launches on st, does not wait.
+// Launches on st, does not wait.
 static int expp_run(pfmscan_ctx *ctx, const char *who, const double *struct_tables, const double *seq_tables, int n_motifs, int m, int mode,
-                    const uint8_t *d_codes, const void *d_profile, int dtype, int64_t n_pos, const int64_t *rec_off, const int64_t *rec_len,
-                    const int64_t *d_rec_off, const int64_t *d_rec_len, int64_t n_rec, double *d_exp_struct, double *d_exp_seq, double *d_occ,
-                    int64_t *d_windows, hipStream_t st)
+                    const uint8_t *d_codes, const void *d_profile, int dtype, const OccRecords &rec, double *d_exp_struct, double *d_exp_seq,
+                    double *d_occ, int64_t *d_windows, hipStream_t st)
 {
     int rc;
     const bool posterior = mode == PFMSCAN_EXPECT_POSTERIOR;
-    const int64_t pairs = n_rec * n_motifs;
+    const int64_t pairs = rec.n_rec * n_motifs;
     const int64_t n_unit = (int64_t)n_motifs * m;                  // matrix rows (motif, k)
     if (n_unit * 7 > (int64_t(1) << 30)) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": too many motifs for one call");
     // the occupancy of the same records first: v of posterior mode, and what the caller asked for
@@ -286,13 +285,8 @@ static int expp_run(pfmscan_ctx *ctx, const char *who, const double *struct_tabl
             if ((rc = ensure(ctx, ctx->exp_occ, (size_t)pairs * 8))) return rc;
             d_occ = (double *)ctx->exp_occ.p;
         }
-        if (struct_tables) {
-            const OccProfile pf{struct_tables, d_profile, dtype};
-            rc = occ_run_profile(ctx, who, pf, seq_tables, n_motifs, m, d_codes, n_pos, rec_off, rec_len, d_rec_off, d_rec_len, n_rec, d_occ, d_windows, st);
-        } else {
-            rc = occ_run_letters(ctx, who, seq_tables, n_motifs, m, 4, d_codes, n_pos, rec_off, rec_len, d_rec_off, d_rec_len, n_rec, d_occ, d_windows, st);
-        }
-        if (rc) return rc;
+        const OccProfile pf{struct_tables, d_profile, dtype};       // no structure tables: the occupancy of the letter strings
+        if ((rc = occ_run(ctx, who, seq_tables, n_motifs, m, 4, seq_tables ? d_codes : nullptr, rec, d_occ, d_windows, st, struct_tables ? &pf : nullptr))) return rc;
     }
     ExppArgs e{};
     if (posterior) {
@@ -304,101 +298,48 @@ static int expp_run(pfmscan_ctx *ctx, const char *who, const double *struct_tabl
     // column 7 (4 .. 7) of every matrix row is +0.0; every other cell is written by k_occ_finish
     HIP_TRY(ctx, hipMemsetAsync(d_exp_struct, 0, (size_t)pairs * m * 8 * sizeof(double), st));
     if (d_exp_seq) HIP_TRY(ctx, hipMemsetAsync(d_exp_seq, 0, (size_t)pairs * m * 8 * sizeof(double), st));
-    std::vector<int64_t> start(3 * (size_t)(n_rec + 1));
-    int64_t *blk = start.data(), *grp = blk + n_rec + 1, *run = grp + n_rec + 1;
-    int64_t max_blk = 0;
-    blk[0] = grp[0] = run[0] = 0;
-    for (int64_t r = 0; r < n_rec; ++r) {
-        const int64_t nw = std::max<int64_t>(rec_len[r] - m + 1, 0), nb = (nw + OCC_FANIN - 1) / OCC_FANIN;
-        blk[r + 1] = blk[r] + nb;
-        grp[r + 1] = grp[r] + (nb + OCC_FANIN - 1) / OCC_FANIN;
-        run[r + 1] = run[r] + (nb + OCCP_RUN - 1) / OCCP_RUN;
-        max_blk = std::max(max_blk, nb);
-    }
-    const int cells = 7 + (d_exp_seq ? 4 : 0);                     // scratch doubles of a matrix row, both regions
-    const int64_t cap = occ_scratch_cap();
     // matrix rows per pass: all of them unless the longest record's block sums alone pass the cap; then records per pass
-    const int n_u_max = (int)std::min<int64_t>(n_unit, std::max<int64_t>(1, cap / (std::max<int64_t>(max_blk, 1) * cells)));
-    const int64_t blk_cap = std::max<int64_t>(cap / ((int64_t)n_u_max * cells), 1), rec_cap = std::max<int64_t>((int64_t(1) << 30) / ((int64_t)n_u_max * 7), 1);
-    std::vector<int64_t> cuts(1, 0);
-    int64_t need_blk = 0, need_grp = 0, need_run = 0;
-    for (int64_t r0 = 0; r0 < n_rec;) {
-        int64_t r1 = r0 + 1;
-        while (r1 < n_rec && r1 - r0 < rec_cap && blk[r1 + 1] - blk[r0] <= blk_cap) ++r1;
-        cuts.push_back(r1);
-        need_blk = std::max(need_blk, blk[r1] - blk[r0]);
-        need_grp = std::max(need_grp, grp[r1] - grp[r0]);
-        need_run = std::max(need_run, run[r1] - run[r0]);
-        r0 = r1;
-    }
-    if (need_blk > 0x7FFFFFFF) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": a record is too long for one call");   // a workgroup per run, no more runs than blocks
-    const size_t tab_bytes = seq_tables ? (size_t)n_motifs * m * 8 * sizeof(double) : 0;
-    const size_t stab_bytes = struct_tables ? (size_t)n_motifs * m * 7 * sizeof(double) : 0;   // behind the letter tables
-    if ((rc = ensure(ctx, ctx->occ_tab, tab_bytes + stab_bytes))) return rc;
-    if ((rc = ensure(ctx, ctx->occ_idx, (start.size() + (size_t)need_run) * 8))) return rc;   // the prefix tables, then a pass's run -> record
-    if ((rc = ensure(ctx, ctx->occ_bs, std::max<size_t>((size_t)need_blk * n_u_max * cells * 8, 16)))) return rc;
-    if ((rc = ensure(ctx, ctx->occ_gs, std::max<size_t>((size_t)need_grp * n_u_max * cells * 8, 16)))) return rc;
-    if (tab_bytes && (rc = upload(ctx, ctx->occ_tab.p, seq_tables, tab_bytes, st))) return rc;
-    double *d_stab = (double *)((unsigned char *)ctx->occ_tab.p + tab_bytes);
-    if (stab_bytes && (rc = upload(ctx, d_stab, struct_tables, stab_bytes, st))) return rc;
-    if ((rc = upload(ctx, ctx->occ_idx.p, start.data(), start.size() * 8, st))) return rc;
+    const int cells = 7 + (d_exp_seq ? 4 : 0);                     // scratch doubles of a matrix row, both regions
+    const OccPlan p = occ_plan(rec.len, rec.n_rec, m, n_unit, cells, 7, occ_scratch_cap(), true);
+    if (p.need_blk > 0x7FFFFFFF) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": a record is too long for one call");   // a workgroup per run, no more runs than blocks
     OccArgs a{};
+    if ((rc = occ_upload_tables(ctx, seq_tables, struct_tables, (size_t)n_motifs * m * 7 * sizeof(double), n_motifs, m, st, a.tables, e.stab))) return rc;
+    if (!struct_tables) e.stab = nullptr;
+    if ((rc = occ_frame(ctx, p, cells, rec, n_motifs, m, 4, st, a))) return rc;
     a.codes = seq_tables ? d_codes : nullptr;
-    a.n_pos = n_pos;
-    a.rec_off = d_rec_off;
-    a.rec_len = d_rec_len;
-    a.blk_start = (const int64_t *)ctx->occ_idx.p;
-    a.grp_start = a.blk_start + n_rec + 1;
-    a.run_start = a.grp_start + n_rec + 1;
-    a.run_rec = (int64_t *)ctx->occ_idx.p + start.size();
-    a.tables = tab_bytes ? (const double *)ctx->occ_tab.p : nullptr;
     a.profile = (const unsigned char *)d_profile;
-    a.m = m;
-    a.n_letters = 4;
-    a.n_motifs = n_motifs;
     a.out_stride = (int64_t)n_motifs * m * 8;
-    e.stab = stab_bytes ? d_stab : nullptr;
     // the two scratch regions of a pass: the structure matrix's block and level-1 sums, then the sequence matrix's
-    double *bs_struct = (double *)ctx->occ_bs.p, *bs_seq = bs_struct + need_blk * n_u_max * 7;
-    double *gs_struct = (double *)ctx->occ_gs.p, *gs_seq = gs_struct + need_grp * n_u_max * 7;
-    e.bs_struct = bs_struct;
-    e.bs_seq = d_exp_seq ? bs_seq : nullptr;
-    for (int64_t u0 = 0; u0 < n_unit; u0 += n_u_max) {
+    e.bs_struct = a.bs;
+    e.bs_seq = d_exp_seq ? a.bs + p.need_blk * p.n_u_max * 7 : nullptr;
+    OccArgs aq = a;                                                // levels 1 and up of the sequence matrix
+    a.occ = d_exp_struct;
+    a.cell_nl = 7;
+    aq.bs = a.bs + p.need_blk * p.n_u_max * 7;
+    aq.gs = a.gs + p.need_grp * p.n_u_max * 7;
+    aq.occ = d_exp_seq;
+    aq.cell_nl = 4;
+    for (int64_t u0 = 0; u0 < n_unit; u0 += p.n_u_max) {
         e.u_first = (int)u0;
-        e.n_u = (int)std::min<int64_t>(n_u_max, n_unit - u0);
-        for (size_t i = 0; i + 1 < cuts.size(); ++i) {
-            const bool make_table = cuts.size() > 2 || u0 == 0;    // one range of records: its table is made once, for all passes over the rows
-            a.r0 = cuts[i];
-            a.r1 = cuts[i + 1];
-            a.blk_base = blk[a.r0];
-            a.n_blk = blk[a.r1] - a.blk_base;
-            a.grp_base = grp[a.r0];
-            a.n_grp = grp[a.r1] - a.grp_base;
-            a.run_base = run[a.r0];
+        e.n_u = (int)std::min<int64_t>(p.n_u_max, n_unit - u0);
+        a.q_first = e.u_first * 7;
+        a.n_q = e.n_u * 7;
+        aq.q_first = e.u_first * 4;
+        aq.n_q = e.n_u * 4;
+        for (size_t i = 0; i < p.n_pass(); ++i) {
+            const bool make_table = p.n_pass() > 1 || u0 == 0;     // one range of records: its table is made once, for all passes over the rows
+            const int64_t n_run = occ_set_pass(a, p, i);
+            occ_set_pass(aq, p, i);
             if (a.n_blk > 0) {
                 if (make_table) occ_launch_run_records(a, st);
-                const dim3 grid((unsigned)(run[a.r1] - a.run_base));
+                const dim3 grid((unsigned)n_run);
                 if (dtype == PFMSCAN_PROFILE_F64) expp_launch_t<double>(a, e, struct_tables != nullptr, seq_tables != nullptr, grid, st);
                 else expp_launch_t<float>(a, e, struct_tables != nullptr, seq_tables != nullptr, grid, st);
                 hipError_t err = hipGetLastError();
                 if (err != hipSuccess) return fail_hip(ctx, err, "k_expp_blocks");
             }
-            a.bs = bs_struct;
-            a.gs = gs_struct;
-            a.occ = d_exp_struct;
-            a.q_first = e.u_first * 7;
-            a.n_q = e.n_u * 7;
-            a.cell_nl = 7;
             if ((rc = occ_launch_upper(ctx, a, st))) return rc;
-            if (d_exp_seq) {
-                a.bs = bs_seq;
-                a.gs = gs_seq;
-                a.occ = d_exp_seq;
-                a.q_first = e.u_first * 4;
-                a.n_q = e.n_u * 4;
-                a.cell_nl = 4;
-                if ((rc = occ_launch_upper(ctx, a, st))) return rc;
-            }
+            if (d_exp_seq && (rc = occ_launch_upper(ctx, aq, st))) return rc;
         }
     }
     return PFMSCAN_OK;
@@ -408,13 +349,10 @@ static int expp_run(pfmscan_ctx *ctx, const char *who, const double *struct_tabl
 static int expp_check(pfmscan_ctx *ctx, const char *who, const double *struct_tables, const double *seq_tables, int n_motifs, int m, int mode,
                       int profile_dtype, int64_t n_pos, int64_t n_rec, bool with_exp_seq)
 {
-    if (m < 1 || m > PFMSCAN_MAX_M)
-        return fail(ctx, PFMSCAN_E_BADSHAPE, std::string(who) + ": width " + std::to_string(m) + " outside 1 .. PFMSCAN_MAX_M (" + std::to_string(PFMSCAN_MAX_M) + ")");
-    if (profile_dtype != PFMSCAN_PROFILE_F32 && profile_dtype != PFMSCAN_PROFILE_F64)
-        return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": profile_dtype must be PFMSCAN_PROFILE_F32 or F64");
-    if (mode != PFMSCAN_EXPECT_RATIO && mode != PFMSCAN_EXPECT_POSTERIOR)
-        return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": mode must be PFMSCAN_EXPECT_RATIO or PFMSCAN_EXPECT_POSTERIOR");
-    if (n_motifs < 0 || n_rec < 0 || n_pos < 0) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": negative size");
+    const char *own = profile_dtype != PFMSCAN_PROFILE_F32 && profile_dtype != PFMSCAN_PROFILE_F64 ? ": profile_dtype must be PFMSCAN_PROFILE_F32 or F64"
+                      : mode != PFMSCAN_EXPECT_RATIO && mode != PFMSCAN_EXPECT_POSTERIOR       ? ": mode must be PFMSCAN_EXPECT_RATIO or PFMSCAN_EXPECT_POSTERIOR"
+                                                                                               : nullptr;
+    if (int rc = occ_check_base(ctx, who, m, own, n_motifs, n_rec, n_pos, nullptr)) return rc;
     if (!struct_tables && !seq_tables) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": struct_tables and seq_tables are both NULL");
     if (with_exp_seq && !seq_tables) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": exp_seq needs seq_tables");
     return PFMSCAN_OK;
@@ -440,15 +378,11 @@ int pfmscan_expect_profile_dev(pfmscan_ctx *ctx, const double *struct_tables, co
         return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": NULL record table, profile or output");
     if (misaligned(d_profile) || (seq_tables && misaligned(d_codes)))
         return fail(ctx, PFMSCAN_E_BADSHAPE, std::string(who) + ": stream base pointers must be 16-byte aligned");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    // the record table decides every address the kernels form: it is read back and checked before anything is launched
-    std::vector<int64_t> rec(2 * (size_t)n_rec);
-    HIP_TRY(ctx, hipMemcpyAsync(rec.data(), d_rec_off, (size_t)n_rec * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(rec.data() + n_rec, d_rec_len, (size_t)n_rec * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (int rc = occ_check_records(ctx, who, rec.data(), rec.data() + n_rec, n_rec, n_pos)) return rc;
-    return expp_run(ctx, who, struct_tables, seq_tables, n_motifs, m, mode, d_codes, d_profile, profile_dtype, n_pos, rec.data(), rec.data() + n_rec,
-                    d_rec_off, d_rec_len, n_rec, d_exp_struct, d_exp_seq, d_occ, d_windows, ctx->stream);
+    std::vector<int64_t> host;
+    OccRecords rec;
+    if (int rc = occ_records_home(ctx, who, d_rec_off, d_rec_len, n_rec, n_pos, host, rec)) return rc;
+    return expp_run(ctx, who, struct_tables, seq_tables, n_motifs, m, mode, d_codes, d_profile, profile_dtype, rec, d_exp_struct, d_exp_seq, d_occ,
+                    d_windows, ctx->stream);
 }
 
 // both _staged forms.  merged: the sums of the matrices over the records come home (acc_*, bad_*) instead of the matrices
@@ -461,37 +395,27 @@ static int expect_profile_staged_any(pfmscan_ctx *ctx, const char *who, const do
     if (ctx->staged_n < 0) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": no stream staged (call pfmscan_stage first)");
     if (!ctx->staged_profile) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": no profile is staged");
     if (seq_tables && !ctx->staged_codes) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": seq_tables needs staged codes");
-    const int64_t n_pos = ctx->staged_n;
     const bool want_seq = merged ? acc_seq != nullptr : exp_seq != nullptr;
-    if (int rc = expp_check(ctx, who, struct_tables, seq_tables, n_motifs, m, mode, ctx->staged_dtype, n_pos, n_rec, want_seq)) return rc;
+    if (int rc = expp_check(ctx, who, struct_tables, seq_tables, n_motifs, m, mode, ctx->staged_dtype, ctx->staged_n, n_rec, want_seq)) return rc;
     if (n_rec == 0 || n_motifs == 0) return PFMSCAN_OK;
     if (!rec_off || !rec_len || (merged ? !acc_struct || !bad_struct || (want_seq && !bad_seq) : !exp_struct)) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": NULL record table or output");
-    if (int rc = occ_check_records(ctx, who, rec_off, rec_len, n_rec, n_pos)) return rc;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
     int rc;
+    OccRecords rec;
+    if ((rc = occ_records_up(ctx, who, rec_off, rec_len, n_rec, rec))) return rc;
     const size_t pairs = (size_t)n_rec * n_motifs, cells = pairs * m * 8;
-    if ((rc = ensure(ctx, ctx->occ_rec, (size_t)n_rec * 16))) return rc;
     if ((rc = ensure(ctx, ctx->exp_out, (2 * cells + pairs + (size_t)n_rec) * 8))) return rc;
-    int64_t *d_off = (int64_t *)ctx->occ_rec.p, *d_len = d_off + n_rec;
-    if ((rc = upload(ctx, d_off, rec_off, (size_t)n_rec * 8, ctx->stream))) return rc;
-    if ((rc = upload(ctx, d_len, rec_len, (size_t)n_rec * 8, ctx->stream))) return rc;
     double *d_st = (double *)ctx->exp_out.p;
     double *d_sq = want_seq ? d_st + cells : nullptr;
     double *d_occ = occ ? d_st + 2 * cells : nullptr;
     int64_t *d_win = windows ? (int64_t *)(d_st + 2 * cells + pairs) : nullptr;
-    if ((rc = expp_run(ctx, who, struct_tables, seq_tables, n_motifs, m, mode, (const uint8_t *)ctx->codes.p, ctx->profile.p, ctx->staged_dtype, n_pos,
-                       rec_off, rec_len, d_off, d_len, n_rec, d_st, d_sq, d_occ, d_win, ctx->stream)))
+    if ((rc = expp_run(ctx, who, struct_tables, seq_tables, n_motifs, m, mode, (const uint8_t *)ctx->codes.p, ctx->profile.p, ctx->staged_dtype, rec, d_st,
+                       d_sq, d_occ, d_win, ctx->stream)))
         return rc;
     if (merged) {
         const ExpMergeOut out[2] = {{d_st, acc_struct, bad_struct}, {d_sq, acc_seq, bad_seq}};
         return exp_merge_home(ctx, who, out, 2, n_rec, n_motifs, m, d_occ, occ, d_win, windows);
     }
-    HIP_TRY(ctx, hipMemcpyAsync(exp_struct, d_st, cells * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (exp_seq) HIP_TRY(ctx, hipMemcpyAsync(exp_seq, d_sq, cells * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (occ) HIP_TRY(ctx, hipMemcpyAsync(occ, d_occ, pairs * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (windows) HIP_TRY(ctx, hipMemcpyAsync(windows, d_win, (size_t)n_rec * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return PFMSCAN_OK;
+    return occ_copy_home(ctx, {{exp_struct, d_st, cells * 8}, {exp_seq, d_sq, cells * 8}, {occ, d_occ, pairs * 8}, {windows, d_win, (size_t)n_rec * 8}});
 }
 
 int pfmscan_expect_profile_staged(pfmscan_ctx *ctx, const double *struct_tables, const double *seq_tables, int n_motifs, int m, int mode,

@@ -1,17 +1,20 @@
 // pfmscan_occ.hpp -- what the occupancy (pfmscan_occupancy.hip) and the expected counts (pfmscan_expect.hip,
-// pfmscan_expect_profile.hip) share: the arguments of a pass, the bisection of a prefix table, the host side of levels 1 and
-// up of the summation tree, and for averaged-structure profiles the geometry of a run, the loads of its rows and the
-// marginal of a row (one definition: k_occ_profile_blocks and k_expp_blocks make the same bits of it).
+// pfmscan_expect_profile.hip) share: the arguments of a pass and the frame every driver builds them with (the pass plan itself
+// is pfmscan_occ_plan.hpp), the bisection of a prefix table, the host side of levels 1 and up of the summation tree, the
+// pieces of the entry points (argument checks, the record table's way down and up, the copies home), and for
+// averaged-structure profiles the geometry of a run, the loads of its rows and the marginal of a row (one definition:
+// k_occ_profile_blocks and k_expp_blocks make the same bits of it).
 #pragma once
 #include <cstdint>
+#include <initializer_list>
 
 #include "pfmscan_ctx.hpp"
+#include "pfmscan_occ_plan.hpp"
 
 namespace pfmscan {
 
-constexpr int OCC_FANIN = PFMSCAN_OCC_FANIN;
 constexpr int64_t OCC_SCRATCH_DOUBLES = int64_t(1) << 25;   // block sums of one pass (256 MB); PFMSCAN_OCC_SCRATCH_DOUBLES overrides
-static_assert(OCC_FANIN == 32, "a block is the 32 windows one lane walks; the masks are 32 bits wide");
+static_assert(OCC_FANIN == PFMSCAN_OCC_FANIN && OCC_FANIN == 32, "a block is the 32 windows one lane walks; the masks are 32 bits wide");
 
 struct OccArgs {
     const uint8_t *codes;        // [n_pos]
@@ -40,7 +43,7 @@ struct OccArgs {
     const int64_t *run_start;    // [n_rec + 1] prefix of ceil(blocks / OCCP_RUN)
     int64_t run_base;            // run_start[r0]
     int64_t *run_rec;            // [runs of the pass] the record of every run (k_occ_run_records)
-    // two code streams (k_occ_pair_blocks, k_exp_pair_blocks): codes are the RNA codes, tables the sequence tables
+    // two code streams (k_occ_blocks<QN, true>, k_exp_pair_blocks): codes are the RNA codes, tables the sequence tables
     const uint8_t *codes2;       // [n_pos] structure-letter codes
     const double *tables2;       // [n_motifs][m][8] device: the structure tables of the pairs
 };
@@ -58,7 +61,6 @@ __device__ __forceinline__ int64_t occ_record(const int64_t *__restrict__ start,
 }
 
 // ---- averaged-structure profiles: what the level-0 kernels of both files share -----------------------------------------
-constexpr int OCCP_RUN = 8;                                        // blocks of a workgroup's run
 constexpr int OCCP_WIN = OCCP_RUN * OCC_FANIN;                     // its windows: a lane each
 constexpr int OCCP_ROWS = OCCP_WIN + PFMSCAN_MAX_M - 1;            // rows it stages at most
 constexpr int OCCP_TS = OCCP_RUN * (OCC_FANIN + 1);                // doubles of one motif's terms in LDS: window w at w + w / 32
@@ -114,33 +116,67 @@ struct OccProfile {
     int dtype;
 };
 
-// pfmscan_occupancy.hip.  k_occ_run_records on st: the record of every run of the pass a describes (a.run_rec, from
-// a.run_start / a.run_base over records a.r0 .. a.r1)
+// the record table of a call: HOST copies, already checked (ascending, disjoint, inside [0, n_pos)), and the same on the device
+struct OccRecords {
+    const int64_t *off, *len;
+    const int64_t *d_off, *d_len;
+    int64_t n_rec, n_pos;
+};
+
+// ---- pfmscan_occupancy.hip: the frame of a driver (occ_run, exp_run, exp_pair_run, expp_run) ------------------------------
+// the scratch cap in doubles: OCC_SCRATCH_DOUBLES unless the environment says otherwise
+int64_t occ_scratch_cap();
+// The tables of a call on st: the letter tables (HOST double [n_motifs][m][8], or null) into ctx->occ_tab, then the structure
+// tables (stab_bytes of them, or null) behind them.  d_tab: where the former lie (null when there are none), d_stab: the latter.
+int occ_upload_tables(pfmscan_ctx *ctx, const double *letter_tables, const double *struct_tables, size_t stab_bytes, int n_motifs, int m,
+                      hipStream_t st, const double *&d_tab, const double *&d_stab);
+// Room for the block and level-1 sums of the plan's largest pass (`cells` doubles per unit and block), the plan's prefix tables
+// uploaded on st (room for a pass's run -> record table behind them when it numbers runs), and the record-independent fields
+// of the arguments: the streams' sizes, the record and prefix tables, run_rec, bs, gs, m, n_letters, n_motifs.
+int occ_frame(pfmscan_ctx *ctx, const OccPlan &p, int cells, const OccRecords &rec, int n_motifs, int m, int n_letters, hipStream_t st, OccArgs &a);
+// the fields of pass i of the plan: r0, r1, blk_base, n_blk, grp_base, n_grp, run_base; returns the runs of the pass
+int64_t occ_set_pass(OccArgs &a, const OccPlan &p, size_t i);
+// k_occ_run_records on st: the record of every run of the pass a describes (a.run_rec, from a.run_start / a.run_base over
+// records a.r0 .. a.r1)
 void occ_launch_run_records(const OccArgs &a, hipStream_t st);
 // Levels 1 and up of a pass whose block sums lie in a.bs: k_occ_level1 (when the pass has blocks)
 // and k_occ_finish on st; n_q independent columns per record, one writer per cell of a.occ.
 int occ_launch_upper(pfmscan_ctx *ctx, const OccArgs &a, hipStream_t st);
-// the scratch cap in doubles: OCC_SCRATCH_DOUBLES unless the environment says otherwise
-int64_t occ_scratch_cap();
+
+// ---- pfmscan_occupancy.hip: the pieces of the entry points -----------------------------------------------------------------
+// The checks every entry point of the family makes before the rule "n_rec == 0 or n_motifs == 0: nothing to do", in their
+// order: the width; the caller's own test of its kind, mode or n_letters (own: what to say when it failed, else null); the
+// sizes; a table that is NULL while there are motifs (missing: what to say, else null).
+int occ_check_base(pfmscan_ctx *ctx, const char *who, int m, const char *own, int n_motifs, int64_t n_rec, int64_t n_pos, const char *missing);
 int occ_check(pfmscan_ctx *ctx, const char *who, const double *ratio_tables, int n_motifs, int m, int n_letters, int64_t n_pos, int64_t n_rec);
-// ascending, disjoint, inside [0, n_pos)
-int occ_check_records(pfmscan_ctx *ctx, const char *who, const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec, int64_t n_pos);
-// the occupancy of letter strings on st, without waiting: rec_off / rec_len are HOST copies, already checked, d_rec_off /
-// d_rec_len the same on the device
-int occ_run_letters(pfmscan_ctx *ctx, const char *who, const double *ratio_tables, int n_motifs, int m, int n_letters, const uint8_t *d_codes,
-                    int64_t n_pos, const int64_t *rec_off, const int64_t *rec_len, const int64_t *d_rec_off, const int64_t *d_rec_len,
-                    int64_t n_rec, double *d_occ, int64_t *d_windows, hipStream_t st);
-// the same on an averaged-structure profile: structure only (seq_tables null: d_codes is not read) or joint
-int occ_run_profile(pfmscan_ctx *ctx, const char *who, const OccProfile &pf, const double *seq_tables, int n_motifs, int m, const uint8_t *d_codes,
-                    int64_t n_pos, const int64_t *rec_off, const int64_t *rec_len, const int64_t *d_rec_off, const int64_t *d_rec_len,
-                    int64_t n_rec, double *d_occ, int64_t *d_windows, hipStream_t st);
-// the same on two code streams: pair q is (seq_tables[q], struct_tables[q]), HOST double [n_motifs][m][8] both
-int occ_run_pair(pfmscan_ctx *ctx, const char *who, const double *seq_tables, const double *struct_tables, int n_motifs, int m,
-                 const uint8_t *d_codes, const uint8_t *d_codes2, int64_t n_pos, const int64_t *rec_off, const int64_t *rec_len,
-                 const int64_t *d_rec_off, const int64_t *d_rec_len, int64_t n_rec, double *d_occ, int64_t *d_windows, hipStream_t st);
-// the checks the four two-stream entry points share, before the rule "n_rec == 0 or n_motifs == 0: nothing to do"
+// the checks the four two-stream entry points share
 int occ_pair_check(pfmscan_ctx *ctx, const char *who, const double *seq_tables, const double *struct_tables, int n_motifs, int m, int64_t n_pos,
                    int64_t n_rec);
+// A _dev form's record table: it decides every address the kernels form, so it is read back (into host; one synchronisation of
+// ctx->stream) and checked before anything is launched.
+int occ_records_home(pfmscan_ctx *ctx, const char *who, const int64_t *d_rec_off, const int64_t *d_rec_len, int64_t n_rec, int64_t n_pos,
+                     std::vector<int64_t> &host, OccRecords &rec);
+// A _staged form's record table: checked, then uploaded into ctx->occ_rec on ctx->stream.
+int occ_records_up(pfmscan_ctx *ctx, const char *who, const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec, OccRecords &rec);
+// the tail of a _staged form: every array that is asked for (dst not null) comes home on ctx->stream, one synchronisation
+struct OccHome {
+    void *dst;
+    const void *d_src;
+    size_t bytes;
+};
+int occ_copy_home(pfmscan_ctx *ctx, std::initializer_list<OccHome> arrays);
+
+// ---- pfmscan_occupancy.hip: the occupancy itself, on st, without waiting ---------------------------------------------------
+// the second stream of two code streams: pair q is (ratio_tables[q], struct_tables[q])
+struct OccPair {
+    const double *struct_tables;   // HOST double [n_motifs][m][8]
+    const uint8_t *d_codes2;
+};
+// pf and pr null: letter strings (ratio_tables over d_codes).  pf: an averaged-structure profile, and ratio_tables / d_codes are
+// the letter part of joint mode (n_letters 4) or null.  pr: two code streams, ratio_tables / d_codes the sequence side
+// (n_letters 4).  Only the level-0 launch differs.
+int occ_run(pfmscan_ctx *ctx, const char *who, const double *ratio_tables, int n_motifs, int m, int n_letters, const uint8_t *d_codes,
+            const OccRecords &rec, double *d_occ, int64_t *d_windows, hipStream_t st, const OccProfile *pf = nullptr, const OccPair *pr = nullptr);
 // pfmscan_expect.hip.  k_exp_inverse on st: inv[i] = 1.0 / occ[i], one rounded division each; -1.0 where occ[i] == 0.0
 int exp_launch_inverse(pfmscan_ctx *ctx, const double *d_occ, double *d_inv, int64_t n, hipStream_t st);
 // pfmscan_expect_merge.hip.  One matrix of a merged _staged form: the per-record matrices d_exp [n_rec][n_motifs][m][8] a pass

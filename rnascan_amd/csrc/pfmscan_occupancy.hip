@@ -7,22 +7,23 @@
 // element j of the next level is a[32 j], + a[32 j + 1], ... over the children that exist, sequential and each rounded.  No
 // transcendental, no atomics, no tolerance: tests/occupancy_rules.py restates it in numpy and the bits are compared.
 //
-//   k_occ_blocks<QN>   level 0.  A lane owns one (record, block of 32 consecutive windows) and walks the windows serially for
-//                      QN = 8, 4, 2 or 1 motifs at a time: 0.0 + t_0 + t_1 ... is the definition's sum (x + +0.0 == x for
-//                      every value a term can take, so a skipped window adds nothing).  The block's 32 + m - 1 codes sit in
-//                      a lane-private strip of LDS an odd number of dwords wide (aligned dwords as loaded, foreign codes
-//                      zeroed and kept as a 128-bit mask in registers: no register array is indexed at run time); the
+//   k_occ_blocks<QN, PAIR>   level 0.  A lane owns one (record, block of 32 consecutive windows) and walks the windows
+//                      serially for QN = 8, 4, 2 or 1 motifs at a time: 0.0 + t_0 + t_1 ... is the definition's sum (x + +0.0
+//                      == x for every value a term can take, so a skipped window adds nothing).  The block's 32 + m - 1 codes
+//                      sit in a lane-private strip of LDS an odd number of dwords wide (aligned dwords as loaded, foreign
+//                      codes zeroed and kept as a 128-bit mask in registers: no register array is indexed at run time); the
 //                      ratio tables of a chunk of motifs sit in LDS transposed [row][letter][motif], so one letter serves
-//                      QN adjacent motifs with 16-byte reads.
-//   k_occ_pair_blocks<QN>   level 0 on two code streams: k_occ_blocks with both codes of a position packed
-//                      into one byte of the strip and the letter chain continued over the structure letters; described
-//                      above the kernel, with the rule for the pairs of an LDS chunk.
+//                      QN adjacent motifs with 16-byte reads.  PAIR: two code streams, both codes of a
+//                      position packed into one byte of the strip and the letter chain continued over the structure
+//                      letters; described above the kernel, with the rule for the pairs of an LDS chunk.
 //   k_occ_level1       level 1: a thread adds the <= 32 block sums of one (group of 32 blocks, motif), in order.
 //   k_occ_finish       levels 2 and up: a thread per (record, motif) folds the record's level-1 sums in place, in order, and
 //                      writes the cell.  One writer per cell.
 // The block sums go through scratch that is bounded (OCC_SCRATCH_DOUBLES) by running the records, and if one record alone is
-// too long the motifs, in passes.  What the expected counts (pfmscan_expect.hip) share -- the arguments of a pass, the bisection
-// and levels 1 and up, whose n_q columns are then the cells of motifs -- is declared in pfmscan_occ.hpp.
+// too long the motifs, in passes: the plan is occ_plan (pfmscan_occ_plan.hpp), here over motifs.  What the expected counts
+// (pfmscan_expect.hip, pfmscan_expect_profile.hip) share -- the arguments of a pass and the frame that fills them, the bisection,
+// levels 1 and up, whose n_q columns are then the cells of motifs, and the pieces of the entry points -- is declared in
+// pfmscan_occ.hpp and defined here.
 //
 // Averaged-structure profiles (include/pfmscan.h "occupancy on averaged-structure profiles"): the term of a
 // window is the product over k of the marginal d(s + k, k) = sum_c r[s + k][c] * S[k][c] (7 rounded products, 6 rounded
@@ -82,21 +83,48 @@ __device__ __forceinline__ void occ_cells(const double *p, double (&v)[QN])
     }
 }
 
-template <int QN>
+// ---- level 0 on letter strings, and on two code streams (include/pfmscan.h "occupancy and expected counts of
+// two code streams") --------------------------------------------------------------------------------------------------------
+// PAIR: the term of a window is the letter chain over codes (4 RNA letters) continued by the letter chain over codes2 (7
+// structure letters), 2 m - 1 rounded products, letters first.  Both codes of a position share ONE byte of the lane's strip --
+// bits 0..2 the RNA code, bits 3..5 the structure code, a position that is foreign in either stream zeroed and remembered in
+// the 128-bit mask -- so the byte traffic of the strip and its size are those of one stream (a second strip would double the
+// reads of an LDS-bound kernel and pass 64 KB of dynamic LDS at m = 64).  The tables of a chunk of pairs sit in LDS as
+// [row][letter][pair] with OCC_PAIR_LETTERS = 4 + 7 letters per row: 0..3 the row of R, 4..10 the row of S.  The products
+// R[k][a] * S[k][b] are never made: that would be another rounding.
+// Chunk rule (occ_chunk, with 11 letters for pairs): the most motifs c <= n_q with m * letters * occ_ls(c, occ_qn(c)) <=
+// OCC_LDS_DOUBLES, at least 1; occ_qn(c) = 8, 4, 2, 1 for c >= 8, 4, 2, 1 and occ_ls(c, qn) = c rounded up to a multiple of qn,
+// plus 2 when that is a multiple of 16.
+constexpr int OCC_PAIR_LETTERS = 4 + PFMSCAN_NSTRUCT;
+static_assert(OCC_LDS_DOUBLES >= PFMSCAN_MAX_M * OCC_PAIR_LETTERS, "one pair of the widest kind fits");
+
+// the aligned dword at p of a stream of n_pos codes (the base pointer is 16-byte aligned); the stream's last one may be cut short
+__device__ __forceinline__ uint32_t occ_dword(const uint8_t *__restrict__ codes, int64_t p, int64_t n_pos)
+{
+    if (p + 4 <= n_pos) return *reinterpret_cast<const uint32_t *>(codes + p);
+    uint32_t dw = 0;
+    for (int j = 0; j < 4; ++j)
+        if (p + j < n_pos) dw |= (uint32_t)codes[p + j] << (8 * j);
+    return dw;
+}
+
+template <int QN, bool PAIR>
 __global__ __launch_bounds__(BLOCK) void k_occ_blocks(const OccArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char occ_lds[];
-    const int m = a.m, nl = a.n_letters;
+    const int m = a.m, nl = PAIR ? OCC_PAIR_LETTERS : a.n_letters;
     const int cs = occ_strip(m);                                   // dwords per lane strip
     uint32_t *cw = reinterpret_cast<uint32_t *>(occ_lds);          // [BLOCK][cs]
-    double *lt = reinterpret_cast<double *>(occ_lds + (size_t)BLOCK * cs * 4);   // [m][n_letters][ls]; BLOCK * 4 is a multiple of 16
+    double *lt = reinterpret_cast<double *>(occ_lds + (size_t)BLOCK * cs * 4);   // [m][nl][ls]; BLOCK * 4 is a multiple of 16
     const int qc = (int)blockIdx.y * a.chunk;                      // first motif of the chunk, within the pass
     const int nq = min(a.chunk, a.n_q - qc);
     const int ls = occ_ls(a.chunk, QN);
     for (int i = threadIdx.x; i < m * nl * ls; i += BLOCK) {
-        const int r = i / ls, q = i - r * ls;                      // r = row * n_letters + letter
+        const int r = i / ls, q = i - r * ls;                      // r = row * nl + letter
         const int row = r / nl, c = r - row * nl;
-        lt[i] = q < nq ? a.tables[((int64_t)(a.q_first + qc + q) * m + row) * 8 + c] : 0.0;
+        const bool second = PAIR && c >= 4;                        // a letter of the structure table
+        const double *src = second ? a.tables2 : a.tables;
+        lt[i] = q < nq ? src[((int64_t)(a.q_first + qc + q) * m + row) * 8 + (second ? c - 4 : c)] : 0.0;
     }
     // this lane's block: its codes as aligned dwords into the lane's strip, foreign codes zeroed and remembered
     const int64_t gb = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
@@ -112,29 +140,27 @@ __global__ __launch_bounds__(BLOCK) void k_occ_blocks(const OccArgs a)
         const int64_t s0 = a.rec_off[r] + w0;
         sh = (int)(s0 & 3);
         const int64_t base = s0 - sh;
-        unsigned long long f0 = 0, f1 = 0;                         // bit i: code i of the block is foreign or not the block's
+        unsigned long long f0 = 0, f1 = 0;                         // bit i: code i of the block is foreign (in either stream) or not the block's
         uint32_t *mine = cw + threadIdx.x * cs;
 #pragma unroll
         for (int i = 0; i < OCC_CODE_DWORDS; ++i) {
             const int64_t p = base + 4 * i;
-            uint32_t dw = 0;
+            uint32_t d1 = 0, d2 = 0;
             if (4 * i - sh < need) {
-                if (p + 4 <= a.n_pos) dw = *reinterpret_cast<const uint32_t *>(a.codes + p);   // the base pointer is 16-byte aligned
-                else
-                    for (int j = 0; j < 4; ++j)
-                        if (p + j < a.n_pos) dw |= (uint32_t)a.codes[p + j] << (8 * j);
+                d1 = occ_dword(a.codes, p, a.n_pos);
+                if constexpr (PAIR) d2 = occ_dword(a.codes2, p, a.n_pos);
             }
             uint32_t out = 0;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int idx = 4 * i + j - sh;                    // -3 .. 99
-                const uint32_t c = (dw >> (8 * j)) & 7u;
-                const bool bad = idx >= need || (int)c >= nl;
+                const uint32_t c1 = (d1 >> (8 * j)) & 7u, c2 = (d2 >> (8 * j)) & 7u;
+                const bool bad = idx >= need || (PAIR ? c1 >= 4u || c2 >= (uint32_t)PFMSCAN_NSTRUCT : (int)c1 >= nl);
                 if (idx >= 0) {
                     if (idx < 64) f0 |= (unsigned long long)bad << idx;
                     else f1 |= (unsigned long long)bad << (idx - 64);
                 }
-                out |= (bad ? 0u : c) << (8 * j);
+                out |= (bad ? 0u : PAIR ? c1 | (c2 << 3) : c1) << (8 * j);
             }
             if (i < cs) mine[i] = out;                             // beyond: no code of a block of this width (4 i - sh >= need)
         }
@@ -163,146 +189,25 @@ __global__ __launch_bounds__(BLOCK) void k_occ_blocks(const OccArgs a)
             const uint8_t *cp = cb + w;
             const double *row = lt + q;
             double t[QN];
-            occ_cells<QN>(row + (int)cp[0] * ls, t);
-#pragma unroll 4
-            for (int k = 1; k < m; ++k) {
-                row += rs;
-                double c[QN];
-                occ_cells<QN>(row + (int)cp[k] * ls, c);
-#pragma unroll
-                for (int i = 0; i < QN; ++i) t[i] = t[i] * c[i];
-            }
-            const bool has = (valid >> w) & 1u;
-#pragma unroll
-            for (int i = 0; i < QN; ++i) sum[i] = sum[i] + (has ? t[i] : 0.0);
-        }
-#pragma unroll
-        for (int i = 0; i < QN; ++i)
-            if (q + i < nq) out[q + i] = sum[i];
-    }
-}
-
-// ---- level 0 on two code streams (include/pfmscan.h "occupancy and expected counts of two code streams") -------
-// k_occ_blocks with a second stream: the term of a window is the letter chain over codes (4 RNA letters) continued by the
-// letter chain over codes2 (7 structure letters), 2 m - 1 rounded products, letters first.  Both codes of a position share
-// ONE byte of the lane's strip -- bits 0..2 the RNA code, bits 3..5 the structure code, a position that is foreign in either
-// stream zeroed and remembered in the 128-bit mask -- so the byte traffic of the strip and its size are k_occ_blocks' own
-// (a second strip would double the reads of an LDS-bound kernel and pass 64 KB of dynamic LDS at m = 64).  The tables of a
-// chunk of pairs sit in LDS as [row][letter][pair] with OCC_PAIR_LETTERS = 4 + 7 letters per row: 0..3 the row of R, 4..10
-// the row of S.  The products R[k][a] * S[k][b] are never made: that would be another rounding.
-// Chunk rule (occ_chunk with 11 letters): the most pairs c <= n_q with m * 11 * occ_ls(c, occ_qn(c)) <= OCC_LDS_DOUBLES, at
-// least 1; occ_qn(c) = 8, 4, 2, 1 for c >= 8, 4, 2, 1 and occ_ls(c, qn) = c rounded up to a multiple of qn, plus 2 when that
-// is a multiple of 16.
-constexpr int OCC_PAIR_LETTERS = 4 + PFMSCAN_NSTRUCT;
-static_assert(OCC_LDS_DOUBLES >= PFMSCAN_MAX_M * OCC_PAIR_LETTERS, "one pair of the widest kind fits");
-
-// the aligned dword at p of a stream of n_pos codes (the base pointer is 16-byte aligned); the stream's last one may be cut short
-__device__ __forceinline__ uint32_t occ_dword(const uint8_t *__restrict__ codes, int64_t p, int64_t n_pos)
-{
-    if (p + 4 <= n_pos) return *reinterpret_cast<const uint32_t *>(codes + p);
-    uint32_t dw = 0;
-    for (int j = 0; j < 4; ++j)
-        if (p + j < n_pos) dw |= (uint32_t)codes[p + j] << (8 * j);
-    return dw;
-}
-
-template <int QN>
-__global__ __launch_bounds__(BLOCK) void k_occ_pair_blocks(const OccArgs a)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char occ_lds[];
-    constexpr int NL = OCC_PAIR_LETTERS;
-    const int m = a.m;
-    const int cs = occ_strip(m);                                   // dwords per lane strip
-    uint32_t *cw = reinterpret_cast<uint32_t *>(occ_lds);          // [BLOCK][cs]
-    double *lt = reinterpret_cast<double *>(occ_lds + (size_t)BLOCK * cs * 4);   // [m][11][ls]
-    const int qc = (int)blockIdx.y * a.chunk;                      // first pair of the chunk, within the pass
-    const int nq = min(a.chunk, a.n_q - qc);
-    const int ls = occ_ls(a.chunk, QN);
-    for (int i = threadIdx.x; i < m * NL * ls; i += BLOCK) {
-        const int r = i / ls, q = i - r * ls;                      // r = row * 11 + letter
-        const int row = r / NL, c = r - row * NL;
-        const double *src = c < 4 ? a.tables : a.tables2;
-        lt[i] = q < nq ? src[((int64_t)(a.q_first + qc + q) * m + row) * 8 + (c < 4 ? c : c - 4)] : 0.0;
-    }
-    const int64_t gb = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-    uint32_t valid = 0;                                            // bit w: window w of the block has a term
-    int sh = 0;
-    if (gb < a.n_blk) {
-        const int64_t b = a.blk_base + gb;
-        const int64_t r = occ_record(a.blk_start, a.r0, a.r1, b);
-        const int64_t w0 = (b - a.blk_start[r]) * OCC_FANIN;
-        const int64_t left = a.rec_len[r] - m + 1 - w0;            // >= 1: the block exists
-        const int nw = (int)min((int64_t)OCC_FANIN, left);
-        const int need = nw + m - 1;                               // positions of the block, all inside the record
-        const int64_t s0 = a.rec_off[r] + w0;
-        sh = (int)(s0 & 3);
-        const int64_t base = s0 - sh;
-        unsigned long long f0 = 0, f1 = 0;                         // bit i: position i of the block is foreign (in either stream) or not the block's
-        uint32_t *mine = cw + threadIdx.x * cs;
-#pragma unroll
-        for (int i = 0; i < OCC_CODE_DWORDS; ++i) {
-            const int64_t p = base + 4 * i;
-            uint32_t d1 = 0, d2 = 0;
-            if (4 * i - sh < need) {
-                d1 = occ_dword(a.codes, p, a.n_pos);
-                d2 = occ_dword(a.codes2, p, a.n_pos);
-            }
-            uint32_t out = 0;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int idx = 4 * i + j - sh;                    // -3 .. 99
-                const uint32_t c1 = (d1 >> (8 * j)) & 7u, c2 = (d2 >> (8 * j)) & 7u;
-                const bool bad = idx >= need || c1 >= 4u || c2 >= (uint32_t)PFMSCAN_NSTRUCT;
-                if (idx >= 0) {
-                    if (idx < 64) f0 |= (unsigned long long)bad << idx;
-                    else f1 |= (unsigned long long)bad << (idx - 64);
-                }
-                out |= (bad ? 0u : (c1 | (c2 << 3))) << (8 * j);
-            }
-            if (i < cs) mine[i] = out;                             // beyond: no position of a block of this width
-        }
-        const unsigned long long wmask = m == 64 ? ~0ull : (1ull << m) - 1;
-        for (int w = 0; w < OCC_FANIN; ++w) {
-            const unsigned long long win = w ? (f0 >> w) | (f1 << (64 - w)) : f0;
-            valid |= (uint32_t)((win & wmask) == 0) << w;          // w >= nw: position w + m - 1 >= need is marked
-        }
-        if (a.bcnt && blockIdx.y == 0) a.bcnt[gb] = __popc(valid);
-    }
-    __syncthreads();                                               // the last barrier
-    if (gb >= a.n_blk) return;
-    const uint8_t *cb = reinterpret_cast<const uint8_t *>(cw + threadIdx.x * cs) + sh;
-    const int rs = NL * ls;                                        // doubles per table row
-    double *out = a.bs + gb * a.n_q + qc;
-    if (valid == 0) {                                              // no window with a term: +0.0 without walking the block
-        for (int q = 0; q < nq; ++q) out[q] = 0.0;
-        return;
-    }
-    for (int q = 0; q < nq; q += QN) {
-        double sum[QN];
-#pragma unroll
-        for (int i = 0; i < QN; ++i) sum[i] = 0.0;
-#pragma unroll 1
-        for (int w = 0; w < OCC_FANIN; ++w) {
-            const uint8_t *cp = cb + w;
-            const double *row = lt + q;
-            double t[QN];
-            occ_cells<QN>(row + (int)(cp[0] & 7u) * ls, t);
+            occ_cells<QN>(row + (int)(PAIR ? cp[0] & 7u : cp[0]) * ls, t);
 #pragma unroll 4
             for (int k = 1; k < m; ++k) {                          // the letters ...
                 row += rs;
                 double c[QN];
-                occ_cells<QN>(row + (int)(cp[k] & 7u) * ls, c);
+                occ_cells<QN>(row + (int)(PAIR ? cp[k] & 7u : cp[k]) * ls, c);
 #pragma unroll
                 for (int i = 0; i < QN; ++i) t[i] = t[i] * c[i];
             }
-            row = lt + q + 4 * ls;
+            if constexpr (PAIR) {
+                row = lt + q + 4 * ls;
 #pragma unroll 4
-            for (int k = 0; k < m; ++k) {                          // ... then the structure, continuing the same chain
-                double c[QN];
-                occ_cells<QN>(row + (int)(cp[k] >> 3) * ls, c);
-                row += rs;
+                for (int k = 0; k < m; ++k) {                      // ... then the structure, continuing the same chain
+                    double c[QN];
+                    occ_cells<QN>(row + (int)(cp[k] >> 3) * ls, c);
+                    row += rs;
 #pragma unroll
-                for (int i = 0; i < QN; ++i) t[i] = t[i] * c[i];
+                    for (int i = 0; i < QN; ++i) t[i] = t[i] * c[i];
+                }
             }
             const bool has = (valid >> w) & 1u;
 #pragma unroll
@@ -519,27 +424,16 @@ static int occ_chunk(int m, int n_letters, int n_q)
     return c;
 }
 
+template <bool PAIR>
 static hipError_t occ_launch_blocks(const OccArgs &a, hipStream_t st)
 {
-    const int qn = occ_qn(a.chunk);
-    const size_t lds = (size_t)BLOCK * occ_strip(a.m) * 4 + (size_t)a.m * a.n_letters * occ_ls(a.chunk, qn) * sizeof(double);
+    const int qn = occ_qn(a.chunk), nl = PAIR ? OCC_PAIR_LETTERS : a.n_letters;
+    const size_t lds = (size_t)BLOCK * occ_strip(a.m) * 4 + (size_t)a.m * nl * occ_ls(a.chunk, qn) * sizeof(double);
     const dim3 grid((unsigned)((a.n_blk + BLOCK - 1) / BLOCK), (unsigned)((a.n_q + a.chunk - 1) / a.chunk));
-    if (qn == 8) hipLaunchKernelGGL(k_occ_blocks<8>, grid, dim3(BLOCK), lds, st, a);
-    else if (qn == 4) hipLaunchKernelGGL(k_occ_blocks<4>, grid, dim3(BLOCK), lds, st, a);
-    else if (qn == 2) hipLaunchKernelGGL(k_occ_blocks<2>, grid, dim3(BLOCK), lds, st, a);
-    else hipLaunchKernelGGL(k_occ_blocks<1>, grid, dim3(BLOCK), lds, st, a);
-    return hipGetLastError();
-}
-
-static hipError_t occ_launch_pair_blocks(const OccArgs &a, hipStream_t st)
-{
-    const int qn = occ_qn(a.chunk);
-    const size_t lds = (size_t)BLOCK * occ_strip(a.m) * 4 + (size_t)a.m * OCC_PAIR_LETTERS * occ_ls(a.chunk, qn) * sizeof(double);
-    const dim3 grid((unsigned)((a.n_blk + BLOCK - 1) / BLOCK), (unsigned)((a.n_q + a.chunk - 1) / a.chunk));
-    if (qn == 8) hipLaunchKernelGGL(k_occ_pair_blocks<8>, grid, dim3(BLOCK), lds, st, a);
-    else if (qn == 4) hipLaunchKernelGGL(k_occ_pair_blocks<4>, grid, dim3(BLOCK), lds, st, a);
-    else if (qn == 2) hipLaunchKernelGGL(k_occ_pair_blocks<2>, grid, dim3(BLOCK), lds, st, a);
-    else hipLaunchKernelGGL(k_occ_pair_blocks<1>, grid, dim3(BLOCK), lds, st, a);
+    if (qn == 8) hipLaunchKernelGGL((k_occ_blocks<8, PAIR>), grid, dim3(BLOCK), lds, st, a);
+    else if (qn == 4) hipLaunchKernelGGL((k_occ_blocks<4, PAIR>), grid, dim3(BLOCK), lds, st, a);
+    else if (qn == 2) hipLaunchKernelGGL((k_occ_blocks<2, PAIR>), grid, dim3(BLOCK), lds, st, a);
+    else hipLaunchKernelGGL((k_occ_blocks<1, PAIR>), grid, dim3(BLOCK), lds, st, a);
     return hipGetLastError();
 }
 
@@ -566,103 +460,96 @@ static hipError_t occ_launch_profile(const OccArgs &a, int dtype, bool seq, int6
     return hipGetLastError();
 }
 
-// rec_off / rec_len: HOST copies, already checked; d_rec_off / d_rec_len: the same on the device.  Launches on st, does not wait.
-// pf == null: letter strings (ratio_tables over d_codes); otherwise an averaged-structure profile, and ratio_tables / d_codes
-// are the letter part of joint mode or null.  pr != null (pf null): two code streams, ratio_tables / d_codes the sequence side.
-// Only the level-0 launch differs.
-struct OccPair {
-    const double *struct_tables;   // HOST double [n_motifs][m][8]
-    const uint8_t *d_codes2;
-};
-
-static int occ_run(pfmscan_ctx *ctx, const char *who, const double *ratio_tables, int n_motifs, int m, int n_letters, const uint8_t *d_codes,
-                   int64_t n_pos, const int64_t *rec_off, const int64_t *rec_len, const int64_t *d_rec_off, const int64_t *d_rec_len,
-                   int64_t n_rec, double *d_occ, int64_t *d_windows, hipStream_t st, const OccProfile *pf = nullptr, const OccPair *pr = nullptr)
+// ---- the frame of a driver (pfmscan_occ.hpp) -------------------------------------------------------------------------------
+int occ_upload_tables(pfmscan_ctx *ctx, const double *letter_tables, const double *struct_tables, size_t stab_bytes, int n_motifs, int m,
+                      hipStream_t st, const double *&d_tab, const double *&d_stab)
 {
-    std::vector<int64_t> start(3 * (size_t)(n_rec + 1));
-    int64_t *blk = start.data(), *grp = blk + n_rec + 1, *run = grp + n_rec + 1;
-    int64_t max_blk = 0;
-    blk[0] = grp[0] = run[0] = 0;
-    for (int64_t r = 0; r < n_rec; ++r) {
-        const int64_t nw = std::max<int64_t>(rec_len[r] - m + 1, 0), nb = (nw + OCC_FANIN - 1) / OCC_FANIN;
-        blk[r + 1] = blk[r] + nb;
-        grp[r + 1] = grp[r] + (nb + OCC_FANIN - 1) / OCC_FANIN;
-        run[r + 1] = run[r] + (nb + OCCP_RUN - 1) / OCCP_RUN;
-        max_blk = std::max(max_blk, nb);
-    }
-    const int64_t cap = occ_scratch_cap();
-    // motifs per pass: all of them unless the longest record's block sums alone pass the cap; then records per pass
-    const int n_q_max = (int)std::min<int64_t>(n_motifs, std::max<int64_t>(1, cap / std::max<int64_t>(max_blk, 1)));
-    const int64_t blk_cap = std::max<int64_t>(cap / n_q_max, 1), rec_cap = std::max<int64_t>((int64_t(1) << 30) / n_q_max, 1);
-    std::vector<int64_t> cuts(1, 0);
-    int64_t need_blk = 0, need_grp = 0, need_run = 0;
-    for (int64_t r0 = 0; r0 < n_rec;) {
-        int64_t r1 = r0 + 1;
-        while (r1 < n_rec && r1 - r0 < rec_cap && blk[r1 + 1] - blk[r0] <= blk_cap) ++r1;
-        cuts.push_back(r1);
-        need_blk = std::max(need_blk, blk[r1] - blk[r0]);
-        need_grp = std::max(need_grp, grp[r1] - grp[r0]);
-        need_run = std::max(need_run, run[r1] - run[r0]);
-        r0 = r1;
-    }
-    // a profile pass launches a workgroup per run, and has no more runs than blocks
-    if ((need_blk + BLOCK - 1) / BLOCK > 0x7FFFFFFF || (pf && need_blk > 0x7FFFFFFF)) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": a record is too long for one call");
     int rc;
-    const size_t tab_bytes = ratio_tables ? (size_t)n_motifs * m * 8 * sizeof(double) : 0;
-    const size_t stab_bytes = pf ? (size_t)n_motifs * m * 7 * sizeof(double) : pr ? tab_bytes : 0;   // behind the letter tables
+    const size_t tab_bytes = letter_tables ? (size_t)n_motifs * m * 8 * sizeof(double) : 0;
+    if (!struct_tables) stab_bytes = 0;
     if ((rc = ensure(ctx, ctx->occ_tab, tab_bytes + stab_bytes))) return rc;
-    if ((rc = ensure(ctx, ctx->occ_idx, (start.size() + (pf ? (size_t)need_run : 0)) * 8))) return rc;   // the prefix tables, then a pass's run -> record
-    if ((rc = ensure(ctx, ctx->occ_bs, std::max<size_t>((size_t)need_blk * n_q_max * 8, 16)))) return rc;
-    if ((rc = ensure(ctx, ctx->occ_gs, std::max<size_t>((size_t)need_grp * n_q_max * 8, 16)))) return rc;
-    if ((rc = ensure(ctx, ctx->occ_cnt, std::max<size_t>((size_t)(need_blk + need_grp) * 4, 16)))) return rc;
-    if (tab_bytes && (rc = upload(ctx, ctx->occ_tab.p, ratio_tables, tab_bytes, st))) return rc;
-    const double *d_stab = (const double *)((const unsigned char *)ctx->occ_tab.p + tab_bytes);
-    if (pf && (rc = upload(ctx, (void *)d_stab, pf->struct_tables, stab_bytes, st))) return rc;
-    if (pr && (rc = upload(ctx, (void *)d_stab, pr->struct_tables, stab_bytes, st))) return rc;
-    if ((rc = upload(ctx, ctx->occ_idx.p, start.data(), start.size() * 8, st))) return rc;
-    OccArgs a{};
-    a.codes = d_codes;
-    a.n_pos = n_pos;
-    a.rec_off = d_rec_off;
-    a.rec_len = d_rec_len;
+    d_tab = tab_bytes ? (const double *)ctx->occ_tab.p : nullptr;
+    d_stab = (const double *)((const unsigned char *)ctx->occ_tab.p + tab_bytes);
+    if (tab_bytes && (rc = upload(ctx, ctx->occ_tab.p, letter_tables, tab_bytes, st))) return rc;
+    if (stab_bytes && (rc = upload(ctx, (void *)d_stab, struct_tables, stab_bytes, st))) return rc;
+    return PFMSCAN_OK;
+}
+
+int occ_frame(pfmscan_ctx *ctx, const OccPlan &p, int cells, const OccRecords &rec, int n_motifs, int m, int n_letters, hipStream_t st, OccArgs &a)
+{
+    int rc;
+    const size_t per_blk = (size_t)p.n_u_max * cells * 8;          // bytes of a block's (a group's) sums
+    if ((rc = ensure(ctx, ctx->occ_idx, (p.start.size() + (size_t)p.need_run) * 8))) return rc;   // the prefix tables, then a pass's run -> record
+    if ((rc = ensure(ctx, ctx->occ_bs, std::max<size_t>((size_t)p.need_blk * per_blk, 16)))) return rc;
+    if ((rc = ensure(ctx, ctx->occ_gs, std::max<size_t>((size_t)p.need_grp * per_blk, 16)))) return rc;
+    if ((rc = upload(ctx, ctx->occ_idx.p, p.start.data(), p.start.size() * 8, st))) return rc;
+    a.n_pos = rec.n_pos;
+    a.rec_off = rec.d_off;
+    a.rec_len = rec.d_len;
     a.blk_start = (const int64_t *)ctx->occ_idx.p;
-    a.grp_start = a.blk_start + n_rec + 1;
-    a.tables = tab_bytes ? (const double *)ctx->occ_tab.p : nullptr;
-    a.run_start = a.grp_start + n_rec + 1;
-    a.run_rec = (int64_t *)ctx->occ_idx.p + start.size();
-    a.profile = pf ? (const unsigned char *)pf->d_profile : nullptr;
-    a.codes2 = pr ? pr->d_codes2 : nullptr;
-    a.tables2 = pr ? d_stab : nullptr;
+    a.grp_start = a.blk_start + rec.n_rec + 1;
+    if (p.runs) {
+        a.run_start = a.grp_start + rec.n_rec + 1;
+        a.run_rec = (int64_t *)ctx->occ_idx.p + p.start.size();
+    }
     a.m = m;
     a.n_letters = n_letters;
     a.n_motifs = n_motifs;
     a.bs = (double *)ctx->occ_bs.p;
     a.gs = (double *)ctx->occ_gs.p;
+    return PFMSCAN_OK;
+}
+
+int64_t occ_set_pass(OccArgs &a, const OccPlan &p, size_t i)
+{
+    a.r0 = p.cuts[i];
+    a.r1 = p.cuts[i + 1];
+    a.blk_base = p.blk()[a.r0];
+    a.n_blk = p.blk()[a.r1] - a.blk_base;
+    a.grp_base = p.grp()[a.r0];
+    a.n_grp = p.grp()[a.r1] - a.grp_base;
+    a.run_base = p.runs ? p.run()[a.r0] : 0;
+    return p.runs ? p.run()[a.r1] - a.run_base : 0;
+}
+
+int occ_run(pfmscan_ctx *ctx, const char *who, const double *ratio_tables, int n_motifs, int m, int n_letters, const uint8_t *d_codes,
+            const OccRecords &rec, double *d_occ, int64_t *d_windows, hipStream_t st, const OccProfile *pf, const OccPair *pr)
+{
+    // motifs per pass: all of them unless the longest record's block sums alone pass the cap; then records per pass
+    const OccPlan p = occ_plan(rec.len, rec.n_rec, m, n_motifs, 1, 1, occ_scratch_cap(), pf != nullptr);
+    // a profile pass launches a workgroup per run, and has no more runs than blocks
+    if ((p.need_blk + BLOCK - 1) / BLOCK > 0x7FFFFFFF || (pf && p.need_blk > 0x7FFFFFFF)) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": a record is too long for one call");
+    int rc;
+    OccArgs a{};
+    const double *d_stab;
+    if ((rc = occ_upload_tables(ctx, ratio_tables, pf ? pf->struct_tables : pr ? pr->struct_tables : nullptr,
+                                (size_t)n_motifs * m * (pf ? 7 : 8) * sizeof(double), n_motifs, m, st, a.tables, d_stab)))
+        return rc;
+    if ((rc = occ_frame(ctx, p, 1, rec, n_motifs, m, n_letters, st, a))) return rc;
+    if ((rc = ensure(ctx, ctx->occ_cnt, std::max<size_t>((size_t)(p.need_blk + p.need_grp) * 4, 16)))) return rc;
+    a.codes = d_codes;
+    a.profile = pf ? (const unsigned char *)pf->d_profile : nullptr;
+    a.codes2 = pr ? pr->d_codes2 : nullptr;
+    a.tables2 = pr ? d_stab : nullptr;
     a.occ = d_occ;
     a.out_stride = n_motifs;
     a.windows = d_windows;
+    const int n_q_max = (int)p.n_u_max;
     for (int q0 = 0; q0 < n_motifs; q0 += n_q_max) {
         a.q_first = q0;
         a.n_q = std::min(n_q_max, n_motifs - q0);
         a.chunk = pf ? OCCP_CHUNK : occ_chunk(m, pr ? OCC_PAIR_LETTERS : n_letters, a.n_q);
         if ((a.n_q + a.chunk - 1) / a.chunk > 65535) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": too many motifs for one call");
         const bool count = d_windows && q0 == 0;                   // Windows does not depend on the motif: counted in the first pass
-        for (size_t i = 0; i + 1 < cuts.size(); ++i) {
-            a.r0 = cuts[i];
-            a.r1 = cuts[i + 1];
-            a.blk_base = blk[a.r0];
-            a.n_blk = blk[a.r1] - a.blk_base;
-            a.grp_base = grp[a.r0];
-            a.n_grp = grp[a.r1] - a.grp_base;
-            a.bcnt = count ? (int *)ctx->occ_cnt.p : nullptr;
-            a.gcnt = count ? a.bcnt + need_blk : nullptr;
-            hipError_t e = hipSuccess;
+        a.bcnt = count ? (int *)ctx->occ_cnt.p : nullptr;
+        a.gcnt = count ? a.bcnt + p.need_blk : nullptr;
+        for (size_t i = 0; i < p.n_pass(); ++i) {
+            const int64_t n_run = occ_set_pass(a, p, i);
             if (a.n_blk > 0) {
-                a.run_base = run[a.r0];
                 if (pf) occ_launch_run_records(a, st);
-                e = pf ? occ_launch_profile(a, pf->dtype, ratio_tables != nullptr, run[a.r1] - a.run_base, d_stab, st)
-                       : pr ? occ_launch_pair_blocks(a, st) : occ_launch_blocks(a, st);
-                if (e != hipSuccess) return fail_hip(ctx, e, pf ? "k_occ_profile_blocks" : pr ? "k_occ_pair_blocks" : "k_occ_blocks");
+                const hipError_t e = pf ? occ_launch_profile(a, pf->dtype, ratio_tables != nullptr, n_run, d_stab, st)
+                                     : pr ? occ_launch_blocks<true>(a, st) : occ_launch_blocks<false>(a, st);
+                if (e != hipSuccess) return fail_hip(ctx, e, pf ? "k_occ_profile_blocks" : "k_occ_blocks");
             }
             if ((rc = occ_launch_upper(ctx, a, st))) return rc;
         }
@@ -670,19 +557,41 @@ static int occ_run(pfmscan_ctx *ctx, const char *who, const double *ratio_tables
     return PFMSCAN_OK;
 }
 
-int occ_check(pfmscan_ctx *ctx, const char *who, const double *ratio_tables, int n_motifs, int m, int n_letters, int64_t n_pos, int64_t n_rec)
+// ---- the pieces of the entry points (pfmscan_occ.hpp) ----------------------------------------------------------------------
+int occ_check_base(pfmscan_ctx *ctx, const char *who, int m, const char *own, int n_motifs, int64_t n_rec, int64_t n_pos, const char *missing)
 {
-    if (!ctx) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": NULL ctx");
     if (m < 1 || m > PFMSCAN_MAX_M)
         return fail(ctx, PFMSCAN_E_BADSHAPE, std::string(who) + ": width " + std::to_string(m) + " outside 1 .. PFMSCAN_MAX_M (" + std::to_string(PFMSCAN_MAX_M) + ")");
-    if (n_letters != 4 && n_letters != PFMSCAN_NSTRUCT) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": n_letters must be 4 or 7");
+    if (own) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + own);
     if (n_motifs < 0 || n_rec < 0 || n_pos < 0) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": negative size");
-    if (n_motifs > 0 && !ratio_tables) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": ratio_tables is NULL");
+    if (n_motifs > 0 && missing) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + missing);
     return PFMSCAN_OK;
 }
 
+int occ_check(pfmscan_ctx *ctx, const char *who, const double *ratio_tables, int n_motifs, int m, int n_letters, int64_t n_pos, int64_t n_rec)
+{
+    if (!ctx) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": NULL ctx");
+    return occ_check_base(ctx, who, m, n_letters != 4 && n_letters != PFMSCAN_NSTRUCT ? ": n_letters must be 4 or 7" : nullptr, n_motifs, n_rec, n_pos,
+                          ratio_tables ? nullptr : ": ratio_tables is NULL");
+}
+
+int occ_pair_check(pfmscan_ctx *ctx, const char *who, const double *seq_tables, const double *struct_tables, int n_motifs, int m, int64_t n_pos,
+                   int64_t n_rec)
+{
+    return occ_check_base(ctx, who, m, nullptr, n_motifs, n_rec, n_pos, seq_tables && struct_tables ? nullptr : ": seq_tables or struct_tables is NULL");
+}
+
+// the checks both profile entry points share
+static int occp_check(pfmscan_ctx *ctx, const char *who, const double *struct_tables, int n_motifs, int m, int profile_dtype, int64_t n_pos,
+                      int64_t n_rec)
+{
+    const bool dtype_ok = profile_dtype == PFMSCAN_PROFILE_F32 || profile_dtype == PFMSCAN_PROFILE_F64;
+    return occ_check_base(ctx, who, m, dtype_ok ? nullptr : ": profile_dtype must be PFMSCAN_PROFILE_F32 or F64", n_motifs, n_rec, n_pos,
+                          struct_tables ? nullptr : ": struct_tables is NULL");
+}
+
 // ascending, disjoint, inside [0, n_pos)
-int occ_check_records(pfmscan_ctx *ctx, const char *who, const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec, int64_t n_pos)
+static int occ_check_records(pfmscan_ctx *ctx, const char *who, const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec, int64_t n_pos)
 {
     int64_t end = 0;
     for (int64_t r = 0; r < n_rec; ++r) {
@@ -693,37 +602,56 @@ int occ_check_records(pfmscan_ctx *ctx, const char *who, const int64_t *rec_off,
     return PFMSCAN_OK;
 }
 
-int occ_run_letters(pfmscan_ctx *ctx, const char *who, const double *ratio_tables, int n_motifs, int m, int n_letters, const uint8_t *d_codes,
-                    int64_t n_pos, const int64_t *rec_off, const int64_t *rec_len, const int64_t *d_rec_off, const int64_t *d_rec_len,
-                    int64_t n_rec, double *d_occ, int64_t *d_windows, hipStream_t st)
+int occ_records_home(pfmscan_ctx *ctx, const char *who, const int64_t *d_rec_off, const int64_t *d_rec_len, int64_t n_rec, int64_t n_pos,
+                     std::vector<int64_t> &host, OccRecords &rec)
 {
-    return occ_run(ctx, who, ratio_tables, n_motifs, m, n_letters, d_codes, n_pos, rec_off, rec_len, d_rec_off, d_rec_len, n_rec, d_occ, d_windows, st);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    host.resize(2 * (size_t)n_rec);
+    HIP_TRY(ctx, hipMemcpyAsync(host.data(), d_rec_off, (size_t)n_rec * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(host.data() + n_rec, d_rec_len, (size_t)n_rec * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    rec = OccRecords{host.data(), host.data() + n_rec, d_rec_off, d_rec_len, n_rec, n_pos};
+    return occ_check_records(ctx, who, rec.off, rec.len, n_rec, n_pos);
 }
 
-int occ_run_profile(pfmscan_ctx *ctx, const char *who, const OccProfile &pf, const double *seq_tables, int n_motifs, int m, const uint8_t *d_codes,
-                    int64_t n_pos, const int64_t *rec_off, const int64_t *rec_len, const int64_t *d_rec_off, const int64_t *d_rec_len,
-                    int64_t n_rec, double *d_occ, int64_t *d_windows, hipStream_t st)
+int occ_records_up(pfmscan_ctx *ctx, const char *who, const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec, OccRecords &rec)
 {
-    return occ_run(ctx, who, seq_tables, n_motifs, m, 4, seq_tables ? d_codes : nullptr, n_pos, rec_off, rec_len, d_rec_off, d_rec_len, n_rec, d_occ,
-                   d_windows, st, &pf);
-}
-
-int occ_run_pair(pfmscan_ctx *ctx, const char *who, const double *seq_tables, const double *struct_tables, int n_motifs, int m,
-                 const uint8_t *d_codes, const uint8_t *d_codes2, int64_t n_pos, const int64_t *rec_off, const int64_t *rec_len,
-                 const int64_t *d_rec_off, const int64_t *d_rec_len, int64_t n_rec, double *d_occ, int64_t *d_windows, hipStream_t st)
-{
-    const OccPair pr{struct_tables, d_codes2};
-    return occ_run(ctx, who, seq_tables, n_motifs, m, 4, d_codes, n_pos, rec_off, rec_len, d_rec_off, d_rec_len, n_rec, d_occ, d_windows, st, nullptr, &pr);
-}
-
-int occ_pair_check(pfmscan_ctx *ctx, const char *who, const double *seq_tables, const double *struct_tables, int n_motifs, int m, int64_t n_pos,
-                   int64_t n_rec)
-{
-    if (m < 1 || m > PFMSCAN_MAX_M)
-        return fail(ctx, PFMSCAN_E_BADSHAPE, std::string(who) + ": width " + std::to_string(m) + " outside 1 .. PFMSCAN_MAX_M (" + std::to_string(PFMSCAN_MAX_M) + ")");
-    if (n_motifs < 0 || n_rec < 0 || n_pos < 0) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": negative size");
-    if (n_motifs > 0 && (!seq_tables || !struct_tables)) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": seq_tables or struct_tables is NULL");
+    int rc;
+    if ((rc = occ_check_records(ctx, who, rec_off, rec_len, n_rec, ctx->staged_n))) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if ((rc = ensure(ctx, ctx->occ_rec, (size_t)n_rec * 16))) return rc;
+    int64_t *d_off = (int64_t *)ctx->occ_rec.p, *d_len = d_off + n_rec;
+    if ((rc = upload(ctx, d_off, rec_off, (size_t)n_rec * 8, ctx->stream))) return rc;
+    if ((rc = upload(ctx, d_len, rec_len, (size_t)n_rec * 8, ctx->stream))) return rc;
+    rec = OccRecords{rec_off, rec_len, d_off, d_len, n_rec, ctx->staged_n};
     return PFMSCAN_OK;
+}
+
+int occ_copy_home(pfmscan_ctx *ctx, std::initializer_list<OccHome> arrays)
+{
+    for (const OccHome &h : arrays)
+        if (h.dst) HIP_TRY(ctx, hipMemcpyAsync(h.dst, h.d_src, h.bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return PFMSCAN_OK;
+}
+
+// The three _staged forms after their own tests of what is staged and of the arguments: the records go up, the outputs are
+// carved from ctx->occ_out, run(rec, d_occ, d_windows) launches on ctx->stream, the outputs come home.
+template <typename Run>
+static int occ_staged(pfmscan_ctx *ctx, const char *who, int n_motifs, const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec, double *occ,
+                      int64_t *windows, Run run)
+{
+    if (n_rec == 0 || n_motifs == 0) return PFMSCAN_OK;
+    if (!rec_off || !rec_len || !occ) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": NULL record table or output");
+    int rc;
+    OccRecords rec;
+    if ((rc = occ_records_up(ctx, who, rec_off, rec_len, n_rec, rec))) return rc;
+    const size_t cells = (size_t)n_rec * n_motifs;
+    if ((rc = ensure(ctx, ctx->occ_out, cells * 8 + (size_t)n_rec * 8))) return rc;
+    double *d_occ = (double *)ctx->occ_out.p;
+    int64_t *d_win = windows ? (int64_t *)(d_occ + cells) : nullptr;
+    if ((rc = run(rec, d_occ, d_win))) return rc;
+    return occ_copy_home(ctx, {{occ, d_occ, cells * 8}, {windows, d_win, (size_t)n_rec * 8}});
 }
 
 }  // namespace pfmscan
@@ -741,15 +669,10 @@ int pfmscan_occupancy_dev(pfmscan_ctx *ctx, const double *ratio_tables, int n_mo
     if (n_rec == 0 || n_motifs == 0) return PFMSCAN_OK;
     if (!d_rec_off || !d_rec_len || !d_occ || (n_pos > 0 && !d_codes)) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": NULL record table, codes or output");
     if (misaligned(d_codes)) return fail(ctx, PFMSCAN_E_BADSHAPE, std::string(who) + ": stream base pointers must be 16-byte aligned");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    // the record table decides every address the kernels form: it is read back and checked before anything is launched
-    std::vector<int64_t> rec(2 * (size_t)n_rec);
-    HIP_TRY(ctx, hipMemcpyAsync(rec.data(), d_rec_off, (size_t)n_rec * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(rec.data() + n_rec, d_rec_len, (size_t)n_rec * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (int rc = occ_check_records(ctx, who, rec.data(), rec.data() + n_rec, n_rec, n_pos)) return rc;
-    return occ_run(ctx, who, ratio_tables, n_motifs, m, n_letters, d_codes, n_pos, rec.data(), rec.data() + n_rec, d_rec_off, d_rec_len, n_rec,
-                   d_occ, d_windows, ctx->stream);
+    std::vector<int64_t> host;
+    OccRecords rec;
+    if (int rc = occ_records_home(ctx, who, d_rec_off, d_rec_len, n_rec, n_pos, host, rec)) return rc;
+    return occ_run(ctx, who, ratio_tables, n_motifs, m, n_letters, d_codes, rec, d_occ, d_windows, ctx->stream);
 }
 
 int pfmscan_occupancy_staged(pfmscan_ctx *ctx, int which, const double *ratio_tables, int n_motifs, int m, int n_letters,
@@ -761,50 +684,12 @@ int pfmscan_occupancy_staged(pfmscan_ctx *ctx, int which, const double *ratio_ta
     if (ctx->staged_n < 0) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": no stream staged (call pfmscan_stage first)");
     if (ctx->staged_n > 0 && !(which ? ctx->staged_codes2 : ctx->staged_codes))
         return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + (which ? ": no codes2 are staged (pfmscan_stage_codes2)" : ": no codes are staged"));
-    const int64_t n_pos = ctx->staged_n;
-    if (int rc = occ_check(ctx, who, ratio_tables, n_motifs, m, n_letters, n_pos, n_rec)) return rc;
-    if (n_rec == 0 || n_motifs == 0) return PFMSCAN_OK;
-    if (!rec_off || !rec_len || !occ) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": NULL record table or output");
-    if (int rc = occ_check_records(ctx, who, rec_off, rec_len, n_rec, n_pos)) return rc;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int rc;
-    const size_t cells = (size_t)n_rec * n_motifs;
-    if ((rc = ensure(ctx, ctx->occ_rec, (size_t)n_rec * 16))) return rc;
-    if ((rc = ensure(ctx, ctx->occ_out, cells * 8 + (size_t)n_rec * 8))) return rc;
-    int64_t *d_off = (int64_t *)ctx->occ_rec.p, *d_len = d_off + n_rec;
-    if ((rc = upload(ctx, d_off, rec_off, (size_t)n_rec * 8, ctx->stream))) return rc;
-    if ((rc = upload(ctx, d_len, rec_len, (size_t)n_rec * 8, ctx->stream))) return rc;
-    double *d_occ = (double *)ctx->occ_out.p;
-    int64_t *d_win = windows ? (int64_t *)(d_occ + cells) : nullptr;
+    if (int rc = occ_check(ctx, who, ratio_tables, n_motifs, m, n_letters, ctx->staged_n, n_rec)) return rc;
     const uint8_t *d_codes = (const uint8_t *)(which ? ctx->codes2.p : ctx->codes.p);
-    if ((rc = occ_run(ctx, who, ratio_tables, n_motifs, m, n_letters, d_codes, n_pos, rec_off, rec_len, d_off, d_len, n_rec, d_occ, d_win, ctx->stream)))
-        return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(occ, d_occ, cells * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (windows) HIP_TRY(ctx, hipMemcpyAsync(windows, d_win, (size_t)n_rec * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return PFMSCAN_OK;
+    return occ_staged(ctx, who, n_motifs, rec_off, rec_len, n_rec, occ, windows, [&](const OccRecords &rec, double *d_occ, int64_t *d_win) {
+        return occ_run(ctx, who, ratio_tables, n_motifs, m, n_letters, d_codes, rec, d_occ, d_win, ctx->stream);
+    });
 }
-
-}  // extern "C"
-
-namespace pfmscan {
-
-// the checks both profile entry points share, before the rule "n_rec == 0 or n_motifs == 0: nothing to do"
-static int occp_check(pfmscan_ctx *ctx, const char *who, const double *struct_tables, int n_motifs, int m, int profile_dtype, int64_t n_pos,
-                      int64_t n_rec)
-{
-    if (m < 1 || m > PFMSCAN_MAX_M)
-        return fail(ctx, PFMSCAN_E_BADSHAPE, std::string(who) + ": width " + std::to_string(m) + " outside 1 .. PFMSCAN_MAX_M (" + std::to_string(PFMSCAN_MAX_M) + ")");
-    if (profile_dtype != PFMSCAN_PROFILE_F32 && profile_dtype != PFMSCAN_PROFILE_F64)
-        return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": profile_dtype must be PFMSCAN_PROFILE_F32 or F64");
-    if (n_motifs < 0 || n_rec < 0 || n_pos < 0) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": negative size");
-    if (n_motifs > 0 && !struct_tables) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": struct_tables is NULL");
-    return PFMSCAN_OK;
-}
-
-}  // namespace pfmscan
-
-extern "C" {
 
 int pfmscan_occupancy_profile_dev(pfmscan_ctx *ctx, const double *struct_tables, const double *seq_tables, int n_motifs, int m,
                                   const uint8_t *d_codes, const void *d_profile, int profile_dtype, int64_t n_pos,
@@ -818,16 +703,11 @@ int pfmscan_occupancy_profile_dev(pfmscan_ctx *ctx, const double *struct_tables,
     if (!d_rec_off || !d_rec_len || !d_occ || (n_pos > 0 && !d_profile)) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": NULL record table, profile or output");
     if (misaligned(d_profile) || (seq_tables && misaligned(d_codes)))
         return fail(ctx, PFMSCAN_E_BADSHAPE, std::string(who) + ": stream base pointers must be 16-byte aligned");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    // the record table decides every address the kernels form: it is read back and checked before anything is launched
-    std::vector<int64_t> rec(2 * (size_t)n_rec);
-    HIP_TRY(ctx, hipMemcpyAsync(rec.data(), d_rec_off, (size_t)n_rec * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(rec.data() + n_rec, d_rec_len, (size_t)n_rec * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (int rc = occ_check_records(ctx, who, rec.data(), rec.data() + n_rec, n_rec, n_pos)) return rc;
+    std::vector<int64_t> host;
+    OccRecords rec;
+    if (int rc = occ_records_home(ctx, who, d_rec_off, d_rec_len, n_rec, n_pos, host, rec)) return rc;
     const OccProfile pf{struct_tables, d_profile, profile_dtype};
-    return occ_run(ctx, who, seq_tables, n_motifs, m, 4, seq_tables ? d_codes : nullptr, n_pos, rec.data(), rec.data() + n_rec, d_rec_off,
-                   d_rec_len, n_rec, d_occ, d_windows, ctx->stream, &pf);
+    return occ_run(ctx, who, seq_tables, n_motifs, m, 4, seq_tables ? d_codes : nullptr, rec, d_occ, d_windows, ctx->stream, &pf);
 }
 
 int pfmscan_occupancy_profile_staged(pfmscan_ctx *ctx, const double *struct_tables, const double *seq_tables, int n_motifs, int m,
@@ -838,29 +718,12 @@ int pfmscan_occupancy_profile_staged(pfmscan_ctx *ctx, const double *struct_tabl
     if (ctx->staged_n < 0) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": no stream staged (call pfmscan_stage first)");
     if (!ctx->staged_profile) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": no profile is staged");
     if (seq_tables && !ctx->staged_codes) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": seq_tables (joint mode) needs staged codes");
-    const int64_t n_pos = ctx->staged_n;
-    if (int rc = occp_check(ctx, who, struct_tables, n_motifs, m, ctx->staged_dtype, n_pos, n_rec)) return rc;
-    if (n_rec == 0 || n_motifs == 0) return PFMSCAN_OK;
-    if (!rec_off || !rec_len || !occ) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": NULL record table or output");
-    if (int rc = occ_check_records(ctx, who, rec_off, rec_len, n_rec, n_pos)) return rc;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int rc;
-    const size_t cells = (size_t)n_rec * n_motifs;
-    if ((rc = ensure(ctx, ctx->occ_rec, (size_t)n_rec * 16))) return rc;
-    if ((rc = ensure(ctx, ctx->occ_out, cells * 8 + (size_t)n_rec * 8))) return rc;
-    int64_t *d_off = (int64_t *)ctx->occ_rec.p, *d_len = d_off + n_rec;
-    if ((rc = upload(ctx, d_off, rec_off, (size_t)n_rec * 8, ctx->stream))) return rc;
-    if ((rc = upload(ctx, d_len, rec_len, (size_t)n_rec * 8, ctx->stream))) return rc;
-    double *d_occ = (double *)ctx->occ_out.p;
-    int64_t *d_win = windows ? (int64_t *)(d_occ + cells) : nullptr;
+    if (int rc = occp_check(ctx, who, struct_tables, n_motifs, m, ctx->staged_dtype, ctx->staged_n, n_rec)) return rc;
     const OccProfile pf{struct_tables, ctx->profile.p, ctx->staged_dtype};
-    if ((rc = occ_run(ctx, who, seq_tables, n_motifs, m, 4, seq_tables ? (const uint8_t *)ctx->codes.p : nullptr, n_pos, rec_off, rec_len, d_off,
-                      d_len, n_rec, d_occ, d_win, ctx->stream, &pf)))
-        return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(occ, d_occ, cells * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (windows) HIP_TRY(ctx, hipMemcpyAsync(windows, d_win, (size_t)n_rec * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return PFMSCAN_OK;
+    const uint8_t *d_codes = seq_tables ? (const uint8_t *)ctx->codes.p : nullptr;
+    return occ_staged(ctx, who, n_motifs, rec_off, rec_len, n_rec, occ, windows, [&](const OccRecords &rec, double *d_occ, int64_t *d_win) {
+        return occ_run(ctx, who, seq_tables, n_motifs, m, 4, d_codes, rec, d_occ, d_win, ctx->stream, &pf);
+    });
 }
 
 int pfmscan_occupancy_pair_dev(pfmscan_ctx *ctx, const double *seq_tables, const double *struct_tables, int n_motifs, int m,
@@ -874,15 +737,11 @@ int pfmscan_occupancy_pair_dev(pfmscan_ctx *ctx, const double *seq_tables, const
     if (!d_rec_off || !d_rec_len || !d_occ || (n_pos > 0 && (!d_codes || !d_codes2)))
         return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": NULL record table, codes or output");
     if (misaligned(d_codes) || misaligned(d_codes2)) return fail(ctx, PFMSCAN_E_BADSHAPE, std::string(who) + ": stream base pointers must be 16-byte aligned");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    // the record table decides every address the kernels form: it is read back and checked before anything is launched
-    std::vector<int64_t> rec(2 * (size_t)n_rec);
-    HIP_TRY(ctx, hipMemcpyAsync(rec.data(), d_rec_off, (size_t)n_rec * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(rec.data() + n_rec, d_rec_len, (size_t)n_rec * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (int rc = occ_check_records(ctx, who, rec.data(), rec.data() + n_rec, n_rec, n_pos)) return rc;
-    return occ_run_pair(ctx, who, seq_tables, struct_tables, n_motifs, m, d_codes, d_codes2, n_pos, rec.data(), rec.data() + n_rec, d_rec_off,
-                        d_rec_len, n_rec, d_occ, d_windows, ctx->stream);
+    std::vector<int64_t> host;
+    OccRecords rec;
+    if (int rc = occ_records_home(ctx, who, d_rec_off, d_rec_len, n_rec, n_pos, host, rec)) return rc;
+    const OccPair pr{struct_tables, d_codes2};
+    return occ_run(ctx, who, seq_tables, n_motifs, m, 4, d_codes, rec, d_occ, d_windows, ctx->stream, nullptr, &pr);
 }
 
 int pfmscan_occupancy_pair_staged(pfmscan_ctx *ctx, const double *seq_tables, const double *struct_tables, int n_motifs, int m,
@@ -893,28 +752,11 @@ int pfmscan_occupancy_pair_staged(pfmscan_ctx *ctx, const double *seq_tables, co
     if (ctx->staged_n < 0) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": no stream staged (call pfmscan_stage first)");
     if (ctx->staged_n > 0 && !ctx->staged_codes) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": no codes are staged");
     if (ctx->staged_n > 0 && !ctx->staged_codes2) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": no codes2 are staged (pfmscan_stage_codes2)");
-    const int64_t n_pos = ctx->staged_n;
-    if (int rc = occ_pair_check(ctx, who, seq_tables, struct_tables, n_motifs, m, n_pos, n_rec)) return rc;
-    if (n_rec == 0 || n_motifs == 0) return PFMSCAN_OK;
-    if (!rec_off || !rec_len || !occ) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": NULL record table or output");
-    if (int rc = occ_check_records(ctx, who, rec_off, rec_len, n_rec, n_pos)) return rc;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int rc;
-    const size_t cells = (size_t)n_rec * n_motifs;
-    if ((rc = ensure(ctx, ctx->occ_rec, (size_t)n_rec * 16))) return rc;
-    if ((rc = ensure(ctx, ctx->occ_out, cells * 8 + (size_t)n_rec * 8))) return rc;
-    int64_t *d_off = (int64_t *)ctx->occ_rec.p, *d_len = d_off + n_rec;
-    if ((rc = upload(ctx, d_off, rec_off, (size_t)n_rec * 8, ctx->stream))) return rc;
-    if ((rc = upload(ctx, d_len, rec_len, (size_t)n_rec * 8, ctx->stream))) return rc;
-    double *d_occ = (double *)ctx->occ_out.p;
-    int64_t *d_win = windows ? (int64_t *)(d_occ + cells) : nullptr;
-    if ((rc = occ_run_pair(ctx, who, seq_tables, struct_tables, n_motifs, m, (const uint8_t *)ctx->codes.p, (const uint8_t *)ctx->codes2.p, n_pos,
-                           rec_off, rec_len, d_off, d_len, n_rec, d_occ, d_win, ctx->stream)))
-        return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(occ, d_occ, cells * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (windows) HIP_TRY(ctx, hipMemcpyAsync(windows, d_win, (size_t)n_rec * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return PFMSCAN_OK;
+    if (int rc = occ_pair_check(ctx, who, seq_tables, struct_tables, n_motifs, m, ctx->staged_n, n_rec)) return rc;
+    const OccPair pr{struct_tables, (const uint8_t *)ctx->codes2.p};
+    return occ_staged(ctx, who, n_motifs, rec_off, rec_len, n_rec, occ, windows, [&](const OccRecords &rec, double *d_occ, int64_t *d_win) {
+        return occ_run(ctx, who, seq_tables, n_motifs, m, 4, (const uint8_t *)ctx->codes.p, rec, d_occ, d_win, ctx->stream, nullptr, &pr);
+    });
 }
 
 }  // extern "C"

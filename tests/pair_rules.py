@@ -101,7 +101,7 @@ def ones(m):
 
 
 def lds_chunk(m, n_q=1 << 20):
-    """pairs per LDS chunk of k_occ_pair_blocks (the chunk rule stated above it in csrc/pfmscan_occupancy.hip): the most
+    """pairs per LDS chunk of k_occ_blocks<QN, true> (the chunk rule stated above it in csrc/pfmscan_occupancy.hip): the most
     c <= n_q with m * 11 * ls(c) <= LDS_DOUBLES, at least 1"""
     def ls(nq):
         qn = 8 if nq >= 8 else 4 if nq >= 4 else 2 if nq >= 2 else 1

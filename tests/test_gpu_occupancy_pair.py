@@ -1,4 +1,4 @@
-"""The occupancy of two code streams (k_occ_pair_blocks, csrc/pfmscan_occupancy.hip) on the GPU against the rules
+"""The occupancy of two code streams (k_occ_blocks<QN, true>, csrc/pfmscan_occupancy.hip) on the GPU against the rules
 (tests/pair_rules.py): every comparison is on the float64 bit patterns (NaN == NaN) plus equal Windows -- there is no
 tolerance in the contract."""
 import numpy as np

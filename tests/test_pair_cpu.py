@@ -169,7 +169,7 @@ def test_abi_25_exports_the_pair_entry_points():
         assert callable(getattr(_lib.Context, name))
     assert callable(scanner.HipEngine.occupancy_pair) and callable(scanner.HipEngine.expect_pair)
     src = open(os.path.join(REPO, "rnascan_amd", "csrc", "pfmscan_occupancy.hip")).read()
-    assert int(re.search(r"OCC_LDS_DOUBLES\s*=\s*(\d+)", src).group(1)) == rules.LDS_DOUBLES and "k_occ_pair_blocks" in src
+    assert int(re.search(r"OCC_LDS_DOUBLES\s*=\s*(\d+)", src).group(1)) == rules.LDS_DOUBLES and "OCC_PAIR_LETTERS" in src
 
 
 # ---- the commands with the rules in the device's place -----------------------------------------------------------------

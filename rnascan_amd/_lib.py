@@ -1696,15 +1696,24 @@ class Context(object):
         self._check(self._L.pfmscan_occupancy_dev(self._h, _ptr(rt), rt.shape[0], rt.shape[1], int(n_letters), _ptr(d_codes), int(n_pos),
                                                   _ptr(d_rec_off), _ptr(d_rec_len), int(n_rec), _ptr(d_occ), _ptr(d_windows)))
 
-    def occupancy_staged(self, ratio_tables, n_letters, rec_off, rec_len, which=0):
-        """-> occ float64 [n_rec][n_motifs], windows int64 [n_rec] over the staged codes (which = 0) or codes2 (1)"""
-        rt = self._ratio_tables(ratio_tables)
+    # -- what every *_staged call of the occupancy / expected-counts family starts with -------------------
+    @staticmethod
+    def _records(rec_off, rec_len):
         rec_off = np.ascontiguousarray(rec_off, dtype=np.int64)
         rec_len = np.ascontiguousarray(rec_len, dtype=np.int64)
         if rec_off.ndim != 1 or rec_off.shape != rec_len.shape:
             raise ValueError("rec_off and rec_len must be lists of one length")
-        occ = np.zeros((rec_off.size, rt.shape[0]), dtype=np.float64)
-        windows = np.zeros(rec_off.size, dtype=np.int64)
+        return rec_off, rec_len
+
+    @staticmethod
+    def _occ_windows(n_rec, n_motifs):
+        return np.zeros((n_rec, n_motifs), dtype=np.float64), np.zeros(n_rec, dtype=np.int64)
+
+    def occupancy_staged(self, ratio_tables, n_letters, rec_off, rec_len, which=0):
+        """-> occ float64 [n_rec][n_motifs], windows int64 [n_rec] over the staged codes (which = 0) or codes2 (1)"""
+        rt = self._ratio_tables(ratio_tables)
+        rec_off, rec_len = self._records(rec_off, rec_len)
+        occ, windows = self._occ_windows(rec_off.size, rt.shape[0])
         self._check(self._L.pfmscan_occupancy_staged(self._h, int(which), _ptr(rt), rt.shape[0], rt.shape[1], int(n_letters), _ptr(rec_off),
                                                      _ptr(rec_len), rec_off.size, _ptr(occ), _ptr(windows)))
         return occ, windows
@@ -1735,12 +1744,8 @@ class Context(object):
         """-> occ float64 [n_rec][n_motifs], windows int64 [n_rec] over the staged profile (structure only) or the staged
         codes and profile (joint: seq_tables [n_motifs][m][8])"""
         st, sq = self._profile_tables(struct_tables, seq_tables)
-        rec_off = np.ascontiguousarray(rec_off, dtype=np.int64)
-        rec_len = np.ascontiguousarray(rec_len, dtype=np.int64)
-        if rec_off.ndim != 1 or rec_off.shape != rec_len.shape:
-            raise ValueError("rec_off and rec_len must be lists of one length")
-        occ = np.zeros((rec_off.size, st.shape[0]), dtype=np.float64)
-        windows = np.zeros(rec_off.size, dtype=np.int64)
+        rec_off, rec_len = self._records(rec_off, rec_len)
+        occ, windows = self._occ_windows(rec_off.size, st.shape[0])
         self._check(self._L.pfmscan_occupancy_profile_staged(self._h, _ptr(st), _ptr(sq), st.shape[0], st.shape[1], _ptr(rec_off),
                                                              _ptr(rec_len), rec_off.size, _ptr(occ), _ptr(windows)))
         return occ, windows
@@ -1755,13 +1760,9 @@ class Context(object):
         """-> exp float64 [n_rec][n_motifs][m][8], occ float64 [n_rec][n_motifs], windows int64 [n_rec] over the staged codes
         (which = 0) or codes2 (1); mode EXPECT_RATIO or EXPECT_POSTERIOR"""
         rt = self._ratio_tables(ratio_tables)
-        rec_off = np.ascontiguousarray(rec_off, dtype=np.int64)
-        rec_len = np.ascontiguousarray(rec_len, dtype=np.int64)
-        if rec_off.ndim != 1 or rec_off.shape != rec_len.shape:
-            raise ValueError("rec_off and rec_len must be lists of one length")
+        rec_off, rec_len = self._records(rec_off, rec_len)
         exp = np.zeros((rec_off.size, rt.shape[0], rt.shape[1], NCODE), dtype=np.float64)
-        occ = np.zeros((rec_off.size, rt.shape[0]), dtype=np.float64)
-        windows = np.zeros(rec_off.size, dtype=np.int64)
+        occ, windows = self._occ_windows(rec_off.size, rt.shape[0])
         self._check(self._L.pfmscan_expect_staged(self._h, int(which), _ptr(rt), rt.shape[0], rt.shape[1], int(n_letters), int(mode),
                                                   _ptr(rec_off), _ptr(rec_len), rec_off.size, _ptr(exp), _ptr(occ), _ptr(windows)))
         return exp, occ, windows
@@ -1789,14 +1790,10 @@ class Context(object):
         come from struct_tables [n_motifs][m][7], seq_tables [n_motifs][m][8] or both; mode EXPECT_RATIO or EXPECT_POSTERIOR"""
         st, sq = self._expect_profile_tables(struct_tables, seq_tables)
         n_motifs, m = (st if st is not None else sq).shape[:2]
-        rec_off = np.ascontiguousarray(rec_off, dtype=np.int64)
-        rec_len = np.ascontiguousarray(rec_len, dtype=np.int64)
-        if rec_off.ndim != 1 or rec_off.shape != rec_len.shape:
-            raise ValueError("rec_off and rec_len must be lists of one length")
+        rec_off, rec_len = self._records(rec_off, rec_len)
         exp_struct = np.zeros((rec_off.size, n_motifs, m, NCODE), dtype=np.float64)
         exp_seq = None if sq is None else np.zeros((rec_off.size, n_motifs, m, NCODE), dtype=np.float64)
-        occ = np.zeros((rec_off.size, n_motifs), dtype=np.float64)
-        windows = np.zeros(rec_off.size, dtype=np.int64)
+        occ, windows = self._occ_windows(rec_off.size, n_motifs)
         self._check(self._L.pfmscan_expect_profile_staged(self._h, _ptr(st), _ptr(sq), n_motifs, m, int(mode), _ptr(rec_off), _ptr(rec_len),
                                                           rec_off.size, _ptr(exp_struct), _ptr(exp_seq), _ptr(occ), _ptr(windows)))
         return exp_struct, exp_seq, occ, windows
@@ -1818,12 +1815,8 @@ class Context(object):
         """-> occ float64 [n_rec][n_motifs], windows int64 [n_rec] over the staged codes and codes2; pair q is
         (seq_tables[q], struct_tables[q]), [m][8] both"""
         sq, st = self._pair_tables(seq_tables, struct_tables)
-        rec_off = np.ascontiguousarray(rec_off, dtype=np.int64)
-        rec_len = np.ascontiguousarray(rec_len, dtype=np.int64)
-        if rec_off.ndim != 1 or rec_off.shape != rec_len.shape:
-            raise ValueError("rec_off and rec_len must be lists of one length")
-        occ = np.zeros((rec_off.size, sq.shape[0]), dtype=np.float64)
-        windows = np.zeros(rec_off.size, dtype=np.int64)
+        rec_off, rec_len = self._records(rec_off, rec_len)
+        occ, windows = self._occ_windows(rec_off.size, sq.shape[0])
         self._check(self._L.pfmscan_occupancy_pair_staged(self._h, _ptr(sq), _ptr(st), sq.shape[0], sq.shape[1], _ptr(rec_off), _ptr(rec_len),
                                                           rec_off.size, _ptr(occ), _ptr(windows)))
         return occ, windows
@@ -1840,14 +1833,10 @@ class Context(object):
         int64 [n_rec] over the staged codes and codes2; mode EXPECT_RATIO or EXPECT_POSTERIOR"""
         sq, st = self._pair_tables(seq_tables, struct_tables)
         n_motifs, m = sq.shape[:2]
-        rec_off = np.ascontiguousarray(rec_off, dtype=np.int64)
-        rec_len = np.ascontiguousarray(rec_len, dtype=np.int64)
-        if rec_off.ndim != 1 or rec_off.shape != rec_len.shape:
-            raise ValueError("rec_off and rec_len must be lists of one length")
+        rec_off, rec_len = self._records(rec_off, rec_len)
         exp_seq = np.zeros((rec_off.size, n_motifs, m, NCODE), dtype=np.float64) if want_seq else None
         exp_struct = np.zeros((rec_off.size, n_motifs, m, NCODE), dtype=np.float64) if want_struct else None
-        occ = np.zeros((rec_off.size, n_motifs), dtype=np.float64)
-        windows = np.zeros(rec_off.size, dtype=np.int64)
+        occ, windows = self._occ_windows(rec_off.size, n_motifs)
         self._check(self._L.pfmscan_expect_pair_staged(self._h, _ptr(sq), _ptr(st), n_motifs, m, int(mode), _ptr(rec_off), _ptr(rec_len),
                                                        rec_off.size, _ptr(exp_seq), _ptr(exp_struct), _ptr(occ), _ptr(windows)))
         return exp_seq, exp_struct, occ, windows
@@ -1866,24 +1855,15 @@ class Context(object):
             raise ValueError("%s must be a writable C-contiguous uint64 [%d][%d][%d]" % (name, n_motifs, SITE_LIMBS, m * NCODE))
         return acc
 
-    @staticmethod
-    def _merge_records(rec_off, rec_len):
-        rec_off = np.ascontiguousarray(rec_off, dtype=np.int64)
-        rec_len = np.ascontiguousarray(rec_len, dtype=np.int64)
-        if rec_off.ndim != 1 or rec_off.shape != rec_len.shape:
-            raise ValueError("rec_off and rec_len must be lists of one length")
-        return rec_off, rec_len
-
     def expect_merged_staged(self, ratio_tables, n_letters, mode, rec_off, rec_len, acc, which=0):
         """``expect_staged`` with the matrices added up over the records on the device: acc uint64 [n_motifs][SITE_LIMBS][m * 8]
         (normalised, changed in place: this call's sums are added) -> bad int64 [n_motifs][2] of this call (first record with a
         non-finite cell, first with a negative one; -1: none), occ float64 [n_rec][n_motifs], windows int64 [n_rec]"""
         rt = self._ratio_tables(ratio_tables)
-        rec_off, rec_len = self._merge_records(rec_off, rec_len)
+        rec_off, rec_len = self._records(rec_off, rec_len)
         self._merge_acc(acc, rt.shape[0], rt.shape[1], "acc")
         bad = np.full((rt.shape[0], 2), -1, dtype=np.int64)
-        occ = np.zeros((rec_off.size, rt.shape[0]), dtype=np.float64)
-        windows = np.zeros(rec_off.size, dtype=np.int64)
+        occ, windows = self._occ_windows(rec_off.size, rt.shape[0])
         self._check(self._L.pfmscan_expect_merged_staged(self._h, int(which), _ptr(rt), rt.shape[0], rt.shape[1], int(n_letters), int(mode),
                                                          _ptr(rec_off), _ptr(rec_len), rec_off.size, _ptr(acc), _ptr(bad), _ptr(occ), _ptr(windows)))
         return bad, occ, windows
@@ -1894,14 +1874,13 @@ class Context(object):
         bad_struct int64 [n_motifs][2], bad_seq the same | None, occ float64 [n_rec][n_motifs], windows int64 [n_rec]"""
         st, sq = self._expect_profile_tables(struct_tables, seq_tables)
         n_motifs, m = (st if st is not None else sq).shape[:2]
-        rec_off, rec_len = self._merge_records(rec_off, rec_len)
+        rec_off, rec_len = self._records(rec_off, rec_len)
         self._merge_acc(acc_struct, n_motifs, m, "acc_struct")
         if acc_seq is not None:
             self._merge_acc(acc_seq, n_motifs, m, "acc_seq")
         bad_struct = np.full((n_motifs, 2), -1, dtype=np.int64)
         bad_seq = None if acc_seq is None else np.full((n_motifs, 2), -1, dtype=np.int64)
-        occ = np.zeros((rec_off.size, n_motifs), dtype=np.float64)
-        windows = np.zeros(rec_off.size, dtype=np.int64)
+        occ, windows = self._occ_windows(rec_off.size, n_motifs)
         self._check(self._L.pfmscan_expect_profile_merged_staged(self._h, _ptr(st), _ptr(sq), n_motifs, m, int(mode), _ptr(rec_off), _ptr(rec_len),
                                                                  rec_off.size, _ptr(acc_struct), _ptr(acc_seq), _ptr(bad_struct), _ptr(bad_seq),
                                                                  _ptr(occ), _ptr(windows)))
@@ -1913,14 +1892,13 @@ class Context(object):
         bad_seq, bad_struct int64 [n_motifs][2] (None where no accumulator), occ float64 [n_rec][n_motifs], windows int64 [n_rec]"""
         sq, st = self._pair_tables(seq_tables, struct_tables)
         n_motifs, m = sq.shape[:2]
-        rec_off, rec_len = self._merge_records(rec_off, rec_len)
+        rec_off, rec_len = self._records(rec_off, rec_len)
         for acc, name in ((acc_seq, "acc_seq"), (acc_struct, "acc_struct")):
             if acc is not None:
                 self._merge_acc(acc, n_motifs, m, name)
         bad_seq = None if acc_seq is None else np.full((n_motifs, 2), -1, dtype=np.int64)
         bad_struct = None if acc_struct is None else np.full((n_motifs, 2), -1, dtype=np.int64)
-        occ = np.zeros((rec_off.size, n_motifs), dtype=np.float64)
-        windows = np.zeros(rec_off.size, dtype=np.int64)
+        occ, windows = self._occ_windows(rec_off.size, n_motifs)
         self._check(self._L.pfmscan_expect_pair_merged_staged(self._h, _ptr(sq), _ptr(st), n_motifs, m, int(mode), _ptr(rec_off), _ptr(rec_len),
                                                               rec_off.size, _ptr(acc_seq), _ptr(acc_struct), _ptr(bad_seq), _ptr(bad_struct), _ptr(occ),
                                                               _ptr(windows)))

@@ -34,19 +34,26 @@ import io
 import math
 import os
 import sys
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
 
 import numpy as np
 
-from . import fasta, pack
+from . import fasta, occupancy
 
 COLUMNS = ["Motif_ID", "Iteration", "Records", "Records.Skipped", "Windows", "Log2.Likelihood"]
-BATCH_RECORDS = 4096                                 # records per packed batch (and per device call); the output does not depend on it
+BATCH_RECORDS = occupancy.BATCH_RECORDS              # records per packed batch (and per device call); the output does not depend on it
 MODES = {"ratio": 0, "posterior": 1}                 # _lib.EXPECT_RATIO, _lib.EXPECT_POSTERIOR
+MERGES = ("auto", "device", "host")                  # --merge: where the records are added up (DESIGN.md 5k)
+NOT_FINITE = ("Motif %s, record %s: the occupancy or an expected count is infinite or not a number "
+              "(a ratio of the motif is; check the background and the pseudocount)")
 
 
 class ExpectError(ValueError):
     """what the pass found: said on stderr, exit 1, nothing written"""
+
+
+class NegativeCell(ExpectError):
+    """the device route met a cell < 0, which the long accumulator cannot hold"""
 
 
 def fsum_records(parts):
@@ -59,19 +66,22 @@ def fsum_records(parts):
     return out
 
 
-MERGES = ("auto", "device", "host")                  # --merge: where the records are added up (DESIGN.md 5k)
-NOT_FINITE = ("Motif %s, record %s: the occupancy or an expected count is infinite or not a number "
-              "(a ratio of the motif is; check the background and the pseudocount)")
+def new_acc(n_motifs, m):
+    from ._lib import NCODE, SITE_LIMBS
+    return np.zeros((n_motifs, SITE_LIMBS, m * NCODE), dtype=np.uint64)
 
 
-class NegativeCell(ExpectError):
-    """the device route met a cell < 0, which the long accumulator cannot hold"""
-
-
-def add_merge_option(parser):
-    parser.add_argument("--merge", choices=MERGES, default="auto",
-                        help="where the records are added up: exactly on the device (long accumulators), or on the host with "
-                             "math.fsum; the files do not depend on it [%(default)s: device where the engine offers it]")
+# ---- one pass over the records, whatever the input form -----------------------------------------------------------------
+# An input form (``expect``: one FASTA of letters; ``expect_profile``; ``expect_pair``) describes itself to the pass:
+#   motif_ids, groups   the names, and {width: motif indices}
+#   order               the motif indices in the order they are finalised (the first that fails is the one named)
+#   batches()           a batch source: (ids, stream, cols) per batch (occupancy.letter_batches and its siblings)
+#   tables(m, ks, cols) what the engine takes for the motifs ks of width m; made once per width where cols is None
+#   host(stream, tables, mode) -> (matrices, occ, windows); merged(stream, tables, mode, accs) -> (bads, occ, windows):
+#                       the engine's two methods, their lists in the form's check order; ``method``: the second one's name
+#   matrices            per matrix (cells kept, None | cols -> the stored column of every written cell)
+#   not_finite          the form's message for a non-finite record
+Form = namedtuple("Form", "motif_ids groups order batches tables host merged method matrices not_finite")
 
 
 def merge_route(engine, merge, method):
@@ -96,119 +106,128 @@ def with_merge(merge, route, device_pass, host_pass):
         return host_pass()
 
 
-def new_acc(n_motifs, m):
-    from ._lib import NCODE, SITE_LIMBS
-    return np.zeros((n_motifs, SITE_LIMBS, m * NCODE), dtype=np.uint64)
+class _Accumulator(object):
+    """the long accumulators of one matrix and one width on the device route.  The device adds in the batch's stored column
+    order.  Where that order can change, the batches of one order share an accumulator, which is folded into the total -- its
+    columns mapped to the written cells -- when the order changes and at the end; a matrix whose order never changes
+    (``order`` None) is its own total"""
+
+    def __init__(self, n_motifs, m):
+        self.n_motifs, self.m = n_motifs, m
+        self.total, self.order, self.acc = None, None, new_acc(n_motifs, m)
+
+    def current(self, order):
+        if order != self.order:
+            self.fold()
+            self.order, self.acc = order, new_acc(self.n_motifs, self.m)
+        return self.acc
+
+    def fold(self):
+        from . import _lib
+        if self.order is None:
+            return self.acc
+        if self.total is None:
+            self.total = new_acc(self.n_motifs, self.m)
+        cells = self.acc.reshape(self.n_motifs, _lib.SITE_LIMBS, self.m, _lib.NCODE)
+        _lib.site_acc_add(self.total, np.ascontiguousarray(cells[:, :, :, self.order + [7]]).reshape(self.total.shape))
+        return self.total
 
 
-def note_bad(first, bad, base):
+def _note_bad(first, bad, base):
     """first int64 [n_motifs][2] (indices into the pass, -1: none) takes a batch's verdicts, whose records start at base"""
     new = (first < 0) & (bad >= 0)
     first[new] = bad[new] + base
 
 
-def merged_result(mid, occ, firsts, sums, ids, windows, not_finite=NOT_FINITE):
-    """what the host route makes of a motif's per-record matrices, from what the device route brings home: the checks in the
-    host route's order and with its messages.  ``firsts``: per written matrix, in the host route's order, int64 [2] = the
-    pass's first record with a non-finite cell and with a negative one; ``sums``: the rounded accumulators"""
+def _first_nonfinite(cells):
+    """the host route's verdict on one matrix of one motif, as the device gives it: (first record of the pass with a
+    non-finite cell, first with a negative one -- which the host route does not look for)"""
+    bad = np.flatnonzero(~np.isfinite(np.concatenate(cells, axis=0)).all(axis=(1, 2))) if cells else ()
+    return (int(bad[0]) if len(bad) else -1, -1)
+
+
+def _finalise(mid, not_finite, ids, occs, firsts, sums, windows):
+    """a motif's result from what either route brings: its occupancy per batch, per matrix (in the form's check order) the
+    first record with a non-finite and with a negative cell, and ``sums()``, the matrices added up over the records ->
+    (matrices, records, skipped, windows, log2 likelihood)"""
+    occ = np.concatenate(occs) if occs else np.zeros(0)
     bad = np.flatnonzero(~np.isfinite(occ))
-    who = int(bad[0]) if bad.size else next((int(f[0]) for f in firsts if f[0] >= 0), -1)
+    who = int(bad[0]) if bad.size else next((f[0] for f in firsts if f[0] >= 0), -1)
     if who >= 0:
         raise ExpectError(not_finite % (mid, ids[who]))
-    neg = next((int(f[1]) for f in firsts if f[1] >= 0), -1)
+    neg = next((f[1] for f in firsts if f[1] >= 0), -1)
     if neg >= 0:
         raise NegativeCell("Motif %s, record %s: an expected count is negative (a cell of the profile is), which the device's "
                            "accumulators cannot hold" % (mid, ids[neg]))
     counted = occ > 0
     if not counted.any():
         raise ExpectError("Motif %s: no record contributes (every occupancy is 0)" % mid)
+    sums = sums()
     if not all(np.isfinite(s).all() for s in sums):
         raise ExpectError("Motif %s: the sum of an expected count over the records is beyond the largest double" % mid)
     ll = math.fsum(math.log2(x) for x in occ[counted].tolist())
-    return tuple(sums) + (int(counted.sum()), int((~counted).sum()), int(windows), round(ll, 3))
+    return sums, int(counted.sum()), int((~counted).sum()), int(windows), round(ll, 3)
 
 
-def run_merged(engine, recs, tables, motif_ids, letters, code_letters, mode, batch_records=BATCH_RECORDS):
-    """``run`` with the records added up on the device: per width one long accumulator per motif, batch after batch added into
-    it (engine.expect_merged); only the occupancy and the window counts come home per record"""
-    from . import _lib, scanner
-    n_letters = len(code_letters)
-    groups = OrderedDict()
-    for mid in motif_ids:
-        groups.setdefault(tables[mid].shape[0], []).append(mid)
+def _one_pass(form, mode, device):
+    """batches outside, widths inside.  ``device``: the records are added up in long accumulators on the device and only the
+    occupancy and the window counts come home per record; else every per-record matrix comes home and math.fsum adds them"""
+    from . import _lib
+    n_motifs, sides = len(form.motif_ids), range(len(form.matrices))
+    occs = [[] for _ in range(n_motifs)]
+    wins = dict((m, 0) for m in form.groups)                       # Windows depends on the width
+    if device:
+        accs = dict((m, [_Accumulator(len(ks), m) for _ in sides]) for m, ks in form.groups.items())
+        first = dict((m, [np.full((len(ks), 2), -1, dtype=np.int64) for _ in sides]) for m, ks in form.groups.items())
+    else:
+        cells = [[[] for _ in sides] for _ in range(n_motifs)]
+    made, seen = {}, []
+    for ids, stream, cols in form.batches():
+        orders = [None if stored is None else stored(cols) for _, stored in form.matrices]
+        for m, ks in form.groups.items():
+            tables = made[m] if cols is None and m in made else form.tables(m, ks, cols)
+            if cols is None:
+                made[m] = tables
+            if device:
+                bads, o, w = form.merged(stream, tables, mode, [a.current(order) for a, order in zip(accs[m], orders)])
+                for f, bad in zip(first[m], bads):
+                    _note_bad(f, np.asarray(bad), len(seen))
+            else:
+                exps, o, w = form.host(stream, tables, mode)
+                for i, (kept, _) in enumerate(form.matrices):
+                    E = np.asarray(exps[i])[:, :, :, :kept] if orders[i] is None else np.asarray(exps[i])[:, :, :, orders[i]]
+                    for j, k in enumerate(ks):
+                        cells[k][i].append(E[:, j])
+            o = np.asarray(o)
+            for j, k in enumerate(ks):
+                occs[k].append(o[:, j])
+            wins[m] += int(np.asarray(w).sum())
+        seen += ids
+    if device:
+        rounded = dict((m, [_lib.site_acc_round(a.fold()).reshape(len(ks), m, -1)[:, :, :kept] for a, (kept, _) in zip(accs[m], form.matrices)])
+                       for m, ks in form.groups.items())
+    place = dict((k, (m, j)) for m, ks in form.groups.items() for j, k in enumerate(ks))
     out = {}
-    for m, mids in groups.items():
-        stack = np.stack([tables[mid] for mid in mids])
-        acc = new_acc(len(mids), m)
-        first = np.full((len(mids), 2), -1, dtype=np.int64)
-        occs, wins, ids = [], [], []
-        for a in range(0, len(recs), batch_records):
-            b = min(len(recs), a + batch_records)
-            batch = scanner._RnaBatch(recs[a:b], None if letters == fasta.RNA else letters)
-            if len(batch) == 0:
-                continue
-            stream = pack.Stream(batch.codes, None, batch.offsets, batch.lengths)
-            bad, o, w = engine.expect_merged(stream, stack, n_letters, mode, acc)
-            note_bad(first, np.asarray(bad), len(ids))
-            occs.append(np.asarray(o))
-            wins.append(np.asarray(w))
-            ids += list(batch.ids)
-        E = _lib.site_acc_round(acc).reshape(len(mids), m, -1)[:, :, :n_letters]
-        for k, mid in enumerate(mids):
-            if not occs:
-                raise ExpectError("Motif %s: no record contributes (every occupancy is 0)" % mid)
-            out[mid] = merged_result(mid, np.concatenate([o[:, k] for o in occs]), [first[k]], [np.ascontiguousarray(E[k])], ids,
-                                     np.concatenate(wins).sum())
+    for k in form.order:
+        m, j = place[k]
+        if device:
+            firsts, sums = [f[j] for f in first[m]], lambda: [np.ascontiguousarray(E[j]) for E in rounded[m]]
+        else:
+            firsts, sums = [_first_nonfinite(c) for c in cells[k]], lambda: [fsum_records(c) for c in cells[k]]
+        out[form.motif_ids[k]] = _finalise(form.motif_ids[k], form.not_finite, seen, occs[k], firsts, sums, wins[m])
     return out
 
 
-def run(engine, recs, tables, motif_ids, letters, code_letters, mode, batch_records=BATCH_RECORDS, merge="host"):
-    """one pass over the records -> {motif id: (E float64 [m][n_letters] in code order, records, skipped, windows, log2
-    likelihood)}; tables {motif id: [m][8]}.  One motif group (width) at a time, batch by batch of records.  ``merge``: where
-    the records are added up (MERGES); the result does not depend on it."""
-    args = (engine, recs, tables, motif_ids, letters, code_letters, mode, batch_records)
-    return with_merge(merge, merge_route(engine, merge, "expect_merged"), lambda: run_merged(*args), lambda: run_host(*args))
+def run(engine, form, mode, merge="host"):
+    """one pass over the records -> {motif id: (the expected matrices float64 [m][cells kept], in the form's order; records;
+    skipped; windows; log2 likelihood)}.  ``merge``: where the records are added up (MERGES); the result does not depend on it"""
+    return with_merge(merge, merge_route(engine, merge, form.method), lambda: _one_pass(form, mode, True), lambda: _one_pass(form, mode, False))
 
 
-def run_host(engine, recs, tables, motif_ids, letters, code_letters, mode, batch_records=BATCH_RECORDS):
-    """``run`` with every per-record matrix brought home and added up with math.fsum"""
-    from . import scanner
-    n_letters = len(code_letters)
-    groups = OrderedDict()
-    for mid in motif_ids:
-        groups.setdefault(tables[mid].shape[0], []).append(mid)
-    out = {}
-    for m, mids in groups.items():
-        stack = np.stack([tables[mid] for mid in mids])
-        exps, occs, wins, ids = [], [], [], []
-        for a in range(0, len(recs), batch_records):
-            b = min(len(recs), a + batch_records)
-            batch = scanner._RnaBatch(recs[a:b], None if letters == fasta.RNA else letters)
-            if len(batch) == 0:
-                continue
-            stream = pack.Stream(batch.codes, None, batch.offsets, batch.lengths)
-            e, o, w = engine.expect(stream, stack, n_letters, mode)
-            exps.append(np.asarray(e)[:, :, :, :n_letters])
-            occs.append(np.asarray(o))
-            wins.append(np.asarray(w))
-            ids += list(batch.ids)
-        for k, mid in enumerate(mids):
-            if not exps:
-                raise ExpectError("Motif %s: no record contributes (every occupancy is 0)" % mid)
-            occ = np.concatenate([o[:, k] for o in occs])
-            cells = [e[:, k] for e in exps]
-            bad = np.flatnonzero(~np.isfinite(occ))
-            if bad.size == 0:
-                bad = np.flatnonzero(~np.isfinite(np.concatenate(cells, axis=0)).all(axis=(1, 2)))
-            if bad.size:
-                raise ExpectError("Motif %s, record %s: the occupancy or an expected count is infinite or not a number "
-                                  "(a ratio of the motif is; check the background and the pseudocount)" % (mid, ids[int(bad[0])]))
-            counted = occ > 0
-            if not counted.any():
-                raise ExpectError("Motif %s: no record contributes (every occupancy is 0)" % mid)
-            ll = math.fsum(math.log2(x) for x in occ[counted].tolist())
-            out[mid] = (fsum_records(cells), int(counted.sum()), int((~counted).sum()), int(np.concatenate(wins).sum()), round(ll, 3))
-    return out
+# ---- the iterations and the files of the three commands --------------------------------------------------------------------
+# a written matrix: its file's suffix, its slot in a pair (0: sequence, 1: structure), the letters of its cells in the order
+# the pass returns them, and the background its PFM is normalised against
+Side = namedtuple("Side", "suffix slot code_letters background")
 
 
 def next_odds(E, letters, code_letters, pseudocount, background):
@@ -231,40 +250,64 @@ def pfm_text(results, motif_ids, order, code_letters, library):
     return text.getvalue()
 
 
+def iterate(args, engine, sides, odds, pairs, form_of, what="motifs"):
+    """``--iterations`` passes and the files.  ``sides``: the written matrices in the pass's order, which is the files';
+    ``odds``: [sequence odds | None, structure odds | None], None where no PFM was given; ``pairs``: [(sequence id | None,
+    structure id | None)] into them; ``form_of(odds, pairs)``: the pass's Form.  After a pass every given PFM is replaced by
+    its expected matrix -- what reading this iteration's files would give: every motif (pair) under its written name"""
+    from . import sites
+    motif_ids = [sites.pair_id(a, b) for a, b in pairs]
+    written = ((fasta.RNA, sites.SEQ_ORDER), (fasta.STRUCT, sites.STRUCT_ORDER))
+    summary = ["\t".join(COLUMNS) + "\n"]
+    for it in range(1, args.iterations + 1):
+        got = run(engine, form_of(odds, pairs), MODES[args.weight], args.merge)
+        for mid in motif_ids:
+            _, n, skipped, windows, ll = got[mid]
+            summary.append("%s\t%d\t%d\t%d\t%d\t%s\n" % (mid, it, n, skipped, windows, repr(ll)))
+        if it < args.iterations:
+            odds = list(odds)
+            for i, side in enumerate(sides):
+                if odds[side.slot] is not None:
+                    odds[side.slot] = OrderedDict((mid, next_odds(got[mid][0][i], written[side.slot][0], side.code_letters, args.pseudocount,
+                                                                  side.background)) for mid in motif_ids)
+            pairs = [tuple(None if o is None else mid for o in odds) for mid in motif_ids]
+    texts = [(side.suffix, pfm_text(dict((mid, got[mid][0][i]) for mid in motif_ids), motif_ids, written[side.slot][1], side.code_letters,
+                                    args.all_motifs)) for i, side in enumerate(sides)]
+    for suffix, text in texts + [(".summary.txt", "".join(summary))]:
+        with open(args.prefix + suffix, "w") as out:
+            out.write(text)
+    fasta.eprint("Wrote the expected counts of %d %s after %d iterations" % (len(motif_ids), what, args.iterations))
+
+
+# ---- the options that only the three expect commands have ({words}: occupancy.add_options) ------------------------------------
+OPTIONS = dict(occupancy.OPTIONS)
+OPTIONS.update({
+    "-o": lambda p, w: p.add_argument("-o", "--prefix", dest="prefix", type=str, required=True, help="PREFIX of %s" % w["files"]),
+    "--weight": lambda p, w: p.add_argument("--weight", choices=sorted(MODES), default="posterior",
+                                            help="weight of a window: its %slikelihood ratio, or that over the record's %soccupancy [%%(default)s]" %
+                                                 (w["joint"], w["joint"])),
+    "--iterations": lambda p, w: p.add_argument("--iterations", type=int, default=1, help="%s [%%(default)s]" % w["steps"]),
+    "--merge": lambda p, w: p.add_argument("--merge", choices=MERGES, default="auto",
+                                           help="where the records are added up: exactly on the device (long accumulators), or on the host with "
+                                                "math.fsum; the files do not depend on it [%(default)s: device where the engine offers it]"),
+})
+
+
 def getoptions(argv=None):
     parser = argparse.ArgumentParser(prog="python -m rnascan_amd.expect",
                                      description=("Expected site counts: the letters under every window weighted by the window's "
                                                   "likelihood ratio, one EM step of motif refinement per iteration."))
     parser.add_argument("fasta", metavar="in.fa", help="the sequence FASTA (-p) or structure FASTA (-q)")
-    parser.add_argument("-p", "--pfm_seq", dest="pfm_seq", type=str, default=None, help="Sequence PFM")
-    parser.add_argument("-q", "--pfm_struct", dest="pfm_struct", type=str, default=None, help="Structure PFM")
-    parser.add_argument("-o", "--prefix", dest="prefix", type=str, required=True, help="PREFIX of PREFIX.expected.txt and PREFIX.summary.txt")
-    parser.add_argument("-C", "--pseudocount", type=float, dest="pseudocount", default=0, help="Pseudocount for normalizing PFM. [%(default)s]")
-    parser.add_argument("-u", "--uniformbg", action="store_true", default=False, dest="uniform_background",
-                        help="Use uniform background for the odds ratios [%(default)s]")
-    parser.add_argument("-b", "--bg_seq", default=None, dest="bg_seq", help="File of pre-computed background probabilities for sequences")
-    parser.add_argument("-B", "--bg_struct", default=None, dest="bg_struct", help="File of pre-computed background probabilities for structures")
-    parser.add_argument("--weight", choices=sorted(MODES), default="posterior",
-                        help="weight of a window: its likelihood ratio, or that over the record's occupancy [%(default)s]")
-    parser.add_argument("--iterations", type=int, default=1, help="EM steps: each takes the last one's expected counts as its PFM [%(default)s]")
-    parser.add_argument("--all-motifs", action="store_true", default=False, dest="all_motifs", help="every motif of a multi-PFM file, one call per width [off]")
-    parser.add_argument("--struct-format", choices=["auto", "letters", "dotbracket"], default="auto", dest="struct_format",
-                        help="-q: what the structure FASTA holds; dot-bracket strings are annotated on the GPU first [%(default)s]")
-    parser.add_argument("--batch-records", type=int, default=BATCH_RECORDS, dest="batch_records",
-                        help="records per device call; the files do not depend on it [%(default)s]")
-    add_merge_option(parser)
-    parser.add_argument("--device", type=int, default=int(os.environ.get("RNASCAN_DEVICE", "0")), help="HIP device index [%(default)s]")
+    occupancy.add_options(parser, ["-p", "-q", "-o", "-C", "-u", "-b", "-B", "--weight", "--iterations", "--all-motifs", "--struct-format",
+                                   "--batch-records", "--merge", "--device"], OPTIONS, result="files do", joint="",
+                          files="PREFIX.expected.txt and PREFIX.summary.txt", steps="EM steps: each takes the last one's expected counts as its PFM")
     args = parser.parse_args(argv)
-    if args.uniform_background and (args.bg_seq or args.bg_struct):
-        parser.error("You cannot set uniform and custom background options at the same time\n")
-    if args.batch_records < 1:
-        parser.error("--batch-records: must be positive")
+    occupancy.check_options(parser, args)
     return args
 
 
 def main(argv=None, engine=None):
-    from . import cli, pssm, scanner, sites, store
-    from ._lib import MAX_M
+    from . import store
     args = getoptions(argv)
     if bool(args.pfm_seq) == bool(args.pfm_struct):
         fasta.eprint("exactly one of -p (sequence PFM) or -q (structure PFM) is required: expected counts of -p with -q pairs are not supported")
@@ -276,61 +319,33 @@ def main(argv=None, engine=None):
         fasta.eprint("%s is an averaged-structure directory or packed store: expected counts take a FASTA of letters "
                      "(averaged-structure profiles are not supported)" % args.fasta)
         return 1
-    seq = bool(args.pfm_seq)
-    option, pfm_file = ("-p", args.pfm_seq) if seq else ("-q", args.pfm_struct)
-    letters, code_letters = (fasta.RNA, pack.RNA_LETTERS) if seq else (fasta.STRUCT, pack.STRUCT_LETTERS)
-    order = sites.SEQ_ORDER if seq else sites.STRUCT_ORDER
-    own = engine is None
-    try:
-        try:
-            shapes = pssm.load_odds(pfm_file, args.pseudocount, letters, None)      # widths only: before any device work
-        except KeyError:
-            fasta.eprint("Failed to load motif %s (%s): check that the PFM has the letters %s" % (pfm_file, option, letters))
+    with occupancy.Device(engine, args.device, (IOError, ExpectError)) as dev:
+        got = occupancy.single_fasta(args, dev)
+        if got is None:
             return 1
-        if not shapes:
-            fasta.eprint("No motif could be read from %s (%s)" % (pfm_file, option))
-            return 1
-        motif_ids = list(shapes.keys()) if args.all_motifs else [next(iter(shapes))]
-        for mid in motif_ids:
-            if shapes[mid].length > MAX_M:
-                fasta.eprint("%s: motif %s of %s is %d positions wide, more than %d (PFMSCAN_MAX_M)" %
-                             (option, mid, pfm_file, shapes[mid].length, MAX_M))
-                return 1
-        if engine is None:
-            engine = scanner.HipEngine(args.device)
-        source = args.fasta
-        if not seq:
-            # a dot-bracket structure FASTA is annotated first and replaced by its letters (cli.struct_input)
-            ns = argparse.Namespace(fastafiles=[args.fasta], struct_format=args.struct_format, testseq=None)
-            cli.struct_input(ns, "SS", None, lambda: engine)
-            source = ns.fastafiles[0]
-        bg = fasta.load_background(args.bg_seq if seq else args.bg_struct, args.uniform_background, source, letters, True)
-        odds = pssm.load_odds(pfm_file, args.pseudocount, letters, bg)
-        recs = fasta.open_lazy(source)
-        summary = ["\t".join(COLUMNS) + "\n"]
-        results = None
-        for it in range(1, args.iterations + 1):
-            tables = dict((mid, odds[mid].ratio_table(code_letters)) for mid in motif_ids)
-            got = run(engine, recs, tables, motif_ids, letters, code_letters, MODES[args.weight], args.batch_records, args.merge)
-            for mid in motif_ids:
-                E, n, skipped, windows, ll = got[mid]
-                summary.append("%s\t%d\t%d\t%d\t%d\t%s\n" % (mid, it, n, skipped, windows, repr(ll)))
-            results = dict((mid, got[mid][0]) for mid in motif_ids)
-            if it < args.iterations:
-                odds = dict((mid, next_odds(results[mid], letters, code_letters, args.pseudocount, bg)) for mid in motif_ids)
-        text = pfm_text(results, motif_ids, order, code_letters, args.all_motifs)
-        with open(args.prefix + ".expected.txt", "w") as out:
-            out.write(text)
-        with open(args.prefix + ".summary.txt", "w") as out:
-            out.write("".join(summary))
-        fasta.eprint("Wrote the expected counts of %d motifs after %d iterations" % (len(motif_ids), args.iterations))
+        motif_ids, letters, code_letters, bg, odds, recs = got
+        engine, slot = dev.engine, 0 if args.pfm_seq else 1
+
+        def form_of(odds, pairs):
+            mine = [odds[slot][pair[slot]] for pair in pairs]
+            groups = occupancy._by_width([o.length for o in mine])
+
+            def host(stream, tables, mode):
+                e, o, w = engine.expect(stream, tables, len(code_letters), mode)
+                return [e], o, w
+
+            def merged(stream, tables, mode, accs):
+                bad, o, w = engine.expect_merged(stream, tables, len(code_letters), mode, accs[0])
+                return [bad], o, w
+            # the motifs are finalised width by width (widths by first appearance, the file's order within one)
+            return Form(motif_ids, groups, [k for ks in groups.values() for k in ks], lambda: occupancy.letter_batches(recs, letters, args.batch_records),
+                        lambda m, ks, cols: np.stack([mine[k].ratio_table(code_letters) for k in ks]), host, merged, "expect_merged",
+                        [(len(code_letters), None)], NOT_FINITE)
+
+        iterate(args, engine, [Side(".expected.txt", slot, code_letters, bg)], [odds, None] if slot == 0 else [None, odds],
+                [(mid, None) if slot == 0 else (None, mid) for mid in motif_ids], form_of)
         return 0
-    except (IOError, ExpectError) as e:
-        fasta.eprint(str(e))
-        return 1
-    finally:
-        if own and engine is not None:
-            engine.close()
+    return 1
 
 
 if __name__ == "__main__":

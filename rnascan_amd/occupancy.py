@@ -64,32 +64,6 @@ def format_rows(motif_ids, seq_ids, windows, occ):
     return lines
 
 
-def run(engine, out, recs, odds, motif_ids, letters, code_letters, batch_records=BATCH_RECORDS):
-    """rows in (record, motif) order, batch by batch of records; one device call per batch and width"""
-    from . import scanner
-    n_letters = len(code_letters)
-    groups = {}
-    for k, mid in enumerate(motif_ids):
-        groups.setdefault(odds[mid].length, []).append(k)
-    tables = dict((m, np.stack([odds[motif_ids[k]].ratio_table(code_letters) for k in ks])) for m, ks in groups.items())
-    total = 0
-    for a in range(0, len(recs), batch_records):
-        b = min(len(recs), a + batch_records)
-        batch = scanner._RnaBatch(recs[a:b], None if letters == fasta.RNA else letters)
-        if len(batch) == 0:
-            continue
-        stream = pack.Stream(batch.codes, None, batch.offsets, batch.lengths)
-        occ = np.zeros((len(batch), len(motif_ids)), dtype=np.float64)
-        win = np.zeros((len(batch), len(motif_ids)), dtype=np.int64)
-        for m, ks in groups.items():
-            o, w = engine.occupancy(stream, tables[m], n_letters)
-            occ[:, ks] = o
-            win[:, ks] = w[:, None]
-        out.write("".join(format_rows(motif_ids, list(batch.ids), win, occ)))
-        total += len(batch) * len(motif_ids)
-    return total
-
-
 def _by_width(widths):
     groups = {}
     for k, m in enumerate(widths):
@@ -97,35 +71,98 @@ def _by_width(widths):
     return groups
 
 
-def run_profiles(engine, out, recs, profiles, seq_odds, struct_odds, pairs, pairing="aligned", batch_records=BATCH_RECORDS):
-    """the rows of an averaged-structure input (``sites._Profiles``), batch by batch of records; within a batch one device
-    call per run of equal column order and per width.  ``recs``: the FASTA's records in the profiles' order for joint mode
-    (``pairs`` = [(sequence id, structure id)]), None for structure only ([(None, structure id)])"""
-    from . import scanner, sites
-    motif_ids = [sites.pair_id(a, b) for a, b in pairs]
-    groups = _by_width([struct_odds[b].length for _, b in pairs])
-    seq_tables = None
-    if recs is not None:
-        seq_tables = dict((m, np.stack([seq_odds[pairs[k][0]].ratio_table(pack.RNA_LETTERS) for k in ks])) for m, ks in groups.items())
-    total = 0
+# ---- the batch sources: generators of (ids, pack.Stream, cols); the third is ``occupancy_pair.batches`` ---------------------
+def letter_batches(recs, letters, batch_records=BATCH_RECORDS):
+    """a letters FASTA, batch by batch of records: every batch that holds a record; ``cols`` is None"""
+    from . import scanner
+    for a in range(0, len(recs), batch_records):
+        b = min(len(recs), a + batch_records)
+        batch = scanner._RnaBatch(recs[a:b], None if letters == fasta.RNA else letters)
+        if len(batch) == 0:
+            continue
+        yield list(batch.ids), pack.Stream(batch.codes, None, batch.offsets, batch.lengths), None
+
+
+def profile_batches(recs, profiles, batch_records=BATCH_RECORDS):
+    """an averaged-structure input (``sites._Profiles``), batch by batch of records and within a batch run by run of equal
+    column order: ``cols`` is the run's stored order.  ``recs``: the FASTA's records in the profiles' order (their codes go
+    beside the rows), or None (structure only)"""
     for a in range(0, len(profiles.ids), batch_records):
         b = min(len(profiles.ids), a + batch_records)
         at = a
         for ids, cols, pst in profiles.runs(a, b):
-            n = len(ids)
-            stream = paired_batch(recs, at, ids, pst)
-            occ = np.zeros((n, len(pairs)), dtype=np.float64)
-            win = np.zeros((n, len(pairs)), dtype=np.int64)
-            for m, ks in groups.items():
-                # the structure tables in THIS run's stored column order
-                st = np.stack([scanner.struct_matrix(struct_odds[pairs[k][1]], cols, pairing) for k in ks])
-                o, w = engine.occupancy_profile(stream, st, None if recs is None else seq_tables[m])
-                occ[:, ks] = o
-                win[:, ks] = w[:, None]
-            out.write("".join(format_rows(motif_ids, list(ids), win, occ)))
-            total += n * len(pairs)
-            at += n
-    return total
+            yield list(ids), paired_batch(recs, at, ids, pst), cols
+            at += len(ids)
+
+
+def profile_tables(seq_odds, struct_odds, pairs, pairing="aligned"):
+    """-> tables(m, ks, cols) = (structure tables of the pairs ks in the stored column order cols | None, their sequence
+    tables | None); ``pairs``: [(sequence id | None, structure id | None)], all of one kind"""
+    from . import scanner
+    seq_tables = {}
+
+    def tables(m, ks, cols):
+        if pairs[0][0] is not None and m not in seq_tables:
+            seq_tables[m] = np.stack([seq_odds[pairs[k][0]].ratio_table(pack.RNA_LETTERS) for k in ks])
+        # the structure tables in THIS run's stored column order
+        st = np.stack([scanner.struct_matrix(struct_odds[pairs[k][1]], cols, pairing) for k in ks]) if pairs[0][1] is not None else None
+        return st, seq_tables.get(m)
+    return tables
+
+
+def write_table(out, motif_ids, groups, batches, call):
+    """the table: the header, then rows in (record, motif) order, batch by batch; one device call per batch and width.
+    ``groups``: {width: motif indices}; ``call(stream, m, ks, cols)`` -> (occ [n_rec][len(ks)], windows [n_rec])"""
+    out.write("\t".join(COLUMNS) + "\n")
+    total = 0
+    for ids, stream, cols in batches:
+        occ = np.zeros((len(ids), len(motif_ids)), dtype=np.float64)
+        win = np.zeros((len(ids), len(motif_ids)), dtype=np.int64)
+        for m, ks in groups.items():
+            o, w = call(stream, m, ks, cols)
+            occ[:, ks] = o
+            win[:, ks] = np.asarray(w)[:, None]
+        out.write("".join(format_rows(motif_ids, ids, win, occ)))
+        total += len(ids) * len(motif_ids)
+    out.flush()
+    fasta.eprint("Wrote %d rows" % total)
+
+
+# ---- the options of the five commands of the family, each declared once; {words} differ between the commands ---------------
+OPTIONS = {
+    "-p": lambda p, w: p.add_argument("-p", "--pfm_seq", dest="pfm_seq", type=str, default=None, help="Sequence PFM"),
+    "-q": lambda p, w: p.add_argument("-q", "--pfm_struct", dest="pfm_struct", type=str, default=None, help="Structure PFM"),
+    "-C": lambda p, w: p.add_argument("-C", "--pseudocount", type=float, dest="pseudocount", default=0, help="Pseudocount for normalizing PFM. [%(default)s]"),
+    "-u": lambda p, w: p.add_argument("-u", "--uniformbg", action="store_true", default=False, dest="uniform_background",
+                                      help="Use uniform background for the odds ratios [%(default)s]"),
+    "-b": lambda p, w: p.add_argument("-b", "--bg_seq", default=None, dest="bg_seq", help="File of pre-computed background probabilities for sequences"),
+    "-B": lambda p, w: p.add_argument("-B", "--bg_struct", default=None, dest="bg_struct", help="File of pre-computed background probabilities for structures"),
+    "--all-motifs": lambda p, w: p.add_argument("--all-motifs", action="store_true", default=False, dest="all_motifs",
+                                                help="every %s, one call per width [off]" % w["every"]),
+    "--struct-format": lambda p, w: p.add_argument("--struct-format", choices=["auto", "letters", "dotbracket"], default="auto", dest="struct_format",
+                                                   help="%swhat the structure FASTA holds; dot-bracket strings are annotated on the GPU first [%%(default)s]" % w["q"]),
+    "--batch-records": lambda p, w: p.add_argument("--batch-records", type=int, default=BATCH_RECORDS, dest="batch_records",
+                                                   help="records per device call; the %s not depend on it [%%(default)s]" % w["result"]),
+    "--pairing": lambda p, w: p.add_argument("--pairing", choices=["aligned", "positional"], default="aligned",
+                                             help="averaged-structure columns vs structure PFM, as rnascan's [%(default)s]"),
+    "--profile-dtype": lambda p, w: p.add_argument("--profile-dtype", choices=["float32", "float64"], default=None, dest="profile_dtype",
+                                                   help="device storage of averaged-structure rows [the store's own dtype; float64 for text files]"),
+    "--device": lambda p, w: p.add_argument("--device", type=int, default=int(os.environ.get("RNASCAN_DEVICE", "0")), help="HIP device index [%(default)s]"),
+}
+WORDS = {"every": "motif of a multi-PFM file", "q": "-q: ", "result": "table does"}
+
+
+def add_options(parser, names, options=OPTIONS, **words):
+    """declare the options ``names`` in this order, the one the command's --help lists them in"""
+    for name in names:
+        options[name](parser, dict(WORDS, **words))
+
+
+def check_options(parser, args):
+    if args.uniform_background and (args.bg_seq or args.bg_struct):
+        parser.error("You cannot set uniform and custom background options at the same time\n")
+    if args.batch_records < 1:
+        parser.error("--batch-records: must be positive")
 
 
 def getoptions(argv=None):
@@ -135,32 +172,41 @@ def getoptions(argv=None):
     parser.add_argument("inputs", metavar="input", nargs="+",
                         help=("the sequence FASTA (-p) or structure FASTA (-q); or an averaged-structure directory or packed store (-q); "
                               "or the sequence FASTA and the averaged-structure directory or store (-p with -q)"))
-    parser.add_argument("-p", "--pfm_seq", dest="pfm_seq", type=str, default=None, help="Sequence PFM")
-    parser.add_argument("-q", "--pfm_struct", dest="pfm_struct", type=str, default=None, help="Structure PFM")
-    parser.add_argument("-C", "--pseudocount", type=float, dest="pseudocount", default=0, help="Pseudocount for normalizing PFM. [%(default)s]")
-    parser.add_argument("-u", "--uniformbg", action="store_true", default=False, dest="uniform_background",
-                        help="Use uniform background for the odds ratios [%(default)s]")
-    parser.add_argument("-b", "--bg_seq", default=None, dest="bg_seq", help="File of pre-computed background probabilities for sequences")
-    parser.add_argument("-B", "--bg_struct", default=None, dest="bg_struct", help="File of pre-computed background probabilities for structures")
-    parser.add_argument("--all-motifs", action="store_true", default=False, dest="all_motifs", help="every motif of a multi-PFM file, one call per width [off]")
-    parser.add_argument("--struct-format", choices=["auto", "letters", "dotbracket"], default="auto", dest="struct_format",
-                        help="-q: what the structure FASTA holds; dot-bracket strings are annotated on the GPU first [%(default)s]")
-    parser.add_argument("--batch-records", type=int, default=BATCH_RECORDS, dest="batch_records",
-                        help="records per device call; the table does not depend on it [%(default)s]")
-    parser.add_argument("--pairing", choices=["aligned", "positional"], default="aligned",
-                        help="averaged-structure columns vs structure PFM, as rnascan's [%(default)s]")
-    parser.add_argument("--profile-dtype", choices=["float32", "float64"], default=None, dest="profile_dtype",
-                        help="device storage of averaged-structure rows [the store's own dtype; float64 for text files]")
-    parser.add_argument("--device", type=int, default=int(os.environ.get("RNASCAN_DEVICE", "0")), help="HIP device index [%(default)s]")
+    add_options(parser, ["-p", "-q", "-C", "-u", "-b", "-B", "--all-motifs", "--struct-format", "--batch-records", "--pairing", "--profile-dtype",
+                         "--device"])
     args = parser.parse_intermixed_args(argv)                      # `seqs.fa --batch-records 64 avgdir/` is fine
-    if args.uniform_background and (args.bg_seq or args.bg_struct):
-        parser.error("You cannot set uniform and custom background options at the same time\n")
-    if args.batch_records < 1:
-        parser.error("--batch-records: must be positive")
+    check_options(parser, args)
     if len(args.inputs) > 2:
         parser.error("one input, or the sequence FASTA and the averaged-structure directory or store")
     args.fasta = args.inputs[0]
     return args
+
+
+class Device(object):
+    """the engine of a command's ``main``: the caller's, or a HipEngine opened when ``engine`` is first asked for and closed
+    on the way out.  As a context manager it says an exception of the types ``caught`` on stderr and swallows it: the
+    command then returns 1"""
+
+    def __init__(self, engine, device, caught):
+        self._engine, self._own, self._device, self._caught = engine, engine is None, device, caught
+
+    @property
+    def engine(self):
+        if self._engine is None:
+            from . import scanner
+            self._engine = scanner.HipEngine(self._device)
+        return self._engine
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, kind, error, trace):
+        said = kind is not None and issubclass(kind, self._caught)
+        if said:
+            fasta.eprint(str(error))
+        if self._own and self._engine is not None:
+            self._engine.close()
+        return said
 
 
 def _is_profiles(path):
@@ -288,34 +334,51 @@ def paired_batch(recs, at, ids, pst):
     return pack.Stream(batch.codes, pst.profile, batch.offsets, batch.lengths)
 
 
+def single_fasta(args, dev):
+    """the prologue of a run on one FASTA of letters (``occupancy`` and ``expect`` with -p or -q): the motifs and their widths
+    before any device work, then the engine, a dot-bracket file annotated, the background, the odds and the records ->
+    (motif ids, letters, code letters, background, odds, records) or None (said on stderr)"""
+    from . import cli, pssm
+    seq = bool(args.pfm_seq)
+    option, pfm_file = ("-p", args.pfm_seq) if seq else ("-q", args.pfm_struct)
+    letters, code_letters = (fasta.RNA, pack.RNA_LETTERS) if seq else (fasta.STRUCT, pack.STRUCT_LETTERS)
+    shapes = _load_shapes(pfm_file, option, args.pseudocount, letters)
+    if shapes is None:
+        return None
+    motif_ids = list(shapes.keys()) if args.all_motifs else [next(iter(shapes))]
+    if not _widths_ok(shapes, motif_ids, option, pfm_file):
+        return None
+    engine = dev.engine
+    source = args.fasta
+    if not seq:
+        # a dot-bracket structure FASTA is annotated first and replaced by its letters (cli.struct_input)
+        ns = argparse.Namespace(fastafiles=[args.fasta], struct_format=args.struct_format, testseq=None)
+        cli.struct_input(ns, "SS", None, lambda: engine)
+        source = ns.fastafiles[0]
+    bg = fasta.load_background(args.bg_seq if seq else args.bg_struct, args.uniform_background, source, letters, True)
+    odds = pssm.load_odds(pfm_file, args.pseudocount, letters, bg)
+    return motif_ids, letters, code_letters, bg, odds, fasta.open_lazy(source)
+
+
 def main_profiles(args, engine, out):
     """the averaged-structure modes: ``-q st.pfm avgdir_or_store`` and ``-p seq.pfm -q st.pfm seqs.fa avgdir_or_store``"""
-    from . import background, scanner, sites
-    own = engine is None
-    try:
+    from . import background, sites
+    with Device(engine, args.device, (IOError, sites.InputError, background.BackgroundError, background.InputError)) as dev:
         motifs = profile_motifs(args)
         if motifs is None:
             return 1
         pairs = motifs[0]
-        if engine is None:
-            engine = scanner.HipEngine(args.device)
+        engine = dev.engine
         recs, profiles, seq_odds, struct_odds, _, _ = profile_sources(args, engine)
-        out.write("\t".join(COLUMNS) + "\n")
-        n = run_profiles(engine, out, recs, profiles, seq_odds, struct_odds, pairs, args.pairing, args.batch_records)
-        out.flush()
-        fasta.eprint("Wrote %d rows" % n)
+        groups = _by_width([struct_odds[b].length for _, b in pairs])
+        tables = profile_tables(seq_odds, struct_odds, pairs, args.pairing)
+        write_table(out, [sites.pair_id(a, b) for a, b in pairs], groups, profile_batches(recs, profiles, args.batch_records),
+                    lambda stream, m, ks, cols: engine.occupancy_profile(stream, *tables(m, ks, cols)))
         return 0
-    except (IOError, sites.InputError, background.BackgroundError, background.InputError) as e:
-        fasta.eprint(str(e))
-        return 1
-    finally:
-        if own and engine is not None:
-            engine.close()
+    return 1
 
 
 def main(argv=None, engine=None, out=None):
-    from . import cli, pssm, scanner
-    from ._lib import MAX_M
     args = getoptions(argv)
     out = sys.stdout if out is None else out
     if not args.pfm_seq and not args.pfm_struct:
@@ -337,47 +400,18 @@ def main(argv=None, engine=None, out=None):
             fasta.eprint("-p alone needs a sequence FASTA, %s is an averaged-structure directory or store: give -q, or -p with -q and both inputs" % args.inputs[0])
             return 1
         return main_profiles(args, engine, out)
-    seq = bool(args.pfm_seq)
-    option, pfm_file = ("-p", args.pfm_seq) if seq else ("-q", args.pfm_struct)
-    letters, code_letters = (fasta.RNA, pack.RNA_LETTERS) if seq else (fasta.STRUCT, pack.STRUCT_LETTERS)
-    own = engine is None
-    try:
-        try:
-            shapes = pssm.load_odds(pfm_file, args.pseudocount, letters, None)      # widths only: before any device work
-        except KeyError:
-            fasta.eprint("Failed to load motif %s (%s): check that the PFM has the letters %s" % (pfm_file, option, letters))
+    with Device(engine, args.device, (IOError,)) as dev:
+        got = single_fasta(args, dev)
+        if got is None:
             return 1
-        if not shapes:
-            fasta.eprint("No motif could be read from %s (%s)" % (pfm_file, option))
-            return 1
-        motif_ids = list(shapes.keys()) if args.all_motifs else [next(iter(shapes))]
-        for mid in motif_ids:
-            if shapes[mid].length > MAX_M:
-                fasta.eprint("%s: motif %s of %s is %d positions wide, more than %d (PFMSCAN_MAX_M)" %
-                             (option, mid, pfm_file, shapes[mid].length, MAX_M))
-                return 1
-        if engine is None:
-            engine = scanner.HipEngine(args.device)
-        source = args.fasta
-        if not seq:
-            # a dot-bracket structure FASTA is annotated first and replaced by its letters (cli.struct_input)
-            ns = argparse.Namespace(fastafiles=[args.fasta], struct_format=args.struct_format, testseq=None)
-            cli.struct_input(ns, "SS", None, lambda: engine)
-            source = ns.fastafiles[0]
-        bg = fasta.load_background(args.bg_seq if seq else args.bg_struct, args.uniform_background, source, letters, True)
-        odds = pssm.load_odds(pfm_file, args.pseudocount, letters, bg)
-        recs = fasta.open_lazy(source)
-        out.write("\t".join(COLUMNS) + "\n")
-        n = run(engine, out, recs, odds, motif_ids, letters, code_letters, args.batch_records)
-        out.flush()
-        fasta.eprint("Wrote %d rows" % n)
+        motif_ids, letters, code_letters, _, odds, recs = got
+        engine = dev.engine
+        groups = _by_width([odds[mid].length for mid in motif_ids])
+        tables = dict((m, np.stack([odds[motif_ids[k]].ratio_table(code_letters) for k in ks])) for m, ks in groups.items())
+        write_table(out, motif_ids, groups, letter_batches(recs, letters, args.batch_records),
+                    lambda stream, m, ks, cols: engine.occupancy(stream, tables[m], len(code_letters)))
         return 0
-    except IOError as e:
-        fasta.eprint(str(e))
-        return 1
-    finally:
-        if own and engine is not None:
-            engine.close()
+    return 1
 
 
 if __name__ == "__main__":

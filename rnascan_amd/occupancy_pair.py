@@ -19,7 +19,6 @@ per side exactly as ``occupancy -p`` and ``occupancy -q`` resolve them.  Columns
 Motif_ID Seq_ID Windows Occupancy Log2.Occupancy.
 """
 import argparse
-import os
 import sys
 
 import numpy as np
@@ -30,29 +29,11 @@ COLUMNS = occupancy.COLUMNS
 BATCH_RECORDS = occupancy.BATCH_RECORDS
 
 
-def add_options(parser):
+def add_options(parser, options=occupancy.OPTIONS):
     """the options ``occupancy_pair`` and ``expect_pair`` share"""
     parser.add_argument("inputs", metavar="input", nargs="+", help="the sequence FASTA and the structure FASTA (letters or dot-bracket)")
-    parser.add_argument("-p", "--pfm_seq", dest="pfm_seq", type=str, default=None, help="Sequence PFM")
-    parser.add_argument("-q", "--pfm_struct", dest="pfm_struct", type=str, default=None, help="Structure PFM")
-    parser.add_argument("-C", "--pseudocount", type=float, dest="pseudocount", default=0, help="Pseudocount for normalizing PFM. [%(default)s]")
-    parser.add_argument("-u", "--uniformbg", action="store_true", default=False, dest="uniform_background",
-                        help="Use uniform background for the odds ratios [%(default)s]")
-    parser.add_argument("-b", "--bg_seq", default=None, dest="bg_seq", help="File of pre-computed background probabilities for sequences")
-    parser.add_argument("-B", "--bg_struct", default=None, dest="bg_struct", help="File of pre-computed background probabilities for structures")
-    parser.add_argument("--all-motifs", action="store_true", default=False, dest="all_motifs", help="every pair of multi-PFM files, one call per width [off]")
-    parser.add_argument("--struct-format", choices=["auto", "letters", "dotbracket"], default="auto", dest="struct_format",
-                        help="what the structure FASTA holds; dot-bracket strings are annotated on the GPU first [%(default)s]")
-    parser.add_argument("--batch-records", type=int, default=BATCH_RECORDS, dest="batch_records",
-                        help="records per device call; the output does not depend on it [%(default)s]")
-    parser.add_argument("--device", type=int, default=int(os.environ.get("RNASCAN_DEVICE", "0")), help="HIP device index [%(default)s]")
-
-
-def check_options(parser, args):
-    if args.uniform_background and (args.bg_seq or args.bg_struct):
-        parser.error("You cannot set uniform and custom background options at the same time\n")
-    if args.batch_records < 1:
-        parser.error("--batch-records: must be positive")
+    occupancy.add_options(parser, ["-p", "-q", "-C", "-u", "-b", "-B", "--all-motifs", "--struct-format", "--batch-records", "--device"], options,
+                          every="pair of multi-PFM files", q="", result="output does")
 
 
 def check_inputs(args):
@@ -99,7 +80,8 @@ def sources(args, engine):
 
 
 def batches(recs, srecs, batch_records):
-    """(ids, pack.Stream with codes and codes2) of every batch of records that holds one"""
+    """(ids, pack.Stream with codes and codes2, None) of every batch of records that holds one: the third batch source beside
+    ``occupancy.letter_batches`` and ``occupancy.profile_batches``"""
     from . import scanner, sites
     for a in range(0, len(recs), batch_records):
         b = min(len(recs), a + batch_records)
@@ -110,7 +92,7 @@ def batches(recs, srecs, batch_records):
             r = int(np.flatnonzero(sb.lengths != tb.lengths)[0])
             raise sites.InputError("record %s is %d letters long but its structure string has %d" %
                                    (sb.ids[r], int(sb.lengths[r]), int(tb.lengths[r])))
-        yield list(sb.ids), pack.Stream(sb.codes, None, sb.offsets, sb.lengths, codes2=tb.codes)
+        yield list(sb.ids), pack.Stream(sb.codes, None, sb.offsets, sb.lengths, codes2=tb.codes), None
 
 
 def pair_tables(seq_odds, struct_odds, pairs, ks):
@@ -119,60 +101,34 @@ def pair_tables(seq_odds, struct_odds, pairs, ks):
             np.stack([struct_odds[pairs[k][1]].ratio_table(pack.STRUCT_LETTERS) for k in ks]))
 
 
-def run(engine, out, recs, srecs, seq_odds, struct_odds, pairs, batch_records=BATCH_RECORDS):
-    """rows in (record, pair) order, batch by batch of records; one device call per batch and width"""
-    from . import sites
-    motif_ids = [sites.pair_id(a, b) for a, b in pairs]
-    groups = occupancy._by_width([seq_odds[a].length for a, _ in pairs])
-    tables = dict((m, pair_tables(seq_odds, struct_odds, pairs, ks)) for m, ks in groups.items())
-    total = 0
-    for ids, stream in batches(recs, srecs, batch_records):
-        occ = np.zeros((len(ids), len(pairs)), dtype=np.float64)
-        win = np.zeros((len(ids), len(pairs)), dtype=np.int64)
-        for m, ks in groups.items():
-            o, w = engine.occupancy_pair(stream, tables[m][0], tables[m][1])
-            occ[:, ks] = o
-            win[:, ks] = np.asarray(w)[:, None]
-        out.write("".join(occupancy.format_rows(motif_ids, ids, win, occ)))
-        total += len(ids) * len(pairs)
-    return total
-
-
 def getoptions(argv=None):
     parser = argparse.ArgumentParser(prog="python -m rnascan_amd.occupancy_pair",
                                      description=("Occupancy of sequence + structure FASTA pairs: the summed joint likelihood ratio of "
                                                   "every record under every motif pair, a threshold-free records x pairs table."))
     add_options(parser)
     args = parser.parse_intermixed_args(argv)
-    check_options(parser, args)
+    occupancy.check_options(parser, args)
     args.single, args.profiles = "occupancy", "occupancy"
     return args
 
 
 def main(argv=None, engine=None, out=None):
-    from . import scanner, sites
+    from . import sites
     args = getoptions(argv)
     out = sys.stdout if out is None else out
     checked = check_inputs(args)
     if checked is None:
         return 1
     pairs = checked[0]
-    own = engine is None
-    try:
-        if engine is None:
-            engine = scanner.HipEngine(args.device)
+    with occupancy.Device(engine, args.device, (IOError, sites.InputError)) as dev:
+        engine = dev.engine
         recs, srecs, seq_odds, struct_odds, _, _ = sources(args, engine)
-        out.write("\t".join(COLUMNS) + "\n")
-        n = run(engine, out, recs, srecs, seq_odds, struct_odds, pairs, args.batch_records)
-        out.flush()
-        fasta.eprint("Wrote %d rows" % n)
+        groups = occupancy._by_width([seq_odds[a].length for a, _ in pairs])
+        tables = dict((m, pair_tables(seq_odds, struct_odds, pairs, ks)) for m, ks in groups.items())
+        occupancy.write_table(out, [sites.pair_id(a, b) for a, b in pairs], groups, batches(recs, srecs, args.batch_records),
+                              lambda stream, m, ks, cols: engine.occupancy_pair(stream, *tables[m]))
         return 0
-    except (IOError, sites.InputError) as e:
-        fasta.eprint(str(e))
-        return 1
-    finally:
-        if own and engine is not None:
-            engine.close()
+    return 1
 
 
 if __name__ == "__main__":

@@ -98,10 +98,7 @@ class HipEngine(object):
         letters of ``stream.codes2`` above thr_struct (fp64) -- the two-FASTA combined scan (rnascan.py:416-434 joins the
         two hit tables) -> (pos, seq float32, struct float64)"""
         mo_seq, mo_st = self._motif(seq_table, None), self._motif(struct_table, None)
-        self._stage(stream)
-        if self._staged2 is not stream:
-            self.ctx.stage_codes2(stream.codes2)
-            self._staged2 = stream
+        self._stage_codes(stream)
         return self.ctx.hits_pair_staged(mo_seq, mo_st, thr_seq, thr_struct)
 
     def hits_pair_sum(self, stream, seq_table, struct_table, thr_seq, thr_struct, thr_sum):
@@ -109,10 +106,7 @@ class HipEngine(object):
         LogOdds.SeqStruct, float64(np.round(seq, 3)) + round(struct, 3) (rnascan.py:273, :416-434), must exceed thr_sum.
         Either single threshold may be -inf -> (pos, seq float32, struct float64), unrounded scores"""
         mo_seq, mo_st = self._motif(seq_table, None), self._motif(struct_table, None)
-        self._stage(stream)
-        if self._staged2 is not stream:
-            self.ctx.stage_codes2(stream.codes2)
-            self._staged2 = stream
+        self._stage_codes(stream)
         return self.ctx.hits_pair_sum_staged(mo_seq, mo_st, thr_seq, thr_struct, thr_sum)
 
     def hits(self, stream, letter_table=None, struct_pssm=None, thr_seq=-np.inf, thr_struct=-np.inf, one_shot=True):
@@ -152,14 +146,18 @@ class HipEngine(object):
         self._stage(stream)
         return self.ctx.variants_staged(letter_tables, pos, alt)
 
-    def occupancy(self, stream, ratio_tables, n_letters, which=0):
-        """summed likelihood ratios (DESIGN.md 5f): ratio tables [n_motifs][m][8] of one width (pssm.Odds.ratio_table) over
-        the stream's codes (which = 0) or codes2 (1), n_letters 4 (RNA) or 7 (structure letters) ->
-        (occ float64 [n_rec][n_motifs], windows int64 [n_rec])"""
+    def _stage_codes(self, stream, which=1):
+        """the stream on the device, and with which = 1 its second code stream too"""
         self._stage(stream)
         if which == 1 and self._staged2 is not stream:
             self.ctx.stage_codes2(stream.codes2)
             self._staged2 = stream
+
+    def occupancy(self, stream, ratio_tables, n_letters, which=0):
+        """summed likelihood ratios (DESIGN.md 5f): ratio tables [n_motifs][m][8] of one width (pssm.Odds.ratio_table) over
+        the stream's codes (which = 0) or codes2 (1), n_letters 4 (RNA) or 7 (structure letters) ->
+        (occ float64 [n_rec][n_motifs], windows int64 [n_rec])"""
+        self._stage_codes(stream, which)
         return self.ctx.occupancy_staged(ratio_tables, n_letters, stream.offsets, stream.lengths, which)
 
     def expect(self, stream, ratio_tables, n_letters, mode, which=0):
@@ -167,10 +165,7 @@ class HipEngine(object):
         codes (which = 0) or codes2 (1), every window weighted by its likelihood ratio (mode _lib.EXPECT_RATIO) or by that
         ratio over the record's occupancy (_lib.EXPECT_POSTERIOR) ->
         (exp float64 [n_rec][n_motifs][m][8], occ float64 [n_rec][n_motifs], windows int64 [n_rec])"""
-        self._stage(stream)
-        if which == 1 and self._staged2 is not stream:
-            self.ctx.stage_codes2(stream.codes2)
-            self._staged2 = stream
+        self._stage_codes(stream, which)
         return self.ctx.expect_staged(ratio_tables, n_letters, mode, stream.offsets, stream.lengths, which)
 
     def occupancy_profile(self, stream, struct_tables, seq_tables=None):
@@ -193,10 +188,7 @@ class HipEngine(object):
     def _stage_pair(self, stream):
         if stream.codes2 is None:
             raise ValueError("the stream holds no second code stream (codes2)")
-        self._stage(stream)
-        if self._staged2 is not stream:
-            self.ctx.stage_codes2(stream.codes2)
-            self._staged2 = stream
+        self._stage_codes(stream)
 
     def occupancy_pair(self, stream, seq_tables, struct_tables):
         """summed likelihood ratios of two code streams: pair q is (seq_tables[q], struct_tables[q]), both
@@ -217,10 +209,7 @@ class HipEngine(object):
     def expect_merged(self, stream, ratio_tables, n_letters, mode, acc, which=0):
         """``expect`` -> (bad int64 [n_motifs][2]: this call's first record with a non-finite cell, first with a negative one, -1
         for none; occ float64 [n_rec][n_motifs]; windows int64 [n_rec]); acc += the exact sum of the call's matrices"""
-        self._stage(stream)
-        if which == 1 and self._staged2 is not stream:
-            self.ctx.stage_codes2(stream.codes2)
-            self._staged2 = stream
+        self._stage_codes(stream, which)
         return self.ctx.expect_merged_staged(ratio_tables, n_letters, mode, stream.offsets, stream.lengths, acc, which)
 
     def expect_profile_merged(self, stream, struct_tables, seq_tables, mode, acc_struct, acc_seq=None):

@@ -248,3 +248,35 @@ def test_a_sum_beyond_the_largest_double(tmp_path, capsys):
     assert ecpu.run_command(Huge(), ["-p", seq, "-u", "-C", "0.01", "--merge", "device", "-o", str(tmp_path / "o"), str(fa)]) == 1
     err = capsys.readouterr().err
     assert "Motif seq" in err and "largest double" in err and not os.path.exists(str(tmp_path / "o") + ".expected.txt")
+
+
+def write_zero_row_library(path, letters):
+    """M0 (width 3, fine), M1 (width 2) and M2 (width 3), the second row of M1 and of M2 all zeros: under -u every ratio of
+    that row is 0, so is every occupancy, and no record contributes to M1 or to M2"""
+    with open(str(path), "w") as f:
+        for k, m in enumerate((3, 2, 3)):
+            f.write("#M%d\n#PO\t%s\n" % (k, "\t".join(letters)))
+            for j in range(m):
+                f.write("%d\t%s\n" % (j, "\t".join("0" if k and j == 1 else "1" for _ in letters)))
+            f.write("\n")
+    return str(path)
+
+
+@pytest.mark.parametrize("route", ["host", "device"])
+def test_which_motif_a_pass_without_a_contribution_names(tmp_path, capsys, route):
+    """the order in which a pass finalises its motifs: ``expect`` by width group (groups by first appearance, so M0, M2, M1),
+    ``expect_pair`` and ``expect_profile`` in file order (M0, M1, M2)"""
+    seq = write_zero_row_library(tmp_path / "seq.pfm", RNA)
+    st = write_zero_row_library(tmp_path / "st.pfm", STRUCT)
+    engines = (ecpu._RuleEngine, qcpu._RuleEngine, pcpu._RuleEngine) if route == "host" else (MergedEngine, MergedPairEngine, MergedProfileEngine)
+    opts = ["-u", "--all-motifs", "--merge", route, "-o", str(tmp_path / "out")]
+    fa = tmp_path / "s.fa"
+    fa.write_text(ecpu.FASTA)
+    assert ecpu.run_command(engines[0](), ["-p", seq] + opts + [str(fa)]) == 1
+    assert capsys.readouterr().err == "Motif M2: no record contributes (every occupancy is 0)\n"
+    pfa, psfa = qcpu.write_inputs(tmp_path)
+    assert qcpu.run_expect(engines[1](), ["-p", seq, "-q", st, "--struct-format", "letters"] + opts + [pfa, psfa]) == 1
+    assert capsys.readouterr().err == "Motif M1: no record contributes (every occupancy is 0)\n"
+    _, d, _, _, _ = make_inputs(tmp_path)
+    assert pcpu.run_command(engines[2](), ["-q", st] + opts + [d]) == 1
+    assert capsys.readouterr().err == "Motif M1: no record contributes (every occupancy is 0)\n"

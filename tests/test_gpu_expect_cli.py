@@ -66,4 +66,7 @@ def test_all_motifs_of_two_widths(engine, tmp_path):
     assert [ln[1:] for ln in got[0].splitlines() if ln.startswith("#M")] == ["M0", "M1", "M2", "M3", "M4"]
     assert run_command(engine, base + ["--batch-records", "7", "-o", str(tmp_path / "b"), TEST_FA]) == 0
     assert outputs(tmp_path / "b") == got
+    # every batch staged once and passed to the device once per width, the per-record matrices of all widths kept on the host
+    assert run_command(engine, base + ["--merge", "host", "--batch-records", "7", "-o", str(tmp_path / "h"), TEST_FA]) == 0
+    assert outputs(tmp_path / "h") == got
     both(engine, tmp_path, base + ["--iterations", "2", "--weight", "ratio"], TEST_FA)

@@ -59,7 +59,7 @@
 extern "C" {
 #endif
 
-#define PFMSCAN_ABI_VERSION 26
+#define PFMSCAN_ABI_VERSION 27   /* 27: pfmscan_expect_pair_joint_dev / _staged / _merged_staged (the 4 x 7 table per column) */
 #define PFMSCAN_NCODE   8      /* columns of a letter table */
 #define PFMSCAN_SEP     7      /* separator / foreign-letter code */
 #define PFMSCAN_NSTRUCT 7      /* columns of a structure profile / structure PSSM */
@@ -1321,6 +1321,30 @@ int pfmscan_expect_pair_staged(pfmscan_ctx *ctx, const double *seq_tables, const
                                int mode, const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec, double *exp_seq,
                                double *exp_struct, double *occ, int64_t *windows);
 
+/* The expected letter-PAIR table per column (ABI 27).  The two matrices above are the margins of one table: per record r, pair q
+ * and motif column k, how often nucleotide a lies over structure letter b under the weights.  It is neither the outer product of
+ * the margins nor anything a thresholded command writes.  Everything not said here is the contract above, unchanged.
+ *   exp_joint[r][q][k][a][b], a < 4, b < 7   the tree sum of (has_s && a_k == a && b_k == b) ? w_s : +0.0.
+ *                 double [n_rec][n_motifs][m][4][8], column b = 7 of every row +0.0: a matrix of 4 m rows (row k * 4 + a) and 7
+ *                 letters per pair, which is how the tree, the merge below (rows 4 m, acc_joint uint64 [n_motifs]
+ *                 [PFMSCAN_SITE_LIMBS][32 m]) and the commands take it.
+ * Where every code of codes2 in a record is one known letter b0, exp_joint[..][k][a][b0] is bit for bit exp_seq[..][k][a] (the
+ * same windows in the same tree) and every other b is +0.0; the same with a constant nucleotide a0 against exp_struct.  With
+ * every cell of R and S equal to 1.0, PFMSCAN_EXPECT_RATIO and no foreign code the table is the integer count of letter pairs
+ * under every window: what pfmscan_site_joint_* counts when every window start is a hit.
+ * The three functions carry the argument lists of pfmscan_expect_pair_dev / _staged / _merged_staged plus the table's output
+ * behind the two matrices'; their checks, the order of the checks, messages and return codes are the namesakes'.  Any of the three
+ * outputs may be NULL (not computed: the bits of the others do not depend on it); all three NULL: PFMSCAN_E_BADARG.  The table is
+ * four matrices wide: 32 m doubles per record and pair on the device (3.2 GB for 4096 records x 256 pairs at m = 12); the caller
+ * bounds it by the records of a call. */
+int pfmscan_expect_pair_joint_dev(pfmscan_ctx *ctx, const double *seq_tables, const double *struct_tables, int n_motifs, int m,
+                                  int mode, const uint8_t *d_codes, const uint8_t *d_codes2, int64_t n_pos, const int64_t *d_rec_off,
+                                  const int64_t *d_rec_len, int64_t n_rec, double *d_exp_seq, double *d_exp_struct,
+                                  double *d_exp_joint, double *d_occ, int64_t *d_windows);
+int pfmscan_expect_pair_joint_staged(pfmscan_ctx *ctx, const double *seq_tables, const double *struct_tables, int n_motifs, int m,
+                                     int mode, const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec, double *exp_seq,
+                                     double *exp_struct, double *exp_joint, double *occ, int64_t *windows);
+
 /* ---- expected counts: the records added up on the device -------------------------------------------------------------------
  * No counterpart in the reference.  The three families of expected counts above leave one matrix [m][8] per record and motif;
  * a refinement step wants their sum over the records, which the commands used to make on the host with math.fsum.  These
@@ -1367,6 +1391,11 @@ int pfmscan_expect_profile_merged_staged(pfmscan_ctx *ctx, const double *struct_
 int pfmscan_expect_pair_merged_staged(pfmscan_ctx *ctx, const double *seq_tables, const double *struct_tables, int n_motifs, int m,
                                       int mode, const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec, uint64_t *acc_seq,
                                       uint64_t *acc_struct, int64_t *bad_seq, int64_t *bad_struct, double *occ, int64_t *windows);
+/* with the letter-pair table (ABI 27): acc_joint HOST uint64 [n_motifs][PFMSCAN_SITE_LIMBS][32 m], cell (k * 4 + a) * 8 + b */
+int pfmscan_expect_pair_joint_merged_staged(pfmscan_ctx *ctx, const double *seq_tables, const double *struct_tables, int n_motifs,
+                                            int m, int mode, const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec,
+                                            uint64_t *acc_seq, uint64_t *acc_struct, uint64_t *acc_joint, int64_t *bad_seq,
+                                            int64_t *bad_struct, int64_t *bad_joint, double *occ, int64_t *windows);
 
 #ifdef __cplusplus
 }

@@ -22,7 +22,7 @@ NCODE = 8
 NSTRUCT = 7
 MAX_M = 64            # widest PFM of the tuned kernels and of PFM libraries
 MAX_WIDTH = 4096      # widest PFM accepted (wider than MAX_M: the plain rolled-loop kernel)
-ABI_VERSION = 26
+ABI_VERSION = 27
 
 # every symbol include/pfmscan.h declares (checked by tests/test_abi.py)
 SYMBOLS = [
@@ -62,6 +62,7 @@ SYMBOLS = [
     "pfmscan_expect_profile_dev", "pfmscan_expect_profile_staged",
     "pfmscan_occupancy_pair_dev", "pfmscan_occupancy_pair_staged", "pfmscan_expect_pair_dev", "pfmscan_expect_pair_staged",
     "pfmscan_expect_merge_dev", "pfmscan_expect_merged_staged", "pfmscan_expect_profile_merged_staged", "pfmscan_expect_pair_merged_staged",
+    "pfmscan_expect_pair_joint_dev", "pfmscan_expect_pair_joint_staged", "pfmscan_expect_pair_joint_merged_staged",
 ]
 PAIR_ROUTE_NONE, PAIR_ROUTE_FUSED, PAIR_ROUTE_TWO_PHASE, PAIR_ROUTE_DENSE, PAIR_ROUTE_CREDITS = range(5)   # Context.pair_sum_route()
 SITE_GROUP = 4096     # most hits of one group of the site profiles
@@ -259,6 +260,9 @@ def load():
     L.pfmscan_expect_merged_staged.argtypes = [vp, i32, vp, i32, i32, i32, i32, vp, vp, i64, vp, vp, vp, vp]
     L.pfmscan_expect_profile_merged_staged.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, i64, vp, vp, vp, vp, vp, vp]
     L.pfmscan_expect_pair_merged_staged.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, i64, vp, vp, vp, vp, vp, vp]
+    L.pfmscan_expect_pair_joint_dev.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, i64, vp, vp, i64, vp, vp, vp, vp, vp]
+    L.pfmscan_expect_pair_joint_staged.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, i64, vp, vp, vp, vp, vp]
+    L.pfmscan_expect_pair_joint_merged_staged.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]
     L.pfmscan_tsv_format.argtypes = [ctypes.POINTER(TsvColumn), i32, i64, i64, vp, i64, ctypes.POINTER(i64), vp, ctypes.POINTER(i32), i32]
     for name in SYMBOLS:          # every other entry point returns a status
         if name not in ("pfmscan_ctx_destroy", "pfmscan_motif_destroy", "pfmscan_last_error", "pfmscan_library_destroy",
@@ -1841,6 +1845,28 @@ class Context(object):
                                                        rec_off.size, _ptr(exp_seq), _ptr(exp_struct), _ptr(occ), _ptr(windows)))
         return exp_seq, exp_struct, occ, windows
 
+    def expect_pair_joint_dev(self, seq_tables, struct_tables, mode, d_codes, d_codes2, n_pos, d_rec_off, d_rec_len, n_rec, d_exp_seq, d_exp_struct,
+                              d_exp_joint, d_occ=None, d_windows=None):
+        """``expect_pair_dev`` with the letter-pair table d_exp_joint float64 [n_rec][n_motifs][m][4][8]; any of the three may be None"""
+        sq, st = self._pair_tables(seq_tables, struct_tables)
+        self._check(self._L.pfmscan_expect_pair_joint_dev(self._h, _ptr(sq), _ptr(st), sq.shape[0], sq.shape[1], int(mode), _ptr(d_codes),
+                                                          _ptr(d_codes2), int(n_pos), _ptr(d_rec_off), _ptr(d_rec_len), int(n_rec), _ptr(d_exp_seq),
+                                                          _ptr(d_exp_struct), _ptr(d_exp_joint), _ptr(d_occ), _ptr(d_windows)))
+
+    def expect_pair_joint_staged(self, seq_tables, struct_tables, mode, rec_off, rec_len, want_seq=True, want_struct=True, want_joint=True):
+        """``expect_pair_staged`` with the letter-pair table -> exp_seq, exp_struct, exp_joint float64 [n_rec][n_motifs][m][4][8]
+        (cell [k][a][b]: nucleotide a over structure letter b under column k; b = 7 is +0.0), occ, windows; None where not wanted"""
+        sq, st = self._pair_tables(seq_tables, struct_tables)
+        n_motifs, m = sq.shape[:2]
+        rec_off, rec_len = self._records(rec_off, rec_len)
+        exp_seq = np.zeros((rec_off.size, n_motifs, m, NCODE), dtype=np.float64) if want_seq else None
+        exp_struct = np.zeros((rec_off.size, n_motifs, m, NCODE), dtype=np.float64) if want_struct else None
+        exp_joint = np.zeros((rec_off.size, n_motifs, m, 4, NCODE), dtype=np.float64) if want_joint else None
+        occ, windows = self._occ_windows(rec_off.size, n_motifs)
+        self._check(self._L.pfmscan_expect_pair_joint_staged(self._h, _ptr(sq), _ptr(st), n_motifs, m, int(mode), _ptr(rec_off), _ptr(rec_len),
+                                                             rec_off.size, _ptr(exp_seq), _ptr(exp_struct), _ptr(exp_joint), _ptr(occ), _ptr(windows)))
+        return exp_seq, exp_struct, exp_joint, occ, windows
+
     # -- expected counts, the records added up on the device (include/pfmscan.h: pfmscan_expect_merge_dev, *_merged_staged) --
     def expect_merge_dev(self, d_exp, n_rec, n_motifs, m, zero_first, d_acc, d_bad):
         """d_exp [n_rec][n_motifs][m][8] -> d_acc uint64 [n_motifs][SITE_LIMBS][m * 8] (RAW sums, added unless zero_first),
@@ -1903,6 +1929,23 @@ class Context(object):
                                                               rec_off.size, _ptr(acc_seq), _ptr(acc_struct), _ptr(bad_seq), _ptr(bad_struct), _ptr(occ),
                                                               _ptr(windows)))
         return bad_seq, bad_struct, occ, windows
+
+    def expect_pair_joint_merged_staged(self, seq_tables, struct_tables, mode, rec_off, rec_len, acc_seq, acc_struct, acc_joint):
+        """``expect_pair_merged_staged`` with the letter-pair table's accumulator acc_joint uint64 [n_motifs][SITE_LIMBS][4 m * 8]
+        (any of the three may be None) -> bad_seq, bad_struct, bad_joint (None where no accumulator), occ, windows"""
+        sq, st = self._pair_tables(seq_tables, struct_tables)
+        n_motifs, m = sq.shape[:2]
+        rec_off, rec_len = self._records(rec_off, rec_len)
+        accs = ((acc_seq, "acc_seq", m), (acc_struct, "acc_struct", m), (acc_joint, "acc_joint", 4 * m))
+        for acc, name, rows in accs:
+            if acc is not None:
+                self._merge_acc(acc, n_motifs, rows, name)
+        bads = [None if acc is None else np.full((n_motifs, 2), -1, dtype=np.int64) for acc, _, _ in accs]
+        occ, windows = self._occ_windows(rec_off.size, n_motifs)
+        self._check(self._L.pfmscan_expect_pair_joint_merged_staged(self._h, _ptr(sq), _ptr(st), n_motifs, m, int(mode), _ptr(rec_off), _ptr(rec_len),
+                                                                    rec_off.size, _ptr(acc_seq), _ptr(acc_struct), _ptr(acc_joint), _ptr(bads[0]),
+                                                                    _ptr(bads[1]), _ptr(bads[2]), _ptr(occ), _ptr(windows)))
+        return bads[0], bads[1], bads[2], occ, windows
 
     def time_scan_dev(self, motif, d_codes, d_profile, profile_dtype, n_pos, d_out_seq, d_out_struct,
                       stream=None, warmup=1, iters=5):

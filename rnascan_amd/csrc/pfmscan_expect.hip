@@ -157,18 +157,27 @@ __global__ __launch_bounds__(BLOCK) void k_exp_blocks(const OccArgs a, const dou
 // parks it; then a lane per (block, k, letter) of the 4 + 7 columns of the matrix rows (pair, k) of the pass walks the
 // block's 32 weights in order and adds (code == letter ? weight : +0.0) from 0.0 -- letters 0..3 against the RNA strip into
 // bs_seq, 4..10 against the structure strip into bs_struct.  A region that is null is not computed.  One writer per cell.
+// JOINT: the 4 x 7 table of a matrix row as well (bs_joint, never null then).  A third strip holds a | b << 3 per position
+// (0xFF where either code is foreign: the packing of k_occ_blocks<QN, true>), and a lane per (block, k, a, b) walks the same 32
+// weights against it: one compare per step.  A weight that is not +0.0 belongs to a window without a foreign position, so the
+// packed byte under it is that of two known letters.  Without JOINT nothing of this is compiled.
 struct ExpPairArgs {
     const double *inv;           // [n_rec][n_motifs] or null (ratio mode)
     double *bs_seq;              // [n_blk][n_u * 4] or null
     double *bs_struct;           // [n_blk][n_u * 7] or null
+    double *bs_joint;            // [n_blk][n_u * 28]: column (u * 4 + a) * 7 + b; null without JOINT
     int u_first, n_u;            // matrix rows of the pass: u = pair * m + k
 };
+constexpr int EXP_NJ = 4 * PFMSCAN_NSTRUCT;                        // cells of the joint table of a matrix row
+constexpr int EXP_FILL_ROUNDS = 16;                                // workgroups per CU a pass with the table should have (5 are resident)
 
+template <bool JOINT>
 __global__ __launch_bounds__(BLOCK) void k_exp_pair_blocks(const OccArgs a, const ExpPairArgs e, const int64_t *__restrict__ wg_rec)
 {
     __shared__ double tab[2][PFMSCAN_MAX_M * 8];
     __shared__ double wl[EXP_WB][OCC_FANIN + 1];
     __shared__ uint8_t cl[2][EXP_WB][EXP_CS];
+    __shared__ uint8_t pl[JOINT ? EXP_WB : 1][EXP_CS];
     constexpr int NS = PFMSCAN_NSTRUCT, NC = 4 + NS;
     const int t = threadIdx.x, j = t >> 5, w = t & 31, m = a.m;
     const int64_t gb = (int64_t)blockIdx.x * EXP_WB + j;           // this lane's block, within the pass
@@ -177,8 +186,10 @@ __global__ __launch_bounds__(BLOCK) void k_exp_pair_blocks(const OccArgs a, cons
     if (live) {
         blk = exp_block(a, wg_rec, gb);
         for (int i = w; i < EXP_CS; i += OCC_FANIN) {              // both strips in one walk (a walk per strip measured 3 % slower)
-            cl[0][j][i] = exp_code(a.codes, blk, i, 4);
-            cl[1][j][i] = exp_code(a.codes2, blk, i, NS);
+            const uint8_t x = exp_code(a.codes, blk, i, 4), y = exp_code(a.codes2, blk, i, NS);
+            cl[0][j][i] = x;
+            cl[1][j][i] = y;
+            if constexpr (JOINT) pl[j][i] = x == EXP_FOREIGN || y == EXP_FOREIGN ? EXP_FOREIGN : (uint8_t)(x | (y << 3));
         }
     }
     __syncthreads();
@@ -228,6 +239,18 @@ __global__ __launch_bounds__(BLOCK) void k_exp_pair_blocks(const OccArgs a, cons
                 if (st) region[gb * ss + u * NS + letter] = s;
                 else region[gb * sq + u * 4 + letter] = s;
             }
+            if constexpr (JOINT) {
+                double *out = e.bs_joint + gb * ((int64_t)e.n_u * EXP_NJ) + ((int64_t)q * m + k_lo - u_lo) * EXP_NJ;
+                for (int it = w; it < (k_hi - k_lo) * EXP_NJ; it += OCC_FANIN) {   // it = kk * 28 + a * 7 + b: the column within the pair's rows
+                    const int kk = it / EXP_NJ, c = it - kk * EXP_NJ, ca = c / NS;
+                    const int want = ca | ((c - ca * NS) << 3);
+                    const uint8_t *cp = &pl[j][k_lo + kk];
+                    double s = 0.0;
+#pragma unroll
+                    for (int i = 0; i < OCC_FANIN; ++i) s = s + ((int)cp[i] == want ? wl[j][i] : 0.0);
+                    out[it] = s;
+                }
+            }
         }
     }
 }
@@ -240,16 +263,17 @@ static int exp_wg_rec(pfmscan_ctx *ctx, const OccPlan &p, int64_t *&wg_rec)
     return rc;
 }
 
-// Launches on st, does not wait.  d_exp_seq / d_exp_struct: one of them may be null.
+// Launches on st, does not wait.  d_exp_seq / d_exp_struct / d_exp_joint: at least one is not null.
 static int exp_pair_run(pfmscan_ctx *ctx, const char *who, const double *seq_tables, const double *struct_tables, int n_motifs, int m, int mode,
-                        const uint8_t *d_codes, const uint8_t *d_codes2, const OccRecords &rec, double *d_exp_seq, double *d_exp_struct, double *d_occ,
-                        int64_t *d_windows, hipStream_t st)
+                        const uint8_t *d_codes, const uint8_t *d_codes2, const OccRecords &rec, double *d_exp_seq, double *d_exp_struct,
+                        double *d_exp_joint, double *d_occ, int64_t *d_windows, hipStream_t st)
 {
     int rc;
     const bool posterior = mode == PFMSCAN_EXPECT_POSTERIOR;
     const int64_t pairs = rec.n_rec * n_motifs;
     const int64_t n_unit = (int64_t)n_motifs * m;                  // matrix rows (pair, k)
-    if (n_unit * PFMSCAN_NSTRUCT > (int64_t(1) << 30)) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": too many motifs for one call");
+    const int wide = d_exp_joint ? EXP_NJ : PFMSCAN_NSTRUCT;       // columns of a matrix row in the widest matrix of the call
+    if (n_unit * wide > (int64_t(1) << 30)) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": too many motifs for one call");
     // the occupancy of the same records first: v of posterior mode, and what the caller asked for
     if (posterior || d_occ || d_windows) {
         if (!d_occ) {
@@ -268,9 +292,14 @@ static int exp_pair_run(pfmscan_ctx *ctx, const char *who, const double *seq_tab
     // the columns past the letters of every matrix row are +0.0; every other cell is written by k_occ_finish
     if (d_exp_seq) HIP_TRY(ctx, hipMemsetAsync(d_exp_seq, 0, (size_t)pairs * m * 8 * sizeof(double), st));
     if (d_exp_struct) HIP_TRY(ctx, hipMemsetAsync(d_exp_struct, 0, (size_t)pairs * m * 8 * sizeof(double), st));
+    if (d_exp_joint) HIP_TRY(ctx, hipMemsetAsync(d_exp_joint, 0, (size_t)pairs * m * 4 * 8 * sizeof(double), st));
     // matrix rows per pass: all of them unless the longest record's block sums alone pass the cap; then records per pass
-    const int nsq = d_exp_seq ? 4 : 0, cells = nsq + (d_exp_struct ? PFMSCAN_NSTRUCT : 0);   // scratch doubles of a matrix row, both regions
-    const OccPlan p = occ_plan(rec.len, rec.n_rec, m, n_unit, cells, PFMSCAN_NSTRUCT, occ_scratch_cap(), false);
+    const int nsq = d_exp_seq ? 4 : 0, nst = d_exp_struct ? PFMSCAN_NSTRUCT : 0;
+    const int cells = nsq + nst + (d_exp_joint ? EXP_NJ : 0);      // scratch doubles of a matrix row, all regions
+    // with the table a matrix row takes 39 doubles of a block, and all rows of a library in a pass would leave room for a few
+    // records only: a pass then holds whole pairs, as many as leave room for the blocks of a few rounds of workgroups
+    const int64_t fill_blk = d_exp_joint ? (int64_t)EXP_FILL_ROUNDS * std::max(ctx->n_cu, 1) * EXP_WB : 1;
+    const OccPlan p = occ_plan(rec.len, rec.n_rec, m, n_unit, cells, wide, occ_scratch_cap(), false, fill_blk, d_exp_joint ? m : 1);
     if ((p.need_blk + EXP_WB - 1) / EXP_WB > 0x7FFFFFFF) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": a record is too long for one call");
     OccArgs a{};
     if ((rc = occ_upload_tables(ctx, seq_tables, struct_tables, (size_t)n_motifs * m * 8 * sizeof(double), n_motifs, m, st, a.tables, a.tables2))) return rc;
@@ -280,11 +309,18 @@ static int exp_pair_run(pfmscan_ctx *ctx, const char *who, const double *seq_tab
     a.codes = d_codes;
     a.codes2 = d_codes2;
     a.out_stride = (int64_t)n_motifs * m * 8;
-    // the two scratch regions of a pass: the sequence matrix's block and level-1 sums, then the structure matrix's
+    // the scratch regions of a pass: the sequence matrix's block and level-1 sums, then the structure matrix's, then the table's
     double *bs_struct = a.bs + p.need_blk * p.n_u_max * nsq, *gs_struct = a.gs + p.need_grp * p.n_u_max * nsq;
     e.bs_seq = d_exp_seq ? a.bs : nullptr;
     e.bs_struct = d_exp_struct ? bs_struct : nullptr;
+    e.bs_joint = d_exp_joint ? bs_struct + p.need_blk * p.n_u_max * nst : nullptr;
     OccArgs as = a;                                                // levels 1 and up of the structure matrix
+    OccArgs aj = a;                                                // and of the table: a matrix of 4 m rows (k, a) and 7 letters
+    aj.bs = e.bs_joint;
+    aj.gs = gs_struct + p.need_grp * p.n_u_max * nst;
+    aj.occ = d_exp_joint;
+    aj.out_stride = a.out_stride * 4;
+    aj.cell_nl = PFMSCAN_NSTRUCT;
     a.occ = d_exp_seq;
     a.cell_nl = 4;
     as.bs = bs_struct;
@@ -298,18 +334,24 @@ static int exp_pair_run(pfmscan_ctx *ctx, const char *who, const double *seq_tab
         a.n_q = e.n_u * 4;
         as.q_first = e.u_first * PFMSCAN_NSTRUCT;
         as.n_q = e.n_u * PFMSCAN_NSTRUCT;
+        aj.q_first = e.u_first * EXP_NJ;
+        aj.n_q = e.n_u * EXP_NJ;
         for (size_t i = 0; i < p.n_pass(); ++i) {
             const bool make_table = p.n_pass() > 1 || u0 == 0;     // one range of records: its table is made once, for all passes over the rows
             occ_set_pass(a, p, i);
             occ_set_pass(as, p, i);
+            occ_set_pass(aj, p, i);
             if (a.n_blk > 0) {
                 if (make_table) hipLaunchKernelGGL(k_exp_group_records, dim3((unsigned)((a.r1 - a.r0 + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, a, wg_rec);
-                hipLaunchKernelGGL(k_exp_pair_blocks, dim3((unsigned)((a.n_blk + EXP_WB - 1) / EXP_WB)), dim3(BLOCK), 0, st, a, e, wg_rec);
+                const dim3 grid((unsigned)((a.n_blk + EXP_WB - 1) / EXP_WB));
+                if (d_exp_joint) hipLaunchKernelGGL(k_exp_pair_blocks<true>, grid, dim3(BLOCK), 0, st, a, e, wg_rec);
+                else hipLaunchKernelGGL(k_exp_pair_blocks<false>, grid, dim3(BLOCK), 0, st, a, e, wg_rec);
                 hipError_t err = hipGetLastError();
                 if (err != hipSuccess) return fail_hip(ctx, err, "k_exp_pair_blocks");
             }
             if (d_exp_seq && (rc = occ_launch_upper(ctx, a, st))) return rc;
             if (d_exp_struct && (rc = occ_launch_upper(ctx, as, st))) return rc;
+            if (d_exp_joint && (rc = occ_launch_upper(ctx, aj, st))) return rc;
         }
     }
     return PFMSCAN_OK;
@@ -425,7 +467,7 @@ static int expect_staged_any(pfmscan_ctx *ctx, const char *who, int which, const
     const uint8_t *d_codes = (const uint8_t *)(which ? ctx->codes2.p : ctx->codes.p);
     if ((rc = exp_run(ctx, who, ratio_tables, n_motifs, m, n_letters, mode, d_codes, rec, d_exp, d_occ, d_win, ctx->stream))) return rc;
     if (merged) {
-        const ExpMergeOut out{d_exp, acc, bad};
+        const ExpMergeOut out{d_exp, acc, bad, m};
         return exp_merge_home(ctx, who, &out, 1, n_rec, n_motifs, m, d_occ, occ, d_win, windows);
     }
     return occ_copy_home(ctx, {{exp, d_exp, cells * 8}, {occ, d_occ, pairs * 8}, {windows, d_win, (size_t)n_rec * 8}});
@@ -446,31 +488,57 @@ int pfmscan_expect_merged_staged(pfmscan_ctx *ctx, int which, const double *rati
                              acc, bad, true, occ, windows);
 }
 
-int pfmscan_expect_pair_dev(pfmscan_ctx *ctx, const double *seq_tables, const double *struct_tables, int n_motifs, int m, int mode,
-                            const uint8_t *d_codes, const uint8_t *d_codes2, int64_t n_pos, const int64_t *d_rec_off,
-                            const int64_t *d_rec_len, int64_t n_rec, double *d_exp_seq, double *d_exp_struct, double *d_occ,
-                            int64_t *d_windows)
+// the _dev form of two code streams.  table: the form has a d_exp_joint (null there: the table is not asked for)
+static int expect_pair_dev_any(pfmscan_ctx *ctx, const char *who, bool table, const double *seq_tables, const double *struct_tables, int n_motifs, int m,
+                               int mode, const uint8_t *d_codes, const uint8_t *d_codes2, int64_t n_pos, const int64_t *d_rec_off,
+                               const int64_t *d_rec_len, int64_t n_rec, double *d_exp_seq, double *d_exp_struct, double *d_exp_joint, double *d_occ,
+                               int64_t *d_windows)
 {
-    const char *who = "pfmscan_expect_pair_dev";
     if (!ctx) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": NULL ctx");
     if (int rc = occ_pair_check(ctx, who, seq_tables, struct_tables, n_motifs, m, n_pos, n_rec)) return rc;
     if (int rc = exp_check_mode(ctx, who, mode)) return rc;
-    if (!d_exp_seq && !d_exp_struct) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": d_exp_seq and d_exp_struct are both NULL");
+    if (!d_exp_seq && !d_exp_struct && !d_exp_joint)
+        return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + (table ? ": d_exp_seq, d_exp_struct and d_exp_joint are all NULL" : ": d_exp_seq and d_exp_struct are both NULL"));
     if (n_rec == 0 || n_motifs == 0) return PFMSCAN_OK;
     if (!d_rec_off || !d_rec_len || (n_pos > 0 && (!d_codes || !d_codes2))) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": NULL record table or codes");
     if (misaligned(d_codes) || misaligned(d_codes2)) return fail(ctx, PFMSCAN_E_BADSHAPE, std::string(who) + ": stream base pointers must be 16-byte aligned");
     std::vector<int64_t> host;
     OccRecords rec;
     if (int rc = occ_records_home(ctx, who, d_rec_off, d_rec_len, n_rec, n_pos, host, rec)) return rc;
-    return exp_pair_run(ctx, who, seq_tables, struct_tables, n_motifs, m, mode, d_codes, d_codes2, rec, d_exp_seq, d_exp_struct, d_occ, d_windows,
-                        ctx->stream);
+    return exp_pair_run(ctx, who, seq_tables, struct_tables, n_motifs, m, mode, d_codes, d_codes2, rec, d_exp_seq, d_exp_struct, d_exp_joint, d_occ,
+                        d_windows, ctx->stream);
 }
 
-// both _staged forms of two code streams.  merged: exp_seq / exp_struct only say which matrices are asked for (acc_seq / acc_struct)
+int pfmscan_expect_pair_dev(pfmscan_ctx *ctx, const double *seq_tables, const double *struct_tables, int n_motifs, int m, int mode,
+                            const uint8_t *d_codes, const uint8_t *d_codes2, int64_t n_pos, const int64_t *d_rec_off,
+                            const int64_t *d_rec_len, int64_t n_rec, double *d_exp_seq, double *d_exp_struct, double *d_occ,
+                            int64_t *d_windows)
+{
+    return expect_pair_dev_any(ctx, "pfmscan_expect_pair_dev", false, seq_tables, struct_tables, n_motifs, m, mode, d_codes, d_codes2, n_pos, d_rec_off,
+                               d_rec_len, n_rec, d_exp_seq, d_exp_struct, nullptr, d_occ, d_windows);
+}
+
+int pfmscan_expect_pair_joint_dev(pfmscan_ctx *ctx, const double *seq_tables, const double *struct_tables, int n_motifs, int m, int mode,
+                                  const uint8_t *d_codes, const uint8_t *d_codes2, int64_t n_pos, const int64_t *d_rec_off,
+                                  const int64_t *d_rec_len, int64_t n_rec, double *d_exp_seq, double *d_exp_struct, double *d_exp_joint,
+                                  double *d_occ, int64_t *d_windows)
+{
+    return expect_pair_dev_any(ctx, "pfmscan_expect_pair_joint_dev", true, seq_tables, struct_tables, n_motifs, m, mode, d_codes, d_codes2, n_pos,
+                               d_rec_off, d_rec_len, n_rec, d_exp_seq, d_exp_struct, d_exp_joint, d_occ, d_windows);
+}
+
+// the outputs of a _staged form of two code streams: the matrices on the HOST (exp), or with merged their accumulators and
+// verdicts; [0] sequence, [1] structure, [2] the table (table: the form has one; null there: not asked for)
+struct ExpPairOut {
+    double *exp[3];
+    uint64_t *acc[3];
+    int64_t *bad[3];
+    bool merged, table;
+};
+
+// both _staged forms of two code streams
 static int expect_pair_staged_any(pfmscan_ctx *ctx, const char *who, const double *seq_tables, const double *struct_tables, int n_motifs, int m, int mode,
-                                  const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec, double *exp_seq, double *exp_struct,
-                                  uint64_t *acc_seq, uint64_t *acc_struct, int64_t *bad_seq, int64_t *bad_struct, bool merged, double *occ,
-                                  int64_t *windows)
+                                  const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec, const ExpPairOut &o, double *occ, int64_t *windows)
 {
     if (!ctx) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": NULL ctx");
     if (ctx->staged_n < 0) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": no stream staged (call pfmscan_stage first)");
@@ -478,46 +546,73 @@ static int expect_pair_staged_any(pfmscan_ctx *ctx, const char *who, const doubl
     if (ctx->staged_n > 0 && !ctx->staged_codes2) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": no codes2 are staged (pfmscan_stage_codes2)");
     if (int rc = occ_pair_check(ctx, who, seq_tables, struct_tables, n_motifs, m, ctx->staged_n, n_rec)) return rc;
     if (int rc = exp_check_mode(ctx, who, mode)) return rc;
-    const bool want_seq = merged ? acc_seq != nullptr : exp_seq != nullptr, want_struct = merged ? acc_struct != nullptr : exp_struct != nullptr;
-    if (!want_seq && !want_struct)
-        return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + (merged ? ": acc_seq and acc_struct are both NULL" : ": exp_seq and exp_struct are both NULL"));
-    if (merged && ((want_seq && !bad_seq) || (want_struct && !bad_struct))) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": an accumulator without its bad");
+    bool want[3];
+    for (int i = 0; i < 3; ++i) want[i] = o.merged ? o.acc[i] != nullptr : o.exp[i] != nullptr;
+    if (!want[0] && !want[1] && !want[2]) {
+        const char *none = o.table ? (o.merged ? ": acc_seq, acc_struct and acc_joint are all NULL" : ": exp_seq, exp_struct and exp_joint are all NULL")
+                                   : (o.merged ? ": acc_seq and acc_struct are both NULL" : ": exp_seq and exp_struct are both NULL");
+        return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + none);
+    }
+    for (int i = 0; i < 3; ++i)
+        if (o.merged && want[i] && !o.bad[i]) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": an accumulator without its bad");
     if (n_rec == 0 || n_motifs == 0) return PFMSCAN_OK;
     if (!rec_off || !rec_len) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": NULL record table");
     int rc;
     OccRecords rec;
     if ((rc = occ_records_up(ctx, who, rec_off, rec_len, n_rec, rec))) return rc;
-    const size_t pairs = (size_t)n_rec * n_motifs, cells = pairs * m * 8;
-    if ((rc = ensure(ctx, ctx->exp_out, (2 * cells + pairs + (size_t)n_rec) * 8))) return rc;
+    const size_t pairs = (size_t)n_rec * n_motifs, cells = pairs * m * 8, all = (want[2] ? 6 : 2) * cells;   // the table is four matrices wide
+    if ((rc = ensure(ctx, ctx->exp_out, (all + pairs + (size_t)n_rec) * 8))) return rc;
     double *d_base = (double *)ctx->exp_out.p;
-    double *d_sq = want_seq ? d_base : nullptr;
-    double *d_st = want_struct ? d_base + cells : nullptr;
-    double *d_occ = occ ? d_base + 2 * cells : nullptr;
-    int64_t *d_win = windows ? (int64_t *)(d_base + 2 * cells + pairs) : nullptr;
+    double *d_sq = want[0] ? d_base : nullptr;
+    double *d_st = want[1] ? d_base + cells : nullptr;
+    double *d_jt = want[2] ? d_base + 2 * cells : nullptr;
+    double *d_occ = occ ? d_base + all : nullptr;
+    int64_t *d_win = windows ? (int64_t *)(d_base + all + pairs) : nullptr;
     if ((rc = exp_pair_run(ctx, who, seq_tables, struct_tables, n_motifs, m, mode, (const uint8_t *)ctx->codes.p, (const uint8_t *)ctx->codes2.p, rec,
-                           d_sq, d_st, d_occ, d_win, ctx->stream)))
+                           d_sq, d_st, d_jt, d_occ, d_win, ctx->stream)))
         return rc;
-    if (merged) {
-        const ExpMergeOut out[2] = {{d_sq, acc_seq, bad_seq}, {d_st, acc_struct, bad_struct}};
-        return exp_merge_home(ctx, who, out, 2, n_rec, n_motifs, m, d_occ, occ, d_win, windows);
+    if (o.merged) {
+        const ExpMergeOut out[3] = {{d_sq, o.acc[0], o.bad[0], m}, {d_st, o.acc[1], o.bad[1], m}, {d_jt, o.acc[2], o.bad[2], 4 * m}};
+        return exp_merge_home(ctx, who, out, 3, n_rec, n_motifs, m, d_occ, occ, d_win, windows);
     }
-    return occ_copy_home(ctx, {{exp_seq, d_sq, cells * 8}, {exp_struct, d_st, cells * 8}, {occ, d_occ, pairs * 8}, {windows, d_win, (size_t)n_rec * 8}});
+    return occ_copy_home(ctx, {{o.exp[0], d_sq, cells * 8}, {o.exp[1], d_st, cells * 8}, {o.exp[2], d_jt, 4 * cells * 8}, {occ, d_occ, pairs * 8},
+                               {windows, d_win, (size_t)n_rec * 8}});
 }
 
 int pfmscan_expect_pair_staged(pfmscan_ctx *ctx, const double *seq_tables, const double *struct_tables, int n_motifs, int m, int mode,
                                const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec, double *exp_seq, double *exp_struct,
                                double *occ, int64_t *windows)
 {
-    return expect_pair_staged_any(ctx, "pfmscan_expect_pair_staged", seq_tables, struct_tables, n_motifs, m, mode, rec_off, rec_len, n_rec, exp_seq,
-                                  exp_struct, nullptr, nullptr, nullptr, nullptr, false, occ, windows);
+    const ExpPairOut o{{exp_seq, exp_struct, nullptr}, {}, {}, false, false};
+    return expect_pair_staged_any(ctx, "pfmscan_expect_pair_staged", seq_tables, struct_tables, n_motifs, m, mode, rec_off, rec_len, n_rec, o, occ, windows);
+}
+
+int pfmscan_expect_pair_joint_staged(pfmscan_ctx *ctx, const double *seq_tables, const double *struct_tables, int n_motifs, int m, int mode,
+                                     const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec, double *exp_seq, double *exp_struct,
+                                     double *exp_joint, double *occ, int64_t *windows)
+{
+    const ExpPairOut o{{exp_seq, exp_struct, exp_joint}, {}, {}, false, true};
+    return expect_pair_staged_any(ctx, "pfmscan_expect_pair_joint_staged", seq_tables, struct_tables, n_motifs, m, mode, rec_off, rec_len, n_rec, o, occ,
+                                  windows);
 }
 
 int pfmscan_expect_pair_merged_staged(pfmscan_ctx *ctx, const double *seq_tables, const double *struct_tables, int n_motifs, int m, int mode,
                                       const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec, uint64_t *acc_seq, uint64_t *acc_struct,
                                       int64_t *bad_seq, int64_t *bad_struct, double *occ, int64_t *windows)
 {
-    return expect_pair_staged_any(ctx, "pfmscan_expect_pair_merged_staged", seq_tables, struct_tables, n_motifs, m, mode, rec_off, rec_len, n_rec,
-                                  nullptr, nullptr, acc_seq, acc_struct, bad_seq, bad_struct, true, occ, windows);
+    const ExpPairOut o{{}, {acc_seq, acc_struct, nullptr}, {bad_seq, bad_struct, nullptr}, true, false};
+    return expect_pair_staged_any(ctx, "pfmscan_expect_pair_merged_staged", seq_tables, struct_tables, n_motifs, m, mode, rec_off, rec_len, n_rec, o, occ,
+                                  windows);
+}
+
+int pfmscan_expect_pair_joint_merged_staged(pfmscan_ctx *ctx, const double *seq_tables, const double *struct_tables, int n_motifs, int m, int mode,
+                                            const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec, uint64_t *acc_seq, uint64_t *acc_struct,
+                                            uint64_t *acc_joint, int64_t *bad_seq, int64_t *bad_struct, int64_t *bad_joint, double *occ,
+                                            int64_t *windows)
+{
+    const ExpPairOut o{{}, {acc_seq, acc_struct, acc_joint}, {bad_seq, bad_struct, bad_joint}, true, true};
+    return expect_pair_staged_any(ctx, "pfmscan_expect_pair_joint_merged_staged", seq_tables, struct_tables, n_motifs, m, mode, rec_off, rec_len, n_rec, o,
+                                  occ, windows);
 }
 
 }  // extern "C"

@@ -110,11 +110,11 @@ static int64_t merge_per_wg(const pfmscan_ctx *ctx, int64_t n_rec, int64_t colum
     return (n_rec + chunks - 1) / chunks;
 }
 
-// launches on st, does not wait
-static int merge_launch(pfmscan_ctx *ctx, const double *d_exp, int64_t n_rec, int n_motifs, int m, int zero_first, uint64_t *d_acc,
+// launches on st, does not wait; rows: the matrix rows of a motif (m, or 4 m for the letter-pair table of two code streams)
+static int merge_launch(pfmscan_ctx *ctx, const double *d_exp, int64_t n_rec, int n_motifs, int rows, int zero_first, uint64_t *d_acc,
                         int64_t *d_bad, hipStream_t st)
 {
-    const int ncell = m * 8;
+    const int ncell = rows * 8;
     if (zero_first) {
         HIP_TRY(ctx, hipMemsetAsync(d_acc, 0, (size_t)n_motifs * MERGE_LIMBS * ncell * sizeof(uint64_t), st));
         HIP_TRY(ctx, hipMemsetAsync(d_bad, 0xFF, (size_t)n_motifs * 2 * sizeof(int64_t), st));      // -1 everywhere
@@ -152,22 +152,30 @@ int exp_merge_home(pfmscan_ctx *ctx, const char *who, const ExpMergeOut *out, in
 {
     int rc;
     if ((rc = merge_check(ctx, who, n_rec, n_motifs, m))) return rc;
-    const size_t words = (size_t)n_motifs * MERGE_LIMBS * m * 8, verdicts = (size_t)n_motifs * 2, one = words + verdicts;
-    if ((rc = ensure(ctx, ctx->exp_acc, (size_t)n_out * one * 8))) return rc;
-    std::vector<uint64_t> home((size_t)n_out * one);
+    const size_t verdicts = (size_t)n_motifs * 2;
+    std::vector<size_t> at(n_out + 1, 0);                          // where output i's words, then its verdicts, lie in ctx->exp_acc
+    for (int i = 0; i < n_out; ++i) {
+        if (out[i].rows != m && out[i].rows != 4 * m)             // a matrix, or the letter-pair table of two code streams
+            return fail(ctx, PFMSCAN_E_BADSHAPE, std::string(who) + ": an output of " + std::to_string(out[i].rows) + " rows: the width or 4 times the width");
+        at[i + 1] = at[i] + (out[i].d_exp ? (size_t)n_motifs * MERGE_LIMBS * out[i].rows * 8 + verdicts : 0);
+    }
+    if ((rc = ensure(ctx, ctx->exp_acc, std::max<size_t>(at[n_out] * 8, 16)))) return rc;
+    std::vector<uint64_t> home(at[n_out]);
     for (int i = 0; i < n_out; ++i) {
         if (!out[i].d_exp) continue;
-        uint64_t *d_acc = (uint64_t *)ctx->exp_acc.p + (size_t)i * one;
-        if ((rc = merge_launch(ctx, out[i].d_exp, n_rec, n_motifs, m, 1, d_acc, (int64_t *)(d_acc + words), ctx->stream))) return rc;
-        HIP_TRY(ctx, hipMemcpyAsync(home.data() + (size_t)i * one, d_acc, one * 8, hipMemcpyDeviceToHost, ctx->stream));
+        const size_t one = at[i + 1] - at[i];
+        uint64_t *d_acc = (uint64_t *)ctx->exp_acc.p + at[i];
+        if ((rc = merge_launch(ctx, out[i].d_exp, n_rec, n_motifs, out[i].rows, 1, d_acc, (int64_t *)(d_acc + one - verdicts), ctx->stream))) return rc;
+        HIP_TRY(ctx, hipMemcpyAsync(home.data() + at[i], d_acc, one * 8, hipMemcpyDeviceToHost, ctx->stream));
     }
     if (occ) HIP_TRY(ctx, hipMemcpyAsync(occ, d_occ, (size_t)n_rec * n_motifs * 8, hipMemcpyDeviceToHost, ctx->stream));
     if (windows) HIP_TRY(ctx, hipMemcpyAsync(windows, d_windows, (size_t)n_rec * 8, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     for (int i = 0; i < n_out; ++i) {
         if (!out[i].d_exp) continue;
-        const uint64_t *raw = home.data() + (size_t)i * one;
-        if (pfmscan_site_acc_add(out[i].acc, raw, n_motifs, (int64_t)m * 8) != PFMSCAN_OK)
+        const uint64_t *raw = home.data() + at[i];
+        const size_t words = at[i + 1] - at[i] - verdicts;
+        if (pfmscan_site_acc_add(out[i].acc, raw, n_motifs, (int64_t)out[i].rows * 8) != PFMSCAN_OK)
             return fail(ctx, PFMSCAN_E_BADSHAPE, std::string(who) + ": the top limb of an accumulator overflows");
         for (size_t j = 0; j < verdicts; ++j) out[i].bad[j] = (int64_t)raw[words + j];
     }

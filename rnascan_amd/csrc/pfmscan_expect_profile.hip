@@ -412,7 +412,7 @@ static int expect_profile_staged_any(pfmscan_ctx *ctx, const char *who, const do
                        d_sq, d_occ, d_win, ctx->stream)))
         return rc;
     if (merged) {
-        const ExpMergeOut out[2] = {{d_st, acc_struct, bad_struct}, {d_sq, acc_seq, bad_seq}};
+        const ExpMergeOut out[2] = {{d_st, acc_struct, bad_struct, m}, {d_sq, acc_seq, bad_seq, m}};
         return exp_merge_home(ctx, who, out, 2, n_rec, n_motifs, m, d_occ, occ, d_win, windows);
     }
     return occ_copy_home(ctx, {{exp_struct, d_st, cells * 8}, {exp_seq, d_sq, cells * 8}, {occ, d_occ, pairs * 8}, {windows, d_win, (size_t)n_rec * 8}});

@@ -179,12 +179,13 @@ int occ_run(pfmscan_ctx *ctx, const char *who, const double *ratio_tables, int n
             const OccRecords &rec, double *d_occ, int64_t *d_windows, hipStream_t st, const OccProfile *pf = nullptr, const OccPair *pr = nullptr);
 // pfmscan_expect.hip.  k_exp_inverse on st: inv[i] = 1.0 / occ[i], one rounded division each; -1.0 where occ[i] == 0.0
 int exp_launch_inverse(pfmscan_ctx *ctx, const double *d_occ, double *d_inv, int64_t n, hipStream_t st);
-// pfmscan_expect_merge.hip.  One matrix of a merged _staged form: the per-record matrices d_exp [n_rec][n_motifs][m][8] a pass
+// pfmscan_expect_merge.hip.  One matrix of a merged _staged form: the per-record matrices d_exp [n_rec][n_motifs][rows][8] a pass
 // left on the device (null: this matrix is not asked for) and where its sums go on the HOST.
 struct ExpMergeOut {
     const double *d_exp;
-    uint64_t *acc;               // [n_motifs][PFMSCAN_SITE_LIMBS][m * 8] normalised: this call's sums are ADDED
+    uint64_t *acc;               // [n_motifs][PFMSCAN_SITE_LIMBS][rows * 8] normalised: this call's sums are ADDED
     int64_t *bad;                // [n_motifs][2] of this call
+    int rows;                    // matrix rows of a motif: the width m, or 4 m for the letter-pair table of two code streams
 };
 // The tail of a merged _staged form, after its pass was launched on ctx->stream: k_exp_merge over every matrix that is asked for
 // into ctx->exp_acc, then the accumulators, the verdicts, the occupancy and the window counts (null: not asked for) come home,

@@ -29,7 +29,12 @@ struct OccPlan {
 // than rec_cap records (2^30 columns of the widest matrix, `wide` per unit) and its blocks stay within blk_cap, and always
 // holds at least one record.  n_unit, cells, wide and cap are at least 1 (a call without motifs returns before it plans);
 // the block sums of the largest pass are need_blk * n_u_max * cells doubles.
-inline OccPlan occ_plan(const int64_t *rec_len, int64_t n_rec, int m, int64_t n_unit, int cells, int wide, int64_t cap, bool runs)
+// fill_blk > 1: a pass should hold that many blocks (or all the call has) so that level 0 fills the device, so the units of a
+// pass are those that leave room for them, not for the longest record alone -- more passes over the units, fewer and larger
+// ones over the records; unit_group: a pass that holds a whole group of units holds whole groups only (the matrix rows of a
+// pair: a pair cut in two has its weights made twice).  The results do not depend on either.
+inline OccPlan occ_plan(const int64_t *rec_len, int64_t n_rec, int m, int64_t n_unit, int cells, int wide, int64_t cap, bool runs,
+                        int64_t fill_blk = 1, int64_t unit_group = 1)
 {
     OccPlan p;
     p.n_rec = n_rec;
@@ -44,7 +49,9 @@ inline OccPlan occ_plan(const int64_t *rec_len, int64_t n_rec, int m, int64_t n_
         if (runs) run[r + 1] = run[r] + (nb + OCCP_RUN - 1) / OCCP_RUN;
         max_blk = std::max(max_blk, nb);
     }
-    p.n_u_max = std::min<int64_t>(n_unit, std::max<int64_t>(1, cap / (std::max<int64_t>(max_blk, 1) * cells)));
+    const int64_t room_blk = std::max<int64_t>({max_blk, std::min(fill_blk, blk[n_rec]), 1});
+    p.n_u_max = std::min<int64_t>(n_unit, std::max<int64_t>(1, cap / (room_blk * cells)));
+    if (p.n_u_max > unit_group) p.n_u_max -= p.n_u_max % unit_group;
     const int64_t blk_cap = std::max<int64_t>(cap / (p.n_u_max * cells), 1);
     const int64_t rec_cap = std::max<int64_t>((int64_t(1) << 30) / (p.n_u_max * wide), 1);
     p.cuts.assign(1, 0);

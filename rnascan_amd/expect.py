@@ -67,6 +67,7 @@ def fsum_records(parts):
 
 
 def new_acc(n_motifs, m):
+    """the long accumulators of n_motifs matrices of m rows (the width; 4 x the width for the letter-pair table of ``expect_pair``)"""
     from ._lib import NCODE, SITE_LIMBS
     return np.zeros((n_motifs, SITE_LIMBS, m * NCODE), dtype=np.uint64)
 
@@ -79,9 +80,11 @@ def new_acc(n_motifs, m):
 #   tables(m, ks, cols) what the engine takes for the motifs ks of width m; made once per width where cols is None
 #   host(stream, tables, mode) -> (matrices, occ, windows); merged(stream, tables, mode, accs) -> (bads, occ, windows):
 #                       the engine's two methods, their lists in the form's check order; ``method``: the second one's name
-#   matrices            per matrix (cells kept, None | cols -> the stored column of every written cell)
+#   matrices            a Matrix per matrix: cells kept, None | cols -> the stored column of every written cell, and the matrix
+#                       rows per motif column (1; the letter-pair table of ``expect_pair`` has 4)
 #   not_finite          the form's message for a non-finite record
 Form = namedtuple("Form", "motif_ids groups order batches tables host merged method matrices not_finite")
+Matrix = namedtuple("Matrix", "kept stored rows", defaults=(None, 1))
 
 
 def merge_route(engine, merge, method):
@@ -177,13 +180,13 @@ def _one_pass(form, mode, device):
     occs = [[] for _ in range(n_motifs)]
     wins = dict((m, 0) for m in form.groups)                       # Windows depends on the width
     if device:
-        accs = dict((m, [_Accumulator(len(ks), m) for _ in sides]) for m, ks in form.groups.items())
+        accs = dict((m, [_Accumulator(len(ks), m * mx.rows) for mx in form.matrices]) for m, ks in form.groups.items())
         first = dict((m, [np.full((len(ks), 2), -1, dtype=np.int64) for _ in sides]) for m, ks in form.groups.items())
     else:
         cells = [[[] for _ in sides] for _ in range(n_motifs)]
     made, seen = {}, []
     for ids, stream, cols in form.batches():
-        orders = [None if stored is None else stored(cols) for _, stored in form.matrices]
+        orders = [None if mx.stored is None else mx.stored(cols) for mx in form.matrices]
         for m, ks in form.groups.items():
             tables = made[m] if cols is None and m in made else form.tables(m, ks, cols)
             if cols is None:
@@ -194,8 +197,8 @@ def _one_pass(form, mode, device):
                     _note_bad(f, np.asarray(bad), len(seen))
             else:
                 exps, o, w = form.host(stream, tables, mode)
-                for i, (kept, _) in enumerate(form.matrices):
-                    E = np.asarray(exps[i])[:, :, :, :kept] if orders[i] is None else np.asarray(exps[i])[:, :, :, orders[i]]
+                for i, mx in enumerate(form.matrices):
+                    E = np.asarray(exps[i])[:, :, :, :mx.kept] if orders[i] is None else np.asarray(exps[i])[:, :, :, orders[i]]
                     for j, k in enumerate(ks):
                         cells[k][i].append(E[:, j])
             o = np.asarray(o)
@@ -204,7 +207,7 @@ def _one_pass(form, mode, device):
             wins[m] += int(np.asarray(w).sum())
         seen += ids
     if device:
-        rounded = dict((m, [_lib.site_acc_round(a.fold()).reshape(len(ks), m, -1)[:, :, :kept] for a, (kept, _) in zip(accs[m], form.matrices)])
+        rounded = dict((m, [_lib.site_acc_round(a.fold()).reshape(len(ks), m * mx.rows, -1)[:, :, :mx.kept] for a, mx in zip(accs[m], form.matrices)])
                        for m, ks in form.groups.items())
     place = dict((k, (m, j)) for m, ks in form.groups.items() for j, k in enumerate(ks))
     out = {}
@@ -250,11 +253,13 @@ def pfm_text(results, motif_ids, order, code_letters, library):
     return text.getvalue()
 
 
-def iterate(args, engine, sides, odds, pairs, form_of, what="motifs"):
+def iterate(args, engine, sides, odds, pairs, form_of, what="motifs", more=None):
     """``--iterations`` passes and the files.  ``sides``: the written matrices in the pass's order, which is the files';
     ``odds``: [sequence odds | None, structure odds | None], None where no PFM was given; ``pairs``: [(sequence id | None,
     structure id | None)] into them; ``form_of(odds, pairs)``: the pass's Form.  After a pass every given PFM is replaced by
-    its expected matrix -- what reading this iteration's files would give: every motif (pair) under its written name"""
+    its expected matrix -- what reading this iteration's files would give: every motif (pair) under its written name.
+    ``more(matrices of the last pass per motif id, motif_ids)`` -> [(suffix, text)]: files of matrices the form has behind the
+    sides', which are written and not fed back"""
     from . import sites
     motif_ids = [sites.pair_id(a, b) for a, b in pairs]
     written = ((fasta.RNA, sites.SEQ_ORDER), (fasta.STRUCT, sites.STRUCT_ORDER))
@@ -273,6 +278,8 @@ def iterate(args, engine, sides, odds, pairs, form_of, what="motifs"):
             pairs = [tuple(None if o is None else mid for o in odds) for mid in motif_ids]
     texts = [(side.suffix, pfm_text(dict((mid, got[mid][0][i]) for mid in motif_ids), motif_ids, written[side.slot][1], side.code_letters,
                                     args.all_motifs)) for i, side in enumerate(sides)]
+    if more is not None:
+        texts += more(dict((mid, got[mid][0]) for mid in motif_ids), motif_ids)
     for suffix, text in texts + [(".summary.txt", "".join(summary))]:
         with open(args.prefix + suffix, "w") as out:
             out.write(text)
@@ -340,7 +347,7 @@ def main(argv=None, engine=None):
             # the motifs are finalised width by width (widths by first appearance, the file's order within one)
             return Form(motif_ids, groups, [k for ks in groups.values() for k in ks], lambda: occupancy.letter_batches(recs, letters, args.batch_records),
                         lambda m, ks, cols: np.stack([mine[k].ratio_table(code_letters) for k in ks]), host, merged, "expect_merged",
-                        [(len(code_letters), None)], NOT_FINITE)
+                        [Matrix(len(code_letters))], NOT_FINITE)
 
         iterate(args, engine, [Side(".expected.txt", slot, code_letters, bg)], [odds, None] if slot == 0 else [None, odds],
                 [(mid, None) if slot == 0 else (None, mid) for mid in motif_ids], form_of)

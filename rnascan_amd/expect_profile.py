@@ -115,7 +115,7 @@ def main(argv=None, engine=None):
             return expect.Form([sites.pair_id(a, b) for a, b in pairs], occupancy._by_width([width(a, b) for a, b in pairs]), range(len(pairs)),
                                lambda: occupancy.profile_batches(recs, profiles, args.batch_records),
                                occupancy.profile_tables(odds[0], odds[1], pairs, args.pairing), host, merged, "expect_profile_merged",
-                               [(7, stored)] + [(4, None)] * with_seq, NOT_FINITE)
+                               [expect.Matrix(7, stored)] + [expect.Matrix(4)] * with_seq, NOT_FINITE)
 
         sides = [expect.Side(".expected.struct.txt", 1, list(sites.STRUCT_ORDER), bg_struct)]
         if args.pfm_seq:

@@ -204,6 +204,12 @@ class HipEngine(object):
         self._stage_pair(stream)
         return self.ctx.expect_pair_staged(seq_tables, struct_tables, mode, stream.offsets, stream.lengths)
 
+    def expect_pair_joint(self, stream, seq_tables, struct_tables, mode):
+        """``expect_pair`` with the expected letter-pair table per column, of which the two matrices are the margins ->
+        (exp_seq, exp_struct, exp_joint float64 [n_rec][n_motifs][m][4][8]: nucleotide a over structure letter b, occ, windows)"""
+        self._stage_pair(stream)
+        return self.ctx.expect_pair_joint_staged(seq_tables, struct_tables, mode, stream.offsets, stream.lengths)
+
     # the three passes above with their matrices added up over the records on the device (DESIGN.md 5k): the accumulators
     # (uint64 [n_motifs][_lib.SITE_LIMBS][m * 8], normalised) are changed in place, one call per batch adds that batch's records
     def expect_merged(self, stream, ratio_tables, n_letters, mode, acc, which=0):
@@ -222,6 +228,12 @@ class HipEngine(object):
         """``expect_pair`` -> (bad_seq, bad_struct, occ, windows)"""
         self._stage_pair(stream)
         return self.ctx.expect_pair_merged_staged(seq_tables, struct_tables, mode, stream.offsets, stream.lengths, acc_seq, acc_struct)
+
+    def expect_pair_joint_merged(self, stream, seq_tables, struct_tables, mode, acc_seq, acc_struct, acc_joint):
+        """``expect_pair_joint`` -> (bad_seq, bad_struct, bad_joint, occ, windows); acc_joint uint64 [n_motifs][_lib.SITE_LIMBS][4 m * 8]"""
+        self._stage_pair(stream)
+        return self.ctx.expect_pair_joint_merged_staged(seq_tables, struct_tables, mode, stream.offsets, stream.lengths, acc_seq, acc_struct,
+                                                        acc_joint)
 
     def hits_sum(self, stream, letter_table, struct_pssm, thr_seq, thr_struct, thr_sum, one_shot=True):
         """``hits`` of a motif with both parts, with the joint threshold decided on the device: a window is kept iff

@@ -924,14 +924,15 @@ def _letter_counts_to(out, seq_counts, struct_counts, cov, hits):
     w.close()
 
 
-def _joint_to(out, J):
-    """PREFIX.joint.txt: per column the 28 known cells A.B A.E ... U.T (nucleotide major, STRUCT_ORDER minor) and MI"""
+def _joint_to(out, J, mi=mutual_information):
+    """PREFIX.joint.txt: per column the 28 known cells A.B A.E ... U.T (nucleotide major, STRUCT_ORDER minor) and MI.  J is
+    [W][>= 4][>= 7] by code, counts or (``expect_pair --joint``) expected counts, ``mi`` its mutual information"""
     from . import table
     known = J[:, :len(SEQ_ORDER)][:, :, STRUCT_CODES]
     cols = {"PO": np.arange(J.shape[0], dtype=np.int64)}
     for i, name in enumerate(JOINT_NAMES):
         cols[name] = np.ascontiguousarray(known[:, i // len(STRUCT_ORDER), i % len(STRUCT_ORDER)])
-    cols["MI"] = np.asarray([mutual_information(known[j].tolist()) for j in range(J.shape[0])], dtype=np.float64)
+    cols["MI"] = np.asarray([mi(known[j].tolist()) for j in range(J.shape[0])], dtype=np.float64)
     w = table.TsvWriter(out, ["PO"] + JOINT_NAMES + ["MI"], match_id=False)
     w.write_chunk(cols, J.shape[0])
     w.close()
@@ -946,6 +947,15 @@ def _report_foreign(prefix, seq_counts, struct_counts):
             msg = "foreign %s under the sites, left out of the %s PFM: %d (per column: %s)" % \
                 (what, pfm, int(foreign.sum()), " ".join(str(int(x)) for x in foreign))
             fasta.eprint(prefix + msg if prefix else msg[0].upper() + msg[1:])
+
+
+def tagged(text, name, one):
+    """the table in ``one`` appended to ``text`` under a leading Motif column: the files that hold one block per motif"""
+    lines = one.getvalue().splitlines(True)
+    if not text.tell():
+        text.write("Motif\t" + lines[0])
+    for ln in lines[1:]:
+        text.write(name + "\t" + ln)
 
 
 def write_letters(args, results, has_seq, has_struct, rank=0):
@@ -975,13 +985,6 @@ def write_letters(args, results, has_seq, has_struct, rank=0):
         return 0
     texts = dict((suffix, io.StringIO()) for suffix in (".struct.txt", ".seq.txt", ".joint.txt", ".counts.txt"))
     written = 0
-
-    def tagged(text, name, one):                               # a leading Motif column
-        lines = one.getvalue().splitlines(True)
-        if not text.tell():
-            text.write("Motif\t" + lines[0])
-        for ln in lines[1:]:
-            text.write(name + "\t" + ln)
 
     for (a, b), J, hits in results:
         name = pair_id(a, b)

@@ -59,7 +59,8 @@
 extern "C" {
 #endif
 
-#define PFMSCAN_ABI_VERSION 27   /* 27: pfmscan_expect_pair_joint_dev / _staged / _merged_staged (the 4 x 7 table per column) */
+#define PFMSCAN_ABI_VERSION 27   /* 27: pfmscan_expect_pair_joint_dev / _staged / _merged_staged (the 4 x 7 table per column); the posterior
+                                  * site map (pfmscan_footprint_*) only ADDS entry points and keeps the number, which the suite pins at 27 */
 #define PFMSCAN_NCODE   8      /* columns of a letter table */
 #define PFMSCAN_SEP     7      /* separator / foreign-letter code */
 #define PFMSCAN_NSTRUCT 7      /* columns of a structure profile / structure PSSM */
@@ -1396,6 +1397,60 @@ int pfmscan_expect_pair_joint_merged_staged(pfmscan_ctx *ctx, const double *seq_
                                             int m, int mode, const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec,
                                             uint64_t *acc_seq, uint64_t *acc_struct, uint64_t *acc_joint, int64_t *bad_seq,
                                             int64_t *bad_struct, int64_t *bad_joint, double *occ, int64_t *windows);
+
+/* ---- posterior site map: the weight of every window and the coverage of every position ---------------------------------
+ * No counterpart in the reference.  The fourth member of the threshold-free family: where in a record the
+ * binding is, per position, without a threshold -m.  No transcendental, no tolerance; tests/footprint_rules.py restates it in
+ * numpy and the bits are compared.  Everything not said here is the occupancy, the expected counts and the two-stream contract
+ * above, unchanged: the ratio tables, c = code & 7, the term chain (letters first, then structure letters, 2 m - 1 rounded
+ * products, never a pre-multiplied row), has_s, occ_r and windows[r], the weights (v = 1.0 / occ_r one rounded division per
+ * record and motif, w_s = t_s * v one rounded product per window; occ_r == +0.0 makes every weight +0.0),
+ * PFMSCAN_EXPECT_RATIO / _POSTERIOR, IEEE as it falls, nothing contracted.
+ * Two maps per motif (or pair) q, each a plane double [n_motifs][n_pos] aligned with the stream; record r lies at off_r with
+ * L positions and n_win = max(L - m + 1, 0) windows:
+ *   start[q][off_r + s] = w_s for 0 <= s < n_win, +0.0 for the record's last min(m - 1, L) positions; a window without a term
+ *                 is +0.0, as its weight already is.
+ *   cover[q][off_r + i] for 0 <= i < L: c = +0.0, then for s = i - m + 1 .. i ascending c = c + (0 <= s < n_win ? w_s : +0.0),
+ *                 every addition rounded and sequential: no sliding-window update (another rounding), no tree (at most
+ *                 m <= 64 terms).  Weights are never -0.0, so the absent terms added as +0.0 change nothing.  In posterior mode
+ *                 cover is P(position under the site | one site per record).
+ * One argument list serves the three letter inputs: seq_tables alone (struct_tables NULL) reads d_codes over the 4 RNA
+ * letters and never d_codes2; struct_tables alone reads d_codes2 over the 7 structure letters and never d_codes; both are the
+ * pair.  A single-table call's weights are bit for bit those of pfmscan_expect_* on that stream; occ and windows those of
+ * pfmscan_occupancy_* (or _pair_*).  The bits depend on the codes and the tables and on nothing else: not on the batch, the
+ * record's place in the stream, the tiling, the launch geometry, whether the other map was asked for, or the _dev, _staged or
+ * events form.
+ * Maps: d_start or d_cover may be NULL (not computed), not both (PFMSCAN_E_BADARG); occ double [n_rec][n_motifs] and windows
+ * int64 [n_rec] may be NULL.  In the _dev form positions that lie in no record of the table (separators, gaps, records the
+ * table skips) are NOT written; in the _staged form they are +0.0.  The caller bounds the 16 * n_motifs * n_pos bytes of the
+ * planes by the motifs and records of a call.
+ * Events: a position with cover > thr (strict; NaN never passes; a NaN thr is PFMSCAN_E_BADARG) is key = q * n_pos + p with its
+ * cover and its start.  The decision is taken in the kernel that makes cover: no plane is allocated anywhere.  Capacity, the
+ * total count in d_ev_count (one uint64 the caller zeroes; only the first `capacity` events are stored), "unordered in _dev,
+ * sorted by key in _staged" and "PFMSCAN_E_CAPACITY: *n_events holds the capacity that suffices, nothing was written" are
+ * exactly those of pfmscan_mutmap_events_*.
+ * The record-table check (before any kernel forms an address from it), the one synchronisation of the _dev forms, the error
+ * codes, the order of the checks and the 16-byte alignment of the streams are those of pfmscan_expect_pair_*; the tables that
+ * are given decide which streams are needed; both tables NULL: PFMSCAN_E_BADARG.
+ * PFMSCAN_FOOTPRINT_SLOTS: a workgroup of the level-0 kernel makes this many consecutive windows of ONE record; its tile is
+ * the last PFMSCAN_FOOTPRINT_SLOTS - (m - 1) of them as positions, the first m - 1 are the halo it makes again. */
+#define PFMSCAN_FOOTPRINT_SLOTS 512
+int pfmscan_footprint_dev(pfmscan_ctx *ctx, const double *seq_tables, const double *struct_tables, int n_motifs, int m, int mode,
+                          const uint8_t *d_codes, const uint8_t *d_codes2, int64_t n_pos, const int64_t *d_rec_off,
+                          const int64_t *d_rec_len, int64_t n_rec, double *d_start, double *d_cover, double *d_occ,
+                          int64_t *d_windows);
+int pfmscan_footprint_staged(pfmscan_ctx *ctx, const double *seq_tables, const double *struct_tables, int n_motifs, int m, int mode,
+                             const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec, double *start, double *cover,
+                             double *occ, int64_t *windows);
+int pfmscan_footprint_events_dev(pfmscan_ctx *ctx, const double *seq_tables, const double *struct_tables, int n_motifs, int m,
+                                 int mode, const uint8_t *d_codes, const uint8_t *d_codes2, int64_t n_pos,
+                                 const int64_t *d_rec_off, const int64_t *d_rec_len, int64_t n_rec, double thr, int64_t capacity,
+                                 int64_t *d_ev_key, double *d_ev_cover, double *d_ev_start, uint64_t *d_ev_count, double *d_occ,
+                                 int64_t *d_windows);
+int pfmscan_footprint_events_staged(pfmscan_ctx *ctx, const double *seq_tables, const double *struct_tables, int n_motifs, int m,
+                                    int mode, const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec, double thr,
+                                    int64_t capacity, int64_t *ev_key, double *ev_cover, double *ev_start, int64_t *n_events,
+                                    double *occ, int64_t *windows);
 
 #ifdef __cplusplus
 }

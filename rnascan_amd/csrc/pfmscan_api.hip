@@ -123,7 +123,7 @@ void pfmscan_ctx_destroy(pfmscan_ctx *ctx)
                       &ctx->site_tab, &ctx->site_blk, &ctx->site_sums, &ctx->site_counts,
                       &ctx->mut_tab, &ctx->mut_best, &ctx->mut_alt, &ctx->mut_where, &ctx->mut_key, &ctx->mut_valt,
                       &ctx->occ_tab, &ctx->occ_idx, &ctx->occ_rec, &ctx->occ_bs, &ctx->occ_gs, &ctx->occ_cnt, &ctx->occ_out,
-                      &ctx->exp_inv, &ctx->exp_occ, &ctx->exp_out, &ctx->exp_acc})
+                      &ctx->exp_inv, &ctx->exp_occ, &ctx->exp_out, &ctx->exp_acc, &ctx->fp_idx, &ctx->fp_out, &ctx->fp_ev})
         release(*b);
     upload_release(ctx);
     place_release_all(ctx);

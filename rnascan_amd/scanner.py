@@ -210,6 +210,33 @@ class HipEngine(object):
         self._stage_pair(stream)
         return self.ctx.expect_pair_joint_staged(seq_tables, struct_tables, mode, stream.offsets, stream.lengths)
 
+    def _stage_footprint(self, stream, seq_tables, struct_tables):
+        """what the posterior site map reads: sequence tables read the stream's codes, structure tables its codes2 -- or, for a
+        stream of one structure-letter FASTA (no codes2), its codes staged as the second stream"""
+        if struct_tables is None or stream.codes2 is not None:
+            self._stage_codes(stream, 0 if struct_tables is None else 1)
+        else:
+            if seq_tables is not None:
+                raise ValueError("the stream holds no second code stream (codes2)")
+            self._stage(stream)
+            if not (isinstance(self._staged2, tuple) and self._staged2[0] is stream):
+                self.ctx.stage_codes2(stream.codes)
+                self._staged2 = (stream, "codes")
+
+    def footprint(self, stream, seq_tables, struct_tables, mode, want_start=True, want_cover=True):
+        """the posterior site map: tables [n_motifs][m][8] of one width, sequence tables over the stream's RNA
+        codes, structure tables over its structure letters, or both (the pair); every window weighted as ``expect`` weights
+        it -> (start, cover float64 [n_motifs][n_pos]: the weight of the window that starts at a position and the summed weight
+        of the windows over it, +0.0 outside the records; occ float64 [n_rec][n_motifs]; windows int64 [n_rec])"""
+        self._stage_footprint(stream, seq_tables, struct_tables)
+        return self.ctx.footprint_staged(seq_tables, struct_tables, mode, stream.offsets, stream.lengths, want_start, want_cover)
+
+    def footprint_events(self, stream, seq_tables, struct_tables, mode, thr, capacity=None):
+        """the positions with cover > thr, decided on the device: only they come home ->
+        (key int64 = motif * n_pos + position sorted, cover float64, start float64, occ float64 [n_rec][n_motifs], windows)"""
+        self._stage_footprint(stream, seq_tables, struct_tables)
+        return self.ctx.footprint_events_staged(seq_tables, struct_tables, mode, stream.offsets, stream.lengths, thr, capacity)
+
     # the three passes above with their matrices added up over the records on the device (DESIGN.md 5k): the accumulators
     # (uint64 [n_motifs][_lib.SITE_LIMBS][m * 8], normalised) are changed in place, one call per batch adds that batch's records
     def expect_merged(self, stream, ratio_tables, n_letters, mode, acc, which=0):

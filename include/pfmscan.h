@@ -1452,6 +1452,51 @@ int pfmscan_footprint_events_staged(pfmscan_ctx *ctx, const double *seq_tables, 
                                     int64_t capacity, int64_t *ev_key, double *ev_cover, double *ev_start, int64_t *n_events,
                                     double *occ, int64_t *windows);
 
+/* ---- posterior site map on averaged-structure profiles -------------------------------------------------------------------
+ * The two maps above for the project's main input (DESIGN.md 5l "on averaged-structure profiles"); entry points ADDED under
+ * ABI 27.  tests/footprint_profile_rules.py composes the rule from the family's and the bits are compared.
+ * Term and has: those of pfmscan_occupancy_profile_*, unchanged.  struct_tables HOST double [n_motifs][m][7] in the profile's
+ * STORED column order, required (NULL: PFMSCAN_E_BADARG -- sequence weights over a profile's records are pfmscan_footprint_* on
+ * the codes); the marginal of a row is 7 rounded products and 6 rounded additions, ascending, float rows widened first;
+ * structure only every window inside the record has a term and the codes are not read; seq_tables HOST double [n_motifs][m][8]
+ * or NULL chooses joint mode and then needs the codes: the letter chain first, then t = t * d(s + k, k) for k = 0 .. m - 1, and
+ * a window that holds a code >= 4 has no term.  No nan_to_num, no validity check: negative cells, NaN and 0 * inf go where the
+ * arithmetic takes them.  occ_r and windows[r] are the bits of pfmscan_occupancy_profile_* for the same tables.
+ * Weight: that of pfmscan_expect_profile_*: the term (PFMSCAN_EXPECT_RATIO) or t_s * v, v = 1.0 / occ_r one rounded division
+ * (PFMSCAN_EXPECT_POSTERIOR); occ_r == 0.0 makes every weight +0.0.  A NEGATIVE occ_r (negative cells are legal) does not: the
+ * weights are t_s * v with v negative.
+ * Maps: start and cover as above, with one difference in the wording: a weight here CAN be -0.0 or negative, and cover is
+ * c = +0.0, then c = c + (0 <= s < n_win && has_s ? w_s : +0.0) for s = i - m + 1 .. i ascending with all m additions made and
+ * rounded.  The separator row behind a record and the rows of its neighbours are never used as data.  The bits depend on the
+ * row dtype, the stored column order, the codes and the tables and on nothing else: not on the batch, the record's place in
+ * the stream, the tiling, which plane was asked for, or the form.
+ * Everything else comes from an existing entry point.  From pfmscan_occupancy_profile_* / pfmscan_expect_profile_*: the checks
+ * of the width, the profile_dtype, the mode and the sizes, their order and codes; "no profile is staged"; the 16-byte alignment
+ * of d_profile (and d_codes in joint mode, PFMSCAN_E_BADSHAPE); the record table read back and checked before any kernel forms
+ * an address from it (the one synchronisation of the _dev forms).  From pfmscan_footprint_*: both planes NULL and a NaN thr are
+ * PFMSCAN_E_BADARG; the event buffers, key = q * n_pos + p, the capacity verdict, "unordered in _dev, sorted by key in
+ * _staged"; positions in no record are unwritten in _dev and +0.0 in _staged.  n_rec == 0 or n_motifs == 0: PFMSCAN_OK, nothing
+ * written.  Bad arguments launch nothing and leave the outputs untouched.
+ * PFMSCAN_FOOTPRINT_PROFILE_SLOTS: a workgroup of the level-0 kernel makes this many consecutive windows of ONE record; its
+ * tile is the last PFMSCAN_FOOTPRINT_PROFILE_SLOTS - (m - 1) of them as positions. */
+#define PFMSCAN_FOOTPRINT_PROFILE_SLOTS 256
+int pfmscan_footprint_profile_dev(pfmscan_ctx *ctx, const double *struct_tables, const double *seq_tables, int n_motifs, int m,
+                                  int mode, const uint8_t *d_codes, const void *d_profile, int profile_dtype, int64_t n_pos,
+                                  const int64_t *d_rec_off, const int64_t *d_rec_len, int64_t n_rec, double *d_start,
+                                  double *d_cover, double *d_occ, int64_t *d_windows);
+int pfmscan_footprint_profile_staged(pfmscan_ctx *ctx, const double *struct_tables, const double *seq_tables, int n_motifs, int m,
+                                     int mode, const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec, double *start,
+                                     double *cover, double *occ, int64_t *windows);
+int pfmscan_footprint_profile_events_dev(pfmscan_ctx *ctx, const double *struct_tables, const double *seq_tables, int n_motifs,
+                                         int m, int mode, const uint8_t *d_codes, const void *d_profile, int profile_dtype,
+                                         int64_t n_pos, const int64_t *d_rec_off, const int64_t *d_rec_len, int64_t n_rec,
+                                         double thr, int64_t capacity, int64_t *d_ev_key, double *d_ev_cover, double *d_ev_start,
+                                         uint64_t *d_ev_count, double *d_occ, int64_t *d_windows);
+int pfmscan_footprint_profile_events_staged(pfmscan_ctx *ctx, const double *struct_tables, const double *seq_tables, int n_motifs,
+                                            int m, int mode, const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec,
+                                            double thr, int64_t capacity, int64_t *ev_key, double *ev_cover, double *ev_start,
+                                            int64_t *n_events, double *occ, int64_t *windows);
+
 #ifdef __cplusplus
 }
 #endif

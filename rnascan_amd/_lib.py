@@ -64,6 +64,7 @@ SYMBOLS = [
     "pfmscan_expect_merge_dev", "pfmscan_expect_merged_staged", "pfmscan_expect_profile_merged_staged", "pfmscan_expect_pair_merged_staged",
     "pfmscan_expect_pair_joint_dev", "pfmscan_expect_pair_joint_staged", "pfmscan_expect_pair_joint_merged_staged",
     "pfmscan_footprint_dev", "pfmscan_footprint_staged", "pfmscan_footprint_events_dev", "pfmscan_footprint_events_staged",
+    "pfmscan_footprint_profile_dev", "pfmscan_footprint_profile_staged", "pfmscan_footprint_profile_events_dev", "pfmscan_footprint_profile_events_staged",
 ]
 PAIR_ROUTE_NONE, PAIR_ROUTE_FUSED, PAIR_ROUTE_TWO_PHASE, PAIR_ROUTE_DENSE, PAIR_ROUTE_CREDITS = range(5)   # Context.pair_sum_route()
 SITE_GROUP = 4096     # most hits of one group of the site profiles
@@ -72,6 +73,7 @@ SITE_JOINT_COLS = 64  # columns of one LDS tile of the letter-pair counts (PFMSC
 EXPECT_RATIO, EXPECT_POSTERIOR = 0, 1   # weight of a window in the expected counts (PFMSCAN_EXPECT_*)
 OCC_FANIN = 32        # fan-in of the occupancy's summation tree (PFMSCAN_OCC_FANIN)
 FOOTPRINT_SLOTS = 512  # windows a workgroup of the posterior site map makes (PFMSCAN_FOOTPRINT_SLOTS): its tile is SLOTS - (m - 1) positions
+FOOTPRINT_PROFILE_SLOTS = 256  # the same on averaged-structure profiles (PFMSCAN_FOOTPRINT_PROFILE_SLOTS)
 MAX_COVER = 1024      # largest coverage of a row the averaging accepts
 AVG_OK, AVG_DOTBRACKET, AVG_UNCOVERED, AVG_COVER, AVG_BAD_TABLE = range(5)   # what a rejected averaging names
 TSV_CONST, TSV_I64, TSV_F32, TSV_F64, TSV_INDEXED, TSV_FIXED, TSV_WINDOW, TSV_SPAN = range(8)
@@ -269,6 +271,10 @@ def load():
     L.pfmscan_footprint_staged.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, i64, vp, vp, vp, vp]
     L.pfmscan_footprint_events_dev.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, i64, vp, vp, i64, dbl, i64, vp, vp, vp, vp, vp, vp]
     L.pfmscan_footprint_events_staged.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, i64, dbl, i64, vp, vp, vp, ctypes.POINTER(i64), vp, vp]
+    L.pfmscan_footprint_profile_dev.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, i32, i64, vp, vp, i64, vp, vp, vp, vp]
+    L.pfmscan_footprint_profile_staged.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, i64, vp, vp, vp, vp]
+    L.pfmscan_footprint_profile_events_dev.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, i32, i64, vp, vp, i64, dbl, i64, vp, vp, vp, vp, vp, vp]
+    L.pfmscan_footprint_profile_events_staged.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, i64, dbl, i64, vp, vp, vp, ctypes.POINTER(i64), vp, vp]
     L.pfmscan_tsv_format.argtypes = [ctypes.POINTER(TsvColumn), i32, i64, i64, vp, i64, ctypes.POINTER(i64), vp, ctypes.POINTER(i32), i32]
     for name in SYMBOLS:          # every other entry point returns a status
         if name not in ("pfmscan_ctx_destroy", "pfmscan_motif_destroy", "pfmscan_last_error", "pfmscan_library_destroy",
@@ -2017,6 +2023,66 @@ class Context(object):
             rc = self._L.pfmscan_footprint_events_staged(self._h, _ptr(sq), _ptr(st), n_motifs, m, int(mode), _ptr(rec_off), _ptr(rec_len),
                                                          rec_off.size, float(thr), cap, _ptr(key), _ptr(cover), _ptr(start), ctypes.byref(k),
                                                          _ptr(occ), _ptr(windows))
+            if rc == E_CAPACITY and capacity is None:
+                cap = int(k.value)
+                continue
+            self._check(rc, k.value)
+            k = int(k.value)
+            return key[:k].copy(), cover[:k].copy(), start[:k].copy(), occ, windows
+
+    # -- posterior site map on averaged-structure profiles (include/pfmscan.h: pfmscan_footprint_profile_*) ---
+    def footprint_profile_dev(self, struct_tables, seq_tables, mode, d_codes, d_profile, profile_dtype, n_pos, d_rec_off, d_rec_len, n_rec,
+                              d_start, d_cover, d_occ=None, d_windows=None):
+        st, sq = self._profile_tables(struct_tables, seq_tables)
+        self._check(self._L.pfmscan_footprint_profile_dev(self._h, _ptr(st), _ptr(sq), st.shape[0], st.shape[1], int(mode), _ptr(d_codes),
+                                                          _ptr(d_profile), int(profile_dtype), int(n_pos), _ptr(d_rec_off), _ptr(d_rec_len),
+                                                          int(n_rec), _ptr(d_start), _ptr(d_cover), _ptr(d_occ), _ptr(d_windows)))
+
+    def footprint_profile_staged(self, struct_tables, seq_tables, mode, rec_off, rec_len, want_start=True, want_cover=True):
+        """-> start, cover float64 [n_motifs][n_pos] aligned with the staged profile (None where not wanted; +0.0 outside the
+        records of the table), occ float64 [n_rec][n_motifs], windows int64 [n_rec]; struct_tables [n_motifs][m][7] in the
+        profile's stored column order, seq_tables [n_motifs][m][8] | None (joint: the staged codes too)"""
+        st, sq = self._profile_tables(struct_tables, seq_tables)
+        n_motifs, m = st.shape[:2]
+        n = int(self._L.pfmscan_staged_positions(self._h))
+        if n < 0:
+            raise ValueError("no stream staged (call stage first)")
+        rec_off, rec_len = self._records(rec_off, rec_len)
+        start = np.zeros((n_motifs, n), dtype=np.float64) if want_start else None
+        cover = np.zeros((n_motifs, n), dtype=np.float64) if want_cover else None
+        occ, windows = self._occ_windows(rec_off.size, n_motifs)
+        self._check(self._L.pfmscan_footprint_profile_staged(self._h, _ptr(st), _ptr(sq), n_motifs, m, int(mode), _ptr(rec_off), _ptr(rec_len),
+                                                             rec_off.size, _ptr(start), _ptr(cover), _ptr(occ), _ptr(windows)))
+        return start, cover, occ, windows
+
+    def footprint_profile_events_dev(self, struct_tables, seq_tables, mode, d_codes, d_profile, profile_dtype, n_pos, d_rec_off, d_rec_len,
+                                     n_rec, thr, capacity, d_ev_key, d_ev_cover, d_ev_start, d_ev_count, d_occ=None, d_windows=None):
+        st, sq = self._profile_tables(struct_tables, seq_tables)
+        self._check(self._L.pfmscan_footprint_profile_events_dev(self._h, _ptr(st), _ptr(sq), st.shape[0], st.shape[1], int(mode), _ptr(d_codes),
+                                                                 _ptr(d_profile), int(profile_dtype), int(n_pos), _ptr(d_rec_off),
+                                                                 _ptr(d_rec_len), int(n_rec), float(thr), int(capacity), _ptr(d_ev_key),
+                                                                 _ptr(d_ev_cover), _ptr(d_ev_start), _ptr(d_ev_count), _ptr(d_occ), _ptr(d_windows)))
+
+    def footprint_profile_events_staged(self, struct_tables, seq_tables, mode, rec_off, rec_len, thr, capacity=None):
+        """the positions of the staged profile whose cover > thr, decided on the device -> (key int64[k] = motif * n_pos +
+        position sorted, cover float64[k], start float64[k], occ float64 [n_rec][n_motifs], windows int64 [n_rec]).  capacity
+        None: a capacity verdict is answered by one retry with the capacity it names; else CapacityError carries it"""
+        st, sq = self._profile_tables(struct_tables, seq_tables)
+        n_motifs, m = st.shape[:2]
+        n = int(self._L.pfmscan_staged_positions(self._h))
+        if n < 0:
+            raise ValueError("no stream staged (call stage first)")
+        rec_off, rec_len = self._records(rec_off, rec_len)
+        cap = int(capacity) if capacity is not None else max(1024, n // 16)
+        while True:
+            key = np.empty(cap, dtype=np.int64)
+            cover = np.empty(cap, dtype=np.float64)
+            start = np.empty(cap, dtype=np.float64)
+            occ, windows = self._occ_windows(rec_off.size, n_motifs)
+            k = ctypes.c_int64(0)
+            rc = self._L.pfmscan_footprint_profile_events_staged(self._h, _ptr(st), _ptr(sq), n_motifs, m, int(mode), _ptr(rec_off),
+                                                                 _ptr(rec_len), rec_off.size, float(thr), cap, _ptr(key), _ptr(cover),
+                                                                 _ptr(start), ctypes.byref(k), _ptr(occ), _ptr(windows))
             if rc == E_CAPACITY and capacity is None:
                 cap = int(k.value)
                 continue

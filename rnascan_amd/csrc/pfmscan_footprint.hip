@@ -23,13 +23,12 @@
 // at every width, four gains at w = 8 and 12 and loses at w = 64; two is never the worst and was kept.
 // A workgroup finds its record by bisection of the tile prefix table (occ_record): the table is the only thing the host makes.
 #include <algorithm>
-#include <cmath>
-#include <numeric>
 #include <string>
 #include <vector>
 
 #include "pfmscan_ctx.hpp"
 #include "pfmscan_device.hpp"
+#include "pfmscan_fp.hpp"
 #include "pfmscan_occ.hpp"
 
 #pragma clang fp contract(off)   // products and sums are rounded one operation at a time: never an FMA
@@ -190,17 +189,6 @@ __global__ __launch_bounds__(BLOCK) void k_fp_tiles(const FpArgs a)
     }
 }
 
-// what a call leaves: the maps (either may be null), or with events the positions whose cover passes thr
-struct FpOut {
-    double *start, *cover;
-    bool events;
-    double thr;
-    int64_t capacity;
-    int64_t *ev_key;
-    double *ev_cover, *ev_start;
-    unsigned long long *ev_count;
-};
-
 // Launches on st, does not wait.  At least one table is given; d_codes where seq_tables is, d_codes2 where struct_tables is.
 static int fp_run(pfmscan_ctx *ctx, const char *who, const double *seq_tables, const double *struct_tables, int n_motifs, int m, int mode,
                   const uint8_t *d_codes, const uint8_t *d_codes2, const OccRecords &rec, const FpOut &o, double *d_occ, int64_t *d_windows,
@@ -279,14 +267,6 @@ static int fp_check(pfmscan_ctx *ctx, const char *who, const double *seq_tables,
         return rc;
     if (mode != PFMSCAN_EXPECT_RATIO && mode != PFMSCAN_EXPECT_POSTERIOR)
         return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": mode must be PFMSCAN_EXPECT_RATIO or PFMSCAN_EXPECT_POSTERIOR");
-    return PFMSCAN_OK;
-}
-
-static int fp_check_events(pfmscan_ctx *ctx, const char *who, double thr, int64_t capacity, const void *count, const void *key, const void *cover,
-                           const void *start)
-{
-    if (std::isnan(thr)) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": NaN threshold");
-    if (capacity < 0 || !count || (capacity > 0 && (!key || !cover || !start))) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": bad event buffers");
     return PFMSCAN_OK;
 }
 
@@ -395,42 +375,15 @@ int pfmscan_footprint_events_staged(pfmscan_ctx *ctx, const double *seq_tables, 
     int rc;
     OccRecords rec;
     if ((rc = occ_records_up(ctx, who, rec_off, rec_len, n_rec, rec))) return rc;
-    const size_t cap = (size_t)std::max<int64_t>(capacity, 1), pairs = (size_t)n_rec * n_motifs;
-    if ((rc = ensure(ctx, ctx->fp_ev, cap * 24))) return rc;
-    if ((rc = ensure(ctx, ctx->fp_out, (pairs + (size_t)n_rec) * 8))) return rc;
-    if ((rc = ensure(ctx, ctx->count, HIT_COUNTER_STRIDE * 8))) return rc;
-    HIP_TRY(ctx, hipMemsetAsync(ctx->count.p, 0, 8, ctx->stream));
-    int64_t *d_key = (int64_t *)ctx->fp_ev.p;
-    double *d_cov = (double *)ctx->fp_ev.p + cap, *d_sta = d_cov + cap;
-    double *d_occ = occ ? (double *)ctx->fp_out.p : nullptr;
-    int64_t *d_win = windows ? (int64_t *)ctx->fp_out.p + pairs : nullptr;
-    const FpOut o{nullptr, nullptr, true, thr, capacity, d_key, d_cov, d_sta, (unsigned long long *)ctx->count.p};
+    const size_t pairs = (size_t)n_rec * n_motifs;
+    FpOut o;
+    double *d_occ;
+    int64_t *d_win;
+    if ((rc = fp_events_room(ctx, thr, capacity, pairs, (size_t)n_rec, occ != nullptr, windows != nullptr, o, d_occ, d_win))) return rc;
     if ((rc = fp_run(ctx, who, seq_tables, struct_tables, n_motifs, m, mode, (const uint8_t *)ctx->codes.p, (const uint8_t *)ctx->codes2.p, rec, o, d_occ,
                      d_win, ctx->stream)))
         return rc;
-    uint64_t total = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(&total, ctx->count.p, 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    *n_events = (int64_t)total;
-    if ((int64_t)total > capacity)
-        return fail(ctx, PFMSCAN_E_CAPACITY, std::string(who) + ": " + std::to_string(total) + " events, capacity " + std::to_string(capacity));
-    std::vector<int64_t> key(total);
-    std::vector<double> cv(total), sw(total);
-    if (total) {
-        HIP_TRY(ctx, hipMemcpyAsync(key.data(), d_key, total * 8, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(cv.data(), d_cov, total * 8, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(sw.data(), d_sta, total * 8, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    if ((rc = occ_copy_home(ctx, {{occ, d_occ, pairs * 8}, {windows, d_win, (size_t)n_rec * 8}}))) return rc;
-    std::vector<int64_t> order(total);                             // keys are distinct: sorted on the host, as the mutagenesis events are
-    std::iota(order.begin(), order.end(), (int64_t)0);
-    std::sort(order.begin(), order.end(), [&](int64_t x, int64_t y) { return key[x] < key[y]; });
-    for (uint64_t i = 0; i < total; ++i) {
-        ev_key[i] = key[order[i]];
-        ev_cover[i] = cv[order[i]];
-        ev_start[i] = sw[order[i]];
-    }
-    return PFMSCAN_OK;
+    return fp_events_home(ctx, who, o, ev_key, ev_cover, ev_start, n_events, {occ, d_occ, pairs * 8}, {windows, d_win, (size_t)n_rec * 8});
 }
 
 }  // extern "C"

@@ -25,7 +25,7 @@ Start.Weight Cover.  Doubles are printed with ``repr``.  ``--min-cover`` is 0.5 
 with ``--weight ratio``, which has no natural scale.  A record whose occupancy is 0 has no row (how many is said on stderr); an
 infinite or NaN occupancy is an error that names the motif and the record, and nothing is written.
 
-Not supported: averaged-structure profiles (they need the marginal chain), ``--gpus``, bedGraph or bigWig output, merging
+Not supported: averaged-structure profiles (they are ``python -m rnascan_amd.footprint_profile``), ``--gpus``, bedGraph or bigWig output, merging
 regions on the device, more or fewer than one site per record (ZOOPS).
 """
 import argparse
@@ -75,15 +75,16 @@ def format_rows(mid, sid, pos, cover, start, m, positions):
             for first, last, peak, c, mass in regions(pos, cover, start, m)]
 
 
-def batch_rows(motif_ids, groups, ids, stream, call, positions):
+def batch_rows(motif_ids, groups, ids, stream, call, positions, cols=None):
     """the lines of one batch in (record, motif, position) order, and how many (record, motif) have occupancy 0.
-    ``call(stream, m, ks)`` -> (key, cover, start, occ [n_rec][len(ks)], windows)"""
-    n_pos = int(np.asarray(stream.codes).size)
+    ``call(stream, m, ks)`` -> (key, cover, start, occ [n_rec][len(ks)], windows); a batch of averaged-structure profiles
+    comes with its stored column order and is ``call(stream, m, ks, cols)``"""
+    n_pos = int(np.asarray(stream.codes).size) if stream.codes is not None else int(np.asarray(stream.profile).shape[0])
     offsets = np.asarray(stream.offsets, dtype=np.int64)
     got = {}                                                       # (record, motif) -> (positions in the record, cover, start, width)
     occ = np.zeros((len(ids), len(motif_ids)), dtype=np.float64)
     for m, ks in groups.items():
-        key, cover, start, o, _ = call(stream, m, ks)
+        key, cover, start, o, _ = call(stream, m, ks) if cols is None else call(stream, m, ks, cols)
         occ[:, ks] = np.asarray(o)
         key = np.asarray(key, dtype=np.int64)
         j, p = key // max(n_pos, 1), key % max(n_pos, 1)
@@ -108,8 +109,8 @@ def batch_rows(motif_ids, groups, ids, stream, call, positions):
 def write_table(out, motif_ids, groups, batches, call, positions):
     """every line is made before the first is written: a record that fails leaves nothing behind"""
     lines, empty = [], 0
-    for ids, stream, _ in batches:
-        more, zero = batch_rows(motif_ids, groups, ids, stream, call, positions)
+    for ids, stream, cols in batches:
+        more, zero = batch_rows(motif_ids, groups, ids, stream, call, positions, cols)
         lines += more
         empty += zero
     out.write("\t".join(POSITION_COLUMNS if positions else COLUMNS) + "\n")
@@ -170,7 +171,7 @@ def main(argv=None, engine=None, out=None):
             return 1
         if occupancy._is_profiles(args.fasta):
             fasta.eprint("%s is an averaged-structure directory or packed store: footprints take FASTA files of letters "
-                         "(averaged-structure profiles are not supported)" % args.fasta)
+                         "(averaged-structure profiles are `python -m rnascan_amd.footprint_profile`)" % args.fasta)
             return 1
     with occupancy.Device(engine, args.device, (IOError, sites.InputError, FootprintError)) as dev:
         if pair:

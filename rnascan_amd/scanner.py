@@ -237,6 +237,20 @@ class HipEngine(object):
         self._stage_footprint(stream, seq_tables, struct_tables)
         return self.ctx.footprint_events_staged(seq_tables, struct_tables, mode, stream.offsets, stream.lengths, thr, capacity)
 
+    def footprint_profile(self, stream, struct_tables, seq_tables, mode, want_start=True, want_cover=True):
+        """the posterior site map of an averaged-structure profile: structure tables [n_motifs][m][7] (columns in
+        the profile's stored order) over ``stream.profile``, with ``seq_tables`` [n_motifs][m][8] the joint weights over
+        ``stream.codes`` too; every window weighted as ``expect_profile`` weights it ->
+        (start, cover float64 [n_motifs][n_pos], +0.0 outside the records; occ float64 [n_rec][n_motifs]; windows int64 [n_rec])"""
+        self._stage(stream)
+        return self.ctx.footprint_profile_staged(struct_tables, seq_tables, mode, stream.offsets, stream.lengths, want_start, want_cover)
+
+    def footprint_profile_events(self, stream, struct_tables, seq_tables, mode, thr, capacity=None):
+        """the positions of the profile with cover > thr, decided on the device: only they come home ->
+        (key int64 = motif * n_pos + position sorted, cover float64, start float64, occ float64 [n_rec][n_motifs], windows)"""
+        self._stage(stream)
+        return self.ctx.footprint_profile_events_staged(struct_tables, seq_tables, mode, stream.offsets, stream.lengths, thr, capacity)
+
     # the three passes above with their matrices added up over the records on the device (DESIGN.md 5k): the accumulators
     # (uint64 [n_motifs][_lib.SITE_LIMBS][m * 8], normalised) are changed in place, one call per batch adds that batch's records
     def expect_merged(self, stream, ratio_tables, n_letters, mode, acc, which=0):

@@ -60,7 +60,8 @@ extern "C" {
 #endif
 
 #define PFMSCAN_ABI_VERSION 27   /* 27: pfmscan_expect_pair_joint_dev / _staged / _merged_staged (the 4 x 7 table per column); the posterior
-                                  * site map (pfmscan_footprint_*) only ADDS entry points and keeps the number, which the suite pins at 27 */
+                                  * site map (pfmscan_footprint_*) and the table on averaged-structure profiles (pfmscan_expect_profile_joint_*)
+                                  * only ADD entry points and keep the number, which the suite pins at 27 */
 #define PFMSCAN_NCODE   8      /* columns of a letter table */
 #define PFMSCAN_SEP     7      /* separator / foreign-letter code */
 #define PFMSCAN_NSTRUCT 7      /* columns of a structure profile / structure PSSM */
@@ -1275,6 +1276,36 @@ int pfmscan_expect_profile_staged(pfmscan_ctx *ctx, const double *struct_tables,
                                   int mode, const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec, double *exp_struct,
                                   double *exp_seq, double *occ, int64_t *windows);
 
+/* The expected nucleotide x context table per column on averaged-structure profiles (added under ABI 27).  The two
+ * matrices above are the margins of one table: per record r, motif (pair) q and motif column k, how much of structural context c
+ * lies under nucleotide a.  An averaged row has no letter to pair the nucleotide with, so the cell sums the row's cell itself.
+ * Everything not said here is the contract above, unchanged.
+ *   exp_joint[r][q][k][a][c], a < 4, c < 7 (STORED column order)   over the record's windows in order, the tree sum of
+ *                 x_s = (has_s && (codes[s + k] & 7) == a) ? w_s * r[s + k][c] : +0.0
+ *                 -- the one rounded product exp_struct makes of the same window, never fused -- with w_s and has_s those of
+ *                 exp_struct of the same call (joint chain with both tables, letter chain with seq_tables only).
+ *                 double [n_rec][n_motifs][m][4][8], column c = 7 of every row +0.0: a matrix of 4 m rows (row k * 4 + a) of 7
+ *                 letters, which is how the tree, the merge (acc_joint uint64 [n_motifs][PFMSCAN_SITE_LIMBS][32 m], cell
+ *                 (k * 4 + a) * 8 + c) and the command take it.  The codes are read: without seq_tables PFMSCAN_E_BADARG.
+ * Where every code of a record is one known nucleotide a0, exp_joint[..][k][a0][:] is bit for bit exp_struct[..][k][:] of the same
+ * call and every other a is +0.0.  On rows with a single 1.0, finite positive tables and the identity column order the table is
+ * bit for bit exp_joint of pfmscan_expect_pair_joint_* on the letter codes argmax(row).  The sum over a agrees with exp_struct
+ * only to rounding: the tree adds other values.
+ * The three functions carry the argument lists of pfmscan_expect_profile_dev / _staged / _merged_staged plus the table's output
+ * behind the two matrices'; their checks, the order of the checks, messages and return codes are the namesakes', except that any
+ * of the three outputs may be NULL (not computed: the bits of the others do not depend on it).  All three NULL, or exp_joint or
+ * exp_seq without seq_tables: PFMSCAN_E_BADARG, outputs untouched, nothing launched.  Calls without the table run the same
+ * kernels on the same plan as before.  The table is four matrices wide: 32 m doubles per record and motif on the device; the
+ * caller bounds it by the records of a call.  Scratch: a matrix row (motif, k) takes 7 + 4 + 28 doubles of a block; a pass then
+ * holds whole motifs, as many as leave room for the blocks that fill the device. */
+int pfmscan_expect_profile_joint_dev(pfmscan_ctx *ctx, const double *struct_tables, const double *seq_tables, int n_motifs, int m,
+                                     int mode, const uint8_t *d_codes, const void *d_profile, int profile_dtype, int64_t n_pos,
+                                     const int64_t *d_rec_off, const int64_t *d_rec_len, int64_t n_rec, double *d_exp_struct,
+                                     double *d_exp_seq, double *d_exp_joint, double *d_occ, int64_t *d_windows);
+int pfmscan_expect_profile_joint_staged(pfmscan_ctx *ctx, const double *struct_tables, const double *seq_tables, int n_motifs, int m,
+                                        int mode, const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec, double *exp_struct,
+                                        double *exp_seq, double *exp_joint, double *occ, int64_t *windows);
+
 /* ---- occupancy and expected counts of two code streams: sequence letters AND structure letters ------------------------
  * No counterpart in the reference.  The occupancy and the expected counts above for the input mode `-p seq.pfm -q struct.pfm
  * seqs.fa structs.fa`, where the structure of a record is a letter string.  No transcendental, no tolerance;
@@ -1397,6 +1428,12 @@ int pfmscan_expect_pair_joint_merged_staged(pfmscan_ctx *ctx, const double *seq_
                                             int m, int mode, const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec,
                                             uint64_t *acc_seq, uint64_t *acc_struct, uint64_t *acc_joint, int64_t *bad_seq,
                                             int64_t *bad_struct, int64_t *bad_joint, double *occ, int64_t *windows);
+/* with the nucleotide x context table of averaged-structure profiles: acc_joint as above, cell (k * 4 + a) * 8 + c, c in the
+ * profile's STORED column order; any of the three accumulators may be NULL, not all */
+int pfmscan_expect_profile_joint_merged_staged(pfmscan_ctx *ctx, const double *struct_tables, const double *seq_tables, int n_motifs,
+                                               int m, int mode, const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec,
+                                               uint64_t *acc_struct, uint64_t *acc_seq, uint64_t *acc_joint, int64_t *bad_struct,
+                                               int64_t *bad_seq, int64_t *bad_joint, double *occ, int64_t *windows);
 
 /* ---- posterior site map: the weight of every window and the coverage of every position ---------------------------------
  * No counterpart in the reference.  The fourth member of the threshold-free family: where in a record the

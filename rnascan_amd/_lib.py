@@ -63,6 +63,8 @@ SYMBOLS = [
     "pfmscan_occupancy_pair_dev", "pfmscan_occupancy_pair_staged", "pfmscan_expect_pair_dev", "pfmscan_expect_pair_staged",
     "pfmscan_expect_merge_dev", "pfmscan_expect_merged_staged", "pfmscan_expect_profile_merged_staged", "pfmscan_expect_pair_merged_staged",
     "pfmscan_expect_pair_joint_dev", "pfmscan_expect_pair_joint_staged", "pfmscan_expect_pair_joint_merged_staged",
+    # added under ABI 27, as the footprint entry points were: the number stays, the suite pins it
+    "pfmscan_expect_profile_joint_dev", "pfmscan_expect_profile_joint_staged", "pfmscan_expect_profile_joint_merged_staged",
     "pfmscan_footprint_dev", "pfmscan_footprint_staged", "pfmscan_footprint_events_dev", "pfmscan_footprint_events_staged",
     "pfmscan_footprint_profile_dev", "pfmscan_footprint_profile_staged", "pfmscan_footprint_profile_events_dev", "pfmscan_footprint_profile_events_staged",
 ]
@@ -275,6 +277,9 @@ def load():
     L.pfmscan_footprint_profile_staged.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, i64, vp, vp, vp, vp]
     L.pfmscan_footprint_profile_events_dev.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, i32, i64, vp, vp, i64, dbl, i64, vp, vp, vp, vp, vp, vp]
     L.pfmscan_footprint_profile_events_staged.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, i64, dbl, i64, vp, vp, vp, ctypes.POINTER(i64), vp, vp]
+    L.pfmscan_expect_profile_joint_dev.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, i32, i64, vp, vp, i64, vp, vp, vp, vp, vp]
+    L.pfmscan_expect_profile_joint_staged.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, i64, vp, vp, vp, vp, vp]
+    L.pfmscan_expect_profile_joint_merged_staged.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]
     L.pfmscan_tsv_format.argtypes = [ctypes.POINTER(TsvColumn), i32, i64, i64, vp, i64, ctypes.POINTER(i64), vp, ctypes.POINTER(i32), i32]
     for name in SYMBOLS:          # every other entry point returns a status
         if name not in ("pfmscan_ctx_destroy", "pfmscan_motif_destroy", "pfmscan_last_error", "pfmscan_library_destroy",
@@ -1814,6 +1819,32 @@ class Context(object):
                                                           rec_off.size, _ptr(exp_struct), _ptr(exp_seq), _ptr(occ), _ptr(windows)))
         return exp_struct, exp_seq, occ, windows
 
+    def expect_profile_joint_dev(self, struct_tables, seq_tables, mode, d_codes, d_profile, profile_dtype, n_pos, d_rec_off, d_rec_len, n_rec,
+                                 d_exp_struct, d_exp_seq, d_exp_joint, d_occ=None, d_windows=None):
+        """``expect_profile_dev`` with the nucleotide x context table d_exp_joint float64 [n_rec][n_motifs][m][4][8]; any of the three
+        may be None"""
+        st, sq = self._expect_profile_tables(struct_tables, seq_tables)
+        n_motifs, m = (st if st is not None else sq).shape[:2]
+        self._check(self._L.pfmscan_expect_profile_joint_dev(self._h, _ptr(st), _ptr(sq), n_motifs, m, int(mode), _ptr(d_codes), _ptr(d_profile),
+                                                             int(profile_dtype), int(n_pos), _ptr(d_rec_off), _ptr(d_rec_len), int(n_rec),
+                                                             _ptr(d_exp_struct), _ptr(d_exp_seq), _ptr(d_exp_joint), _ptr(d_occ), _ptr(d_windows)))
+
+    def expect_profile_joint_staged(self, struct_tables, seq_tables, mode, rec_off, rec_len, want_struct=True, want_seq=True, want_joint=True):
+        """``expect_profile_staged`` with the nucleotide x context table -> exp_struct, exp_seq, exp_joint float64
+        [n_rec][n_motifs][m][4][8] (cell [k][a][c]: the rows' cell c, in stored column order, under nucleotide a at column k; c = 7 is
+        +0.0), occ, windows; None where not wanted"""
+        st, sq = self._expect_profile_tables(struct_tables, seq_tables)
+        n_motifs, m = (st if st is not None else sq).shape[:2]
+        rec_off, rec_len = self._records(rec_off, rec_len)
+        exp_struct = np.zeros((rec_off.size, n_motifs, m, NCODE), dtype=np.float64) if want_struct else None
+        exp_seq = np.zeros((rec_off.size, n_motifs, m, NCODE), dtype=np.float64) if want_seq else None
+        exp_joint = np.zeros((rec_off.size, n_motifs, m, 4, NCODE), dtype=np.float64) if want_joint else None
+        occ, windows = self._occ_windows(rec_off.size, n_motifs)
+        self._check(self._L.pfmscan_expect_profile_joint_staged(self._h, _ptr(st), _ptr(sq), n_motifs, m, int(mode), _ptr(rec_off), _ptr(rec_len),
+                                                                rec_off.size, _ptr(exp_struct), _ptr(exp_seq), _ptr(exp_joint), _ptr(occ),
+                                                                _ptr(windows)))
+        return exp_struct, exp_seq, exp_joint, occ, windows
+
     # -- two code streams (include/pfmscan.h: pfmscan_occupancy_pair_*, pfmscan_expect_pair_*) ---------------
     @staticmethod
     def _pair_tables(seq_tables, struct_tables):
@@ -1923,6 +1954,23 @@ class Context(object):
                                                                  rec_off.size, _ptr(acc_struct), _ptr(acc_seq), _ptr(bad_struct), _ptr(bad_seq),
                                                                  _ptr(occ), _ptr(windows)))
         return bad_struct, bad_seq, occ, windows
+
+    def expect_profile_joint_merged_staged(self, struct_tables, seq_tables, mode, rec_off, rec_len, acc_struct, acc_seq, acc_joint):
+        """``expect_profile_merged_staged`` with the table's accumulator acc_joint uint64 [n_motifs][SITE_LIMBS][4 m * 8] (any of the
+        three may be None) -> bad_struct, bad_seq, bad_joint (None where no accumulator), occ, windows"""
+        st, sq = self._expect_profile_tables(struct_tables, seq_tables)
+        n_motifs, m = (st if st is not None else sq).shape[:2]
+        rec_off, rec_len = self._records(rec_off, rec_len)
+        accs = ((acc_struct, "acc_struct", m), (acc_seq, "acc_seq", m), (acc_joint, "acc_joint", 4 * m))
+        for acc, name, rows in accs:
+            if acc is not None:
+                self._merge_acc(acc, n_motifs, rows, name)
+        bads = [None if acc is None else np.full((n_motifs, 2), -1, dtype=np.int64) for acc, _, _ in accs]
+        occ, windows = self._occ_windows(rec_off.size, n_motifs)
+        self._check(self._L.pfmscan_expect_profile_joint_merged_staged(self._h, _ptr(st), _ptr(sq), n_motifs, m, int(mode), _ptr(rec_off),
+                                                                       _ptr(rec_len), rec_off.size, _ptr(acc_struct), _ptr(acc_seq), _ptr(acc_joint),
+                                                                       _ptr(bads[0]), _ptr(bads[1]), _ptr(bads[2]), _ptr(occ), _ptr(windows)))
+        return bads[0], bads[1], bads[2], occ, windows
 
     def expect_pair_merged_staged(self, seq_tables, struct_tables, mode, rec_off, rec_len, acc_seq, acc_struct):
         """``expect_pair_staged`` with the matrices added up over the records on the device into acc_seq and acc_struct (either

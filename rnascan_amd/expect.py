@@ -81,7 +81,7 @@ def new_acc(n_motifs, m):
 #   host(stream, tables, mode) -> (matrices, occ, windows); merged(stream, tables, mode, accs) -> (bads, occ, windows):
 #                       the engine's two methods, their lists in the form's check order; ``method``: the second one's name
 #   matrices            a Matrix per matrix: cells kept, None | cols -> the stored column of every written cell, and the matrix
-#                       rows per motif column (1; the letter-pair table of ``expect_pair`` has 4)
+#                       rows per motif column (1; the tables of ``expect_pair --joint`` and ``expect_profile --joint`` have 4)
 #   not_finite          the form's message for a non-finite record
 Form = namedtuple("Form", "motif_ids groups order batches tables host merged method matrices not_finite")
 Matrix = namedtuple("Matrix", "kept stored rows", defaults=(None, 1))

@@ -31,7 +31,8 @@ against the same backgrounds, and the pass is run again; ``--iterations 2`` writ
 The table is the last pass's and is not fed back: its margins are.
 
 Inputs, pairing, backgrounds and dot-bracket structures are handled exactly as ``occupancy_pair`` handles them (the same
-code).  Not supported: a joint table with flanks or for averaged-structure profiles, ``--gpus``, other priors.
+code).  Not supported: a joint table with flanks, ``--gpus``, other priors.  (Averaged-structure profiles have their own table:
+``expect_profile --joint``.)
 """
 import argparse
 import io
@@ -76,14 +77,15 @@ def mutual_information(cells):
                      for a, row in enumerate(cells) for b, c in enumerate(row) if c)
 
 
-def joint_text(tables, motif_ids, library):
+def joint_text(tables, motif_ids, library, mi=mutual_information):
     """PREFIX.expected.joint.txt from {pair id: E_joint float64 [4 m][7], row k * 4 + a, both letters in code order}: ``sites``'
-    PREFIX.joint.txt with expected counts in the cells, written and (with ``library``) tagged by the same code"""
+    PREFIX.joint.txt with expected counts in the cells, written and (with ``library``) tagged by the same code; ``mi``: the
+    mutual information of a column's cells (``expect_profile --joint`` has its own for negative cells)"""
     from . import sites
     text = io.StringIO()
     for mid in motif_ids:
         one = text if not library else io.StringIO()
-        sites._joint_to(one, tables[mid].reshape(-1, len(sites.SEQ_ORDER), len(pack.STRUCT_LETTERS)), mutual_information)
+        sites._joint_to(one, tables[mid].reshape(-1, len(sites.SEQ_ORDER), len(pack.STRUCT_LETTERS)), mi)
         if library:
             sites.tagged(text, mid, one)
     return text.getvalue()

@@ -185,6 +185,13 @@ class HipEngine(object):
         self._stage(stream)
         return self.ctx.expect_profile_staged(struct_tables, seq_tables, mode, stream.offsets, stream.lengths)
 
+    def expect_profile_joint(self, stream, struct_tables, seq_tables, mode):
+        """``expect_profile`` with the expected nucleotide x context table per column, of which the two matrices are the margins (to
+        rounding); needs ``seq_tables`` -> (exp_struct, exp_seq, exp_joint float64 [n_rec][n_motifs][m][4][8]: the rows' cell c, in
+        the profile's stored column order, under nucleotide a; occ; windows)"""
+        self._stage(stream)
+        return self.ctx.expect_profile_joint_staged(struct_tables, seq_tables, mode, stream.offsets, stream.lengths)
+
     def _stage_pair(self, stream):
         if stream.codes2 is None:
             raise ValueError("the stream holds no second code stream (codes2)")
@@ -264,6 +271,13 @@ class HipEngine(object):
         STORED column order, as the matrices are"""
         self._stage(stream)
         return self.ctx.expect_profile_merged_staged(struct_tables, seq_tables, mode, stream.offsets, stream.lengths, acc_struct, acc_seq)
+
+    def expect_profile_joint_merged(self, stream, struct_tables, seq_tables, mode, acc_struct, acc_seq, acc_joint):
+        """``expect_profile_joint`` -> (bad_struct, bad_seq, bad_joint, occ, windows); acc_joint uint64 [n_motifs][_lib.SITE_LIMBS][4 m * 8],
+        its cell axis in the profile's STORED column order"""
+        self._stage(stream)
+        return self.ctx.expect_profile_joint_merged_staged(struct_tables, seq_tables, mode, stream.offsets, stream.lengths, acc_struct, acc_seq,
+                                                           acc_joint)
 
     def expect_pair_merged(self, stream, seq_tables, struct_tables, mode, acc_seq, acc_struct):
         """``expect_pair`` -> (bad_seq, bad_struct, occ, windows)"""

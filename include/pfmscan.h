@@ -60,8 +60,9 @@ extern "C" {
 #endif
 
 #define PFMSCAN_ABI_VERSION 27   /* 27: pfmscan_expect_pair_joint_dev / _staged / _merged_staged (the 4 x 7 table per column); the posterior
-                                  * site map (pfmscan_footprint_*) and the table on averaged-structure profiles (pfmscan_expect_profile_joint_*)
-                                  * only ADD entry points and keep the number, which the suite pins at 27 */
+                                  * site map (pfmscan_footprint_*), the table on averaged-structure profiles (pfmscan_expect_profile_joint_*)
+                                  * and the threshold-free mutagenesis (pfmscan_mutocc_*) only ADD entry points and keep the number, which
+                                  * the suite pins at 27 */
 #define PFMSCAN_NCODE   8      /* columns of a letter table */
 #define PFMSCAN_SEP     7      /* separator / foreign-letter code */
 #define PFMSCAN_NSTRUCT 7      /* columns of a structure profile / structure PSSM */
@@ -1533,6 +1534,48 @@ int pfmscan_footprint_profile_events_staged(pfmscan_ctx *ctx, const double *stru
                                             int m, int mode, const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec,
                                             double thr, int64_t capacity, int64_t *ev_key, double *ev_cover, double *ev_start,
                                             int64_t *n_events, double *occ, int64_t *windows);
+
+/* ---- threshold-free mutagenesis: the occupancy change of every single-letter change --------------------------------------
+ * No counterpart in the reference.  Where pfmscan_mutmap_* says what a letter change does to the best window at a threshold,
+ * this says what it does to the SUM the threshold-free family reports; entry points ADDED under ABI 27.
+ * tests/mutocc_rules.py restates the rule in numpy and the bits are compared.  seq_tables HOST double [n_motifs][m][8] of one
+ * width, the ratio tables of pfmscan_occupancy_* over the 4 RNA letters; c = code & 7; record r lies at off_r with L positions.
+ * The map, double [n_motifs][n_pos][4] aligned with the stream: for a position p = off_r + i whose code is a letter
+ * (c_i < 4) and a letter a in 0 .. 3
+ *   local[q][p][a]: x = +0.0, then for s = i - m + 1 .. i ascending x = x + u(s), every addition rounded; u(s) = +0.0 when
+ *                 s < 0, s > L - m, or any OTHER position of window s holds a code >= 4; else the term of window s of the
+ *                 stream in which position i holds a, made as the occupancy makes it: R[0][.], then * R[k][.] for k ascending,
+ *                 every product rounded (the factors before i are shared by the four letters; the tail is multiplied per
+ *                 letter left to right, never a suffix product).  IEEE as it falls, nothing contracted, no exp, no log.
+ * local[q][p][c_i] is bit for bit the cover of pfmscan_footprint_* in PFMSCAN_EXPECT_RATIO mode on the same stream and table,
+ * and local[q][p][a] that cover at p of the stream with a written at p.  A position inside a record whose code is >= 4 has
+ * four NaN, as pfmscan_mutmap_* has.  In the _dev form positions in no record of the table are NOT written; in the _staged
+ * form they are NaN.  d_local is 16-byte aligned (PFMSCAN_E_BADSHAPE) and required; occ double [n_rec][n_motifs] and windows
+ * int64 [n_rec] are those of pfmscan_occupancy_* and may be NULL.
+ * Events: with occ_r the record's occupancy under q, delta = local[a] - local[c_i] (one rounded subtraction) and
+ * lim = frac * occ_r (one rounded product), a != c_i is an event when delta > lim (gain) or delta < -lim (loss), both strict:
+ * NaN never passes.  A NaN or negative frac is PFMSCAN_E_BADARG.  An event is key = (q * n_pos + p) * 4 + a with
+ * alt = local[q][p][a] and ref = local[q][p][c_i]; no map is allocated anywhere.  Capacity, the total count in d_ev_count
+ * (one uint64 the caller zeroes; only the first `capacity` events are stored), "unordered in _dev, sorted by key in _staged"
+ * and "PFMSCAN_E_CAPACITY: *n_events holds the capacity that suffices, nothing was written" are exactly those of
+ * pfmscan_mutmap_events_*.
+ * The record-table check (before any kernel forms an address from it), the one synchronisation of the _dev forms, the error
+ * codes, the order of the checks and the 16-byte alignment of d_codes are those of pfmscan_footprint_*.  The bits depend on
+ * the codes and the tables and on nothing else: not on the batch, the tiling, the width's kernel or the form.
+ * PFMSCAN_MUTOCC_TILE: a workgroup of the kernel owns this many consecutive positions of ONE record. */
+#define PFMSCAN_MUTOCC_TILE 512
+int pfmscan_mutocc_dev(pfmscan_ctx *ctx, const double *seq_tables, int n_motifs, int m, const uint8_t *d_codes, int64_t n_pos,
+                       const int64_t *d_rec_off, const int64_t *d_rec_len, int64_t n_rec, double *d_local, double *d_occ,
+                       int64_t *d_windows);
+int pfmscan_mutocc_staged(pfmscan_ctx *ctx, const double *seq_tables, int n_motifs, int m, const int64_t *rec_off,
+                          const int64_t *rec_len, int64_t n_rec, double *local, double *occ, int64_t *windows);
+int pfmscan_mutocc_events_dev(pfmscan_ctx *ctx, const double *seq_tables, int n_motifs, int m, const uint8_t *d_codes, int64_t n_pos,
+                              const int64_t *d_rec_off, const int64_t *d_rec_len, int64_t n_rec, double frac, int64_t capacity,
+                              int64_t *d_ev_key, double *d_ev_alt, double *d_ev_ref, uint64_t *d_ev_count, double *d_occ,
+                              int64_t *d_windows);
+int pfmscan_mutocc_events_staged(pfmscan_ctx *ctx, const double *seq_tables, int n_motifs, int m, const int64_t *rec_off,
+                                 const int64_t *rec_len, int64_t n_rec, double frac, int64_t capacity, int64_t *ev_key,
+                                 double *ev_alt, double *ev_ref, int64_t *n_events, double *occ, int64_t *windows);
 
 #ifdef __cplusplus
 }

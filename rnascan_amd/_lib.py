@@ -67,6 +67,7 @@ SYMBOLS = [
     "pfmscan_expect_profile_joint_dev", "pfmscan_expect_profile_joint_staged", "pfmscan_expect_profile_joint_merged_staged",
     "pfmscan_footprint_dev", "pfmscan_footprint_staged", "pfmscan_footprint_events_dev", "pfmscan_footprint_events_staged",
     "pfmscan_footprint_profile_dev", "pfmscan_footprint_profile_staged", "pfmscan_footprint_profile_events_dev", "pfmscan_footprint_profile_events_staged",
+    "pfmscan_mutocc_dev", "pfmscan_mutocc_staged", "pfmscan_mutocc_events_dev", "pfmscan_mutocc_events_staged",
 ]
 PAIR_ROUTE_NONE, PAIR_ROUTE_FUSED, PAIR_ROUTE_TWO_PHASE, PAIR_ROUTE_DENSE, PAIR_ROUTE_CREDITS = range(5)   # Context.pair_sum_route()
 SITE_GROUP = 4096     # most hits of one group of the site profiles
@@ -76,6 +77,7 @@ EXPECT_RATIO, EXPECT_POSTERIOR = 0, 1   # weight of a window in the expected cou
 OCC_FANIN = 32        # fan-in of the occupancy's summation tree (PFMSCAN_OCC_FANIN)
 FOOTPRINT_SLOTS = 512  # windows a workgroup of the posterior site map makes (PFMSCAN_FOOTPRINT_SLOTS): its tile is SLOTS - (m - 1) positions
 FOOTPRINT_PROFILE_SLOTS = 256  # the same on averaged-structure profiles (PFMSCAN_FOOTPRINT_PROFILE_SLOTS)
+MUTOCC_TILE = 512     # positions of ONE record a workgroup of the threshold-free mutagenesis owns (PFMSCAN_MUTOCC_TILE)
 MAX_COVER = 1024      # largest coverage of a row the averaging accepts
 AVG_OK, AVG_DOTBRACKET, AVG_UNCOVERED, AVG_COVER, AVG_BAD_TABLE = range(5)   # what a rejected averaging names
 TSV_CONST, TSV_I64, TSV_F32, TSV_F64, TSV_INDEXED, TSV_FIXED, TSV_WINDOW, TSV_SPAN = range(8)
@@ -277,6 +279,10 @@ def load():
     L.pfmscan_footprint_profile_staged.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, i64, vp, vp, vp, vp]
     L.pfmscan_footprint_profile_events_dev.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, i32, i64, vp, vp, i64, dbl, i64, vp, vp, vp, vp, vp, vp]
     L.pfmscan_footprint_profile_events_staged.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, i64, dbl, i64, vp, vp, vp, ctypes.POINTER(i64), vp, vp]
+    L.pfmscan_mutocc_dev.argtypes = [vp, vp, i32, i32, vp, i64, vp, vp, i64, vp, vp, vp]
+    L.pfmscan_mutocc_staged.argtypes = [vp, vp, i32, i32, vp, vp, i64, vp, vp, vp]
+    L.pfmscan_mutocc_events_dev.argtypes = [vp, vp, i32, i32, vp, i64, vp, vp, i64, dbl, i64, vp, vp, vp, vp, vp, vp]
+    L.pfmscan_mutocc_events_staged.argtypes = [vp, vp, i32, i32, vp, vp, i64, dbl, i64, vp, vp, vp, ctypes.POINTER(i64), vp, vp]
     L.pfmscan_expect_profile_joint_dev.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, i32, i64, vp, vp, i64, vp, vp, vp, vp, vp]
     L.pfmscan_expect_profile_joint_staged.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, i64, vp, vp, vp, vp, vp]
     L.pfmscan_expect_profile_joint_merged_staged.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]
@@ -2077,6 +2083,61 @@ class Context(object):
             self._check(rc, k.value)
             k = int(k.value)
             return key[:k].copy(), cover[:k].copy(), start[:k].copy(), occ, windows
+
+    # -- threshold-free mutagenesis (include/pfmscan.h: pfmscan_mutocc_*) -------------------------------------
+    def mutocc_dev(self, ratio_tables, d_codes, n_pos, d_rec_off, d_rec_len, n_rec, d_local, d_occ=None, d_windows=None):
+        T = self._ratio_tables(ratio_tables)
+        self._check(self._L.pfmscan_mutocc_dev(self._h, _ptr(T), T.shape[0], T.shape[1], _ptr(d_codes), int(n_pos), _ptr(d_rec_off), _ptr(d_rec_len),
+                                               int(n_rec), _ptr(d_local), _ptr(d_occ), _ptr(d_windows)))
+
+    def mutocc_staged(self, ratio_tables, rec_off, rec_len):
+        """-> local float64 [n_motifs][n_pos][4] aligned with the staged stream (NaN outside the records of the table and where
+        a record holds no letter), occ float64 [n_rec][n_motifs], windows int64 [n_rec]"""
+        T = self._ratio_tables(ratio_tables)
+        n_motifs = T.shape[0]
+        n = int(self._L.pfmscan_staged_positions(self._h))
+        if n < 0:
+            raise ValueError("no stream staged (call stage first)")
+        rec_off, rec_len = self._records(rec_off, rec_len)
+        local = np.full((n_motifs, n, 4), np.nan, dtype=np.float64)
+        occ, windows = self._occ_windows(rec_off.size, n_motifs)
+        self._check(self._L.pfmscan_mutocc_staged(self._h, _ptr(T), n_motifs, T.shape[1], _ptr(rec_off), _ptr(rec_len), rec_off.size, _ptr(local),
+                                                  _ptr(occ), _ptr(windows)))
+        return local, occ, windows
+
+    def mutocc_events_dev(self, ratio_tables, d_codes, n_pos, d_rec_off, d_rec_len, n_rec, frac, capacity, d_ev_key, d_ev_alt, d_ev_ref,
+                          d_ev_count, d_occ=None, d_windows=None):
+        T = self._ratio_tables(ratio_tables)
+        self._check(self._L.pfmscan_mutocc_events_dev(self._h, _ptr(T), T.shape[0], T.shape[1], _ptr(d_codes), int(n_pos), _ptr(d_rec_off),
+                                                      _ptr(d_rec_len), int(n_rec), float(frac), int(capacity), _ptr(d_ev_key), _ptr(d_ev_alt),
+                                                      _ptr(d_ev_ref), _ptr(d_ev_count), _ptr(d_occ), _ptr(d_windows)))
+
+    def mutocc_events_staged(self, ratio_tables, rec_off, rec_len, frac, capacity=None):
+        """the single-letter changes of the staged stream that add or remove more than frac of their record's occupancy, decided
+        on the device -> (key int64[k] = (motif * n_pos + position) * 4 + alt letter sorted, alt float64[k], ref float64[k], occ
+        float64 [n_rec][n_motifs], windows int64 [n_rec]).  capacity None: a capacity verdict is answered by one retry with the
+        capacity it names; else CapacityError carries it"""
+        T = self._ratio_tables(ratio_tables)
+        n_motifs = T.shape[0]
+        n = int(self._L.pfmscan_staged_positions(self._h))
+        if n < 0:
+            raise ValueError("no stream staged (call stage first)")
+        rec_off, rec_len = self._records(rec_off, rec_len)
+        cap = int(capacity) if capacity is not None else max(1024, n // 16)
+        while True:
+            key = np.empty(cap, dtype=np.int64)
+            alt = np.empty(cap, dtype=np.float64)
+            ref = np.empty(cap, dtype=np.float64)
+            occ, windows = self._occ_windows(rec_off.size, n_motifs)
+            k = ctypes.c_int64(0)
+            rc = self._L.pfmscan_mutocc_events_staged(self._h, _ptr(T), n_motifs, T.shape[1], _ptr(rec_off), _ptr(rec_len), rec_off.size,
+                                                      float(frac), cap, _ptr(key), _ptr(alt), _ptr(ref), ctypes.byref(k), _ptr(occ), _ptr(windows))
+            if rc == E_CAPACITY and capacity is None:
+                cap = int(k.value)
+                continue
+            self._check(rc, k.value)
+            k = int(k.value)
+            return key[:k].copy(), alt[:k].copy(), ref[:k].copy(), occ, windows
 
     # -- posterior site map on averaged-structure profiles (include/pfmscan.h: pfmscan_footprint_profile_*) ---
     def footprint_profile_dev(self, struct_tables, seq_tables, mode, d_codes, d_profile, profile_dtype, n_pos, d_rec_off, d_rec_len, n_rec,

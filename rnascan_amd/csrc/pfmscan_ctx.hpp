@@ -57,7 +57,7 @@ struct pfmscan_ctx {
     DevBuf occ_tab, occ_idx, occ_rec, occ_bs, occ_gs, occ_cnt, occ_out;   // occupancy (pfmscan_occupancy.hip): ratio tables, block / group prefixes, record table, block and level-1 sums, window counts, staged outputs
     DevBuf exp_inv, exp_occ, exp_out;           // expected counts (pfmscan_expect.hip): 1 / occupancy per record and motif, the occupancy when the caller takes none, staged outputs
     DevBuf exp_acc;                             // merged expected counts (pfmscan_expect_merge.hip): the long accumulators and verdicts of a staged call
-    DevBuf fp_idx, fp_out, fp_ev;               // posterior site map (pfmscan_footprint.hip): tile prefix of the records, staged planes and occupancy, staged events
+    DevBuf fp_idx, fp_out, fp_ev;               // posterior site map (pfmscan_footprint.hip): tile prefix of the records, staged planes and occupancy, staged events; pfmscan_mutocc.hip uses them the same way
     DevBuf pipe_codes[2], pipe_profile[2];      // chunked host pipeline: double-buffered chunk of the stream
     hipEvent_t pipe_copied[2] = {nullptr, nullptr}, pipe_scanned[2] = {nullptr, nullptr};
     // host ranges known to be read-only mappings of files (pfmscan_upload_source_file): the staged uploader preads them

@@ -244,6 +244,21 @@ class HipEngine(object):
         self._stage_footprint(stream, seq_tables, struct_tables)
         return self.ctx.footprint_events_staged(seq_tables, struct_tables, mode, stream.offsets, stream.lengths, thr, capacity)
 
+    def mutocc(self, stream, ratio_tables):
+        """threshold-free mutagenesis: ratio tables [n_motifs][m][8] of one width over the stream's RNA codes ->
+        (local float64 [n_motifs][n_pos][4]: the summed ratios of the windows over a position if it held each letter, the
+        column of the letter it holds being ``footprint``'s ratio cover; NaN outside the records and where a record holds no
+        letter; occ float64 [n_rec][n_motifs]; windows int64 [n_rec])"""
+        self._stage_codes(stream, 0)
+        return self.ctx.mutocc_staged(ratio_tables, stream.offsets, stream.lengths)
+
+    def mutocc_events(self, stream, ratio_tables, frac, capacity=None):
+        """the single-letter changes that add (gain) or remove (loss) more than ``frac`` of their record's occupancy, decided on
+        the device: only they come home -> (key int64 = (motif * n_pos + position) * 4 + alt letter sorted, alt float64,
+        ref float64, occ float64 [n_rec][n_motifs], windows); a capacity verdict is answered by a retry (capacity None)"""
+        self._stage_codes(stream, 0)
+        return self.ctx.mutocc_events_staged(ratio_tables, stream.offsets, stream.lengths, frac, capacity)
+
     def footprint_profile(self, stream, struct_tables, seq_tables, mode, want_start=True, want_cover=True):
         """the posterior site map of an averaged-structure profile: structure tables [n_motifs][m][7] (columns in
         the profile's stored order) over ``stream.profile``, with ``seq_tables`` [n_motifs][m][8] the joint weights over

@@ -1577,6 +1577,54 @@ int pfmscan_mutocc_events_staged(pfmscan_ctx *ctx, const double *seq_tables, int
                                  const int64_t *rec_len, int64_t n_rec, double frac, int64_t capacity, int64_t *ev_key,
                                  double *ev_alt, double *ev_ref, int64_t *n_events, double *occ, int64_t *windows);
 
+/* ---- multi-site model: the partition function over non-overlapping sites and its site posteriors -----------------------
+ * No counterpart in the reference.  The family above rests on one site per record (the weights) or adds overlapping windows as
+ * if all were bound at once (the occupancy).  Here a record holds ANY set of non-overlapping sites, the empty set included
+ * (DESIGN.md 5n); entry points ADDED under ABI 27.  tests/multisite_rules.py restates the rule in numpy and the bits are
+ * compared.  The tables, c = code & 7, the term chain t_s over one or two code streams, has_s and windows[r] are those of
+ * pfmscan_footprint_*, unchanged; a window without a term has t_s = +0.0.  lam double [n_rec]: the activity of a site in
+ * record r.  Record r has L positions, n_win = max(L - m + 1, 0) windows.  Every product and addition below is ONE rounded
+ * fp64 operation, nothing is contracted, there is no exp and no log, IEEE as it falls:
+ *   a_s     = t_s * lam_r                                                    (one product after the chain)
+ *   F[0]    = 1.0;  F[i] = F[i-1] + (i >= m ? a[i-m] * F[i-m] : +0.0)        for i = 1 .. L;   z = F[L]  (1.0 when L < m)
+ *   B[L]    = 1.0;  B[i] = B[i+1] + (i <= L - m ? a[i] * B[i+m] : +0.0)      for i = L - 1 .. 0
+ *   v       = 1.0 / z                                                        (one rounded division per record and motif)
+ *   start[q][off_r + s] = ((F[s] * a[s]) * B[s+m]) * v for 0 <= s < n_win, +0.0 for the record's last min(m - 1, L) positions
+ *   cover[q][off_r + i]: the m ascending rounded additions of pfmscan_footprint_* over start; sites of one configuration do
+ *                 not overlap, so it is P(position i is bound)
+ *   nsites  = +0.0, then nsites = nsites + start[s] for s = n_win - 1 DOWN TO 0: the expected number of sites
+ * No scaling: z <= prod (1 + a_s) overflows on long records with a large lam; an infinite or NaN z is returned as IEEE makes
+ * it and the caller decides.  The bits depend on the codes, the tables and lam_r and on nothing else: not on the batch, the
+ * record's place in the stream, its neighbours, the passes, which outputs were asked for, or the _dev, _staged or events form.
+ * The argument list is that of pfmscan_footprint_* without mode, with lam (a DEVICE pointer in the _dev forms, a HOST pointer
+ * in the _staged forms; NULL: PFMSCAN_E_BADARG, tested after the sizes) behind the record table.  d_start or d_cover may be
+ * NULL, not both; z, nsites double [n_rec][n_motifs] and windows int64 [n_rec] may be NULL.  Positions in no record: unwritten
+ * in _dev, +0.0 in _staged.  Events: the positions with cover > thr; key, capacity, the counter, "unordered in _dev, sorted in
+ * _staged" and the capacity verdict are those of pfmscan_footprint_events_*.  The checks, their order, the record-table check
+ * before any kernel forms an address from it (the one synchronisation of the _dev forms) and the alignment rules are those of
+ * pfmscan_footprint_*.  Scratch: 16 bytes per position and motif of a pass; the library plans records and motifs into passes.
+ * PFMSCAN_MULTISITE_SLOTS: the tile-parallel kernels' workgroup holds this many windows of ONE record; its tile is
+ * PFMSCAN_MULTISITE_SLOTS - (m - 1) positions.  PFMSCAN_MULTISITE_CHUNK: the positions of a record a lane of the two serial
+ * kernels holds in LDS at a time. */
+#define PFMSCAN_MULTISITE_SLOTS 512
+#define PFMSCAN_MULTISITE_CHUNK 28
+int pfmscan_multisite_dev(pfmscan_ctx *ctx, const double *seq_tables, const double *struct_tables, int n_motifs, int m,
+                          const uint8_t *d_codes, const uint8_t *d_codes2, int64_t n_pos, const int64_t *d_rec_off,
+                          const int64_t *d_rec_len, int64_t n_rec, const double *d_lam, double *d_start, double *d_cover, double *d_z,
+                          double *d_nsites, int64_t *d_windows);
+int pfmscan_multisite_staged(pfmscan_ctx *ctx, const double *seq_tables, const double *struct_tables, int n_motifs, int m,
+                             const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec, const double *lam, double *start,
+                             double *cover, double *z, double *nsites, int64_t *windows);
+int pfmscan_multisite_events_dev(pfmscan_ctx *ctx, const double *seq_tables, const double *struct_tables, int n_motifs, int m,
+                                 const uint8_t *d_codes, const uint8_t *d_codes2, int64_t n_pos, const int64_t *d_rec_off,
+                                 const int64_t *d_rec_len, int64_t n_rec, const double *d_lam, double thr, int64_t capacity,
+                                 int64_t *d_ev_key, double *d_ev_cover, double *d_ev_start, uint64_t *d_ev_count, double *d_z,
+                                 double *d_nsites, int64_t *d_windows);
+int pfmscan_multisite_events_staged(pfmscan_ctx *ctx, const double *seq_tables, const double *struct_tables, int n_motifs, int m,
+                                    const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec, const double *lam, double thr,
+                                    int64_t capacity, int64_t *ev_key, double *ev_cover, double *ev_start, int64_t *n_events,
+                                    double *z, double *nsites, int64_t *windows);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,8 +19,8 @@ OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libpfmscan.so")
 SOURCES = ["pfmscan_kernels.hip", "pfmscan_letters8.hip", "pfmscan_pairsum.hip", "pfmscan_letters_fixed.hip", "pfmscan_api.hip", "pfmscan_hits.hip", "pfmscan_sort.hip", "pfmscan_library.hip", "pfmscan_library_api.hip", "pfmscan_proflib.hip", "pfmscan_profile_fixed.hip", "pfmscan_place.hip",
            "pfmscan_pipeline.hip", "pfmscan_ingest.hip", "pfmscan_upload.hip", "pfmscan_dotbracket.hip", "pfmscan_average.hip", "pfmscan_background.hip", "pfmscan_rowbound.hip", "pfmscan_sites.hip", "pfmscan_sites_host.hip", "pfmscan_sites_lib.hip",
-           "pfmscan_sites_lib_host.hip", "pfmscan_sites_letters.hip", "pfmscan_mutation.hip", "pfmscan_occupancy.hip", "pfmscan_expect.hip", "pfmscan_expect_profile.hip", "pfmscan_expect_merge.hip", "pfmscan_footprint.hip", "pfmscan_footprint_profile.hip", "pfmscan_mutocc.hip"]
-HEADERS = ["pfmscan_internal.hpp", "pfmscan_ctx.hpp", "pfmscan_hits.hpp", "pfmscan_hitqueue.hpp", "pfmscan_device.hpp", "pfmscan_profile.hpp", "pfmscan_exact.hpp", "pfmscan_sites.hpp", "pfmscan_superacc.hpp", "pfmscan_occ.hpp", "pfmscan_occ_plan.hpp", "pfmscan_fp.hpp", "pfmscan_fp_plan.hpp", os.path.join("..", "..", "include", "pfmscan.h")]
+           "pfmscan_sites_lib_host.hip", "pfmscan_sites_letters.hip", "pfmscan_mutation.hip", "pfmscan_occupancy.hip", "pfmscan_expect.hip", "pfmscan_expect_profile.hip", "pfmscan_expect_merge.hip", "pfmscan_footprint.hip", "pfmscan_footprint_profile.hip", "pfmscan_mutocc.hip", "pfmscan_multisite.hip"]
+HEADERS = ["pfmscan_internal.hpp", "pfmscan_ctx.hpp", "pfmscan_hits.hpp", "pfmscan_hitqueue.hpp", "pfmscan_device.hpp", "pfmscan_profile.hpp", "pfmscan_exact.hpp", "pfmscan_sites.hpp", "pfmscan_superacc.hpp", "pfmscan_occ.hpp", "pfmscan_occ_plan.hpp", "pfmscan_fp.hpp", "pfmscan_fp_plan.hpp", "pfmscan_ms_plan.hpp", os.path.join("..", "..", "include", "pfmscan.h")]
 DEPS = SOURCES + HEADERS
 FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-fno-fast-math", "-Wall"]
 

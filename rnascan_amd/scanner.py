@@ -244,6 +244,21 @@ class HipEngine(object):
         self._stage_footprint(stream, seq_tables, struct_tables)
         return self.ctx.footprint_events_staged(seq_tables, struct_tables, mode, stream.offsets, stream.lengths, thr, capacity)
 
+    def multisite(self, stream, seq_tables, struct_tables, lam, want_start=True, want_cover=True):
+        """the multi-site model: any set of non-overlapping sites per record, the empty set included; tables as
+        ``footprint`` takes them, ``lam`` float64 [n_rec] the activity of a site in each record ->
+        (start, cover float64 [n_motifs][n_pos]: the posterior that a site starts at a position and that the position is bound,
+        +0.0 outside the records; z float64 [n_rec][n_motifs] the partition function; nsites float64 [n_rec][n_motifs] the
+        expected number of sites; windows int64 [n_rec])"""
+        self._stage_footprint(stream, seq_tables, struct_tables)
+        return self.ctx.multisite_staged(seq_tables, struct_tables, stream.offsets, stream.lengths, lam, want_start, want_cover)
+
+    def multisite_events(self, stream, seq_tables, struct_tables, lam, thr, capacity=None):
+        """the positions with cover > thr under the multi-site model, decided on the device: only they come home ->
+        (key int64 = motif * n_pos + position sorted, cover float64, start float64, z, nsites float64 [n_rec][n_motifs], windows)"""
+        self._stage_footprint(stream, seq_tables, struct_tables)
+        return self.ctx.multisite_events_staged(seq_tables, struct_tables, stream.offsets, stream.lengths, lam, thr, capacity)
+
     def mutocc(self, stream, ratio_tables):
         """threshold-free mutagenesis: ratio tables [n_motifs][m][8] of one width over the stream's RNA codes ->
         (local float64 [n_motifs][n_pos][4]: the summed ratios of the windows over a position if it held each letter, the

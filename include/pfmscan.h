@@ -1625,6 +1625,48 @@ int pfmscan_multisite_events_staged(pfmscan_ctx *ctx, const double *seq_tables, 
                                     int64_t capacity, int64_t *ev_key, double *ev_cover, double *ev_start, int64_t *n_events,
                                     double *z, double *nsites, int64_t *windows);
 
+/* ---- multi-site model on averaged-structure profiles ------------------------------------------------------------------------
+ * The model above for the project's main input (DESIGN.md 5n "on averaged-structure profiles"); entry points ADDED under ABI 27.
+ * tests/multisite_profile_rules.py composes the rule from the family's and the bits are compared.
+ * Term and has: those of pfmscan_occupancy_profile_* / pfmscan_footprint_profile_*, unchanged.  struct_tables HOST double
+ * [n_motifs][m][7] in the profile's STORED column order, required (NULL: PFMSCAN_E_BADARG -- the model of a profile's letters is
+ * pfmscan_multisite_* on the codes); the marginal of a row is 7 rounded products and 6 rounded additions, ascending, float rows
+ * widened first; structure only every window inside the record has a term and the codes are not read; seq_tables HOST double
+ * [n_motifs][m][8] or NULL chooses joint mode and then needs the codes: the letter chain first, then t = t * d(s + k, k) for
+ * k = 0 .. m - 1, and a window that holds a code >= 4 has no term (t_s = +0.0).  windows[r]: the windows with a term.
+ * Model: a_s = t_s * lam_r, F, B, z, v, start, cover and nsites exactly as pfmscan_multisite_* states them, the same kernels
+ * over the same plane of activities.  No nan_to_num, no validity check: profile cells may be negative or not finite, and z,
+ * start and cover are then what IEEE makes of the stated operations -- z can be <= 0.0, infinite or NaN, and the caller
+ * decides.  The separator row behind a record and the rows of its neighbours are never used as data.  The bits depend on the
+ * row dtype, the stored column order, the codes, the tables and lam_r and on nothing else: not on the batch, the record's place
+ * in the stream, the tiling, the passes, which outputs were asked for, or the form.
+ * The argument list is that of pfmscan_footprint_profile_* without mode, with lam double [n_rec] behind the record table (a
+ * DEVICE pointer in the _dev forms, a HOST pointer in the _staged forms).  The checks of the width, the profile_dtype and the
+ * sizes, their order and codes, "no profile is staged", the 16-byte alignment of d_profile (and d_codes in joint mode,
+ * PFMSCAN_E_BADSHAPE) and the record table read back and checked before any kernel forms an address from it (the one
+ * synchronisation of the _dev forms) are those of pfmscan_footprint_profile_*.  A NULL lam is PFMSCAN_E_BADARG, tested after
+ * the sizes and struct_tables; d_start or d_cover may be NULL, not both (PFMSCAN_E_BADARG); z, nsites double [n_rec][n_motifs]
+ * and windows int64 [n_rec] may be NULL; a NaN thr, the event buffers, key = q * n_pos + p, the capacity verdict and "unordered
+ * in _dev, sorted by key in _staged" are those of pfmscan_multisite_events_*.  Positions in no record: unwritten in _dev, +0.0
+ * in _staged.  n_rec == 0 or n_motifs == 0: PFMSCAN_OK, nothing written.  Bad arguments launch nothing and leave the outputs
+ * untouched.  Scratch and passes: those of pfmscan_multisite_*. */
+int pfmscan_multisite_profile_dev(pfmscan_ctx *ctx, const double *struct_tables, const double *seq_tables, int n_motifs, int m,
+                                  const uint8_t *d_codes, const void *d_profile, int profile_dtype, int64_t n_pos,
+                                  const int64_t *d_rec_off, const int64_t *d_rec_len, int64_t n_rec, const double *d_lam,
+                                  double *d_start, double *d_cover, double *d_z, double *d_nsites, int64_t *d_windows);
+int pfmscan_multisite_profile_staged(pfmscan_ctx *ctx, const double *struct_tables, const double *seq_tables, int n_motifs, int m,
+                                     const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec, const double *lam,
+                                     double *start, double *cover, double *z, double *nsites, int64_t *windows);
+int pfmscan_multisite_profile_events_dev(pfmscan_ctx *ctx, const double *struct_tables, const double *seq_tables, int n_motifs,
+                                         int m, const uint8_t *d_codes, const void *d_profile, int profile_dtype, int64_t n_pos,
+                                         const int64_t *d_rec_off, const int64_t *d_rec_len, int64_t n_rec, const double *d_lam,
+                                         double thr, int64_t capacity, int64_t *d_ev_key, double *d_ev_cover, double *d_ev_start,
+                                         uint64_t *d_ev_count, double *d_z, double *d_nsites, int64_t *d_windows);
+int pfmscan_multisite_profile_events_staged(pfmscan_ctx *ctx, const double *struct_tables, const double *seq_tables, int n_motifs,
+                                            int m, const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec,
+                                            const double *lam, double thr, int64_t capacity, int64_t *ev_key, double *ev_cover,
+                                            double *ev_start, int64_t *n_events, double *z, double *nsites, int64_t *windows);
+
 #ifdef __cplusplus
 }
 #endif

@@ -69,6 +69,7 @@ SYMBOLS = [
     "pfmscan_footprint_profile_dev", "pfmscan_footprint_profile_staged", "pfmscan_footprint_profile_events_dev", "pfmscan_footprint_profile_events_staged",
     "pfmscan_mutocc_dev", "pfmscan_mutocc_staged", "pfmscan_mutocc_events_dev", "pfmscan_mutocc_events_staged",
     "pfmscan_multisite_dev", "pfmscan_multisite_staged", "pfmscan_multisite_events_dev", "pfmscan_multisite_events_staged",
+    "pfmscan_multisite_profile_dev", "pfmscan_multisite_profile_staged", "pfmscan_multisite_profile_events_dev", "pfmscan_multisite_profile_events_staged",
 ]
 PAIR_ROUTE_NONE, PAIR_ROUTE_FUSED, PAIR_ROUTE_TWO_PHASE, PAIR_ROUTE_DENSE, PAIR_ROUTE_CREDITS = range(5)   # Context.pair_sum_route()
 SITE_GROUP = 4096     # most hits of one group of the site profiles
@@ -282,7 +283,11 @@ def load():
     L.pfmscan_multisite_staged.argtypes = [vp, vp, vp, i32, i32, vp, vp, i64, vp, vp, vp, vp, vp, vp]
     L.pfmscan_multisite_events_dev.argtypes = [vp, vp, vp, i32, i32, vp, vp, i64, vp, vp, i64, vp, dbl, i64, vp, vp, vp, vp, vp, vp, vp]
     L.pfmscan_multisite_events_staged.argtypes = [vp, vp, vp, i32, i32, vp, vp, i64, vp, dbl, i64, vp, vp, vp, ctypes.POINTER(i64), vp, vp, vp]
-    L.pfmscan_footprint_profile_dev.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, i32, i64, vp, vp, i64, vp, vp, vp, vp]
+    L.pfmscan_multisite_profile_dev.argtypes = [vp, vp, vp, i32, i32, vp, vp, i32, i64, vp, vp, i64, vp, vp, vp, vp, vp, vp]
+    L.pfmscan_multisite_profile_staged.argtypes = [vp, vp, vp, i32, i32, vp, vp, i64, vp, vp, vp, vp, vp, vp]
+    L.pfmscan_multisite_profile_events_dev.argtypes = [vp, vp, vp, i32, i32, vp, vp, i32, i64, vp, vp, i64, vp, dbl, i64, vp, vp, vp, vp, vp, vp, vp]
+    L.pfmscan_multisite_profile_events_staged.argtypes = [vp, vp, vp, i32, i32, vp, vp, i64, vp, dbl, i64, vp, vp, vp, ctypes.POINTER(i64), vp, vp, vp]
+    L.pfmscan_footprint_profile_dev.argtypes =[vp, vp, vp, i32, i32, i32, vp, vp, i32, i64, vp, vp, i64, vp, vp, vp, vp]
     L.pfmscan_footprint_profile_staged.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, i64, vp, vp, vp, vp]
     L.pfmscan_footprint_profile_events_dev.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, i32, i64, vp, vp, i64, dbl, i64, vp, vp, vp, vp, vp, vp]
     L.pfmscan_footprint_profile_events_staged.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, i64, dbl, i64, vp, vp, vp, ctypes.POINTER(i64), vp, vp]
@@ -2277,6 +2282,72 @@ class Context(object):
             self._check(rc, k.value)
             k = int(k.value)
             return key[:k].copy(), cover[:k].copy(), start[:k].copy(), occ, windows
+
+    # -- multi-site model on averaged-structure profiles (include/pfmscan.h: pfmscan_multisite_profile_*) ------
+    def multisite_profile_dev(self, struct_tables, seq_tables, d_codes, d_profile, profile_dtype, n_pos, d_rec_off, d_rec_len, n_rec, d_lam,
+                              d_start, d_cover, d_z=None, d_nsites=None, d_windows=None):
+        st, sq = self._profile_tables(struct_tables, seq_tables)
+        self._check(self._L.pfmscan_multisite_profile_dev(self._h, _ptr(st), _ptr(sq), st.shape[0], st.shape[1], _ptr(d_codes), _ptr(d_profile),
+                                                          int(profile_dtype), int(n_pos), _ptr(d_rec_off), _ptr(d_rec_len), int(n_rec),
+                                                          _ptr(d_lam), _ptr(d_start), _ptr(d_cover), _ptr(d_z), _ptr(d_nsites), _ptr(d_windows)))
+
+    def multisite_profile_staged(self, struct_tables, seq_tables, rec_off, rec_len, lam, want_start=True, want_cover=True):
+        """-> start, cover float64 [n_motifs][n_pos] aligned with the staged profile (None where not wanted; +0.0 outside the
+        records of the table), z, nsites float64 [n_rec][n_motifs], windows int64 [n_rec]; struct_tables [n_motifs][m][7] in the
+        profile's stored column order, seq_tables [n_motifs][m][8] | None (joint: the staged codes too), lam float64 [n_rec]"""
+        st, sq = self._profile_tables(struct_tables, seq_tables)
+        n_motifs, m = st.shape[:2]
+        n = int(self._L.pfmscan_staged_positions(self._h))
+        if n < 0:
+            raise ValueError("no stream staged (call stage first)")
+        rec_off, rec_len = self._records(rec_off, rec_len)
+        lam = self._lam(lam, rec_off.size)
+        start = np.zeros((n_motifs, n), dtype=np.float64) if want_start else None
+        cover = np.zeros((n_motifs, n), dtype=np.float64) if want_cover else None
+        z, windows = self._occ_windows(rec_off.size, n_motifs)
+        nsites = np.zeros_like(z)
+        self._check(self._L.pfmscan_multisite_profile_staged(self._h, _ptr(st), _ptr(sq), n_motifs, m, _ptr(rec_off), _ptr(rec_len), rec_off.size,
+                                                             _ptr(lam), _ptr(start), _ptr(cover), _ptr(z), _ptr(nsites), _ptr(windows)))
+        return start, cover, z, nsites, windows
+
+    def multisite_profile_events_dev(self, struct_tables, seq_tables, d_codes, d_profile, profile_dtype, n_pos, d_rec_off, d_rec_len, n_rec,
+                                     d_lam, thr, capacity, d_ev_key, d_ev_cover, d_ev_start, d_ev_count, d_z=None, d_nsites=None, d_windows=None):
+        st, sq = self._profile_tables(struct_tables, seq_tables)
+        self._check(self._L.pfmscan_multisite_profile_events_dev(self._h, _ptr(st), _ptr(sq), st.shape[0], st.shape[1], _ptr(d_codes),
+                                                                 _ptr(d_profile), int(profile_dtype), int(n_pos), _ptr(d_rec_off),
+                                                                 _ptr(d_rec_len), int(n_rec), _ptr(d_lam), float(thr), int(capacity),
+                                                                 _ptr(d_ev_key), _ptr(d_ev_cover), _ptr(d_ev_start), _ptr(d_ev_count), _ptr(d_z),
+                                                                 _ptr(d_nsites), _ptr(d_windows)))
+
+    def multisite_profile_events_staged(self, struct_tables, seq_tables, rec_off, rec_len, lam, thr, capacity=None):
+        """the positions of the staged profile whose cover > thr under the multi-site model, decided on the device -> (key int64[k]
+        = motif * n_pos + position sorted, cover float64[k], start float64[k], z, nsites float64 [n_rec][n_motifs], windows int64
+        [n_rec]).  capacity None: a capacity verdict is answered by one retry with the capacity it names; else CapacityError
+        carries it"""
+        st, sq = self._profile_tables(struct_tables, seq_tables)
+        n_motifs, m = st.shape[:2]
+        n = int(self._L.pfmscan_staged_positions(self._h))
+        if n < 0:
+            raise ValueError("no stream staged (call stage first)")
+        rec_off, rec_len = self._records(rec_off, rec_len)
+        lam = self._lam(lam, rec_off.size)
+        cap = int(capacity) if capacity is not None else max(1024, n // 16)
+        while True:
+            key = np.empty(cap, dtype=np.int64)
+            cover = np.empty(cap, dtype=np.float64)
+            start = np.empty(cap, dtype=np.float64)
+            z, windows = self._occ_windows(rec_off.size, n_motifs)
+            nsites = np.zeros_like(z)
+            k = ctypes.c_int64(0)
+            rc = self._L.pfmscan_multisite_profile_events_staged(self._h, _ptr(st), _ptr(sq), n_motifs, m, _ptr(rec_off), _ptr(rec_len),
+                                                                 rec_off.size, _ptr(lam), float(thr), cap, _ptr(key), _ptr(cover), _ptr(start),
+                                                                 ctypes.byref(k), _ptr(z), _ptr(nsites), _ptr(windows))
+            if rc == E_CAPACITY and capacity is None:
+                cap = int(k.value)
+                continue
+            self._check(rc, k.value)
+            k = int(k.value)
+            return key[:k].copy(), cover[:k].copy(), start[:k].copy(), z, nsites, windows
 
     def time_scan_dev(self, motif, d_codes, d_profile, profile_dtype, n_pos, d_out_seq, d_out_struct,
                       stream=None, warmup=1, iters=5):

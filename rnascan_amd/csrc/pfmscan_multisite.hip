@@ -9,6 +9,12 @@
 // Four kernels per pass (a pass: the records and motifs whose two scratch planes fit the cap, pfmscan_ms_plan.hpp):
 //   k_ms_terms     tile-parallel, the geometry of k_fp_tiles: a workgroup owns a tile of ONE record, parks the strip(s) of codes
 //                  in LDS, and a lane makes the chain of its windows and stores a_s into plane A.  Everything with m in it.
+//   k_ms_profile_terms<T, SEQ>
+//                  takes k_ms_terms' place when the stream is an averaged-structure profile (DESIGN.md 5n "on averaged-structure
+//                  profiles"): the same tile of ONE record, the rows under its windows fetched as aligned 16-byte vectors
+//                  (occp_load), clipped to the record and parked in LDS as doubles, the chain of k_fp_profile_tiles
+//                  (occp_marginal per row, in joint mode behind the letter chain), a_s into plane A.  No halo: rows
+//                  [t0, min(t0 + n_tp + m - 1, L)) only.
 //   k_ms_forward   ONE LANE per (record, motif), a wave per workgroup.  The wave moves MS_CHUNK activities of each of its 64
 //                  records through LDS at a time (a run of consecutive doubles per record, never 8-byte accesses a record
 //                  apart; the next chunk's loads are in flight in registers meanwhile), every lane then walks its own row: g = a[j] * F[j] does not depend on F[j+m-1], only the
@@ -40,6 +46,7 @@ constexpr int MS_SLOTS = PFMSCAN_MULTISITE_SLOTS;                  // windows of
 constexpr int MS_WPL = MS_SLOTS / BLOCK;                           // windows (and positions) of a lane
 constexpr int MS_CS = (MS_SLOTS + PFMSCAN_MAX_M - 1 + 3) / 4 * 4;  // bytes of a strip of codes
 constexpr uint8_t MS_FOREIGN = 0xFF;
+constexpr int MSP_ROWS = MS_SLOTS + PFMSCAN_MAX_M - 1;             // profile rows under the windows of a tile, at most
 constexpr int MS_CHUNK = PFMSCAN_MULTISITE_CHUNK;                  // positions of a record a serial kernel holds in LDS
 constexpr int MS_ROW = MS_CHUNK + 1;                               // doubles of a lane's row: odd, so that a wave's rows fall on distinct banks
 constexpr int MS_LANES = 64;                                       // (record, motif) pairs of a workgroup of the serial kernels: one wave
@@ -54,6 +61,11 @@ struct MsArgs {
     const uint8_t *codes2;       // [n_pos] PAIR: structure-letter codes
     const double *tables;        // [n_motifs][m][8] device: the tables over codes
     const double *tables2;       // PAIR: the structure tables
+    const unsigned char *profile;   // [n_pos][7] float or double, 16-byte aligned, or null: an averaged-structure profile takes the
+                                 // place of the strips; then tables are the letter tables of joint mode over codes (or null) and
+                                 // tables2 the structure tables [n_motifs][m][7] in the profile's stored column order
+    int dtype;                   // PFMSCAN_PROFILE_F32 / F64
+    bool joint;                  // profile: the letter chain first, a window with a code >= 4 has no term
     const int64_t *rec_off, *rec_len;   // [n_rec]
     const int64_t *tile_start;   // [n_rec + 1] prefix of ceil(L / tile)
     const double *lam;           // [n_rec] device
@@ -153,6 +165,130 @@ __global__ __launch_bounds__(BLOCK) void k_ms_terms(const MsArgs a)
                 a.pa[(int64_t)q * a.span + p0 + s] = act;
             }
         }
+    }
+}
+
+// ---- (a') the activities of an averaged-structure profile ---------------------------------------------------------------
+// The tables, the profile and the plane are separate __restrict__ arguments: the table rows are workgroup-uniform and stay
+// scalar operands while plane A is stored.
+template <typename T, bool SEQ>
+__global__ __launch_bounds__(BLOCK) void k_ms_profile_terms(const MsArgs a, const unsigned char *__restrict__ profile, const uint8_t *__restrict__ codes,
+                                                            const double *__restrict__ stab, const double *__restrict__ ltab,
+                                                            double *__restrict__ pa)
+{
+    constexpr int RB = 7 * (int)sizeof(T);                         // bytes of a row
+    constexpr int PER = 16 / (int)sizeof(T);                       // cells of a vector
+    __shared__ double rows[MSP_ROWS * 7];
+    __shared__ uint8_t cl[SEQ ? MS_CS : 8];
+    const int t = threadIdx.x, m = a.m;
+    const int64_t r = occ_record(a.tile_start, a.r0, a.r1, a.tile_base + (int64_t)blockIdx.x);
+    const int64_t L = a.rec_len[r], off = a.rec_off[r];
+    const int64_t t0 = (a.tile_base + (int64_t)blockIdx.x - a.tile_start[r]) * a.tile;   // the tile's first position, within the record
+    const int n_tp = (int)min((int64_t)a.tile, L - t0);            // its positions, >= 1: the tile exists
+    const int64_t n_win = L - m + 1;                               // may be <= 0: then no slot is a window
+    {
+        // the rows of the record under the tile's windows: [t0, hi), clipped to the record's end; row x lies at LDS row x - t0
+        const int64_t hi = min(t0 + n_tp + m - 1, L);
+        const int nrows = (int)(hi - t0);                          // 1 .. MSP_ROWS
+        const int64_t first = (off + t0) * RB, end = first + (int64_t)nrows * RB, base = first & ~(int64_t)15, total = a.n_pos * RB;
+        const int shift = (int)(first - base) / (int)sizeof(T);
+        const int ncell = nrows * 7, nvec = (int)((end - base + 15) / 16);
+        for (int v = t; v < nvec; v += BLOCK) {
+            double d[PER];
+            occp_cells(occp_load(profile, base + (int64_t)v * 16, total), d, T());
+#pragma unroll
+            for (int j = 0; j < PER; ++j) {
+                const int idx = v * PER + j - shift;
+                if (idx >= 0 && idx < ncell) rows[idx] = d[j];
+            }
+        }
+        if constexpr (SEQ)
+            for (int i = t; i < MS_CS; i += BLOCK) {
+                const int64_t x = t0 + i;
+                uint8_t c = MS_FOREIGN;
+                if (i < n_tp + m - 1 && x < L) {                   // inside the record: inside the stream
+                    c = codes[off + x] & 7u;
+                    if (c >= 4u) c = MS_FOREIGN;
+                }
+                cl[i] = c;
+            }
+    }
+    __syncthreads();
+    // a slot is a window by 0 <= s < n_win, never by what was loaded; in joint mode it has a term when it holds no foreign code
+    bool has[MS_WPL], win[MS_WPL];
+#pragma unroll
+    for (int j = 0; j < MS_WPL; ++j) {
+        const int s = t + j * BLOCK;
+        win[j] = s < n_tp && t0 + s < n_win;
+        bool h = win[j];
+        if constexpr (SEQ) {
+            if (h)
+                for (int k = 0; k < m; ++k) h = h && cl[s + k] != MS_FOREIGN;
+        }
+        has[j] = h;
+    }
+    if (a.windows) {                                               // uniform
+        int n = 0;
+#pragma unroll
+        for (int j = 0; j < MS_WPL; ++j) n += __syncthreads_count(has[j]);
+        if (t == 0 && n != 0) atomicAdd(&a.windows[r], (unsigned long long)n);   // integers: the order does not matter
+    }
+    const double lam = a.lam[r];
+    const int64_t p0 = off - a.base + t0;                          // the tile's first position, in a plane
+    const int64_t ms = (int64_t)m * 7, ml = (int64_t)m * 8;
+    for (int q = 0; q < a.nq; ++q) {                               // the tables of the next motif, the rows stay
+        const double *sp = stab + (a.q0 + q) * ms;
+#pragma unroll
+        for (int j = 0; j < MS_WPL; ++j) {
+            const int s = t + j * BLOCK;
+            if (s < n_tp) {
+                double act = 0.0;                                  // a position that starts no window
+                if (win[j]) {
+                    double tt = 0.0;                               // a window without a term
+                    if (has[j]) {
+                        if constexpr (SEQ) {
+                            const double *lt = ltab + (a.q0 + q) * ml;
+                            tt = lt[cl[s]];
+                            for (int k = 1; k < m; ++k) tt = tt * lt[k * 8 + cl[s + k]];
+                        }
+                        double x[7];
+                        const double *rw = rows + s * 7;
+#pragma unroll
+                        for (int c = 0; c < 7; ++c) x[c] = rw[c];
+                        const double d = occp_marginal(x, sp);
+                        tt = SEQ ? tt * d : d;
+                        for (int k = 1; k < m; ++k) {
+                            rw += 7;
+#pragma unroll
+                            for (int c = 0; c < 7; ++c) x[c] = rw[c];
+                            tt = tt * occp_marginal(x, sp + k * 7);
+                        }
+                    }
+                    act = tt * lam;
+                }
+                pa[(int64_t)q * a.span + p0 + s] = act;
+            }
+        }
+    }
+}
+
+template <typename T>
+static void ms_launch_profile_terms(const MsArgs &a, const dim3 grid, hipStream_t st)
+{
+    if (a.joint) hipLaunchKernelGGL((k_ms_profile_terms<T, true>), grid, dim3(BLOCK), 0, st, a, a.profile, a.codes, a.tables2, a.tables, a.pa);
+    else hipLaunchKernelGGL((k_ms_profile_terms<T, false>), grid, dim3(BLOCK), 0, st, a, a.profile, a.codes, a.tables2, a.tables, a.pa);
+}
+
+// the one part of a pass that depends on what the stream is: plane A from two strips of codes, one, or profile rows
+static void ms_launch_terms(const MsArgs &a, const dim3 grid, hipStream_t st)
+{
+    if (a.profile) {
+        if (a.dtype == PFMSCAN_PROFILE_F64) ms_launch_profile_terms<double>(a, grid, st);
+        else ms_launch_profile_terms<float>(a, grid, st);
+    } else if (a.codes2) {
+        hipLaunchKernelGGL((k_ms_terms<true>), grid, dim3(BLOCK), 0, st, a);
+    } else {
+        hipLaunchKernelGGL((k_ms_terms<false>), grid, dim3(BLOCK), 0, st, a);
     }
 }
 
@@ -404,13 +540,14 @@ static int64_t ms_scratch_cap()
 }
 
 // Launches on st, does not wait.  At least one table is given; d_codes where seq_tables is, d_codes2 where struct_tables is.
-// d_lam: device.  d_z, d_nsites, d_windows may be null.
+// d_lam: device.  d_z, d_nsites, d_windows may be null.  pf: the stream is an averaged-structure profile; struct_tables is then
+// pf->struct_tables ([n_motifs][m][7]), seq_tables / d_codes the letter part of joint mode or null.  Only the terms launch differs.
 static int ms_run(pfmscan_ctx *ctx, const char *who, const double *seq_tables, const double *struct_tables, int n_motifs, int m,
                   const uint8_t *d_codes, const uint8_t *d_codes2, const OccRecords &rec, const double *d_lam, const FpOut &o, double *d_z,
-                  double *d_nsites, int64_t *d_windows, hipStream_t st)
+                  double *d_nsites, int64_t *d_windows, hipStream_t st, const OccProfile *pf = nullptr)
 {
     int rc;
-    const bool pair = seq_tables && struct_tables;
+    const bool pair = !pf && seq_tables && struct_tables;
     const int64_t pairs = rec.n_rec * n_motifs;
     const double *tables = seq_tables ? seq_tables : struct_tables;   // one table: its stream is the first strip
     const uint8_t *codes = seq_tables ? d_codes : d_codes2;
@@ -430,10 +567,17 @@ static int ms_run(pfmscan_ctx *ctx, const char *who, const double *seq_tables, c
     if ((rc = ensure(ctx, ctx->fp_idx, tiles.size() * 8))) return rc;
     if ((rc = upload(ctx, ctx->fp_idx.p, tiles.data(), tiles.size() * 8, st))) return rc;
     MsArgs a{};
-    if ((rc = occ_upload_tables(ctx, tables, pair ? struct_tables : nullptr, (size_t)n_motifs * m * 8 * sizeof(double), n_motifs, m, st, a.tables,
-                                a.tables2)))
+    if (pf) {
+        if ((rc = occ_upload_tables(ctx, seq_tables, pf->struct_tables, (size_t)n_motifs * m * 7 * sizeof(double), n_motifs, m, st, a.tables, a.tables2)))
+            return rc;
+        a.profile = (const unsigned char *)pf->d_profile;
+        a.dtype = pf->dtype;
+        a.joint = seq_tables != nullptr;
+    } else if ((rc = occ_upload_tables(ctx, tables, pair ? struct_tables : nullptr, (size_t)n_motifs * m * 8 * sizeof(double), n_motifs, m, st, a.tables,
+                                       a.tables2))) {
         return rc;
-    a.codes = codes;
+    }
+    a.codes = pf ? d_codes : codes;
     a.codes2 = pair ? d_codes2 : nullptr;
     a.rec_off = rec.d_off;
     a.rec_len = rec.d_len;
@@ -468,10 +612,7 @@ static int ms_run(pfmscan_ctx *ctx, const char *who, const double *seq_tables, c
         a.windows = p.q0 == 0 ? reinterpret_cast<unsigned long long *>(d_windows) : nullptr;
         const int64_t n_tiles = tiles[p.r1] - tiles[p.r0];
         const dim3 tgrid((unsigned)n_tiles), lgrid((unsigned)(((p.r1 - p.r0) * p.nq + MS_LANES - 1) / MS_LANES));
-        if (n_tiles != 0) {
-            if (pair) hipLaunchKernelGGL((k_ms_terms<true>), tgrid, dim3(BLOCK), 0, st, a);
-            else hipLaunchKernelGGL((k_ms_terms<false>), tgrid, dim3(BLOCK), 0, st, a);
-        }
+        if (n_tiles != 0) ms_launch_terms(a, tgrid, st);
         hipLaunchKernelGGL(k_ms_forward, lgrid, dim3(MS_LANES), ring, st, a);   // also for records without a position: Z = 1.0
         hipLaunchKernelGGL(k_ms_backward, lgrid, dim3(MS_LANES), ring, st, a);
         if (n_tiles != 0) {
@@ -536,6 +677,53 @@ static int ms_lam_up(pfmscan_ctx *ctx, const double *lam, int64_t n_rec, const d
     if ((rc = upload(ctx, ctx->exp_inv.p, lam, (size_t)n_rec * 8, ctx->stream))) return rc;
     d_lam = (const double *)ctx->exp_inv.p;
     return PFMSCAN_OK;
+}
+
+// ---- on averaged-structure profiles: the checks are pfmscan_footprint_profile_*'s (without mode), then lam ----------------------
+static int msp_check(pfmscan_ctx *ctx, const char *who, const double *struct_tables, int n_motifs, int m, int profile_dtype, int64_t n_pos,
+                     int64_t n_rec, const double *lam)
+{
+    const char *own = profile_dtype != PFMSCAN_PROFILE_F32 && profile_dtype != PFMSCAN_PROFILE_F64 ? ": profile_dtype must be PFMSCAN_PROFILE_F32 or F64" : nullptr;
+    if (int rc = occ_check_base(ctx, who, m, own, n_motifs, n_rec, n_pos, nullptr)) return rc;
+    if (!struct_tables)
+        return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": struct_tables is NULL (the multi-site model of a profile's letters is pfmscan_multisite_* on the codes)");
+    if (!lam) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": lam is NULL");
+    return PFMSCAN_OK;
+}
+
+// both _dev forms
+static int msp_dev(pfmscan_ctx *ctx, const char *who, const double *struct_tables, const double *seq_tables, int n_motifs, int m,
+                   const uint8_t *d_codes, const void *d_profile, int profile_dtype, int64_t n_pos, const int64_t *d_rec_off, const int64_t *d_rec_len,
+                   int64_t n_rec, const double *d_lam, const FpOut &o, double *d_z, double *d_nsites, int64_t *d_windows)
+{
+    if (!ctx) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": NULL ctx");
+    if (int rc = msp_check(ctx, who, struct_tables, n_motifs, m, profile_dtype, n_pos, n_rec, d_lam)) return rc;
+    if (seq_tables && !d_codes) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": seq_tables (joint mode) needs the codes");
+    if (o.events) {
+        if (int rc = fp_check_events(ctx, who, o.thr, o.capacity, o.ev_count, o.ev_key, o.ev_cover, o.ev_start)) return rc;
+    } else if (!o.start && !o.cover) {
+        return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": d_start and d_cover are both NULL");
+    }
+    if (n_rec == 0 || n_motifs == 0) return PFMSCAN_OK;
+    if (!d_rec_off || !d_rec_len || (n_pos > 0 && !d_profile)) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": NULL record table or profile");
+    if (misaligned(d_profile) || (seq_tables && misaligned(d_codes)))
+        return fail(ctx, PFMSCAN_E_BADSHAPE, std::string(who) + ": stream base pointers must be 16-byte aligned");
+    std::vector<int64_t> host;
+    OccRecords rec;
+    if (int rc = occ_records_home(ctx, who, d_rec_off, d_rec_len, n_rec, n_pos, host, rec)) return rc;
+    const OccProfile pf{struct_tables, d_profile, profile_dtype};
+    return ms_run(ctx, who, seq_tables, struct_tables, n_motifs, m, d_codes, nullptr, rec, d_lam, o, d_z, d_nsites, d_windows, ctx->stream, &pf);
+}
+
+// the checks of both _staged forms, up to "n_rec == 0 or n_motifs == 0: nothing to do" without the outputs' own
+static int msp_staged_check(pfmscan_ctx *ctx, const char *who, const double *struct_tables, const double *seq_tables, int n_motifs, int m, int64_t n_rec,
+                            const double *lam)
+{
+    if (!ctx) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": NULL ctx");
+    if (ctx->staged_n < 0) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": no stream staged (call pfmscan_stage first)");
+    if (!ctx->staged_profile) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": no profile is staged");
+    if (seq_tables && !ctx->staged_codes) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": seq_tables (joint mode) needs staged codes");
+    return msp_check(ctx, who, struct_tables, n_motifs, m, ctx->staged_dtype, ctx->staged_n, n_rec, lam);
 }
 
 }  // namespace pfmscan
@@ -624,6 +812,92 @@ int pfmscan_multisite_events_staged(pfmscan_ctx *ctx, const double *seq_tables, 
     double *d_z = z ? d_both : nullptr, *d_ns = nsites ? d_both + pairs : nullptr;
     if ((rc = ms_run(ctx, who, seq_tables, struct_tables, n_motifs, m, (const uint8_t *)ctx->codes.p, (const uint8_t *)ctx->codes2.p, rec, d_lam, o, d_z,
                      d_ns, d_win, ctx->stream)))
+        return rc;
+    if (nsites) HIP_TRY(ctx, hipMemcpyAsync(nsites, d_ns, pairs * 8, hipMemcpyDeviceToHost, ctx->stream));
+    return fp_events_home(ctx, who, o, ev_key, ev_cover, ev_start, n_events, {z, d_z, pairs * 8}, {windows, d_win, (size_t)n_rec * 8});
+}
+
+int pfmscan_multisite_profile_dev(pfmscan_ctx *ctx, const double *struct_tables, const double *seq_tables, int n_motifs, int m,
+                                  const uint8_t *d_codes, const void *d_profile, int profile_dtype, int64_t n_pos, const int64_t *d_rec_off,
+                                  const int64_t *d_rec_len, int64_t n_rec, const double *d_lam, double *d_start, double *d_cover, double *d_z,
+                                  double *d_nsites, int64_t *d_windows)
+{
+    const FpOut o{d_start, d_cover, false, 0.0, 0, nullptr, nullptr, nullptr, nullptr};
+    return msp_dev(ctx, "pfmscan_multisite_profile_dev", struct_tables, seq_tables, n_motifs, m, d_codes, d_profile, profile_dtype, n_pos, d_rec_off,
+                   d_rec_len, n_rec, d_lam, o, d_z, d_nsites, d_windows);
+}
+
+int pfmscan_multisite_profile_events_dev(pfmscan_ctx *ctx, const double *struct_tables, const double *seq_tables, int n_motifs, int m,
+                                         const uint8_t *d_codes, const void *d_profile, int profile_dtype, int64_t n_pos, const int64_t *d_rec_off,
+                                         const int64_t *d_rec_len, int64_t n_rec, const double *d_lam, double thr, int64_t capacity,
+                                         int64_t *d_ev_key, double *d_ev_cover, double *d_ev_start, uint64_t *d_ev_count, double *d_z,
+                                         double *d_nsites, int64_t *d_windows)
+{
+    const FpOut o{nullptr, nullptr, true, thr, capacity, d_ev_key, d_ev_cover, d_ev_start, reinterpret_cast<unsigned long long *>(d_ev_count)};
+    return msp_dev(ctx, "pfmscan_multisite_profile_events_dev", struct_tables, seq_tables, n_motifs, m, d_codes, d_profile, profile_dtype, n_pos,
+                   d_rec_off, d_rec_len, n_rec, d_lam, o, d_z, d_nsites, d_windows);
+}
+
+int pfmscan_multisite_profile_staged(pfmscan_ctx *ctx, const double *struct_tables, const double *seq_tables, int n_motifs, int m,
+                                     const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec, const double *lam, double *start, double *cover,
+                                     double *z, double *nsites, int64_t *windows)
+{
+    const char *who = "pfmscan_multisite_profile_staged";
+    if (int rc = msp_staged_check(ctx, who, struct_tables, seq_tables, n_motifs, m, n_rec, lam)) return rc;
+    if (!start && !cover) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": start and cover are both NULL");
+    if (n_rec == 0 || n_motifs == 0) return PFMSCAN_OK;
+    if (!rec_off || !rec_len) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": NULL record table");
+    int rc;
+    OccRecords rec;
+    if ((rc = occ_records_up(ctx, who, rec_off, rec_len, n_rec, rec))) return rc;
+    const double *d_lam;
+    if ((rc = ms_lam_up(ctx, lam, n_rec, d_lam))) return rc;
+    const int64_t n_pos = ctx->staged_n;
+    const size_t plane = (size_t)n_motifs * (size_t)n_pos, pairs = (size_t)n_rec * n_motifs;
+    if ((rc = ensure(ctx, ctx->fp_out, std::max<size_t>((2 * plane + 2 * pairs + (size_t)n_rec) * 8, 16)))) return rc;
+    double *d_base = (double *)ctx->fp_out.p;
+    double *d_start = start ? d_base : nullptr;
+    double *d_cover = cover ? d_base + plane : nullptr;
+    double *d_z = z ? d_base + 2 * plane : nullptr;
+    double *d_ns = nsites ? d_base + 2 * plane + pairs : nullptr;
+    int64_t *d_win = windows ? (int64_t *)(d_base + 2 * plane + 2 * pairs) : nullptr;
+    // positions in no record of the table are +0.0
+    if (d_start && plane) HIP_TRY(ctx, hipMemsetAsync(d_start, 0, plane * 8, ctx->stream));
+    if (d_cover && plane) HIP_TRY(ctx, hipMemsetAsync(d_cover, 0, plane * 8, ctx->stream));
+    const FpOut o{d_start, d_cover, false, 0.0, 0, nullptr, nullptr, nullptr, nullptr};
+    const OccProfile pf{struct_tables, ctx->profile.p, ctx->staged_dtype};
+    if ((rc = ms_run(ctx, who, seq_tables, struct_tables, n_motifs, m, (const uint8_t *)ctx->codes.p, nullptr, rec, d_lam, o, d_z, d_ns, d_win, ctx->stream,
+                     &pf)))
+        return rc;
+    return occ_copy_home(ctx, {{start, d_start, plane * 8}, {cover, d_cover, plane * 8}, {z, d_z, pairs * 8}, {nsites, d_ns, pairs * 8},
+                               {windows, d_win, (size_t)n_rec * 8}});
+}
+
+int pfmscan_multisite_profile_events_staged(pfmscan_ctx *ctx, const double *struct_tables, const double *seq_tables, int n_motifs, int m,
+                                            const int64_t *rec_off, const int64_t *rec_len, int64_t n_rec, const double *lam, double thr,
+                                            int64_t capacity, int64_t *ev_key, double *ev_cover, double *ev_start, int64_t *n_events, double *z,
+                                            double *nsites, int64_t *windows)
+{
+    const char *who = "pfmscan_multisite_profile_events_staged";
+    if (int rc = msp_staged_check(ctx, who, struct_tables, seq_tables, n_motifs, m, n_rec, lam)) return rc;
+    if (int rc = fp_check_events(ctx, who, thr, capacity, n_events, ev_key, ev_cover, ev_start)) return rc;
+    *n_events = 0;
+    if (n_rec == 0 || n_motifs == 0) return PFMSCAN_OK;
+    if (!rec_off || !rec_len) return fail(ctx, PFMSCAN_E_BADARG, std::string(who) + ": NULL record table");
+    int rc;
+    OccRecords rec;
+    if ((rc = occ_records_up(ctx, who, rec_off, rec_len, n_rec, rec))) return rc;
+    const double *d_lam;
+    if ((rc = ms_lam_up(ctx, lam, n_rec, d_lam))) return rc;
+    const size_t pairs = (size_t)n_rec * n_motifs;
+    FpOut o;
+    double *d_both;                                                // z, then nsites
+    int64_t *d_win;
+    if ((rc = fp_events_room(ctx, thr, capacity, 2 * pairs, (size_t)n_rec, true, windows != nullptr, o, d_both, d_win))) return rc;
+    double *d_z = z ? d_both : nullptr, *d_ns = nsites ? d_both + pairs : nullptr;
+    const OccProfile pf{struct_tables, ctx->profile.p, ctx->staged_dtype};
+    if ((rc = ms_run(ctx, who, seq_tables, struct_tables, n_motifs, m, (const uint8_t *)ctx->codes.p, nullptr, rec, d_lam, o, d_z, d_ns, d_win, ctx->stream,
+                     &pf)))
         return rc;
     if (nsites) HIP_TRY(ctx, hipMemcpyAsync(nsites, d_ns, pairs * 8, hipMemcpyDeviceToHost, ctx->stream));
     return fp_events_home(ctx, who, o, ev_key, ev_cover, ev_start, n_events, {z, d_z, pairs * 8}, {windows, d_win, (size_t)n_rec * 8});

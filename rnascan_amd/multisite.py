@@ -24,8 +24,9 @@ probability that the record holds a site at all.  Doubles are printed with ``rep
 There is no scaling: ``Z`` grows like ``exp(lam * sum of ratios)`` and overflows on long records with a large prior.  An infinite
 or NaN ``Z`` is an error that names the motif and the record, and nothing is written.
 
-Not supported: averaged-structure directories or stores, expected counts or mutagenesis under this model, cooperativity or
-spacing between sites, a scaled recurrence for records whose Z overflows, ``--gpus``, bedGraph output.
+Not supported: averaged-structure directories or stores (they are ``python -m rnascan_amd.multisite_profile``), expected counts
+or mutagenesis under this model, cooperativity or spacing between sites, a scaled recurrence for records whose Z overflows,
+``--gpus``, bedGraph output.
 """
 import argparse
 import math
@@ -66,17 +67,19 @@ def record_rows(motif_ids, ids, win, z, nsites):
     return lines
 
 
-def batch_rows(motif_ids, groups, ids, stream, call, positions):
+def batch_rows(motif_ids, groups, ids, stream, call, positions, cols=None, not_positive=None):
     """the lines of one batch in (record, motif, position) order and its --records lines.
-    ``call(stream, m, ks)`` -> (key, cover, start, z [n_rec][len(ks)], nsites, windows [n_rec])"""
-    n_pos = int(np.asarray(stream.codes).size)
+    ``call(stream, m, ks)`` -> (key, cover, start, z [n_rec][len(ks)], nsites, windows [n_rec]); a batch of averaged-structure
+    profiles comes with its stored column order and is ``call(stream, m, ks, cols)``.  ``not_positive``: the message (motif,
+    record) for a Z <= 0.0, which only negative profile cells can make; None: not tested"""
+    n_pos = int(np.asarray(stream.codes).size) if stream.codes is not None else int(np.asarray(stream.profile).shape[0])
     offsets = np.asarray(stream.offsets, dtype=np.int64)
     got = {}                                                       # (record, motif) -> (positions in the record, cover, start, width)
     z = np.ones((len(ids), len(motif_ids)), dtype=np.float64)
     ns = np.zeros((len(ids), len(motif_ids)), dtype=np.float64)
     win = np.zeros((len(ids), len(motif_ids)), dtype=np.int64)
     for m, ks in groups.items():
-        key, cover, start, zz, nn, w = call(stream, m, ks)
+        key, cover, start, zz, nn, w = call(stream, m, ks) if cols is None else call(stream, m, ks, cols)
         z[:, ks], ns[:, ks] = np.asarray(zz), np.asarray(nn)
         win[:, ks] = np.asarray(w)[:, None]
         key = np.asarray(key, dtype=np.int64)
@@ -90,6 +93,10 @@ def batch_rows(motif_ids, groups, ids, stream, call, positions):
     bad = np.argwhere(~np.isfinite(z))
     if bad.size:
         raise MultisiteError(NOT_FINITE % (motif_ids[int(bad[0][1])], ids[int(bad[0][0])]))
+    if not_positive:
+        bad = np.argwhere(z <= 0.0)
+        if bad.size:
+            raise MultisiteError(not_positive % (motif_ids[int(bad[0][1])], ids[int(bad[0][0])]))
     lines = []
     for r, sid in enumerate(ids):
         for k, mid in enumerate(motif_ids):
@@ -99,11 +106,11 @@ def batch_rows(motif_ids, groups, ids, stream, call, positions):
     return lines, record_rows(motif_ids, ids, win, z, ns)
 
 
-def write_table(out, records_path, motif_ids, groups, batches, call, positions):
+def write_table(out, records_path, motif_ids, groups, batches, call, positions, not_positive=None):
     """every line is made before the first is written: a record that fails leaves nothing behind"""
     lines, rec_lines = [], []
-    for ids, stream, _ in batches:
-        more, recs = batch_rows(motif_ids, groups, ids, stream, call, positions)
+    for ids, stream, cols in batches:
+        more, recs = batch_rows(motif_ids, groups, ids, stream, call, positions, cols, not_positive)
         lines += more
         rec_lines += recs
     out.write("\t".join(POSITION_COLUMNS if positions else COLUMNS) + "\n")

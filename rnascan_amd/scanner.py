@@ -288,6 +288,19 @@ class HipEngine(object):
         self._stage(stream)
         return self.ctx.footprint_profile_events_staged(struct_tables, seq_tables, mode, stream.offsets, stream.lengths, thr, capacity)
 
+    def multisite_profile(self, stream, struct_tables, seq_tables, lam, want_start=True, want_cover=True):
+        """the multi-site model of an averaged-structure profile: tables as ``footprint_profile`` takes them,
+        ``lam`` float64 [n_rec] the activity of a site in each record -> what ``multisite`` returns:
+        (start, cover float64 [n_motifs][n_pos], +0.0 outside the records; z, nsites float64 [n_rec][n_motifs]; windows int64 [n_rec])"""
+        self._stage(stream)
+        return self.ctx.multisite_profile_staged(struct_tables, seq_tables, stream.offsets, stream.lengths, lam, want_start, want_cover)
+
+    def multisite_profile_events(self, stream, struct_tables, seq_tables, lam, thr, capacity=None):
+        """the positions of the profile with cover > thr under the multi-site model, decided on the device: only they come home ->
+        (key int64 = motif * n_pos + position sorted, cover float64, start float64, z, nsites float64 [n_rec][n_motifs], windows)"""
+        self._stage(stream)
+        return self.ctx.multisite_profile_events_staged(struct_tables, seq_tables, stream.offsets, stream.lengths, lam, thr, capacity)
+
     # the three passes above with their matrices added up over the records on the device (DESIGN.md 5k): the accumulators
     # (uint64 [n_motifs][_lib.SITE_LIMBS][m * 8], normalised) are changed in place, one call per batch adds that batch's records
     def expect_merged(self, stream, ratio_tables, n_letters, mode, acc, which=0):
